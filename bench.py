@@ -11,9 +11,15 @@ Every rank owns one independent sequence (weak scaling); the only collective is 
 MAX(elapsed) reduction.  Frames are resident in HBM before the timed region starts.
 
 Rank 0's FINAL stdout line is the record the driver parses: one JSON object below 4 KB (compact_line) with the
-metric, `roofline` (measured live on the launch stream for the dominant kernel) and `cpu_baseline` (the oracle
-port -- test infrastructure -- of the same path timed on the host cores over a bounded sample).  Everything else
-the run measures goes to gpurun_out/bench_details.json and is printed as one {"bench_details": ...} line before it.
+metric, `value`, `ms_per_step` and the configuration.  A plain run does only what that line needs: set-up (with
+--mode auto, the calibration that picks the launch form), W warm-up steps, exactly K timed steps, the outputs of the
+last timed step if --dump-outputs DIR is given, the line.
+
+--full adds everything else the bench measures, as extra figures in the line and beside it: `roofline` (measured
+live on the launch stream for the dominant kernel), `cpu_baseline` (the oracle port -- test infrastructure -- of the
+same path timed on the host cores over a bounded sample), the dense network, the variants, several sequences per GPU,
+per-layer tables; the K steps are repeated for --min-seconds as well.  Everything that does not fit the line goes to
+a side file bench_details.json (emit) and is printed as one {"bench_details": ...} line before it.
 """
 import argparse
 import contextlib
@@ -83,13 +89,21 @@ def parse():
     ap.add_argument("--no-fuse-pool", action="store_true",
                     help="keep the change-based pool launches (default: pooling is folded into the next "
                          "layer's change detection, pycbinfer.fusePoolingIntoDetection; same results)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well (dense network, variants, several "
+                         "sequences, per-kernel tables and roofline, secondary configurations, CPU baseline; the "
+                         "--no-* switches skip parts of it) and write the details side file; a plain run times the "
+                         "headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the network output of the last timed step of every sequence "
+                         "as float32 DIR/output.npy (DIR/output_seq<q>.npy with several sequences)")
     ap.add_argument("--multi", type=int, default=4,
-                    help="also report the throughput with this many concurrent sequences (0/1: skip)")
-    ap.add_argument("--min-seconds", type=float, default=0.5,
+                    help="with --full: also report the throughput with this many concurrent sequences (0/1: skip)")
+    ap.add_argument("--min-seconds", type=float, default=None,
                     help="the timed region repeats the K steps until it lasts at least this long (a 20-step "
-                         "region is 2 ms: too short for a stable headline); `steps` in the JSON line is the "
-                         "number of steps actually timed, `steps_requested` is K, `steps_policy` says which "
-                         "rule applied.  --min-seconds 0: exactly K steps are timed")
+                         "region is 2 ms: too short for a stable headline) and `value` becomes the median of three "
+                         "literal K-step regions; the details' `steps_requested` is K, `steps_policy` says which "
+                         "rule applied.  Default 0.5 with --full, else 0: exactly K steps are timed, once")
     ap.add_argument("--no-variants", action="store_true",
                     help="skip the extra measurements that price the structural choices of the headline "
                          "configuration (reference-structured network, one-moving-rectangle video)")
@@ -114,7 +128,10 @@ def parse():
     ap.add_argument("--pool-clone", action="store_true",
                     help="CBPoolMax2d returns a fresh copy of its state every frame like the reference "
                          "(default: the state tensor itself; identical results, one copy kernel less)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.min_seconds is None:
+        args.min_seconds = 0.5 if args.full else 0.0
+    return args
 
 
 def log(*a):
@@ -178,8 +195,11 @@ def compact_line(result):
     return line
 
 
-def emit(result):
-    """Side file + details line, then the final (compact) line."""
+def emit(result, full=True):
+    """Side file + details line, then the final (compact) line; a plain run (full=False) prints the final line alone."""
+    if not full:
+        print(json.dumps(compact_line(result)), flush=True)
+        return
     details = {k: v for k, v in result.items()}
     path = None
     for d in (os.path.join(REPO, "gpurun_out"), REPO, os.getcwd()):
@@ -201,6 +221,25 @@ def emit(result):
         text = json.dumps(line)
     print(json.dumps({"bench_details": details}), flush=True)
     print(text, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the network output of every
+    sequence -- as float32 .npy files, so that two builds can be compared output for output on the same inputs (the
+    weights and the video are seeded: the same arguments give the same frames).  With more sequences than fit into
+    DUMP_LIMIT_BYTES, the first ones that fit are written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for q, o in enumerate(outs):
+        a = o.detach().float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            break
+        np.save(os.path.join(path, "output.npy" if len(outs) == 1 else "output_seq%d.npy" % q), a)
 
 
 class PipelinedRunner(object):
@@ -1532,7 +1571,7 @@ def main():
     # FIRST: with a single-sequence graph captured earlier in the process the same measurement comes out
     # ~17 % lower (7.4k vs 8.9k frames/s; cause not found).
     multi_result = None
-    if S == 1 and world == 1 and args.multi > 1 and capturable:
+    if args.full and S == 1 and world == 1 and args.multi > 1 and capturable:
         melapsed, msteps, mseqs = run_sequences(args.multi, args.steps, args.warmup, 1, lambda: None, "graph",
                                                 min_seconds=args.min_seconds)
         multi_result = {"sequences_per_gpu": args.multi, "steps": msteps,
@@ -1738,6 +1777,8 @@ def main():
         total_frames, elapsed = sorted(shots, key=lambda te: te[1])[1]
         steps_timed = args.steps
     fps = total_frames / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [q['runner'].out for q in seqs])
 
     dist_backend = shard.backend if shard.dist is not None else None
     if rank != 0:
@@ -1789,7 +1830,7 @@ def main():
 
     if multi_result is not None:
         result["multi_sequence"] = multi_result
-    if world == 1 and S == 1 and not args.no_pipelined and args.experiment in (5, 6):
+    if args.full and world == 1 and S == 1 and not args.no_pipelined and args.experiment in (5, 6):
         pel, psteps, pseqs = run_sequences(1, args.steps, args.warmup, 50, lambda: None, "eager",
                                            min_seconds=args.min_seconds, pipelined=True)
         result["pipelined"] = {"value": psteps / pel, "unit": "frames/s", "steps": psteps,
@@ -1801,7 +1842,7 @@ def main():
 
     # the reference's own timing protocol (poseDetection/evalTools.py:7-35; dense: sceneLabeling/eval01.py:68):
     # state cleared, frames 0..T-2 untimed, the LAST frame + device sync timed on the host, min of 3 repeats
-    if world == 1 and S == 1 and not args.no_last_frame:
+    if args.full and world == 1 and S == 1 and not args.no_last_frame:
         from cbinfer_amd import evalTools
         fs = frames[:8]
         t_cb = evalTools.inferFramesetBenchmark(test, fs, cuda=True, numIter=3)
@@ -1821,7 +1862,7 @@ def main():
     # what the structural choices of the headline configuration are worth: the same measurement on (a) the
     # reference-structured network -- change-based pool launches with a cloned output, dense torch 1x1 tail
     # (sceneLabeling/modelLoader.py:62-78 as is) -- and (b) the video as ONE moving rectangle of the same area
-    if world == 1 and S == 1 and not args.no_variants:
+    if args.full and world == 1 and S == 1 and not args.no_variants:
         result["variants"] = {}
         for name, var in (("f16x2", dict(env=dict(CBINFER_ARITH="f16x2"))),
                           ("exact_f32", dict(env=dict(CBINFER_EXACT_F32="1"))),
@@ -1871,7 +1912,7 @@ def main():
     # dense network on the same GPU, timed the same way (eval01.py:68) -- in MIOpen's default find mode AND with its
     # exhaustive find (torch.backends.cudnn.benchmark = True; the find runs in the untimed priming frames): `dense_fps`
     # is the better of the two, so the speed-up is quoted against the fastest dense network this GPU offers (round 6)
-    if not args.no_dense and world == 1:
+    if args.full and not args.no_dense and world == 1:
         # (with S sequences per GPU the dense network gets them as one batch of S frames)
         dframes = [torch.cat([q['frames'][i] for q in seqs]) for i in range(min(len(frames), 64))]
         dense = {}
@@ -1916,7 +1957,7 @@ def main():
             log("bench: dense_on_cb_kernels: %r" % (e,))
 
     # per-kernel measurement (HIP events on the launch stream) -> roofline of the dominant kernel
-    if world == 1:
+    if args.full and world == 1:
         got = inframe_layer_times(test, frames, seqs[0]['pos'])
         if got is not None:
             test_rows, _, pair_us = got
@@ -2094,7 +2135,7 @@ def main():
                     log(json.dumps(r))
 
     # every layer in isolation at a post-dilation change ratio of exactly 10 %
-    if world == 1 and S == 1 and not args.no_isolated and args.experiment in (4, 5, 6):
+    if args.full and world == 1 and S == 1 and not args.no_isolated and args.experiment in (4, 5, 6):
         try:
             result["isolated_layers"] = isolated_layers(test, ratio=args.ratio)
             result["isolated_layers_note"] = isolated_layers.__doc__.split("\n\n")[0].replace("\n    ", " ")
@@ -2102,17 +2143,17 @@ def main():
             result["isolated_layers"] = "failed: %r" % (e,)
 
     # BASELINE.json configs[2] and [3] (bounded samples; tools/sweep.py has the full tables)
-    if world == 1 and S == 1 and not args.no_secondary:
+    if args.full and world == 1 and S == 1 and not args.no_secondary:
         try:
             sec = secondary_configs(args)
             result.setdefault("variants", {}).update(sec)
         except Exception as e:      # the headline must not depend on it
             result.setdefault("variants", {})["secondary_failed"] = repr(e)
 
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         result["cpu_baseline"] = cpu_baseline(args)
 
-    emit(result)
+    emit(result, full=args.full)
     shard.finish()
 
 

@@ -31,7 +31,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(CBINFER_DIST_BACKEND="gloo", CBINFER_ALLOW_SHARED_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--min-seconds", "0.05", "--mode", "auto"]
+           "--min-seconds", "0.05", "--mode", "auto", "--full"]
     out = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
@@ -65,7 +65,7 @@ def test_bench_control_flow_over_rccl_with_one_rank():
                                                             "CBINFER_DIST_BACKEND")}
     env.update(CBINFER_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-           "--min-seconds", "0.05", "--mode", "auto", "--multi", "0", "--no-variants", "--no-secondary",
+           "--min-seconds", "0.05", "--mode", "auto", "--full", "--multi", "0", "--no-variants", "--no-secondary",
            "--no-isolated", "--no-cpu-baseline", "--no-dense", "--no-pipelined", "--no-last-frame"]
     out = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-3000:]

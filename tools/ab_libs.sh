@@ -10,10 +10,10 @@ trap 'cp tmp_ab/new.so cbinfer_amd/libcbinfer_hip.so' EXIT
 for i in $(seq $R); do
   for v in old new; do
     if [ $v = old ]; then cp tmp_ab/libcbinfer_hip_old.so cbinfer_amd/libcbinfer_hip.so; E="$AB_ENV_OLD"; else cp tmp_ab/new.so cbinfer_amd/libcbinfer_hip.so; E="$AB_ENV_NEW"; fi
-    env $E python bench.py --no-variants --no-isolated --multi 0 --no-pipelined --no-cpu-baseline --no-secondary --no-last-frame --no-dense "$@" 2>/dev/null | tail -1 > /tmp/l.json
+    env $E python bench.py --full --no-variants --no-isolated --multi 0 --no-pipelined --no-cpu-baseline --no-secondary --no-last-frame --no-dense "$@" 2>/dev/null | tail -1 > tmp_ab/line.json
     python - <<PY
 import json
-d=json.load(open("/tmp/l.json"))
+d=json.load(open("tmp_ab/line.json"))
 k=json.load(open("gpurun_out/bench_details.json"))["kernel_trace"]["kernels_as_traced"]
 dd=json.load(open("gpurun_out/bench_details.json"))
 ms=dd.get("multi_sequence") or {}

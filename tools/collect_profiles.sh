@@ -13,15 +13,15 @@ COMMIT=${1:-unknown}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run() { "$@"; rc=$?; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "killed: $*"; exit 1; fi; return $rc; }
-run timeout -k 10 420 python3 $R/bench.py > $O/bench.json 2> $O/bench.err || exit 1
+run timeout -k 10 420 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 echo "bench done"
 run timeout -k 10 420 rocprofv3 --kernel-trace --stats -d $O/stats -o s --output-format csv -- \
-    python3 $R/bench.py --no-cpu-baseline --multi 0 --no-secondary > $O/bench_under_rocprof.json 2> $O/stats.err || exit 1
+    python3 $R/bench.py --full --no-cpu-baseline --multi 0 --no-secondary > $O/bench_under_rocprof.json 2> $O/stats.err || exit 1
 echo "stats done"
 for c in FETCH_SIZE WRITE_SIZE; do
   d=$O/pmc_$(echo $c | tr A-Z a-z | sed 's/_size//')
   run timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d $d -o p --output-format csv -- \
-      python3 $R/bench.py --mode eager --steps 40 --warmup 5 --min-seconds 0 --no-cpu-baseline --no-dense --multi 0 --no-variants --no-last-frame --no-pipelined --no-secondary --no-isolated \
+      python3 $R/bench.py --full --mode eager --steps 40 --warmup 5 --min-seconds 0 --no-cpu-baseline --no-dense --multi 0 --no-variants --no-last-frame --no-pipelined --no-secondary --no-isolated \
       > $d.json 2> $d.err || exit 1
   echo "$c done"
 done

@@ -70,7 +70,7 @@ for label, (_, short, fm, wm) in extra.items():      # second launch of the same
 if out_json:
     import bench
     table["_note"] = ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, counters + kernel trace only; "
-                      "tools/collect_profiles.sh) over `python3 bench.py --mode eager --steps 40 --warmup 5 "
+                      "tools/collect_profiles.sh) over `python3 bench.py --full --mode eager --steps 40 --warmup 5 "
                       "--no-cpu-baseline --no-dense --multi 0`, MI355X.  Per-dispatch medians in KB as reported "
                       "(x1024 = bytes).  FETCH_SIZE counts L2->fabric read requests: bytes still resident in the "
                       "XCD's L2 are not counted, and on gfx950 it under-reports wide 16-B/lane streaming reads by 2x "
