@@ -18,13 +18,12 @@ CBPoolMax2d between them, an optional CBTail1x1 at the end.  Anything else raise
 sequence per stream instead.
 """
 import ctypes
-import os
 
 import torch
 
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, stream_ptr
-from .conv2d import CBConv2d, CBPoolMax2d, CBTail1x1
+from .conv2d import CBConv2d, CBPoolMax2d, CBTail1x1, _switch
 
 
 def _ptr_array(tensors):
@@ -94,7 +93,7 @@ class SequenceBatch(object):
                 pm = prod['m']
                 pK, pC, pkH, pkW = pm.weight.size()
                 L['folded'] = bool(prod['ws'] is not None and m.in_channels == pK and
-                                   os.environ.get('CBINFER_NO_TAILFOLD', '0') != '1' and
+                                   not _switch('CBINFER_NO_TAILFOLD') and
                                    C.cbinfer_split_tail_supported(pC, pK, pkH, pkW, m.hidden_channels, m.out_channels))
                 if L['folded']:
                     st = _lib.SplitTail()
@@ -189,7 +188,7 @@ class SequenceBatch(object):
             if (L['kind'] == 'split' and L.get('pooled') is not None and layers[L['pooled'][0]].get('pairs') and
                     layers[L['pooled'][0]]['K'] == 16 and L['C'] == 16 and L['pooled'][0] == li - 1 and
                     layers[li - 1]['m'].__dict__.get('_fusedNext') is not None and
-                    os.environ.get('CBINFER_NO_NEXTFOLD', '0') != '1'):
+                    not _switch('CBINFER_NO_NEXTFOLD')):
                 P = layers[li - 1]
                 nd = _lib.NextDetect()
                 nd.H, nd.W, nd.kH, nd.kW = L['H'], L['W'], L['kH'], L['kW']

@@ -16,7 +16,9 @@ Two execution modes, chosen per module by `syncIndexes` (default False):
          and the reference-structured op sequence (changeDetection, changeIndexesExtr, genXMatrix,
          matrixMult, updateOutput) of conv2d_cg.py is what runs.
 """
+import contextlib
 import ctypes
+import functools
 import math
 import os
 
@@ -35,7 +37,80 @@ def _same_shape(t, shape):
     return t is not None and tuple(t.size()) == tuple(shape)
 
 
-_NO_CHAIN = os.environ.get('CBINFER_NO_CHAIN', '0') == '1'
+@functools.lru_cache(maxsize=None)
+def _split_fits(Cin, K, kH, kW, H, W):
+    """The shape-only part of the split-state tests: the library takes the layer, the frame mask fits its records."""
+    return (bool(C.cbinfer_split_supported(Cin, K, kH, kW)) and
+            C.cbinfer_mask_words(H, W) <= C.cbinfer_split_max_mask_words(K) and H * W * W < (1 << 32))
+
+
+# Every CBINFER_* switch the Python package reads: name -> (default, what it does); a bool switch is on when set to '1'.
+# They are read through _switch() when a frame takes the general path, so a test may flip one in mid-run; a call plan
+# replayed instead looks only at the switches of its own path (the split-state plans: _split_switches()).
+# CBINFER_NO_CHAIN is read once, at import; shard.py reads the last two itself.
+SWITCHES = {
+    'CBINFER_ARITH': ('x3', "fp32 split-state arithmetic: 'x3' (bf16 triples), 'f16x2'; else the list kernels"),
+    'CBINFER_EXACT_F32': (False, "every fp32 layer on the exact f32 fma chain, as exactF32=True"),
+    'CBINFER_NO_SPLIT': (False, "no split-state frames (fp32 and fp16)"),
+    'CBINFER_NO_SPLIT_FG': (False, "no fine-grained frames on the split-state kernels"),
+    'CBINFER_SPLIT_MINK': (0, "fewest output channels of an fp32 split-state layer"),
+    'CBINFER_SPLIT_MAXK': (100000, "most output channels of an fp32 split-state layer"),
+    'CBINFER_NO_HSPLIT': (False, "no fp16 split-state frames"),
+    'CBINFER_HSPLIT_DEEP': (True, "fp16 split-state frames also for contractions of 48 k-stages and more"),
+    'CBINFER_NO_SELFCOMPACT': (False, "no self-compacting frames: detection, compaction and contraction apart"),
+    'CBINFER_NO_ROWCONV': (False, "no row-segment contraction (cb_rowconv.hip)"),
+    'CBINFER_ROWCONV_MAXK': (16, "most output channels of a row-segment layer"),
+    'CBINFER_NO_BLOCKCONV': (False, "no patch-staged block contraction (cb_blockconv.hip)"),
+    'CBINFER_BLOCKCONV_MAXK': (64, "most output channels of a block-contraction layer"),
+    'CBINFER_NO_ROWPAIRS': (False, "row-segment layers on cb_rowconv.hip instead of the row-pair kernel"),
+    'CBINFER_NO_PAIRDET': (False, "a row-pair layer's change detection in a launch of its own"),
+    'CBINFER_NO_NEXTFOLD': (False, "no consumer's change detection inside its producer's launch"),
+    'CBINFER_NO_TAILFOLD': (False, "a fused 1x1 tail in a launch of its own"),
+    'CBINFER_NO_WINFOLD': (False, "split-state producers stay in pixel order (no window-order fold)"),
+    'CBINFER_NO_FASTPATH': (False, "no per-frame call plans: every frame takes the general path"),
+    'CBINFER_NO_CHAINMASK': (False, "chained fp16 layers test every pixel, not only their producer's changed ones"),
+    'CBINFER_NO_CHAIN': (False, "no chained frames (cbinfer_cbconv2d_forward_after); read at import"),
+    'CBINFER_DIST_BACKEND': (None, "torch.distributed backend of shard.py (default: nccl on GPUs, else gloo)"),
+    'CBINFER_FORCE_DIST': (False, "shard.py makes a process group also for one rank"),
+}
+
+
+# (os.environ's own table: os.environ.get raises and catches a KeyError for every unset name -- about 1.3 us against
+#  0.1 us for this lookup -- and the split-state plans read six switches twice per layer and frame.  Do not go back to
+#  os.environ.get here: it costs some 15 us per layer and frame.)
+_ENVIRON, _ENV_KEYS = os.environ._data, {name: os.environ.encodekey(name) for name in SWITCHES}
+_SPLIT_KEYS = tuple(_ENV_KEYS[name] for name in ('CBINFER_ARITH', 'CBINFER_EXACT_F32', 'CBINFER_NO_SPLIT',
+                                                 'CBINFER_SPLIT_MINK', 'CBINFER_SPLIT_MAXK', 'CBINFER_NO_SELFCOMPACT'))
+
+
+def _switch(name):
+    default = SWITCHES[name][0]
+    value = _ENVIRON.get(_ENV_KEYS[name])
+    if value is None:
+        return default
+    value = os.environ.decodevalue(value)
+    if default is True or default is False:
+        return value == '1'
+    return int(value) if type(default) is int else value
+
+
+def _split_switches():
+    """The raw values of the switches CBConv2d._split_ok reads: what a fast path that assumes its answer compares."""
+    return tuple(map(_ENVIRON.get, _SPLIT_KEYS))
+
+
+@contextlib.contextmanager
+def _switch_set(name, value):
+    """Set a switch for the duration of a with-block."""
+    saved = os.environ.get(name)
+    os.environ[name] = value
+    try:
+        yield
+    finally:
+        os.environ.pop(name) if saved is None else os.environ.update({name: saved})
+
+
+_NO_CHAIN = _switch('CBINFER_NO_CHAIN')
 
 
 def _no_tag():
@@ -100,18 +175,12 @@ class CBPoolMax2d(nn.Module):
         self.kernel_size = ks
         self.ceil_mode = m.ceil_mode
         self.propChangeIndexes = False
-        # reference behaviour (conv2d.py:73): hand out a private copy of the state every frame.  With
-        # cloneOutput=False the state tensor itself is returned (tagged, so that a consumer about to
-        # keep a reference to it -- CBConv2d with copyInput=False -- takes its copy then); this removes
-        # one full-tensor copy per frame when the consumer copies or feeds back anyway.
+        # True: a private copy of the state every frame (conv2d.py:73); False: the state itself, tagged, so that a
+        # consumer that keeps a reference to it (copyInput=False) copies it then
         self.cloneOutput = True
-        # reference behaviour (conv2d.py:80-83): with propChangeIndexes the INPUT-resolution list is
-        # handed on as it came in.  downsampleIndexes=True hands on the list of changed OUTPUT pixels
-        # instead, which is what a consumer working at the pooled resolution needs.
+        # True: hand on the list of changed OUTPUT pixels instead of the input-resolution one (conv2d.py:80-83)
         self.downsampleIndexes = False
-        # lazy=True (set by fusePoolingIntoDetection when the consumer is a feedback-mode CBConv2d): do
-        # not pool at all, hand the consumer a LazyPool; it computes the pooled values inside its change
-        # detection.  One launch less per pool and frame, identical results.
+        # True (fusePoolingIntoDetection): hand the consumer a LazyPool; it pools inside its change detection
         self.lazy = False
         self.register_buffer('outputState', torch.zeros(0))
         self.clearMemory()
@@ -122,30 +191,22 @@ class CBPoolMax2d(nn.Module):
         self.outputState = self.outputState.new_zeros(0)
 
     def getStateTensors(self):
-        state = []
-        if hasattr(self, 'outputState'):
-            state += [self.outputState]
-        return state
+        return [self.outputState] if hasattr(self, 'outputState') else []
 
     def forward(self, inp):
         assert type(inp) == tuple and inp[0] == 'changeIndexes'
         input = inp[1].detach().contiguous()
         changeIndexes = inp[2]
         require_device(input)
+        nc, h, w = input.size(-3), input.size(-2), input.size(-1)
+        oh, ow = ((h - 1) // 2 + 1, (w - 1) // 2 + 1) if self.ceil_mode else (h // 2, w // 2)
         if getattr(self, 'lazy', False) and not self.propChangeIndexes:
-            nc, h, w = input.size(-3), input.size(-2), input.size(-1)
-            oh, ow = ((h - 1) // 2 + 1, (w - 1) // 2 + 1) if self.ceil_mode else (h // 2, w // 2)
             return LazyPool(input, (1, nc, oh, ow), self.ceil_mode, changeIndexes)
         exact = isinstance(changeIndexes, torch.Tensor)
         if exact:
             changeIndexes = changeIndexes.detach().contiguous()
             assert changeIndexes.dim() == 1
         if not exact or changeIndexes.numel() != 0:
-            nc, h, w = input.size(-3), input.size(-2), input.size(-1)
-            if self.ceil_mode:
-                oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-            else:
-                oh, ow = h // 2, w // 2
             if (not _same_shape(self.outputState, (1, nc, oh, ow)) or
                     self.outputState.dtype != input.dtype or self.outputState.device != input.device):
                 self.outputState = torch.full((1, nc, oh, ow), float('inf'), dtype=input.dtype,
@@ -204,11 +265,9 @@ class CBConv2d(nn.Module):
         self.finegrained = False
         self.copyInput = True
         self.feedbackLoop = False
-        # Extension: a layer fed propagated change indexes skips its own change detection whatever its
-        # filter size and recomputes exactly the listed pixels (conv2d.py:180-190, :220) -- right for 1x1, short of
-        # the filter's reach for k > 1 (the reference's behaviour, kept as the default).  True: the incoming list is
-        # dilated by the filter support on the device first (cbinfer_dilate_change_indexes): every output pixel a
-        # listed input pixel reaches is recomputed, which is what the layer's own detection would have found.
+        # Extension: a layer fed propagated change indexes recomputes exactly the listed pixels (the reference's
+        # behaviour, conv2d.py:180-190 -- short of the filter's reach for k > 1).  True: the list is first dilated by
+        # the filter support on the device (cbinfer_dilate_change_indexes), as the layer's own detection would find.
         self.dilatePropagatedIndexes = False
         self._setDefaultValues()
 
@@ -233,18 +292,12 @@ class CBConv2d(nn.Module):
         self._lastIndexes = None
 
     def getStateTensors(self):
-        state = []
-        if hasattr(self, 'prevInput'):
-            state += [self.prevInput]
-        if hasattr(self, 'prevOutput'):
-            state += [self.prevOutput]
-        return state
+        return [getattr(self, n) for n in ('prevInput', 'prevOutput') if hasattr(self, n)]
 
     def _setDefaultValues(self):
         # back-fill attributes missing in modules pickled by older versions (conv2d.py:292-304)
-        for name, val in (('saveChangeMap', False), ('propChangeIndexes', False),
-                          ('gatherComputationStats', False), ('finegrained', False),
-                          ('copyInput', True), ('feedbackLoop', False), ('syncIndexes', False),
+        for name, val in (('saveChangeMap', False), ('propChangeIndexes', False), ('gatherComputationStats', False),
+                          ('finegrained', False), ('copyInput', True), ('feedbackLoop', False), ('syncIndexes', False),
                           ('deterministicFG', False), ('atomicFG', False), ('fgInPlace', False), ('exactF32', False),
                           ('dilatePropagatedIndexes', False), ('_work', None), ('_wprep', None),
                           ('_inputIsLiveState', False), ('_plan', None), ('_wrows', None), ('_lastIndexes', None)):
@@ -253,11 +306,7 @@ class CBConv2d(nn.Module):
 
     def __getstate__(self):
         d = dict(self.__dict__)
-        d['_work'] = None     # transient device buffers are not serialised
-        d['_wprep'] = None
-        d['_plan'] = None
-        d['_wrows'] = None
-        d['_lastIndexes'] = None
+        d.update(_work=None, _wprep=None, _plan=None, _wrows=None, _lastIndexes=None)      # (transient device buffers)
         return d
 
     def lastChangeIndexes(self):
@@ -266,64 +315,60 @@ class CBConv2d(nn.Module):
         return self._lastIndexes
 
     def invalidateWeights(self):
-        """Forget the cached re-laid-out copies of the filter bank and the per-frame call plan.  They are
-        refreshed on their own when the Parameter object or its version counter changes; a write through
-        `weight.data` (the reference's own idiom) bumps neither, so call this after one."""
+        """Forget the cached re-laid-out copies of the filter bank and the call plan -- after a write through
+        `weight.data`, which bumps neither the Parameter object nor its version counter."""
         self._wprep = self._wrows = self._plan = None
 
     def _rows_path(self, dtype, H, W):
-        """Which mask-driven contraction, if any, runs this layer's sync-free fp32 frame (no int8 mask copy):
-          'rows'    cb_rowconv.hip, at most 16 output channels (3->16 7x7: 15 us in the frame against the list
-                    kernel's 21 on MI355X at 480x320 @10 %);
-          'blocks'  cb_blockconv.hip (bf16x3 arithmetic, so not with exactF32), 17..64 output channels
-                    (16->64 7x7: 19 us stand-alone against 27); wider layers stay on the list kernel, whose
-                    64-pixel tiles reuse the streamed weights better while few pixels change;
-          None      the list kernel (cb_conv.hip).
-        CBINFER_NO_ROWCONV=1 / CBINFER_NO_BLOCKCONV=1 switch a kernel off, CBINFER_BLOCKCONV_MAXK moves the bound."""
+        """Which mask-driven contraction, if any, runs this layer's sync-free fp32 frame (no int8 mask copy): 'rows'
+        (cb_rowconv.hip, at most 16 output channels), 'blocks' (cb_blockconv.hip, bf16x3 arithmetic, 17..64 output
+        channels) or None: the list kernel (cb_conv.hip), whose 64-pixel tiles reuse the weights better beyond."""
         K, Cin, kH, kW = self.weight.size()
-        if (dtype != torch.float32 or self.syncIndexes or self.saveChangeMap or
-                os.environ.get('CBINFER_NO_SELFCOMPACT', '0') == '1'):
+        if dtype != torch.float32 or self.syncIndexes or self.saveChangeMap or _switch('CBINFER_NO_SELFCOMPACT'):
             return None
-        if (K <= int(os.environ.get('CBINFER_ROWCONV_MAXK', '16')) and
-                os.environ.get('CBINFER_NO_ROWCONV', '0') != '1' and C.cbinfer_rowconv_supported(Cin, K, kH, kW)):
+        if (K <= _switch('CBINFER_ROWCONV_MAXK') and not _switch('CBINFER_NO_ROWCONV') and
+                C.cbinfer_rowconv_supported(Cin, K, kH, kW)):
             return 'rows'
-        if (K <= int(os.environ.get('CBINFER_BLOCKCONV_MAXK', '64')) and self._arith_code(dtype) == _lib.CB_F32S and
-                os.environ.get('CBINFER_NO_BLOCKCONV', '0') != '1' and
-                C.cbinfer_blockconv_supported(Cin, K, kH, kW)):
+        if (K <= _switch('CBINFER_BLOCKCONV_MAXK') and self._arith_code(dtype) == _lib.CB_F32S and
+                not _switch('CBINFER_NO_BLOCKCONV') and C.cbinfer_blockconv_supported(Cin, K, kH, kW)):
             return 'blocks'
         return None
 
-    def _masked_call(self, path):
-        """(library entry point, prepared weights) of a mask-driven path."""
+    def _relaid(self, key, nbytes, prep, extra=lambda w: ()):
+        """(buffer, *extra(weights)): the filter bank re-laid out for one kernel family by prep(weights, buffer, K, Cin,
+        kH, kW, *extra(weights), stream) into nbytes(Cin, K, kH, kW) bytes.  One such copy at a time, made again when the
+        weights or `key` change; `extra` is evaluated only then."""
         w = self.weight
-        key = (path, w.data_ptr(), w._version, w.device)
+        key = key + (w.data_ptr(), w._version, w.device)
         if self._wrows is None or self._wrows[0] != key:
             K, Cin, kH, kW = w.size()
-            if path == 'rows':
-                nbytes, prep = C.cbinfer_rowconv_prepared_bytes(Cin, K, kH, kW), C.cbinfer_rowconv_prep_weights
-            else:
-                nbytes, prep = C.cbinfer_blockconv_prepared_bytes(Cin, K, kH, kW), C.cbinfer_blockconv_prep_weights
-            wp = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-            check(prep(ptr(w.detach().contiguous()), ptr(wp), K, Cin, kH, kW, stream_ptr(w)))
-            self._wrows = (key, wp)
-        fn = C.cbinfer_cbconv2d_forward_rows if path == 'rows' else C.cbinfer_cbconv2d_forward_blocks
-        return fn, self._wrows[1]
+            more = tuple(extra(w))
+            wp = torch.empty(nbytes(Cin, K, kH, kW), dtype=torch.uint8, device=w.device)
+            check(prep(ptr(w.detach().contiguous()), ptr(wp), K, Cin, kH, kW, *more, stream_ptr(w)))
+            self._wrows = (key, wp) + more
+        return self._wrows[1:]
+
+    def _masked_call(self, path):
+        """(library entry point, prepared weights) of a mask-driven path."""
+        if path == 'rows':
+            return C.cbinfer_cbconv2d_forward_rows, self._relaid(
+                ('rows',), C.cbinfer_rowconv_prepared_bytes, C.cbinfer_rowconv_prep_weights)[0]
+        return C.cbinfer_cbconv2d_forward_blocks, self._relaid(
+            ('blocks',), C.cbinfer_blockconv_prepared_bytes, C.cbinfer_blockconv_prep_weights)[0]
 
     def _pairs_ok(self, H, W):
         """Does the row-segment frame of this layer run on the row-PAIR kernel (cb_rowpair.hip: persistent over the
         non-empty (row pair, mask word) units, and able to do the next layer's pooled detection)?  Feedback mode, at
         most 4 input and 16 output channels, 3x3 / 5x5 / 7x7; CBINFER_NO_ROWPAIRS=1 switches it off."""
         K, Cin, kH, kW = self.weight.size()
-        return (self.feedbackLoop and os.environ.get('CBINFER_NO_ROWPAIRS', '0') != '1' and
+        return (self.feedbackLoop and not _switch('CBINFER_NO_ROWPAIRS') and
                 bool(C.cbinfer_rowpairs_supported(Cin, K, kH, kW, H, W)))
 
     def _pair_detect_ok(self, nxt, kH):
-        """Does this row-pair layer run its own change detection inside its launch (cbinfer_conv_rowpairs_detect, round 6)?
-        Only while the consumer behind the pool takes the detection of ITS input from this launch (nxt) and its last frame
-        ran a contraction that can carry this layer's state refresh on its idle workgroups (cbinfer_split_conv_next_refresh
-        in window order, cbinfer_split_conv_refresh in pixel order).
-        CBINFER_NO_PAIRDET=1 switches the form off."""
-        if nxt is None or kH != 7 or os.environ.get('CBINFER_NO_PAIRDET', '0') == '1':
+        """Does this row-pair layer run its own change detection inside its launch (cbinfer_conv_rowpairs_detect)?  Only
+        while the consumer behind the pool takes its detection from this launch (nxt) and its last frame ran a contraction
+        that can carry this layer's state refresh on idle workgroups (cbinfer_split_conv_[next_]refresh)."""
+        if nxt is None or kH != 7 or _switch('CBINFER_NO_PAIRDET'):
             return False
         link = self.__dict__.get('_fusedNext')
         cons = link[1] if link is not None else None
@@ -335,17 +380,14 @@ class CBConv2d(nn.Module):
         the state buffers and the threshold.  None while this layer cannot take such a detection (no split-state frame
         yet, a state that was written from outside and must be re-split, a threshold that differs from last frame's)."""
         sp = self._work.get('split') if self._work else None
-        if sp is None or sp['stateKey'] is None:
-            return None
         prev = self._buffers['prevInput']
-        if sp['stateKey'] != (prev.data_ptr(), prev._version):
+        if (sp is None or sp['stateKey'] != (prev.data_ptr(), prev._version) or self.__dict__.get('_rangeFallback') or
+                self.__dict__.get('_pmaskThreshold') != float(self.threshold)):
             return None
-        th = float(self.threshold)
-        if self.__dict__.get('_pmaskThreshold') != th or self.__dict__.get('_rangeFallback'):
-            return None
-        return (id(self), prev.data_ptr(), sp['S'].data_ptr(), sp['bits'].data_ptr(), th, sp['arith'])
+        return self._split_token(sp, prev)
 
-    def _detect_token_with(self, sp, prev):
+    def _split_token(self, sp, prev):
+        """The detection token of this layer's split-state frame (state buffers, threshold, arithmetic)."""
         return (id(self), prev.data_ptr(), sp['S'].data_ptr(), sp['bits'].data_ptr(), float(self.threshold),
                 sp['arith'])
 
@@ -353,42 +395,39 @@ class CBConv2d(nn.Module):
         """(cbNextDetect, token) if this layer's row-pair launch can also be the pooled change detection of the layer
         behind the following CBPoolMax2d (pycbinfer.fuseDetectionIntoProducer), else (None, None)."""
         link = self.__dict__.get('_fusedNext')
-        if (link is None or self.__dict__.get('_noNextFold') or os.environ.get('CBINFER_NO_NEXTFOLD', '0') == '1'):
+        if link is None or self.__dict__.get('_noNextFold') or _switch('CBINFER_NO_NEXTFOLD'):
             return None, None
         pool, cons = link
-        # (per-frame fast path: the consumer's token and the flags the full test below looks at are what they were when the
-        #  structure was made -- this function runs once per frame and producer inside the call plans)
+        if type(cons) is not CBConv2d:
+            return None, None
+        # (runs every frame inside the call plans: the outcome is reused while every input of the test below is what it
+        #  was -- the consumer's state and threshold by its token, everything else, both sides, by `key`)
+        w, w2, prev2 = self._parameters['weight'], cons._parameters['weight'], cons._buffers.get('prevInput')
+        key = (getattr(pool, 'lazy', False), pool.propChangeIndexes, pool.ceil_mode, cons.feedbackLoop, cons.copyInput,
+               cons.syncIndexes, cons.saveChangeMap, cons.gatherComputationStats, cons.finegrained, cons.exactF32,
+               w2.dtype, w2.shape, None if prev2 is None else (prev2.shape, prev2.device), H, W, _split_switches(),
+               w.shape[0], w.device)
+        tok = cons._detect_token()
         nd = self.__dict__.get('_nextStruct')
-        if nd is not None and type(cons) is CBConv2d:
-            flags = (getattr(pool, 'lazy', False), pool.propChangeIndexes, cons.feedbackLoop, cons.syncIndexes,
-                     cons.saveChangeMap, cons.gatherComputationStats, cons.finegrained, H, W)
-            if len(nd) > 2 and nd[2] == flags and nd[0] == cons._detect_token():
-                return nd[1], nd[0]
-        K = self.weight.size(0)
-        if (not getattr(pool, 'lazy', False) or pool.propChangeIndexes or type(cons) is not CBConv2d or
-                cons.in_channels != K or not cons.feedbackLoop or cons.syncIndexes or cons.saveChangeMap or
-                cons.gatherComputationStats or cons.finegrained or cons.weight.dtype != torch.float32):
+        if nd is not None and nd[0] == tok and nd[2] == key:
+            return nd[1], tok
+        K = w.size(0)
+        if (not key[0] or pool.propChangeIndexes or cons.in_channels != K or not cons.feedbackLoop or cons.syncIndexes or
+                cons.saveChangeMap or cons.gatherComputationStats or cons.finegrained or w2.dtype != torch.float32):
             return None, None
         H2, W2 = ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if pool.ceil_mode else (H // 2, W // 2)
-        prev2 = cons._buffers.get('prevInput')
-        if (prev2 is None or tuple(prev2.shape) != (1, K, H2, W2) or prev2.device != self.weight.device or
-                not cons._split_ok(torch.float32, H2, W2)):
+        if (prev2 is None or tuple(prev2.shape) != (1, K, H2, W2) or prev2.device != w.device or
+                not cons._split_ok(torch.float32, H2, W2) or tok is None):
             return None, None
-        tok = cons._detect_token()
-        if tok is None:
-            return None, None
-        nd = self.__dict__.get('_nextStruct')
         if nd is None or nd[0] != tok:
             sp = cons._work['split']
             st = _lib.NextDetect()
             st.state, st.splitState, st.frameMasks = prev2.data_ptr(), sp['S'].data_ptr(), sp['bits'].data_ptr()
             st.rangeFlag, st.H, st.W = sp['flag'].data_ptr(), H2, W2
-            st.kH, st.kW, st.threshold = cons.weight.size(2), cons.weight.size(3), float(cons.threshold)
+            st.kH, st.kW, st.threshold = w2.size(2), w2.size(3), float(cons.threshold)
             st.arith = 1 if sp['arith'] == 'x3' else 0
             nd = (tok, st)
-        flags = (getattr(pool, 'lazy', False), pool.propChangeIndexes, cons.feedbackLoop, cons.syncIndexes,
-                 cons.saveChangeMap, cons.gatherComputationStats, cons.finegrained, H, W)
-        nd = self.__dict__['_nextStruct'] = (nd[0], nd[1], flags)
+        self.__dict__['_nextStruct'] = (tok, nd[1], key)
         return nd[1], tok
 
     def _rows_workspace(self, work, H, W, dev):
@@ -401,27 +440,22 @@ class CBConv2d(nn.Module):
 
     @staticmethod
     def _split_arith():
-        """Arithmetic of the split-state kernels for fp32 layers (CBINFER_ARITH): 'x3' (default, round 5) -- bf16
-        TRIPLES: every f32 operand exactly, six term products, f32 accumulation: f32-equivalent, what
-        conv2d_cg.py:342-349's sgemm multiplies --, or 'f16x2' -- f16 PAIRS, 22-23 significant bits per operand, three
-        products (rounds 3-4's default, narrower than f32).  Any other value ('bf16x3') keeps the layer on rounds 1-2's
-        list / patch-staged kernels.  Returns 'x3', 'f16x2' or None."""
-        a = os.environ.get('CBINFER_ARITH', 'x3')
+        """Arithmetic of the split-state kernels for fp32 layers (CBINFER_ARITH): 'x3' (default: bf16 triples, every f32
+        operand exactly, f32-equivalent) or 'f16x2' (f16 pairs, 22-23 significant bits per operand); None for any
+        other value ('bf16x3'), which keeps the layer on the list / patch-staged kernels."""
+        a = _switch('CBINFER_ARITH')
         return a if a in ('x3', 'f16x2') else None
 
     def _arith_code(self, dtype):
         if dtype == torch.float16:
             return _lib.CB_F16
-        if not self.exactF32 and os.environ.get('CBINFER_EXACT_F32', '0') != '1':
+        if not self.exactF32 and not _switch('CBINFER_EXACT_F32'):
             return _lib.CB_F32S
         return _lib.CB_F32
 
     def _arith(self, t):
-        """Arithmetic code of the fused contraction for the library's list / patch-staged kernels: fp16 as is; fp32 as
-        split products on the 16-bit MFMA (CB_F32S: bf16x3 there -- three bf16 terms per operand, the six cross
-        products above 2^-24, f32 accumulation; the split-state kernels, which this code also admits (_split_ok), use
-        f16 pairs instead: 22-23 significant bits per operand, three products) unless exactF32 asks for the exact f32
-        fma chain on the f32 MFMA (CB_F32)."""
+        """Arithmetic code of the list / patch-staged kernels: fp16 as is; fp32 as split bf16x3 products on the 16-bit
+        MFMA (CB_F32S, which also admits the split-state kernels) unless exactF32 asks for the f32 MFMA (CB_F32)."""
         dtype_code(t)     # (rejects anything but fp32 / fp16)
         return self._arith_code(t.dtype)
 
@@ -434,22 +468,21 @@ class CBConv2d(nn.Module):
 
     # ---------------------------------------------------------------- split-state frame (cb_split.hip)
     def _split_ok(self, dtype, H, W):
-        """Does this layer's sync-free frame run on the split-state kernels (cbinfer_split_forward)?  fp32,
-        feedback mode (the pre-split copy of the state is refreshed at the changed pixels), 16/32/64 input
-        channels, default arithmetic (f16-pair products; exactF32 / CBINFER_ARITH=bf16x3 keep the other forms);
-        CBINFER_NO_SPLIT=1 switches it off."""
+        """Does this layer's sync-free frame run on the split-state kernels (cbinfer_split_forward)?  fp32 in the split
+        products' arithmetic, a layer that keeps its input (feedback or copy), a shape the library takes."""
+        K = self.weight.size(0)
+        return ((self.feedbackLoop or self.copyInput) and not self.syncIndexes and not self.saveChangeMap
+                and not self.finegrained and self._split_kernels_ok(dtype, H, W)
+                and _switch('CBINFER_SPLIT_MINK') <= K <= _switch('CBINFER_SPLIT_MAXK')
+                and not _switch('CBINFER_NO_SELFCOMPACT'))
+
+    def _split_kernels_ok(self, dtype, H, W):
+        """What both split-state frames need: fp32 in the split products' arithmetic, the library takes the shape."""
         K, Cin, kH, kW = self.weight.size()
-        return (dtype == torch.float32 and (self.feedbackLoop or self.copyInput)
-                and not self.syncIndexes and not self.saveChangeMap
-                and not self.finegrained and self._arith_code(dtype) == _lib.CB_F32S
+        return (dtype == torch.float32 and self._arith_code(dtype) == _lib.CB_F32S
                 and (not self.__dict__.get('_rangeFallback') or self._split_arith() == 'x3')
-                and os.environ.get('CBINFER_NO_SPLIT', '0') != '1'
-                and int(os.environ.get('CBINFER_SPLIT_MINK', '0')) <= K <= int(os.environ.get('CBINFER_SPLIT_MAXK', '100000'))
-                and self._split_arith() is not None
-                and os.environ.get('CBINFER_NO_SELFCOMPACT', '0') != '1'
-                and bool(C.cbinfer_split_supported(Cin, K, kH, kW))
-                and C.cbinfer_mask_words(H, W) <= C.cbinfer_split_max_mask_words(K)
-                and H * W * W < (1 << 32))
+                and not _switch('CBINFER_NO_SPLIT') and self._split_arith() is not None
+                and _split_fits(Cin, K, kH, kW, H, W))
 
     def _hsplit_ok(self, dtype, H, W):
         """Does this fp16 layer's sync-free frame run on the split-state machinery (cbinfer_hsplit_forward: pixel-major
@@ -458,25 +491,20 @@ class CBConv2d(nn.Module):
         K, Cin, kH, kW = self.weight.size()
         return (dtype == torch.float16 and (self.feedbackLoop or self.copyInput)
                 and not self.syncIndexes and not self.saveChangeMap and not self.finegrained
-                and os.environ.get('CBINFER_NO_SPLIT', '0') != '1' and os.environ.get('CBINFER_NO_HSPLIT', '0') != '1'
-                and os.environ.get('CBINFER_NO_SELFCOMPACT', '0') != '1'
+                and not _switch('CBINFER_NO_SPLIT') and not _switch('CBINFER_NO_HSPLIT')
+                and not _switch('CBINFER_NO_SELFCOMPACT')
                 and bool(C.cbinfer_hsplit_supported(Cin, K, kH, kW))
-                # (deep contractions -- 48 k-stages and more: 7x7 on 128 channels, 3x3 on 512 -- are taken since round 5:
-                #  on a network whose deep layers do change they are the bulk of the work, and with few tiles the kernel
-                #  cuts their depth into 8 or 16 chunks; rounds 4's artefact of random weights -- 31 idle layers, where the
-                #  second launch of a deep contraction only cost -- had kept them off: CBINFER_HSPLIT_DEEP=0 does that again.
-                #  Channels that are not a multiple of 64 are padded (OpenPose's 185 -> 192); up to a quarter of padding.)
-                and (kH * kW * ((Cin + 63) // 64) < 48 or os.environ.get('CBINFER_HSPLIT_DEEP', '1') == '1')
+                # (deep contractions, 48 k-stages and more, unless CBINFER_HSPLIT_DEEP=0; channels padded to a multiple
+                #  of 64 -- OpenPose's 185 -> 192 -- by up to a quarter)
+                and (kH * kW * ((Cin + 63) // 64) < 48 or _switch('CBINFER_HSPLIT_DEEP'))
                 and 4 * ((Cin + 63) // 64 * 64 - Cin) <= (Cin + 63) // 64 * 64
                 and C.cbinfer_mask_words(H, W) <= C.cbinfer_hsplit_max_mask_words(K)
                 and C.cbinfer_hsplit_state_bytes(Cin, H, W, kH, kW) < (1 << 31) and H * W * W < (1 << 32))
 
     def _forward_hsplit(self, input, work, lazy=None):
-        """One fp16 frame on the split-state machinery: detection + refresh of prevInput and of its pixel-major copy,
-        then the LDS-DMA contraction -- whose launch also runs the change detection of the layers that consume this
-        layer's output (pycbinfer.fuseDetectionIntoProducer; round 6), and whose own detection is skipped when the
-        PRODUCING layer's launch did it.  `lazy`: the layer sits behind a CBPoolMax2d folded into its detection --
-        `input` is the pool's INPUT, the layer runs at the pooled size."""
+        """One fp16 frame on the split-state machinery: detection + refresh of the state and its pixel-major copy, then
+        the contraction, whose launch may also run its consumers' detection (and whose own detection is skipped when its
+        producer's launch did it).  `lazy`: behind a folded CBPoolMax2d, `input` is the pool's input."""
         K, Cin, kH, kW = self.weight.size()
         H, W = (lazy.outSize[-2], lazy.outSize[-1]) if lazy is not None else (input.size(-2), input.size(-1))
         dev = input.device
@@ -490,7 +518,8 @@ class CBConv2d(nn.Module):
                 copy=torch.zeros(C.cbinfer_mask_words(H, W), dtype=torch.int64, device=dev),
                 ws=torch.zeros(wsBytes, dtype=torch.uint8, device=dev) if wsBytes > 0 else None, stateKey=None,
                 layer=(_lib.HalfLayer * 1)())
-        wp = self._hsplit_weights(H, W)
+        wp = self._relaid(('hsplit', H, W), C.cbinfer_hsplit_prepared_bytes, C.cbinfer_hsplit_prep_weights,
+                          lambda w: (H, W))[0]
         prev = self.prevInput
         if not prev.is_contiguous():
             prev = self.prevInput = prev.contiguous()
@@ -501,16 +530,10 @@ class CBConv2d(nn.Module):
             # copy is made again from it
             check(C.cbinfer_hsplit_state_rebuild(ptr(prev), ptr(hs['S']), Cin, H, W, kH, kW, stream_ptr(input)))
             hs['stateKey'] = stateKey
-        # (the producer-mask shortcut assumes the skipped segments compared below THIS threshold last frame and a
-        #  state that has seen every pixel: not on a fresh or restored state, not after a change of the threshold)
-        sameTh = self.__dict__.get('_pmaskThreshold') == float(self.threshold)
-        self.__dict__['_pmaskThreshold'] = float(self.threshold)
-        pmask = None
-        if lazy is not None:
-            pmask = None if (rebuilt or not sameTh) else lazy.producerMask()
-        elif not rebuilt and sameTh:
-            pmask = self._chain_mask(H, W)      # (round 5: a chained layer skips the segments its producer left alone)
         pooled = lazy is not None
+        ok = self._pmask_ok(rebuilt)
+        # (round 5: a chained layer skips the segments its producer left alone)
+        pmask = (lazy.producerMask() if pooled else self._chain_mask(H, W)) if ok else None
         L = hs['layer'][0]
         L.upstreamCount, L.input, L.producerMask = None, ptr(input), ptr(pmask)
         L.state, L.pixelState, L.frameMasks = ptr(prev), ptr(hs['S']), ptr(hs['bits'])
@@ -519,7 +542,7 @@ class CBConv2d(nn.Module):
         L.K, L.threshold, L.relu = K, float(self.threshold), int(bool(self.withReLU))
         # this layer's own detection: done by the producing layer's launch?  (never on a fresh / restored state, after a
         # change of the threshold, or behind a pool)
-        mine = None if (rebuilt or not sameTh or pooled) else self._half_token(hs, prev)
+        mine = self._half_token(hs, prev) if (ok and not pooled) else None
         L.detect = 0 if (mine is not None and self._detected_upstream(mine)) else 1
         tokens = self._fill_consumers(L, H, W)
         args = [hs['layer'], 1, int(pooled), input.size(-2) if pooled else 0, input.size(-1) if pooled else 0,
@@ -531,40 +554,25 @@ class CBConv2d(nn.Module):
             self._make_plan(pooled, input, C.cbinfer_hsplit_forward_group, args, None, pmask=ptr(pmask))
             if self._plan is not None:
                 self._plan.update(hsplit=True, chain=True, stateVersion=prev._version, checkPmask=pooled,
-                                  layer=L, size=(H, W), hs=hs, nextTokens=tokens)
-        result = MaskChangeIndexes(hs['copy'], (H, W), work['idx'], work['count'], made=True)
+                                  layer=L, size=(H, W), hs=hs)
+        self._lastIndexes = MaskChangeIndexes(hs['copy'], (H, W), work['idx'], work['count'], made=True)
         if self._plan is not None:
-            self._plan['indexes'] = result
-        return result
+            self._plan['indexes'] = self._lastIndexes
+        return self._emit(self._lastIndexes)
 
-    def _hsplit_weights(self, H, W):
-        w = self.weight
-        K, Cin, kH, kW = w.size()
-        key = ('hsplit', w.data_ptr(), w._version, w.device, H, W)
-        if self._wrows is None or self._wrows[0] != key:
-            wp = torch.empty(C.cbinfer_hsplit_prepared_bytes(Cin, K, kH, kW), dtype=torch.uint8, device=w.device)
-            check(C.cbinfer_hsplit_prep_weights(ptr(w.detach().contiguous()), ptr(wp), K, Cin, kH, kW, H, W,
-                                                stream_ptr(w)))
-            self._wrows = (key, wp)
-        return self._wrows[1]
-
-    # ---- the change detection of an fp16 layer inside the launch of the layer that PRODUCES its input (round 6) ----
-    # The reference chains layers through their state tensors: a CBConv2d's input is the prevOutput of the one in front
-    # (conv2d.py:259), and with propChangeIndexes the producer's change list travels along (:180-186, :256-259).  A
-    # consumer in copy mode (feedbackLoop = False, copyInput = True) compares every value of that buffer with its
-    # prevInput -- a copy of last frame's buffer -- so only the pixels the producer just recomputed can trigger, and the
-    # producer's launch can do the whole detection for them (cb_split.hip: the fp16 epilogue / cbh_reduce_kernel).  What
-    # makes that exact is checked on the host every frame, from both sides, with a token that names the consumer's
-    # state buffers and threshold: the PRODUCER folds a consumer in only if that consumer's last frame consumed this
-    # producer's last frame from this very buffer into the state the token names (its _upSeen) on the fp16 split-state
-    # path; the CONSUMER skips its detection launch only if the tag on its input carries its token of this frame.
+    # ---- the change detection of an fp16 layer inside the launch of the layer that PRODUCES its input ----
+    # A consumer in copy mode compares the producer's output buffer with a copy of last frame's, so only the pixels the
+    # producer just recomputed can trigger, and the producer's launch can do the whole detection for them.  Checked on
+    # the host every frame from both sides, with a token naming the consumer's state buffers and threshold: the PRODUCER
+    # folds a consumer in only if that consumer's last frame consumed this producer's last frame from this very buffer
+    # (its _upSeen); the CONSUMER skips its detection only if the tag on its input carries its token of this frame.
     def _half_token(self, hs, prev):
         return (id(self), prev.data_ptr(), hs['S'].data_ptr(), hs['bits'].data_ptr(), float(self.threshold))
 
     def _detected_upstream(self, token):
         d = self.__dict__
         return (d.get('_upNow') is not None and token in (d.get('_upTokens') or ()) and
-                os.environ.get('CBINFER_NO_NEXTFOLD', '0') != '1')
+                not _switch('CBINFER_NO_NEXTFOLD'))
 
     def _half_detect_token(self, prod, prodSerial, pout, H, W):
         """The token under which `prod`'s launch of its NEXT frame may run this layer's change detection, or None."""
@@ -592,7 +600,7 @@ class CBConv2d(nn.Module):
         this launch may run.  Returns their tokens."""
         L.nNext = 0
         links = self.__dict__.get('_fusedConsumers')
-        if not links or os.environ.get('CBINFER_NO_NEXTFOLD', '0') == '1' or self.weight.size(0) < 64:
+        if not links or _switch('CBINFER_NO_NEXTFOLD') or self.weight.size(0) < 64:
             return ()
         pout = self._buffers['prevOutput']
         tag = getattr(pout, '_cbProduced', None)      # (still the PREVIOUS frame's)
@@ -616,37 +624,22 @@ class CBConv2d(nn.Module):
     def _split_fg_ok(self, dtype, H, W):
         """Does this layer's fine-grained in-place frame run on the split-state kernels (cbinfer_split_forward_fg)?
         As _split_ok, for a layer in fine-grained mode."""
-        K, Cin, kH, kW = self.weight.size()
-        return (dtype == torch.float32 and self._arith_code(dtype) == _lib.CB_F32S
-                and (not self.__dict__.get('_rangeFallback') or self._split_arith() == 'x3')
-                and os.environ.get('CBINFER_NO_SPLIT', '0') != '1' and os.environ.get('CBINFER_NO_SPLIT_FG', '0') != '1'
-                and self._split_arith() is not None
-                and bool(C.cbinfer_split_supported(Cin, K, kH, kW))
-                and C.cbinfer_mask_words(H, W) <= C.cbinfer_split_max_mask_words(K)
-                and H * W * W < (1 << 32))
+        return not _switch('CBINFER_NO_SPLIT_FG') and self._split_kernels_ok(dtype, H, W)
 
     def _split_weights(self, H, W):
         """(prepared buffer, weight scale).  f16 pairs: a power of two with max |w| * scale in [2^13, 2^14); bf16
         triples ('x3'): the weights as they are -- scale 0.0, which is also what tells the library's frame functions
         which form the buffers hold (include/cbinfer_hip.h)."""
-        w = self.weight
-        arith = self._split_arith()
-        key = ('split', w.data_ptr(), w._version, w.device, H, W, arith)
-        if self._wrows is None or self._wrows[0] != key:
-            K, Cin, kH, kW = w.size()
-            if arith == 'x3':
-                scale = 0.0
-                wp = torch.empty(C.cbinfer_split3_prepared_bytes(Cin, K, kH, kW), dtype=torch.uint8, device=w.device)
-                check(C.cbinfer_split3_prep_weights(ptr(w.detach().contiguous()), ptr(wp), K, Cin, kH, kW, H, W,
-                                                    stream_ptr(w)))
-            else:
-                wmax = float(w.detach().abs().max())          # (one host sync when the weights change)
-                scale = 2.0 ** (13 - math.floor(math.log2(wmax))) if wmax > 0 and math.isfinite(wmax) else 1.0
-                wp = torch.empty(C.cbinfer_split_prepared_bytes(Cin, K, kH, kW), dtype=torch.uint8, device=w.device)
-                check(C.cbinfer_split_prep_weights(ptr(w.detach().contiguous()), ptr(wp), K, Cin, kH, kW, H, W,
-                                                   scale, stream_ptr(w)))
-            self._wrows = (key, wp, scale)
-        return self._wrows[1], self._wrows[2]
+        if self._split_arith() == 'x3':
+            return self._relaid(('x3', H, W), C.cbinfer_split3_prepared_bytes, C.cbinfer_split3_prep_weights,
+                                lambda w: (H, W))[0], 0.0
+
+        def scaled(w):
+            wmax = float(w.detach().abs().max())          # (one host sync when the weights change)
+            return H, W, 2.0 ** (13 - math.floor(math.log2(wmax))) if wmax > 0 and math.isfinite(wmax) else 1.0
+        wp, _, _, scale = self._relaid(('f16x2', H, W), C.cbinfer_split_prepared_bytes, C.cbinfer_split_prep_weights,
+                                       scaled)
+        return wp, scale
 
     def _split_workspace(self, work, H, W, dev):
         sp = work.get('split')
@@ -654,18 +647,15 @@ class CBConv2d(nn.Module):
         if sp is None or sp['arith'] != arith:      # (the records of the two arithmetics differ in size and content)
             K, Cin, kH, kW = self.weight.size()
             words = C.cbinfer_mask_words(H, W)
-            if arith == 'x3':
-                S = torch.empty(C.cbinfer_split3_state_bytes(Cin, H, W, kH, kW), dtype=torch.uint8, device=dev)
-                check(C.cbinfer_split3_state_init(ptr(S), Cin, H, W, kH, kW, stream_ptr(S)))
-            else:
-                S = torch.empty(C.cbinfer_split_state_bytes(Cin, H, W, kH, kW), dtype=torch.uint8, device=dev)
-                check(C.cbinfer_split_state_init(ptr(S), Cin, H, W, kH, kW, stream_ptr(S)))
+            x3 = arith == 'x3'
+            S = torch.empty((C.cbinfer_split3_state_bytes if x3 else C.cbinfer_split_state_bytes)(Cin, H, W, kH, kW),
+                            dtype=torch.uint8, device=dev)
+            check((C.cbinfer_split3_state_init if x3 else C.cbinfer_split_state_init)(ptr(S), Cin, H, W, kH, kW,
+                                                                                      stream_ptr(S)))
             # (slabs only for deep contractions -- 48 k-stages and more: 0 bytes otherwise)
             wsBytes = C.cbinfer_split_workspace_bytes(1, Cin, H, W, K, kH, kW)
             ws = torch.zeros(wsBytes, dtype=torch.uint8, device=dev) if wsBytes > 0 else None
-            # (a frame mask of its own: the list kernels' protocol -- two masks alternating by a device-side parity --
-            #  and the split-state kernels' -- one mask, an arrival counter behind it -- must never meet in one
-            #  buffer when a module changes paths in mid-sequence)
+            # (a frame mask of its own: the list and split-state kernels' mask protocols must never share a buffer)
             sp = work['split'] = dict(S=S, arith=arith, flag=torch.zeros(1, dtype=torch.int32, device=dev),
                                       bits=torch.zeros(C.cbinfer_frame_mask_bytes(H, W) // 8, dtype=torch.int64,
                                                        device=dev),
@@ -673,18 +663,24 @@ class CBConv2d(nn.Module):
                                       stateKey=None, seq=(_lib.SplitSeq * 1)())
         return sp
 
+    def _fill_seq(self, sp, work, src, pmask):
+        """The split-state record (cbSplitSeq) of this frame's buffers."""
+        q = sp['seq'][0]
+        q.input, q.state, q.splitState = src.data_ptr(), self.prevInput.data_ptr(), sp['S'].data_ptr()
+        q.frameMasks, q.producerMask = sp['bits'].data_ptr(), ptr(pmask)
+        q.output, q.idxOut, q.countOut = self.prevOutput.data_ptr(), work['idx'].data_ptr(), work['count'].data_ptr()
+        q.rangeFlag, q.maskCopy = sp['flag'].data_ptr(), sp['copy'].data_ptr()
+        return q
+
     def _folded_tail(self, sp, H, W, dev):
         """The CBTail1x1 behind this layer if its evaluation can ride in this layer's second launch
-        (cbinfer_split_forward_tail), with sp['tail'] (cbSplitTail) filled in -- else None: the tail module then
-        runs its own launch.  CBINFER_NO_TAILFOLD=1 switches the folding off."""
-        t = self.__dict__.get('_fusedTail')
+        (cbinfer_split_forward_tail), with sp['tail'] (cbSplitTail) filled in -- else None (it runs its own launch)."""
+        t = self._fusedTailCandidate()
         K, Cin, kH, kW = self.weight.size()
-        if (t is None or sp['ws'] is None or not self.propChangeIndexes or t.in_channels != K or
-                self.__dict__.get('_noTailFold') or
+        if (t is None or sp['ws'] is None or t.in_channels != K or
                 t.weight1.dtype != torch.float32 or t.weight1.device != dev or
                 # (the second launch reads the layer's bias and the tail's first four values at a time)
                 (self.bias.data_ptr() | t.bias1.data_ptr()) & 15 or
-                os.environ.get('CBINFER_NO_TAILFOLD', '0') == '1' or
                 not C.cbinfer_split_tail_supported(Cin, K, kH, kW, t.hidden_channels, t.out_channels)):
             return None
         out = t._output_for(H, W, dev, torch.float32)
@@ -698,30 +694,30 @@ class CBConv2d(nn.Module):
         return t
 
     def _fusedTailCandidate(self):
-        """The fused tail this layer would fold into its second launch right now (cheap form of _folded_tail's test,
-        for the call plans), or None."""
+        """The fused tail this layer would fold into its second launch right now (_folded_tail's cheap part), or None."""
         t = self.__dict__.get('_fusedTail')
-        if (t is None or not self.propChangeIndexes or self.__dict__.get('_noTailFold') or
-                os.environ.get('CBINFER_NO_TAILFOLD', '0') == '1'):
+        if t is None or not self.propChangeIndexes or self.__dict__.get('_noTailFold') or _switch('CBINFER_NO_TAILFOLD'):
             return None
         return t
+
+    def _tail_unchanged(self, plan):
+        """Does a split-state plan's tail folding still hold (a FramePipeline may take it away or give it back)?"""
+        t = plan['tail']
+        return self._fusedTailCandidate() is plan['tailCand'] and (t is None or t._fold_key() == plan['tailKey'])
 
     def rangeExceeded(self):
         """True if a state value of this layer ever left the range of the f16-pair arithmetic (|x| >= 2^20, or a
         non-finite input) since the state was cleared (one host sync unless the module has noticed already).  The
-        outputs are right either way: from the frame that trips the flag on, the contraction kernel itself computes
-        the layer from prevInput with plain f32 arithmetic (cb_split.hip: cbs_exact_tile) -- slowly -- until the module
-        notices (`_poll_range`, no sync) and moves the layer to the bf16x3 kernels, which have f32's range."""
+        outputs are right either way: the kernel computes such frames in plain f32 (cbs_exact_tile), slowly, until
+        `_poll_range` moves the layer to the bf16x3 kernels."""
         if self.__dict__.get('_rangeFallback'):
             return True
         sp = self._work.get('split') if self._work else None
         return bool(sp is not None and int(sp['flag'].item()) != 0)
 
     def _poll_range(self, sp):
-        """Every 64th split-state frame: an asynchronous copy of the layer's range flag into pinned memory, and a look
-        at what the previous copy brought (no sync, no wait).  A tripped flag moves the layer to the bf16x3 kernels for
-        good (`_rangeFallback`; clearMemory resets it): the in-kernel exact path that kept the frames since the trip
-        right is orders of magnitude slower than either."""
+        """Every 64th split-state frame: an asynchronous copy of the range flag into pinned memory and a look at what the
+        previous copy brought (no sync).  A tripped flag moves the layer to the bf16x3 kernels until clearMemory."""
         if sp['arith'] == 'x3':      # (bf16 triples have f32's range: the flag is never set)
             return
         n = sp['poll'] = sp.get('poll', 0) + 1
@@ -740,16 +736,12 @@ class CBConv2d(nn.Module):
 
     def _window_fold(self, sp, tail, H, W):
         """Can this split-state layer's contraction run in pooling-window order and carry the pooled change detection of
-        the layer behind the following CBPoolMax2d (cbinfer_split_*_next, round 6)?  -> (eligible at all, cbNextDetect or
-        None, the token the consumer will look for or None, _next_detect's token before the library's own test).
-        pycbinfer.fuseDetectionIntoProducer(windowOrder=...) says whether: True, False, or 'auto' (default) -- decided when
-        the call plan is made (NOT per frame: the one place where the layer's last change count is read back, outside any
-        stream capture) from the tiles the window-order form would need: it pays while they fit one round of the grid
-        (DESIGN 5.8).  CBINFER_NO_WINFOLD=1 switches the form off."""
+        the layer behind the following CBPoolMax2d (cbinfer_split_*_next)?  -> (eligible at all, cbNextDetect or None, the
+        token the consumer will look for or None, _next_detect's token before the library's own test).  windowOrder of
+        pycbinfer.fuseDetectionIntoProducer: True, False or 'auto' (DESIGN 5.8); CBINFER_NO_WINFOLD=1 switches it off."""
         K, Cin, kH, kW = self.weight.size()
         mode = self.__dict__.get('_winFold', 'auto')
-        eligible = (tail is None and sp['arith'] == 'x3' and mode is not False and
-                    os.environ.get('CBINFER_NO_WINFOLD', '0') != '1')
+        eligible = tail is None and sp['arith'] == 'x3' and mode is not False and not _switch('CBINFER_NO_WINFOLD')
         nxt, ntok, rawTok = None, None, None
         if eligible:
             nxt, ntok = self._next_detect(H, W)
@@ -757,12 +749,9 @@ class CBConv2d(nn.Module):
             if nxt is not None and not C.cbinfer_split_next_supported(Cin, K, kH, kW, H, W, ctypes.pointer(nxt)):
                 nxt, ntok = None, None
             if nxt is not None and mode == 'auto':
-                # decided ONCE per module, from the first frame that recomputed some but not all of the layer's pixels (the
-                # first frame of a sequence recomputes all of them, a repeated frame none): the tiles of 16 windows the form
-                # would need for that many pixels (a touched window's unchanged pixels cost slots: + ~20 %) -- beyond one
-                # round of the persistent grid its longer prologue and epilogue are paid once more per round, and its tile
-                # count crosses that line before pixel order's does.  Until then (at most four looks, each a read-back of
-                # the layer's change count while its call plan is made -- never inside a stream capture): the form is used.
+                # decided ONCE per module, when a call plan is made outside any capture, from the first frame that
+                # recomputed some but not all pixels: the form pays while its tiles of 16 windows (+ ~20 % for a touched
+                # window's unchanged pixels) fit one round of the persistent grid.  Until then (four looks): used.
                 st = self.__dict__.setdefault('_winAuto', {'fold': None, 'looks': 0})
                 if st['fold'] is None and not torch.cuda.is_current_stream_capturing():
                     n = int(self._work['count'].item())
@@ -790,22 +779,12 @@ class CBConv2d(nn.Module):
         if rebuilt:
             # first frame, or prevInput was (re)allocated or written by somebody else (restored states,
             # eval03.py:88-95): the pre-split copy is made again from it
-            if sp['arith'] == 'x3':
-                check(C.cbinfer_split3_state_rebuild(ptr(prev), ptr(sp['S']), Cin, H, W, kH, kW, stream_ptr(src)))
-            else:
-                check(C.cbinfer_split_state_rebuild(ptr(prev), ptr(sp['S']), Cin, H, W, kH, kW, ptr(sp['flag']),
-                                                    stream_ptr(src)))
+            flag = () if sp['arith'] == 'x3' else (ptr(sp['flag']),)
+            rebuild = C.cbinfer_split3_state_rebuild if sp['arith'] == 'x3' else C.cbinfer_split_state_rebuild
+            check(rebuild(ptr(prev), ptr(sp['S']), Cin, H, W, kH, kW, *flag, stream_ptr(src)))
             sp['stateKey'] = stateKey
-        pmask = None
-        if lazy is not None:
-            sameTh = self.__dict__.get('_pmaskThreshold') == float(self.threshold)
-            self.__dict__['_pmaskThreshold'] = float(self.threshold)
-            pmask = None if (rebuilt or not sameTh) else lazy.producerMask()
-        q = sp['seq'][0]
-        q.input, q.state, q.splitState = src.data_ptr(), prev.data_ptr(), sp['S'].data_ptr()
-        q.frameMasks, q.producerMask = sp['bits'].data_ptr(), ptr(pmask)
-        q.output, q.idxOut, q.countOut = self.prevOutput.data_ptr(), work['idx'].data_ptr(), work['count'].data_ptr()
-        q.rangeFlag, q.maskCopy = sp['flag'].data_ptr(), sp['copy'].data_ptr()
+        pmask = lazy.producerMask() if (lazy is not None and self._pmask_ok(rebuilt)) else None
+        q = self._fill_seq(sp, work, src, pmask)
         # (mode: bit 0 = behind a folded pool, bit 1 = not in feedback mode -- both states take every value of the frame)
         args = [sp['seq'], 1, int(lazy is not None) | (0 if self.feedbackLoop else 2),
                 src.size(-2) if lazy is not None else 0,
@@ -817,9 +796,7 @@ class CBConv2d(nn.Module):
         # launch has done already (cb_rowpair.hip; its change indexes carry this layer's token)
         cargs = [sp['seq'], 1, ptr(wp), ptr(self.bias.detach()), Cin, H, W, K, kH, kW, float(scale),
                  int(bool(self.withReLU)), ptr(sp['ws']), 0]
-        # round 6: with a split-state consumer behind a lazy pool (pycbinfer.fuseDetectionIntoProducer) the contraction runs
-        # in pooling-window order and is that consumer's pooled change detection as well (cbinfer_split_*_next), as the
-        # row-pair kernel is for its consumer
+        # with a split-state consumer behind a lazy pool, the contraction in window order is its detection as well
         nextEligible, nxt, ntok, rawTok = self._window_fold(sp, tail, H, W)
         if tail is not None:
             fn, cfn = C.cbinfer_split_forward_tail, C.cbinfer_split_conv_tail
@@ -833,13 +810,10 @@ class CBConv2d(nn.Module):
             fn, cfn = C.cbinfer_split_forward, C.cbinfer_split_conv
             args += [stream_ptr(src)]
             cargs += [stream_ptr(src)]
-        myTok = None if rebuilt else self._detect_token_with(sp, prev)
-        done = (lazy is not None and myTok is not None and
-                getattr(lazy.indexes, 'nextDetect', None) == myTok)
+        token = self._split_token(sp, prev)
+        done = lazy is not None and not rebuilt and getattr(lazy.indexes, 'nextDetect', None) == token
         # (round 6: the row-pair layer in front left its state refresh to this launch's idle workgroups)
-        side = sp.get('side')
-        if side is None:
-            side = sp['side'] = _lib.SideRefresh()
+        side = sp.get('side') or sp.setdefault('side', _lib.SideRefresh())
         sfn, sargs = None, None
         if nxt is not None:
             sfn, sargs = C.cbinfer_split_conv_next_refresh, cargs[:-1] + [ctypes.pointer(side), cargs[-1]]
@@ -860,54 +834,21 @@ class CBConv2d(nn.Module):
         self._lastIndexes = MaskChangeIndexes(sp['copy'], (H, W), work['idx'], work['count'], made=True)
         self._lastIndexes.tailDone = tail
         self._lastIndexes.nextDetect = ntok
-        w, b = self._parameters.get('weight'), self._parameters.get('bias')
-        if (w is not None and b is not None and not self.gatherComputationStats and
-                os.environ.get('CBINFER_NO_FASTPATH', '0') != '1'):
-            self._plan = dict(
-                split=True, arith=sp['arith'], pooled=lazy is not None, shape=tuple(src.shape), dtype=src.dtype,
-                device=dev,
-                flags=self._flags(), w=(w.data_ptr(), w._version), b=(b.data_ptr(), b._version),
-                state=(self._buffers['prevInput'].data_ptr(), self._buffers['prevOutput'].data_ptr()),
-                stateVersion=prev._version, stream=args[-1], work=work, args=args, seq=q, pmask=ptr(pmask),
-                indexes=self._lastIndexes, fn=fn, tail=tail, tailKey=tail._fold_key() if tail is not None else None,
-                convFn=cfn, convArgs=cargs, tailBlocked=bool(self.__dict__.get('_noTailFold')),
-                detectToken=(id(self), prev.data_ptr(), sp['S'].data_ptr(), sp['bits'].data_ptr(),
-                             float(self.threshold), sp['arith']),
+        self._make_plan(lazy is not None, src, fn, args, None, pmask=ptr(pmask))
+        if self._plan is not None:
+            self._plan.update(
+                split=True, arith=sp['arith'], switches=_split_switches(), checkPmask=True, stateVersion=prev._version,
+                seq=q, indexes=self._lastIndexes, tail=tail, tailKey=tail._fold_key() if tail is not None else None,
+                tailCand=self._fusedTailCandidate(), convFn=cfn, convArgs=cargs, detectToken=token,
                 nextEligible=nextEligible, nextToken=ntok, nextRaw=rawTok, keep=nxt, hw=(H, W), side=side,
                 sideFn=sfn, sideArgs=sargs)
-        if self.propChangeIndexes:
-            return 'changeIndexes', self.prevOutput, self._lastIndexes
-        return self.prevOutput
+        return self._emit(self._lastIndexes)
 
-    def _run_split_plan(self, inp):
-        plan = self._plan
-        if plan['pooled']:
-            if type(inp) is not LazyPool:
-                return None
-            src = inp.source
-            pm = inp.producerMask()
-            if (pm.data_ptr() if pm is not None else None) != plan['pmask']:
-                return None
-        else:
-            if type(inp) is not torch.Tensor:
-                return None
-            src = inp
-        w, b, bufs = self._parameters['weight'], self._parameters['bias'], self._buffers
-        prev = bufs['prevInput']
-        if (src.shape != plan['shape'] or src.dtype != plan['dtype'] or src.device != plan['device'] or
-                not src.is_contiguous() or self._flags() != plan['flags'] or
-                (w.data_ptr(), w._version) != plan['w'] or (b.data_ptr(), b._version) != plan['b'] or
-                (prev.data_ptr(), bufs['prevOutput'].data_ptr()) != plan['state'] or
-                prev._version != plan['stateVersion'] or
-                self._work is not plan['work'] or raw_stream(src.device.index) != plan['stream'] or
-                plan['arith'] != os.environ.get('CBINFER_ARITH', 'x3')):
-            return None
-        if plan['tailBlocked'] != bool(self.__dict__.get('_noTailFold')):
-            return None      # (a FramePipeline took the tail's folding away, or gave it back)
-        if plan['tail'] is not None and (self.__dict__.get('_fusedTail') is not plan['tail'] or
-                                         self.__dict__.get('_noTailFold') or
-                                         os.environ.get('CBINFER_NO_TAILFOLD', '0') == '1' or
-                                         plan['tail']._fold_key() != plan['tailKey']):
+    def _run_split_plan(self, plan, inp, src):
+        """The split-state plan's own conditions and per-frame arguments (_plan_source has checked the common ones)."""
+        if plan['switches'] != _split_switches():
+            return None      # (the arithmetic, or whether the layer runs on these kernels at all, may have changed)
+        if not self._tail_unchanged(plan):
             return None
         if plan['nextEligible'] and self._next_detect(*plan['hw'])[1] != plan['nextRaw']:
             return None      # (the consumer's state or threshold is not the one this plan folds -- or it can fold now)
@@ -935,19 +876,12 @@ class CBConv2d(nn.Module):
             check(status)
         self._poll_range(plan['work']['split'])
         self._inputIsLiveState = False
-        self._lastIndexes = plan['indexes']
-        if self.propChangeIndexes:
-            return 'changeIndexes', bufs['prevOutput'], self._lastIndexes
-        return bufs['prevOutput']
+        return self._emit(plan['indexes'])
 
     def _workspace(self, input, wantMap=None):
         H, W = input.size(-2), input.size(-1)
-        # self-compacting frame pipeline (detection + fused kernel, no compaction launch): mask small
-        # enough for the kernel's LDS prefix, and no int8 copy of the mask requested
         wantMap = self.saveChangeMap if wantMap is None else wantMap
-        selfc = (not wantMap and
-                 C.cbinfer_mask_words(H, W) <= C.cbinfer_frame_mask_max_words() and
-                 os.environ.get('CBINFER_NO_SELFCOMPACT', '0') != '1')
+        selfc = not wantMap and self._selfc_ok(H, W)      # (self-compacting, and no int8 copy of the mask wanted)
         key = (H, W, input.device, selfc)
         if self._work is None or self._work['key'] != key:
             dev = input.device
@@ -962,48 +896,37 @@ class CBConv2d(nn.Module):
                 bits=torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=dev),
                 idx=torch.empty(H * W, dtype=torch.int32, device=dev),
                 count=torch.zeros(1, dtype=torch.int32, device=dev),
-                conv=conv, map=None,
-                # row-segment contraction (cbinfer_conv_changed_rows): single mask, arrival counters, mask copy
-                rows=None,
-                # split-state frame (cbinfer_split_forward): pre-split state copy, range flag, mask copy, slabs
-                split=None)
+                conv=conv, map=None, rows=None, split=None)      # (rows, split: _rows_workspace, _split_workspace)
         if wantMap and self._work['map'] is None:
             self._work['map'] = torch.zeros(H, W, dtype=torch.int8, device=input.device)
         return self._work
 
     # ---------------------------------------------------------------- fine-grained
-    # Execution forms of a fine-grained frame (results agree within the fp32 bar; selected by attributes):
-    #   default      cbinfer_cbconv2d_forward_fg: per-value detection + accumulating fused contraction,
-    #                two launches, no atomics, no host sync, deterministic
-    #   atomicFG     the reference-structured op sequence changeDetectionFG -> compaction ->
-    #                updateOutputFG (f32 atomics), also without a host sync
-    #   fgInPlace    default form updating the module's own tensors in place: prevOutput (and the
-    #                relu'd copy handed out when withReLU) alias the state across frames, as in
-    #                coarse-grained mode, and prevInput is the module's own copy -- no clone, no full-tensor
-    #                ReLU pass, capturable.  The reference hands out fresh tensors (conv2d.py:169,173) and
-    #                keeps the caller's input tensor as state (:175); that is the default here too.
+    # Fine-grained frames (_path): by default per-value detection + accumulating fused contraction, no atomics, no host
+    # sync; atomicFG: the reference-structured op sequence (f32 atomics).  fgInPlace updates the module's own tensors
+    # in place (prevOutput and its relu'd copy alias the state across frames; capturable); without it, as the
+    # reference does, fresh tensors are handed out and the caller's input is kept as state (conv2d.py:169-175).
     def _fg_workspace(self, x):
+        """(work buffers, the relu'd copy of prevOutput an in-place frame keeps up to date or None)."""
         work = self._workspace(x, wantMap=False)     # (saveChangeMap has no meaning in fine-grained mode)
         assert work['selfc']
         if work.get('delta') is None or work['delta'].shape != x.shape:
             work['delta'] = torch.empty_like(x)
             work['relu'] = None
-        return work
+        if not (self.fgInPlace and self.withReLU):
+            return work, None
+        if work['relu'] is None:
+            work['relu'] = F.relu(self.prevOutput)
+        return work, work['relu']
 
     def _forward_fg_split(self, src, lazy, H, W, work, relu):
-        """The fine-grained in-place frame on the split-state kernels (round 4): the detection leaves the thresholded
-        differences of EVERY value as f16 pairs in the pixel-major records, the LDS-DMA contraction adds W * delta to
-        prevOutput at the mask's pixels.  `lazy`: the layer sits behind a CBPoolMax2d folded into its detection -- `src`
-        is the pool's INPUT, H x W the pooled size."""
+        """The fine-grained in-place frame on the split-state kernels: the detection leaves the thresholded differences
+        in the pixel-major records, the contraction adds W * delta to prevOutput at the mask's pixels.  `lazy`: behind a
+        folded CBPoolMax2d, `src` is the pool's input and H x W the pooled size."""
         K, Cin, kH, kW = self.weight.size()
         sp = self._split_workspace(work, H, W, src.device)
         wp, scale = self._split_weights(H, W)
-        q = sp['seq'][0]
-        q.input, q.state, q.splitState = src.data_ptr(), self.prevInput.data_ptr(), sp['S'].data_ptr()
-        q.frameMasks, q.producerMask = sp['bits'].data_ptr(), None
-        q.output, q.idxOut, q.countOut = (self.prevOutput.data_ptr(), work['idx'].data_ptr(),
-                                          work['count'].data_ptr())
-        q.rangeFlag, q.maskCopy = sp['flag'].data_ptr(), sp['copy'].data_ptr()
+        q = self._fill_seq(sp, work, src, None)
         q.delta, q.reluOut = work['delta'].data_ptr(), ptr(relu)
         sp['stateKey'] = None      # (the records hold differences now: a coarse-grained frame re-splits the state)
         pooled = lazy is not None
@@ -1021,11 +944,9 @@ class CBConv2d(nn.Module):
         check(fn(*args))
         self._poll_range(sp)
         self.__dict__['_ranSplit'] = True
-        result = relu if self.withReLU else self.prevOutput
-        self._lastIndexes = MaskChangeIndexes(sp['copy'], (H, W), work['idx'], work['count'], made=True)
-        self._lastIndexes.tailDone = tail
-        if self.propChangeIndexes:
-            result = ('changeIndexes', result, self._lastIndexes)
+        indexes = MaskChangeIndexes(sp['copy'], (H, W), work['idx'], work['count'], made=True)
+        indexes.tailDone = tail
+        result = self._emit(indexes, relu if self.withReLU else None)
         self._make_plan(pooled, src, fn, args, None, result=result)
         if self._plan is not None:
             self._plan.update(fgSplit=True, arith=sp['arith'], seq=q, wsplit=(wp, scale), relu=relu,
@@ -1035,27 +956,17 @@ class CBConv2d(nn.Module):
 
     def forward_fg(self, inp):
         if isinstance(inp, LazyPool):
-            # behind a CBPoolMax2d folded into the detection (pycbinfer.fusePoolingIntoDetection): the in-place frame
-            # on the split-state kernels takes the pool's input as it is; anything else pools first
-            lazy, size = inp, tuple(inp.outSize)
-            src = lazy.source.detach()
-            H, W = size[-2], size[-1]
-            if (self.fgInPlace and not self.atomicFG and src.is_cuda and src.dtype == torch.float32 and
-                    src.is_contiguous() and tuple(self.prevInput.size()) == size and
-                    C.cbinfer_mask_words(H, W) <= C.cbinfer_frame_mask_max_words() and
-                    os.environ.get('CBINFER_NO_SELFCOMPACT', '0') != '1' and self._split_fg_ok(src.dtype, H, W)):
+            # (behind a folded CBPoolMax2d: the in-place split-state frame takes the pool's input, the rest pools first)
+            src, (H, W) = inp.source.detach(), inp.outSize[-2:]
+            if self._path(src, H, W, pooled=True) == 'fg-split':
                 if not self.prevInput.is_contiguous():
                     self.prevInput = self.prevInput.contiguous()
-                work = self._fg_workspace(self.prevInput)
-                relu = None
-                if self.withReLU:
-                    if work['relu'] is None:
-                        work['relu'] = F.relu(self.prevOutput)
-                    relu = work['relu']
-                return self._forward_fg_split(src, lazy, H, W, work, relu)
-            inp = lazy.tensor()
+                work, relu = self._fg_workspace(self.prevInput)
+                return self._forward_fg_split(src, inp, H, W, work, relu)
+            inp = inp.tensor()
         x = inp.detach()
         K, Cin, kH, kW = self.weight.size()
+        H, W = x.size(-2), x.size(-1)
         if self.prevInput.size() != x.size():
             # first frame / new size: dense convolution incl. bias (conv2d.py:163-167)
             self.prevOutput = F.conv2d(x, self.weight.detach(), bias=self.bias.detach(),
@@ -1064,120 +975,146 @@ class CBConv2d(nn.Module):
             if self._work is not None:
                 self._work['relu'] = None
             first = F.relu(self.prevOutput) if self.withReLU else self.prevOutput
-            if self.propChangeIndexes and x.is_cuda:      # every output pixel is new on the first frame
-                H, W = x.size(-2), x.size(-1)
-                allpix = torch.arange(H * W, dtype=torch.int32, device=x.device)
-                return 'changeIndexes', first, allpix
-            return first
+            if not (self.propChangeIndexes and x.is_cuda):
+                return first
+            # (every output pixel is new on the first frame)
+            return self._emit(torch.arange(H * W, dtype=torch.int32, device=x.device), first, last=False)
         x = x.contiguous()
-        H, W = x.size(-2), x.size(-1)
-        fused = (x.is_cuda and not self.atomicFG and x.dtype == torch.float32 and
-                 C.cbinfer_mask_words(H, W) <= C.cbinfer_frame_mask_max_words() and
-                 os.environ.get('CBINFER_NO_SELFCOMPACT', '0') != '1')
-        # layers of few output channels: the frame on the mask-driven contractions (row-segment / patch-staged
-        # kernel with an accumulating epilogue), as in coarse-grained mode
-        path = self._rows_path(x.dtype, H, W) if fused else None
-        if fused and self.fgInPlace:
-            work = self._fg_workspace(x)
-            relu = None
-            if self.withReLU:
-                if work['relu'] is None:
-                    work['relu'] = F.relu(self.prevOutput)
-                relu = work['relu']
-            if not self.prevInput.is_contiguous():
-                self.prevInput = self.prevInput.contiguous()
-            if self._split_fg_ok(x.dtype, H, W):
-                return self._forward_fg_split(x, None, H, W, work, relu)
-            if path:
-                rows = self._rows_workspace(work, H, W, x.device)
-                args = (int(path == 'blocks'), ptr(x), ptr(self.prevInput), ptr(work['delta']),
-                        ptr(self.prevOutput), ptr(relu), ptr(rows['bits']), ptr(rows['arrive']), ptr(rows['copy']),
-                        ptr(self._masked_call(path)[1]), Cin, H, W, K, kH, kW, float(self.threshold), 1,
-                        stream_ptr(x))
-                check(C.cbinfer_cbconv2d_forward_fg_masked(*args))
-                result = relu if self.withReLU else self.prevOutput
-                self._lastIndexes = MaskChangeIndexes(rows['copy'], (H, W), work['idx'], work['count'])
-                if self.propChangeIndexes:
-                    result = ('changeIndexes', result, self._lastIndexes)
-                self._make_plan(False, x, C.cbinfer_cbconv2d_forward_fg_masked, args, 1, result=result, rows=True)
-                return result
-            arith = self._arith(x)
-            args = (ptr(x), ptr(self.prevInput), ptr(work['delta']), ptr(self.prevOutput), ptr(relu),
-                    ptr(work['bits']), ptr(work['idx']), ptr(work['count']),
-                    ptr(self._prepared_weights(H, W, arith)), Cin, H, W, K, kH, kW, float(self.threshold), 1,
-                    ptr(work['conv']), arith, stream_ptr(x))
-            check(C.cbinfer_cbconv2d_forward_fg(*args))
-            result = relu if self.withReLU else self.prevOutput
-            if self.propChangeIndexes:      # (extension: the reference's forward_fg hands no indexes on)
-                result = ('changeIndexes', result, ChangeIndexes(work['idx'], work['count'], (H, W)))
-            self._make_plan(False, x, C.cbinfer_cbconv2d_forward_fg, args, 0, result=result)
-            return result
-        po = self.prevOutput.clone()                                 # conv2d.py:169
+        path = self._path(x, H, W)
+        inplace = self.fgInPlace and path not in ('fg-det', 'fg-atomic')
+        po = None if inplace else self.prevOutput.clone()           # conv2d.py:169
         indexes = None
-        if fused and path:
-            work = self._fg_workspace(x)
-            rows = self._rows_workspace(work, H, W, x.device)
-            check(C.cbinfer_cbconv2d_forward_fg_masked(
-                int(path == 'blocks'), ptr(x), ptr(self.prevInput.contiguous()), ptr(work['delta']), ptr(po), None,
-                ptr(rows['bits']), ptr(rows['arrive']), ptr(rows['copy']), ptr(self._masked_call(path)[1]),
-                Cin, H, W, K, kH, kW, float(self.threshold), 0, stream_ptr(x)))
-            indexes = MaskChangeIndexes(rows['copy'], (H, W), work['idx'], work['count'])
-        elif fused:
-            work = self._fg_workspace(x)
-            indexes = ChangeIndexes(work['idx'], work['count'], (H, W))
-            arith = self._arith(x)
-            check(C.cbinfer_cbconv2d_forward_fg(
-                ptr(x), ptr(self.prevInput.contiguous()), ptr(work['delta']), ptr(po), None,
-                ptr(work['bits']), ptr(work['idx']), ptr(work['count']),
-                ptr(self._prepared_weights(H, W, arith)), Cin, H, W, K, kH, kW, float(self.threshold), 0,
-                ptr(work['conv']), arith, stream_ptr(x)))
-        elif x.is_cuda and self.deterministicFG and not self.atomicFG:
+        if path == 'fg-det':
             po = cbconvFG_deterministic(x, self.prevInput, po, self.weight.detach(), self.threshold,
                                         weightsPrepared=self._prepared_weights(H, W))
-        else:
+        elif path == 'fg-atomic':
             po = cbconvFG(x, self.prevInput, po, self.weight.detach(), self.threshold)
+        else:
+            work, relu = self._fg_workspace(x)
+            if inplace:
+                if not self.prevInput.is_contiguous():
+                    self.prevInput = self.prevInput.contiguous()
+                if path == 'fg-split':
+                    return self._forward_fg_split(x, None, H, W, work, relu)
+                return self._forward_fg_fused(x, path, work, self.prevInput, self.prevOutput, relu)
+            indexes = self._forward_fg_fused(x, path, work, self.prevInput.contiguous(), po, None)
         self.prevOutput = po
         self.prevInput = x                                           # conv2d.py:175
         outp = F.relu(po) if self.withReLU else po
-        if self.propChangeIndexes and x.is_cuda:
-            if indexes is None:
-                # the atomic / deterministic / oversized-mask forms keep no list of the output pixels they
-                # touched: hand on EVERY pixel, so that a consumer fed by the tuple protocol (CBTail1x1 behind
-                # a fine-grained head) stays correct -- it then recomputes the whole map
-                indexes = torch.arange(H * W, dtype=torch.int32, device=x.device)
-            return 'changeIndexes', outp, indexes
-        return outp
+        if not (self.propChangeIndexes and x.is_cuda):
+            return outp
+        if indexes is None:
+            # the atomic / deterministic forms keep no list of the pixels they touched: hand on EVERY pixel, so that a
+            # consumer fed by the tuple protocol stays correct
+            indexes = torch.arange(H * W, dtype=torch.int32, device=x.device)
+        return self._emit(indexes, outp, last=False)
+
+    def _forward_fg_fused(self, x, path, work, prev, out, relu):
+        """A fine-grained frame on the mask-driven ('fg-rows', 'fg-blocks') or the list contraction ('fg-list'): in place
+        (fgInPlace: `out` is prevOutput, `relu` its relu'd copy; returns the frame's result and keeps a call plan) or
+        into `out`, a fresh copy of it (returns the change indexes)."""
+        K, Cin, kH, kW = self.weight.size()
+        H, W = x.size(-2), x.size(-1)
+        inplace = self.fgInPlace
+        if path == 'fg-list':
+            arith = self._arith(x)
+            fn, srcSlot = C.cbinfer_cbconv2d_forward_fg, 0
+            args = (ptr(x), ptr(prev), ptr(work['delta']), ptr(out), ptr(relu), ptr(work['bits']), ptr(work['idx']),
+                    ptr(work['count']), ptr(self._prepared_weights(H, W, arith)), Cin, H, W, K, kH, kW,
+                    float(self.threshold), int(inplace), ptr(work['conv']), arith, stream_ptr(x))
+            indexes = ChangeIndexes(work['idx'], work['count'], (H, W))
+        else:
+            rows = self._rows_workspace(work, H, W, x.device)
+            fn, srcSlot = C.cbinfer_cbconv2d_forward_fg_masked, 1
+            args = (int(path == 'fg-blocks'), ptr(x), ptr(prev), ptr(work['delta']), ptr(out), ptr(relu),
+                    ptr(rows['bits']), ptr(rows['arrive']), ptr(rows['copy']), ptr(self._masked_call(path[3:])[1]),
+                    Cin, H, W, K, kH, kW, float(self.threshold), int(inplace), stream_ptr(x))
+            indexes = MaskChangeIndexes(rows['copy'], (H, W), work['idx'], work['count'])
+        check(fn(*args))
+        if not inplace:
+            return indexes
+        # (extension: the reference's forward_fg hands no indexes on)
+        result = self._emit(indexes, relu if self.withReLU else None, last=path != 'fg-list')
+        self._make_plan(False, x, fn, args, srcSlot, result=result, rows=path != 'fg-list')
+        return result
 
     # ---------------------------------------------------------------- coarse-grained
+    def _path(self, x, H, W, pooled=False, have=False):
+        """Which kernel family runs this frame, from what it offers: the source `x` (behind a lazy pool, the pool's
+        input), the layer's size H x W, a folded lazy pool or not, propagated change indexes or not, and the mode:
+          coarse-grained  'split' / 'hsplit' (fp32 / fp16 split-state kernels), 'pairs' (cb_rowpair.hip), 'rows' /
+                          'blocks' (mask-driven, _rows_path), 'list' (cb_conv.hip), 'ops' (the reference's op sequence)
+          fine-grained    'fg-split', 'fg-rows', 'fg-blocks', 'fg-list', 'fg-det' (deterministicFG), 'fg-atomic'
+          'dense'         behind a lazy pool: pool densely first."""
+        dtype = x.dtype
+        if self.finegrained:
+            fused = x.is_cuda and not self.atomicFG and dtype == torch.float32 and self._selfc_ok(H, W)
+            if pooled:
+                return 'fg-split' if (fused and self.fgInPlace and x.is_contiguous() and
+                                      tuple(self.prevInput.size()) == (1, x.size(-3), H, W) and
+                                      self._split_fg_ok(dtype, H, W)) else 'dense'
+            if fused:
+                if self.fgInPlace and self._split_fg_ok(dtype, H, W):
+                    return 'fg-split'
+                return 'fg-' + (self._rows_path(dtype, H, W) or 'list')
+            return 'fg-det' if (x.is_cuda and self.deterministicFG and not self.atomicFG) else 'fg-atomic'
+        if pooled:
+            if (not self._selfc_ok(H, W) or dtype != self.weight.dtype or self.syncIndexes or self.saveChangeMap or
+                    self.gatherComputationStats):
+                return 'dense'
+        elif self.syncIndexes:
+            return 'ops'
+        elif have or self.saveChangeMap or not self._selfc_ok(H, W):
+            return 'list'
+        if self._split_ok(dtype, H, W):
+            return 'split'
+        if self._hsplit_ok(dtype, H, W):
+            return 'hsplit'
+        if pooled and not self.feedbackLoop:      # (the other pooled frames refresh the state at the changed pixels only)
+            return 'dense'
+        path = self._rows_path(dtype, H, W)
+        if path == 'rows' and not pooled and self._pairs_ok(H, W):
+            return 'pairs'
+        return path or 'list'
+
+    def _selfc_ok(self, H, W):
+        """The self-compacting frame (detection + fused contraction, no compaction launch) takes an H x W mask."""
+        return C.cbinfer_mask_words(H, W) <= C.cbinfer_frame_mask_max_words() and not _switch('CBINFER_NO_SELFCOMPACT')
+
+    def _pmask_ok(self, fresh):
+        """May this frame's detection skip what the producer's change mask leaves out?  Not on a fresh or restored state,
+        nor after a change of the threshold (the skipped segments compared below THIS threshold last frame)."""
+        th = float(self.threshold)
+        same = self.__dict__.get('_pmaskThreshold') == th
+        self.__dict__['_pmaskThreshold'] = th
+        return same and not fresh
+
+    def _emit(self, indexes, out=None, last=True):
+        """A frame's result: `out` (default prevOutput), a tuple with propChangeIndexes; `last`: lastChangeIndexes()"""
+        if last:
+            self._lastIndexes = indexes
+        if out is None:
+            out = self._buffers['prevOutput']
+        return ('changeIndexes', out, indexes) if self.propChangeIndexes else out
+
     def forward_normal(self, inp):
         # input parsing and checks (conv2d.py:180-190)
         changeIndexes = None
-        pooled = None
         if isinstance(inp, LazyPool):
-            if (self.feedbackLoop and not self.syncIndexes and not self.saveChangeMap and
-                    not self.gatherComputationStats and inp.source.dtype == self.weight.dtype):
-                pooled = inp
-                return self._forward_pooled(pooled)
-            # (round 4: a layer WITHOUT feedback loop that keeps a copy of its input, on the split-state kernels -- the
-            #  detection's copy-all form takes the 2x2 max on the fly and the pooled map lives in prevInput)
-            if (self.copyInput and not self.feedbackLoop and not self.syncIndexes and not self.saveChangeMap and
-                    not self.gatherComputationStats and inp.source.dtype == self.weight.dtype and
-                    inp.source.is_cuda and (self._split_ok(inp.source.dtype, inp.outSize[-2], inp.outSize[-1]) or
-                                            self._hsplit_ok(inp.source.dtype, inp.outSize[-2], inp.outSize[-1]))):
-                return self._forward_pooled(inp)
-            inp = inp.tensor()           # any other configuration: pool densely, then as usual
+            path = self._path(inp.source, inp.outSize[-2], inp.outSize[-1], pooled=True)
+            if path != 'dense':
+                return self._forward_pooled(inp, path)
+            inp = inp.tensor()
         src = inp[1] if type(inp) == tuple else inp
         # a producer that hands out its in-place-updated state (CBPoolMax2d.cloneOutput=False) tags it
         self._inputIsLiveState = bool(getattr(src, '_cbinfer_inplace_state', False))
+        input = src.detach().contiguous()
         if type(inp) == tuple:
             assert inp[0] == 'changeIndexes'
-            input = inp[1].detach().contiguous()
             changeIndexes = inp[2]
             if isinstance(changeIndexes, torch.Tensor):
                 changeIndexes = changeIndexes.detach().contiguous()
             assert changeIndexes.dim() == 1
-        else:
-            input = inp.detach().contiguous()
         assert input.size(-3) == self.in_channels
         assert input.dim() == 4 and input.size(0) == 1
         require_device(input)
@@ -1192,87 +1129,52 @@ class CBConv2d(nn.Module):
             # (the reference-structured mode hands exact tensors on, conv2d_cg.py:207)
             changeIndexes = dilated.tensor().clone() if self.syncIndexes else dilated
 
-        # (re)allocate the state, +inf => the first frame is 100 % change (conv2d.py:192-199)
-        if (self.prevInput.size() != input.size() or self.prevInput.dtype != input.dtype or
-                self.prevInput.device != input.device):
-            self.prevInput = torch.full_like(input, float('inf'))
-        outpSize = list(input.size())
-        outpSize[-3] = self.out_channels
-        if (not _same_shape(self.prevOutput, outpSize) or self.prevOutput.dtype != input.dtype or
-                self.prevOutput.device != input.device):
-            self.prevOutput = torch.full(outpSize, float('inf'), dtype=input.dtype,
-                                         device=input.device)
+        self._state_for(input.size(), input)
 
         if self.gatherComputationStats:
             self._gatherStats(input)
 
-        if self.syncIndexes:
-            changeIndexes = self._forward_ops(input, changeIndexes)
-            self._lastIndexes = (changeIndexes if isinstance(changeIndexes, ChangeIndexes) else
-                                 ChangeIndexes(changeIndexes, torch.tensor([changeIndexes.numel()],
-                                                                          dtype=torch.int32, device=input.device),
-                                               (input.size(-2), input.size(-1))))
-        else:
-            changeIndexes = self._forward_fused(input, changeIndexes)
+        path = self._path(input, input.size(-2), input.size(-1), have=changeIndexes is not None)
+        if path != 'ops':
+            return self._forward_fused(input, changeIndexes, path)
+        changeIndexes = self._forward_ops(input, changeIndexes)
+        self._lastIndexes = (changeIndexes if isinstance(changeIndexes, ChangeIndexes) else
+                             ChangeIndexes(changeIndexes, torch.tensor([changeIndexes.numel()],
+                                                                      dtype=torch.int32, device=input.device),
+                                           (input.size(-2), input.size(-1))))
+        return self._emit(changeIndexes, last=False)
 
-        if self.propChangeIndexes:
-            return 'changeIndexes', self.prevOutput, changeIndexes
-        return self.prevOutput
+    def _state_for(self, size, like):
+        """(Re)allocate the state, +inf: a first frame is 100 % change (conv2d.py:192-199).  -> prevInput is new"""
+        fresh = (tuple(self.prevInput.size()) != tuple(size) or self.prevInput.dtype != like.dtype or
+                 self.prevInput.device != like.device)
+        if fresh:
+            self.prevInput = torch.full(size, float('inf'), dtype=like.dtype, device=like.device)
+        outpSize = list(size)
+        outpSize[-3] = self.out_channels
+        if (not _same_shape(self.prevOutput, outpSize) or self.prevOutput.dtype != like.dtype or
+                self.prevOutput.device != like.device):
+            self.prevOutput = torch.full(outpSize, float('inf'), dtype=like.dtype, device=like.device)
+        return fresh
 
-    def _forward_pooled(self, lazy):
-        """Feedback-mode layer behind a lazy CBPoolMax2d: detection on pooled values computed on the fly
-        + self-compacting contraction (cbinfer_cbconv2d_forward_pooled).  Falls back to dense pooling
-        when the mask is too large for the self-compacting kernel."""
+    def _forward_pooled(self, lazy, path):
+        """A layer behind a lazy CBPoolMax2d (pycbinfer.fusePoolingIntoDetection) on `path` (_path): its change detection
+        takes the 2x2 max of the pool's input on the fly (cbinfer_cbconv2d_forward_pooled and its kin)."""
         src = lazy.source.detach().contiguous()
         size = lazy.outSize
         H, W = size[-2], size[-1]
         assert size[-3] == self.in_channels and src.dim() == 4 and src.size(0) == 1
         require_device(src)
-        if C.cbinfer_mask_words(H, W) > C.cbinfer_frame_mask_max_words():
-            return self.forward_normal(lazy.tensor())
-        fresh = (tuple(self.prevInput.size()) != tuple(size) or self.prevInput.dtype != src.dtype or
-                 self.prevInput.device != src.device)
-        if fresh:
-            self.prevInput = torch.full(size, float('inf'), dtype=src.dtype, device=src.device)
-        outpSize = list(size)
-        outpSize[-3] = self.out_channels
-        if (not _same_shape(self.prevOutput, outpSize) or self.prevOutput.dtype != src.dtype or
-                self.prevOutput.device != src.device):
-            self.prevOutput = torch.full(outpSize, float('inf'), dtype=src.dtype, device=src.device)
+        fresh = self._state_for(size, src)
         self._inputIsLiveState = False
         work = self._workspace(self.prevInput)
-        if not work['selfc']:
-            return self.forward_normal(lazy.tensor())
-        K, Cin, kH, kW = self.weight.size()
-        if self._split_ok(src.dtype, H, W):
+        if path == 'split':
             return self._forward_split(src, lazy, work)
-        if self._hsplit_ok(src.dtype, H, W):
-            self._lastIndexes = self._forward_hsplit(src, work, lazy)
-            if self.propChangeIndexes:
-                return 'changeIndexes', self.prevOutput, self._lastIndexes
-            return self.prevOutput
-        if not self.feedbackLoop:      # (the other pooled frames refresh the state at the changed pixels only)
-            return self.forward_normal(lazy.tensor())
-        path = self._rows_path(src.dtype, H, W)
-        if path:
-            rows = self._rows_workspace(work, H, W, src.device)
-            fn, wprep = self._masked_call(path)
-            # (a state that was just (re)allocated must see every pixel, whatever the producer rewrote; and the
-            #  producer-mask shortcut assumes the skipped segments compared below THIS threshold last frame: the
-            #  first frame after a change of the threshold looks at every segment again)
-            sameTh = self.__dict__.get('_pmaskThreshold') == float(self.threshold)
-            self.__dict__['_pmaskThreshold'] = float(self.threshold)
-            pmask = None if (fresh or not sameTh) else lazy.producerMask()
-            args = (None, ptr(src), src.size(-2), src.size(-1), ptr(pmask), ptr(self.prevInput),
-                    ptr(self.prevOutput), ptr(rows['bits']), ptr(rows['arrive']), ptr(rows['copy']), ptr(wprep),
-                    ptr(self.bias.detach()), Cin, H, W, K, kH, kW, float(self.threshold), 1, 0,
-                    int(bool(self.withReLU)), stream_ptr(src))
-            check(fn(*args))
-            self._make_plan(True, src, fn, args, 1, rows=True, pmask=ptr(pmask))
-            self._lastIndexes = MaskChangeIndexes(rows['copy'], (H, W), work['idx'], work['count'])
-            if self.propChangeIndexes:
-                return 'changeIndexes', self.prevOutput, self._lastIndexes
-            return self.prevOutput
+        if path == 'hsplit':
+            return self._forward_hsplit(src, work, lazy)
+        if path != 'list':
+            return self._emit(self._forward_masked(src, work, path, lazy, fresh))
+        K, Cin, kH, kW = self.weight.size()
         arith = self._arith(src)
         args = (ptr(src), src.size(-2), src.size(-1), ptr(self.prevInput), ptr(self.prevOutput),
                 ptr(work['bits']), ptr(work['idx']), ptr(work['count']),
@@ -1280,14 +1182,89 @@ class CBConv2d(nn.Module):
                 float(self.threshold), int(bool(self.withReLU)), ptr(work['conv']), arith, stream_ptr(src))
         check(C.cbinfer_cbconv2d_forward_pooled(*args))
         self._make_plan(True, src, C.cbinfer_cbconv2d_forward_pooled, args, 0)
-        self._lastIndexes = ChangeIndexes(work['idx'], work['count'], (H, W))
-        if self.propChangeIndexes:
-            return 'changeIndexes', self.prevOutput, self._lastIndexes
-        return self.prevOutput
+        return self._emit(ChangeIndexes(work['idx'], work['count'], (H, W)))
 
-    def _forward_fused(self, input, changeIndexes):
-        """One library call per frame: no host sync (see cbinfer_cbconv2d_forward)."""
+    def _forward_fused(self, input, changeIndexes, path):
+        """One library call per frame on `path` (_path): no host sync (see cbinfer_cbconv2d_forward)."""
         work = self._workspace(input)
+        if not self.prevInput.is_contiguous():
+            self.prevInput = self.prevInput.contiguous()
+        if path == 'split':
+            return self._forward_split(input, None, work)
+        if path == 'hsplit':
+            return self._forward_hsplit(input, work)
+        if path == 'pairs':
+            result = self._forward_pairs(input, work)
+        elif path == 'list':
+            result = self._forward_list(input, changeIndexes, work)
+        else:
+            result = self._forward_masked(input, work, path)
+        if not self.feedbackLoop and not self.copyInput:
+            # alias, conv2d.py:237-238 (a producer's in-place-updated state is copied first)
+            self.prevInput = input.clone() if self._inputIsLiveState else input
+        return self._emit(result)
+
+    def _forward_masked(self, src, work, path, lazy=None, fresh=False):
+        """A frame on a mask-driven contraction ('rows' / 'blocks'); `lazy`: behind a folded pool (`src` is its input,
+        `fresh`: the state was just allocated).  Returns the indexes."""
+        K, Cin, kH, kW = self.weight.size()
+        H, W = self.prevInput.size(-2), self.prevInput.size(-1)
+        rows = self._rows_workspace(work, H, W, src.device)
+        fn, wprep = self._masked_call(path)
+        if lazy is None:
+            pmask, head = None, (ptr(src), None, 0, 0, None)
+        else:
+            pmask = lazy.producerMask() if self._pmask_ok(fresh) else None
+            head = (None, ptr(src), src.size(-2), src.size(-1), ptr(pmask))
+        args = head + (ptr(self.prevInput), ptr(self.prevOutput), ptr(rows['bits']), ptr(rows['arrive']),
+                       ptr(rows['copy']), ptr(wprep), ptr(self.bias.detach()), Cin, H, W, K, kH, kW,
+                       float(self.threshold), int(bool(self.feedbackLoop)), int(lazy is None and bool(self.copyInput)),
+                       int(bool(self.withReLU)), stream_ptr(src))
+        check(fn(*args))
+        if not self._inputIsLiveState:
+            self._make_plan(lazy is not None, src, fn, args, int(lazy is not None), rows=True, pmask=ptr(pmask))
+        return MaskChangeIndexes(rows['copy'], (H, W), work['idx'], work['count'])
+
+    def _forward_pairs(self, input, work):
+        """The row-pair kernel: persistent over the non-empty units, and -- with a split-state consumer behind a lazy pool
+        (pycbinfer.fuseDetectionIntoProducer) -- that consumer's pooled change detection in the same launch."""
+        K, Cin, kH, kW = self.weight.size()
+        H, W = input.size(-2), input.size(-1)
+        prev = self.prevInput
+        rows = self._rows_workspace(work, H, W, input.device)
+        _, wprep = self._masked_call('rows')
+        nxt, tok = self._next_detect(H, W)
+        det = self._pair_detect_ok(nxt, kH)
+        if det:
+            # round 6: this layer's own detection inside the row-pair launch; the state is refreshed by the consumer's
+            # contraction (or, failing that, by a launch of its own behind the consumer's: CBConv2d.forward)
+            cons = self.__dict__['_fusedNext'][1]
+            old = cons.__dict__.pop('_sidePending', None)
+            if old is not None:      # (the consumer was not called last frame)
+                _flush_side(old)
+            fn = C.cbinfer_conv_rowpairs_detect
+            args = (ptr(input), ptr(prev), ptr(self.prevOutput), ptr(rows['copy']), ptr(wprep),
+                    ptr(self.bias.detach()), Cin, H, W, K, kH, kW, float(self.threshold), int(bool(self.withReLU)),
+                    ctypes.pointer(nxt), stream_ptr(input))
+            check(fn(*args))
+            cons.__dict__['_sidePending'] = (input, prev, Cin, H, W, float(self.threshold))      # (tensors: kept alive)
+        else:
+            fn = C.cbinfer_cbconv2d_forward_rowpairs
+            args = (ptr(input), ptr(prev), ptr(self.prevOutput), ptr(rows['bits']), ptr(rows['arrive']),
+                    ptr(rows['copy']), ptr(wprep), ptr(self.bias.detach()), Cin, H, W, K, kH, kW,
+                    float(self.threshold), int(bool(self.withReLU)),
+                    ctypes.pointer(nxt) if nxt is not None else None, stream_ptr(input))
+            check(fn(*args))
+        result = MaskChangeIndexes(rows['copy'], (H, W), work['idx'], work['count'])
+        result.nextDetect = tok
+        if not self._inputIsLiveState:
+            self._make_plan(False, input, fn, args, 0, rows=True)
+            if self._plan is not None:
+                self._plan.update(pairs=True, nextToken=tok, keep=nxt, det=det)
+        return result
+
+    def _forward_list(self, input, changeIndexes, work):
+        """The list kernel (cb_conv.hip): this layer's own detection, or the propagated change indexes."""
         K, Cin, kH, kW = self.weight.size()
         H, W = input.size(-2), input.size(-1)
         have = changeIndexes is not None
@@ -1312,6 +1289,9 @@ class CBConv2d(nn.Module):
                                         "tensor (conv2d_cg.py:207: nonzero(...).int())")
             cap = min(cap, H * W)
             result = changeIndexes
+            if count is None:
+                # exact host-side list: write its length where the kernels look for it
+                count = torch.full((1,), cap, dtype=torch.int32, device=input.device)
         else:
             idx, count, cap = work['idx'], work['count'], H * W
             result = ChangeIndexes(idx, count, (H, W))
@@ -1321,71 +1301,10 @@ class CBConv2d(nn.Module):
                 off = C.cbinfer_frame_mask_copy_offset(H, W) // 8
                 result = MaskChangeIndexes(work['bits'][off:off + C.cbinfer_mask_words(H, W)], (H, W), idx, count,
                                            made=True)
-        if have and count is None:
-            # exact host-side list: write its length where the kernels look for it
-            count = torch.full((1,), cap, dtype=torch.int32, device=input.device)
-        prev = self.prevInput
-        if not prev.is_contiguous():
-            prev = self.prevInput = prev.contiguous()
         mapOut = work['map'] if (self.saveChangeMap and not have) else None
-        if not have and work['selfc'] and self._split_ok(input.dtype, H, W):
-            self._forward_split(input, None, work)
-            return self._lastIndexes
-        if not have and work['selfc'] and mapOut is None and self._hsplit_ok(input.dtype, H, W):
-            self._lastIndexes = self._forward_hsplit(input, work)
-            return self._lastIndexes
-        path = self._rows_path(input.dtype, H, W) if (not have and work['selfc']) else None
-        if path == 'rows' and self._pairs_ok(H, W):
-            # the row-pair kernel: persistent over the non-empty units, and -- with a split-state consumer behind a lazy
-            # pool (pycbinfer.fuseDetectionIntoProducer) -- that consumer's pooled change detection in the same launch
-            rows = self._rows_workspace(work, H, W, input.device)
-            _, wprep = self._masked_call(path)
-            nxt, tok = self._next_detect(H, W)
-            det = self._pair_detect_ok(nxt, kH)
-            if det:
-                # round 6: this layer's own detection inside the row-pair launch; the state is refreshed by the consumer's
-                # contraction (or, failing that, by a launch of its own behind the consumer's: CBConv2d.forward)
-                cons = self.__dict__['_fusedNext'][1]
-                old = cons.__dict__.pop('_sidePending', None)
-                if old is not None:      # (the consumer was not called last frame)
-                    _flush_side(old)
-                fn = C.cbinfer_conv_rowpairs_detect
-                args = (ptr(input), ptr(prev), ptr(self.prevOutput), ptr(rows['copy']), ptr(wprep),
-                        ptr(self.bias.detach()), Cin, H, W, K, kH, kW, float(self.threshold), int(bool(self.withReLU)),
-                        ctypes.pointer(nxt), stream_ptr(input))
-                check(fn(*args))
-                cons.__dict__['_sidePending'] = (input, prev, Cin, H, W, float(self.threshold))      # (tensors: kept alive)
-            else:
-                fn = C.cbinfer_cbconv2d_forward_rowpairs
-                args = (ptr(input), ptr(prev), ptr(self.prevOutput), ptr(rows['bits']), ptr(rows['arrive']),
-                        ptr(rows['copy']), ptr(wprep), ptr(self.bias.detach()), Cin, H, W, K, kH, kW,
-                        float(self.threshold), int(bool(self.withReLU)),
-                        ctypes.pointer(nxt) if nxt is not None else None, stream_ptr(input))
-                check(fn(*args))
-            result = MaskChangeIndexes(rows['copy'], (H, W), work['idx'], work['count'])
-            result.nextDetect = tok
-            if not self._inputIsLiveState:
-                self._make_plan(False, input, fn, args, 0, rows=True)
-                if self._plan is not None:
-                    self._plan['pairs'], self._plan['nextToken'], self._plan['keep'] = True, tok, nxt
-                    self._plan['det'] = det
-            cap = 0      # (done)
-        elif path:
-            rows = self._rows_workspace(work, H, W, input.device)
-            fn, wprep = self._masked_call(path)
-            args = (ptr(input), None, 0, 0, None, ptr(prev), ptr(self.prevOutput), ptr(rows['bits']),
-                    ptr(rows['arrive']), ptr(rows['copy']), ptr(wprep),
-                    ptr(self.bias.detach()), Cin, H, W, K, kH, kW, float(self.threshold),
-                    int(bool(self.feedbackLoop)), int(bool(self.copyInput)), int(bool(self.withReLU)),
-                    stream_ptr(input))
-            check(fn(*args))
-            if not self._inputIsLiveState:
-                self._make_plan(False, input, fn, args, 0, rows=True)
-            result = MaskChangeIndexes(rows['copy'], (H, W), work['idx'], work['count'])
-            cap = 0      # (done)
         if cap > 0:
             arith = self._arith(input)
-            args = (ptr(input), ptr(prev), ptr(self.prevOutput), None if have else ptr(work['bits']),
+            args = (ptr(input), ptr(self.prevInput), ptr(self.prevOutput), None if have else ptr(work['bits']),
                     ptr(idx), ptr(count), ptr(mapOut), ptr(self._prepared_weights(H, W, arith)),
                     ptr(self.bias.detach()), Cin, H, W, K, kH, kW, float(self.threshold),
                     int(bool(self.feedbackLoop)), int(bool(self.copyInput)), int(bool(self.withReLU)),
@@ -1409,10 +1328,6 @@ class CBConv2d(nn.Module):
             # (a view of the module's work buffer, rewritten by the next frame -- clone it to keep it; the
             #  reference allocates a fresh map per frame)
             self.changeMap = mapOut
-        if not self.feedbackLoop and not self.copyInput:
-            # alias, conv2d.py:237-238 (a producer's in-place-updated state is copied first)
-            self.prevInput = input.clone() if self._inputIsLiveState else input
-        self._lastIndexes = result
         return result
 
     def _forward_ops(self, input, changeIndexes):
@@ -1454,11 +1369,9 @@ class CBConv2d(nn.Module):
             totalInputValues=changeTensor.size(-1) * changeTensor.size(-2) * nC * opsPerValue)
 
     # ---------------------------------------------------------------- per-frame fast path
-    # The sync-free forward is one library call; everything around it (shape checks, state allocation,
-    # workspace and weight lookups, pointer extraction) is invariant from frame to frame.  After a frame
-    # went through the general path, the call is kept as a plan -- a pre-built argument list plus the few
-    # facts that must still hold -- and replayed while they hold; anything else falls back.  This is what
-    # keeps the host ahead of the GPU without graph capture (~10 instead of ~35 us per layer and frame).
+    # After a frame went through the general path, its library call is kept as a plan -- a pre-built argument list plus
+    # the facts that must still hold (_plan_source, and each path's own) -- and replayed while they hold: ~10 instead
+    # of ~35 us of host time per layer and frame.
     def _flags(self):
         return (self.threshold, self.feedbackLoop, self.copyInput, self.withReLU, self.propChangeIndexes,
                 self.syncIndexes, self.saveChangeMap, self.gatherComputationStats, self.finegrained,
@@ -1472,7 +1385,7 @@ class CBConv2d(nn.Module):
         if not (self.feedbackLoop or self.copyInput or result is not None):
             return
         w, b = self._parameters.get('weight'), self._parameters.get('bias')
-        if w is None or b is None or os.environ.get('CBINFER_NO_FASTPATH', '0') == '1':
+        if w is None or b is None or _switch('CBINFER_NO_FASTPATH'):
             return
         work = self._work
         self._plan = dict(
@@ -1483,7 +1396,7 @@ class CBConv2d(nn.Module):
             indexes=ChangeIndexes(work['idx'], work['count'], work['key'][:2]))
 
     def _plan_source(self, inp):
-        """The source tensor if the kept call plan (not a split-state fp32 one) applies to `inp` as it stands -- no side
+        """The source tensor if the kept call plan applies to `inp` as it stands -- what every plan assumes; no side
         effects --, else None."""
         plan = self._plan
         if plan['pooled']:
@@ -1511,11 +1424,11 @@ class CBConv2d(nn.Module):
 
     def _run_plan(self, inp):
         plan = self._plan
-        if plan.get('split'):
-            return self._run_split_plan(inp)
         src = self._plan_source(inp)
         if src is None:
             return None
+        if plan.get('split'):
+            return self._run_split_plan(plan, inp, src)
         bufs = self._buffers
         if plan.get('hsplit'):
             tokens = self._prepare_hsplit(plan, src, bufs)
@@ -1539,11 +1452,9 @@ class CBConv2d(nn.Module):
                                                  float(self.threshold))
         args = plan['args']
         if plan.get('fgSplit'):
-            if plan['arith'] != os.environ.get('CBINFER_ARITH', 'x3'):
+            if plan['arith'] != _switch('CBINFER_ARITH'):
                 return None
-            t = plan.get('tail')
-            if self._fusedTailCandidate() is not plan['tailCand'] or (
-                    t is not None and t._fold_key() != plan['tailKey']):
+            if not self._tail_unchanged(plan):
                 return None
             plan['seq'].input = src.data_ptr()
         else:
@@ -1552,10 +1463,6 @@ class CBConv2d(nn.Module):
         if chain:
             up = self.__dict__.get('_upNow')
             args[0] = up.data_ptr() if up is not None else None
-            cm = plan.get('chainMask')
-            if cm is not None:      # (the producer's mask of this frame, under the chain's own conditions)
-                pm = self._chain_mask(cm[1], cm[2])
-                args[cm[0]] = pm.data_ptr() if pm is not None else None
         status = plan['fn'](*args)
         if status != 0:
             check(status)
@@ -1564,29 +1471,20 @@ class CBConv2d(nn.Module):
         if plan.get('fgSplit'):
             self._poll_range(plan['work']['split'])
         self._inputIsLiveState = False
-        if plan['result'] is not None:          # fine-grained in-place frame: prevOutput or its relu'd copy
-            res = plan['result']
-            if plan['rows']:                    # mask-driven: this frame's list is made from its own mask copy
-                work = plan['work']
-                self._lastIndexes = MaskChangeIndexes(work['rows']['copy'], work['key'][:2], work['idx'],
-                                                      work['count'])
-                if isinstance(res, tuple):
-                    res = (res[0], res[1], self._lastIndexes)
-            return res
-        if plan['rows']:                        # mask-driven frame: the list is made when somebody asks
-            work = plan['work']
-            self._lastIndexes = MaskChangeIndexes(work['rows']['copy'], work['key'][:2], work['idx'],
-                                                  work['count'])
-            self._lastIndexes.nextDetect = plan.get('nextToken')
-        else:
-            self._lastIndexes = plan['indexes']
-        if self.propChangeIndexes:
-            return 'changeIndexes', bufs['prevOutput'], self._lastIndexes
-        return bufs['prevOutput']
+        res = plan['result']                    # (fine-grained in-place frame: prevOutput or its relu'd copy)
+        if not plan['rows']:
+            return self._emit(plan['indexes']) if res is None else res
+        # mask-driven frame: the list is made from this frame's mask copy when somebody asks
+        work = plan['work']
+        indexes = MaskChangeIndexes(work['rows']['copy'], work['key'][:2], work['idx'], work['count'])
+        if res is not None:
+            return self._emit(indexes, res[1] if isinstance(res, tuple) else res)
+        indexes.nextDetect = plan.get('nextToken')
+        return self._emit(indexes)
 
     def _prepare_hsplit(self, plan, src, bufs):
-        """The per-frame part of an fp16 split-state frame in front of the library call (the plan's invariants hold): input
-        pointer, the chain's count and mask, whose detection rides where.  Returns the consumers' tokens."""
+        """The per-frame arguments of an fp16 split-state plan: input, the chain's count and mask, whose detection rides
+        where.  Returns the consumers' tokens."""
         L, hs = plan['layer'], plan['hs']
         H, W = plan['size']
         L.input = src.data_ptr()
@@ -1602,20 +1500,14 @@ class CBConv2d(nn.Module):
         self.__dict__['_ranSplit'] = True
         self._publish_count(plan['work']['count'], tokens)
         self._inputIsLiveState = False
-        self._lastIndexes = plan['indexes']
-        if self.propChangeIndexes:
-            return 'changeIndexes', bufs['prevOutput'], self._lastIndexes
-        return bufs['prevOutput']
+        return self._emit(plan['indexes'])
 
     # ---------------------------------------------------------------- chains of change-based layers
-    # A layer whose self-compacting contraction ran leaves its change count on the device (work['count']) and says so
-    # on its output buffer: (module, frame serial, buffer version, count).  The next CBConv2d that is handed this
-    # very buffer may tell its two launches where that count is (cbinfer_cbconv2d_forward_after): zero there and the
-    # frame is over for it after a scalar load each -- the buffer is what it was, nothing can have changed.  What
-    # makes that exact is checked here, on the host, every frame: the tag is of the producer's LATEST forward, nobody
-    # wrote to the buffer through torch since (version counter), this layer's previous forward consumed the
-    # producer's previous frame from the same buffer, and nobody rewrote this layer's state through torch either.
-    # (Threshold and mode are pinned by the plan that carries the call.)  CBINFER_NO_CHAIN=1 switches it off.
+    # A layer whose self-compacting contraction ran tags its output buffer with where its change count is (_Produced).
+    # The next CBConv2d handed this very buffer may pass that count to its launches (cbinfer_cbconv2d_forward_after):
+    # zero there ends its frame at once.  Checked on the host every frame: the tag is of the producer's latest forward,
+    # nobody wrote the buffer or this layer's state through torch since, and this layer's previous forward consumed
+    # the producer's previous frame from the same buffer.  CBINFER_NO_CHAIN=1 switches it off.
     def _publish_count(self, count, tokens=()):
         out = self._buffers['prevOutput']
         out._cbProduced = _Produced(self, self.__dict__.get('_serial', 0), out._version, count, tokens)
@@ -1626,7 +1518,7 @@ class CBConv2d(nn.Module):
         layer consumed its previous one from the same buffer into the same state) -- else None.  CBINFER_NO_CHAINMASK=1
         switches it off."""
         d = self.__dict__
-        if d.get('_upNow') is None or os.environ.get('CBINFER_NO_CHAINMASK', '0') == '1':
+        if d.get('_upNow') is None or _switch('CBINFER_NO_CHAINMASK'):
             return None
         ix = getattr(d['_upSeen'][0], '_lastIndexes', None)
         if isinstance(ix, MaskChangeIndexes) and tuple(ix.size) == (H, W) and ix._mask is not None:
@@ -1652,9 +1544,7 @@ class CBConv2d(nn.Module):
 
     def forward(self, inp):
         out = self._forward(inp)
-        # round 6: the row-pair layer in front detected its changes inside its own launch and left its state alone
-        # (cbinfer_conv_rowpairs_detect); this layer's contraction carries that refresh on its idle workgroups when it runs in
-        # window order (cbinfer_split_conv_next_refresh) -- and whenever it did not, the refresh is a launch of its own, here
+        # a row-pair layer in front that left its state refresh to this layer's contraction, which did not carry it
         pend = self.__dict__.pop('_sidePending', None)
         if pend is not None:
             _flush_side(pend)
@@ -1675,15 +1565,12 @@ class CBConv2d(nn.Module):
         else:
             out = self.forward_normal(inp)
         if not self.__dict__['_ranSplit']:
-            # A frame on any other path refreshes prevInput through raw pointers (neither its address nor its
-            # version counter moves): the pre-split copy of the state is stale from here on and is made again from
-            # prevInput when the module returns to the split-state kernels
-            sp = self._work.get('split') if self._work else None
-            if sp is not None:
-                sp['stateKey'] = None
-            hs = self._work.get('hsplit') if self._work else None
-            if hs is not None:
-                hs['stateKey'] = None
+            # a frame on any other path refreshes prevInput through raw pointers: the split copies of the state are
+            # stale and are made again when the module returns to the split-state kernels
+            for name in ('split', 'hsplit'):
+                st = self._work.get(name) if self._work else None
+                if st is not None:
+                    st['stateKey'] = None
         return out
 
     def __repr__(self):

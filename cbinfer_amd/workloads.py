@@ -305,23 +305,16 @@ def calibrateChangeRatio(converted, nextFrame, target=0.10, pairs=4, settle=8, f
     its steady state.  A WORKLOAD generator for measurements (BASELINE.md budgets config 4 at 10 % of the dense work,
     SURVEY 8(d): "r = 10 % at every layer"), not the reference's accuracy-driven tuner
     (pycbinfer.tuneThresholdParameters).  Returns the thresholds; the network is left warm: continue the same video."""
-    import os
     from . import CBConv2d
+    from .conv2d import _switch_set
     convs = [m for m in converted.modules() if type(m) is CBConv2d]
     for m in convs:
         m.threshold = 0.0
     # (the recorded |input - prevInput| maps need every layer's state as its OWN detection finds it: while a producer's
     #  launch runs its consumer's detection (pycbinfer.fuseDetectionIntoProducer) that state is refreshed before the
     #  consumer's forward -- and this hook -- is reached.  The folding is decided per frame: off while calibrating.)
-    saved = os.environ.get('CBINFER_NO_NEXTFOLD')
-    os.environ['CBINFER_NO_NEXTFOLD'] = '1'
-    try:
+    with _switch_set('CBINFER_NO_NEXTFOLD', '1'):
         return _calibrate(converted, convs, nextFrame, target, pairs, settle, finalSettle)
-    finally:
-        if saved is None:
-            os.environ.pop('CBINFER_NO_NEXTFOLD', None)
-        else:
-            os.environ['CBINFER_NO_NEXTFOLD'] = saved
 
 
 def _calibrate(converted, convs, nextFrame, target, pairs, settle, finalSettle):

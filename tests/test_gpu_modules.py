@@ -1255,6 +1255,36 @@ def test_window_order_fold_in_the_bench_network(pkg):
     assert producer(auto)[0]._plan is not None and producer(auto)[0]._plan.get("keep") is None
 
 
+@pytest.mark.parametrize("flip", ["exactF32", "CBINFER_NO_SPLIT"])
+@pytest.mark.parametrize("consumer,window_order", [(1, False), (2, True)])
+def test_folded_detection_follows_its_consumer_off_the_split_path(pkg, monkeypatch, flip, consumer, window_order):
+    """a producer that runs its consumer's pooled change detection in its own launch (the row-pair 3 -> 16
+    layer for the 16 -> 64 one; the 16 -> 64 layer in window order for the 64 -> 256 one) must stop doing so in the very
+    frame the consumer leaves the split-state kernels -- exactF32 set, or CBINFER_NO_SPLIT=1, between two steady frames.
+    Otherwise the producer refreshes the consumer's state and the consumer, on another path, finds nothing changed and keeps
+    stale outputs.  Outputs and states equal those of a twin without the fold, frame by frame."""
+    import bench
+    _, fused = bench.build_bench_model(window_order=window_order)
+    _, plain = bench.build_bench_model(fuse_detect=False)
+    convs = lambda net: [m for m in net.modules() if type(m) is pkg.CBConv2d]
+    frames = bench.bench_video(93).frames(8)
+    with torch.no_grad():
+        for t, f in enumerate(frames):
+            if t == 4:
+                assert convs(fused)[consumer - 1]._plan.get("keep") is not None      # (the fold runs up to here)
+                if flip == "exactF32":
+                    convs(fused)[consumer].exactF32 = convs(plain)[consumer].exactF32 = True
+                else:
+                    monkeypatch.setenv("CBINFER_NO_SPLIT", "1")
+            yf, yp = fused(f), plain(f)
+            torch.cuda.synchronize()
+            assert torch.equal(yf, yp), t
+            for a, b in zip(convs(fused), convs(plain)):
+                assert torch.equal(a.prevOutput, b.prevOutput), t
+                assert torch.equal(a.prevInput, b.prevInput), t
+    assert not convs(fused)[consumer]._split_ok(torch.float32, *convs(fused)[consumer].prevInput.shape[-2:])
+
+
 @pytest.mark.parametrize("name", ["seq_half", "seq_half_k3"])
 @pytest.mark.parametrize("sync", [False, True])
 def test_golden_sequences_half(pkg, golden_dir, name, sync):
