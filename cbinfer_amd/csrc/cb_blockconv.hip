@@ -80,29 +80,15 @@ __device__ __forceinline__ unsigned long long cb_uniform64(unsigned long long v)
            (unsigned)__builtin_amdgcn_readfirstlane((int)v);
 }
 
-#ifdef CB_BLK_STAMP
-// diagnostic build only (make EXTRA=-DCB_BLK_STAMP): per-workgroup time stamps (100 MHz constant clock);
-// slots 0..15: multiplier wave 0 (entry, prologue done, after barrier c = 2+c, loop done, end), 16..31: stager
-__device__ unsigned long long cb_blk_stamps[2048 * 32];
-#define CB_BSTAMP(who, i)                                                                            \
-    do {                                                                                             \
-        const unsigned bid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;         \
-        if (threadIdx.x == ((who) ? 512 : 0) && bid < 2048 && (i) < 16)                              \
-            cb_blk_stamps[bid * 32 + (who) * 16 + (i)] = __builtin_amdgcn_s_memrealtime();           \
-    } while (0)
-#else
-#define CB_BSTAMP(who, i)
-#endif
 #define CB_BLK_THREADS 768   // at most: 8 multiplier waves (4 channel tiles x 2 k-halves) + 4 stager waves
 #define CB_BLK_SPT 3         // patch pixels per stager thread (PR*PC <= 768)
 
-// MG = 16-channel tiles per workgroup (2 MG multiplier waves + 4 stager waves): 4 for wide layers; 2 for layers
-// of at most 64 output channels, whose units are too few to fill the chip with four tiles each
+// R = mask rows per unit, MG = 16-channel tiles per workgroup (2 MG multiplier waves + 4 stager waves); the library
+// launches <2, 2> (blk_geom)
 template <int R, int MG>
 __global__ __launch_bounds__(64 * (2 * MG + 4)) void cb_blockconv_kernel(BlkParams p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];   // patch [2 buffers][3 planes][PR][PC] x 16 B
     constexpr int NTMAX = 4 * R;
-    CB_BSTAMP(0, 0);
     const int tx = blockIdx.x, y0 = blockIdx.y * R, mg = blockIdx.z;
     unsigned long long word[R];
     bool any = false;
@@ -201,17 +187,14 @@ __global__ __launch_bounds__(64 * (2 * MG + 4)) void cb_blockconv_kernel(BlkPara
                 }
             }
         };
-        CB_BSTAMP(1, 0);
         gather(va, 0);
         for (int c = 0; c < p.CH; c += 2) {
             if (c + 1 < p.CH) gather(vb, c + 1);
             put(va, c);
-            CB_BSTAMP(1, 1 + c);
             __syncthreads();   // barrier c (the multipliers run CH of them as well)
             if (c + 1 < p.CH) {
                 if (c + 2 < p.CH) gather(va, c + 2);
                 put(vb, c + 1);
-                CB_BSTAMP(1, 2 + c);
                 __syncthreads();   // barrier c + 1
             }
         }
@@ -260,7 +243,6 @@ __global__ __launch_bounds__(64 * (2 * MG + 4)) void cb_blockconv_kernel(BlkPara
         for (int r = 0; r < 4; ++r)
             bv[r] = p.bias ? p.bias[min(min(mt, p.MT - 1) * 16 + 4 * kg + r, p.K - 1)] : 0.f;
 
-        CB_BSTAMP(0, 1);
         const uint4* Aw = p.wb + (long)min(mt, p.MT - 1) * p.CH * p.SPC * 192 + lane;   // step: 3 planes x 64 lanes
         // Weight fragments: a ring of four register sets, the loads of step s+4 are issued while step s is
         // multiplied (a step is only 12..48 MFMAs = 0.1..0.4 us: one step of look-ahead does not cover an L2
@@ -331,7 +313,6 @@ __global__ __launch_bounds__(64 * (2 * MG + 4)) void cb_blockconv_kernel(BlkPara
 #define CB_BLK_STEP(A, J)                                                                           \
     if ((J) < own) {                                                                                \
         if (fresh) {                                                                                \
-            CB_BSTAMP(0, 2 + c);                                                                    \
             __syncthreads(); /* barrier c: chunk c staged, every multiplier done with chunk c-1 */  \
             pat = lds + (c & 1) * bufBytes;                                                         \
             fresh = false;                                                                          \
@@ -379,7 +360,6 @@ __global__ __launch_bounds__(64 * (2 * MG + 4)) void cb_blockconv_kernel(BlkPara
             for (int s = 0; s < NTMAX; ++s)
                 if (s < nTt) acc[s] += *(const floatx4*)(lds + (((wave % MG) * NTMAX + s) * 64 + lane) * 16);
         }
-        CB_BSTAMP(0, 14);
         // ---- bias / ReLU / scatter: D tile col = lane % 16 (pixel), rows 4 (lane/16) + r (channel) ----------
         if (active && kh == 0) {
 #pragma unroll
@@ -404,7 +384,6 @@ __global__ __launch_bounds__(64 * (2 * MG + 4)) void cb_blockconv_kernel(BlkPara
             }
         }
     }
-    CB_BSTAMP(0, 15);
     // the last consumer of the unit zeroes its mask words (and the counter) for the next frame's detection
     if (t == 0) {
         if (gridDim.z == 1 || arrived == (int)gridDim.z - 1) {
@@ -428,24 +407,8 @@ BlkGeom blk_geom(int C, int K, int kH, int kW) {
     g.SPC = kH * g.KXQ;
     g.MT = (K + 15) / 16;
     g.MG = 2;   // two tiles per workgroup, two workgroups per CU: 65 vs 68 us (64->256, 27 %), 117 vs 131 (100 %)
-    {
-        static int mgo = -1;
-        if (mgo < 0) {
-            const char* e = getenv("CBINFER_BLK_MG");   // tuning aid
-            mgo = e ? atoi(e) : 0;
-        }
-        if (mgo == 2 || mgo == 4) g.MG = mgo;
-    }
     g.ZM = (g.MT + g.MG - 1) / g.MG;
     g.R = 2;   // measured on 16->64 @160x240, 18 % changed: 18.7 us with two-row units, 22 with one-row units
-    {
-        static int rr = -1;
-        if (rr < 0) {
-            const char* e = getenv("CBINFER_BLK_R");   // tuning aid
-            rr = e ? atoi(e) : 0;
-        }
-        if (rr == 1 || rr == 2) g.R = rr;
-    }
     g.PR = g.R + kH - 1;
     g.PC = 64 + 4 * g.KXQ;
     g.PLANE = g.PR * g.PC * 16;
@@ -545,14 +508,7 @@ static int cb_blocks_launch(const float* state, uint64_t* bits, int32_t* arrive,
     p.reluOut = reluOut;
     p.wpr = cbinfer_mask_words_per_row(W);
     dim3 grid(p.wpr, (H + g.R - 1) / g.R, g.ZM), block(64 * (2 * g.MG + 4));
-    if (g.R == 2 && g.MG == 4)
-        hipLaunchKernelGGL((cb_blockconv_kernel<2, 4>), grid, block, (size_t)g.ldsBytes, (hipStream_t)stream, p);
-    else if (g.R == 2)
-        hipLaunchKernelGGL((cb_blockconv_kernel<2, 2>), grid, block, (size_t)g.ldsBytes, (hipStream_t)stream, p);
-    else if (g.MG == 4)
-        hipLaunchKernelGGL((cb_blockconv_kernel<1, 4>), grid, block, (size_t)g.ldsBytes, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL((cb_blockconv_kernel<1, 2>), grid, block, (size_t)g.ldsBytes, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((cb_blockconv_kernel<2, 2>), grid, block, (size_t)g.ldsBytes, (hipStream_t)stream, p);   // (g.R, g.MG)
     return cb_launch_status();
 }
 
@@ -572,14 +528,3 @@ int cbinfer_conv_accumulate_blocks(const float* delta, uint64_t* bits, int32_t* 
 }
 
 }  // extern "C"
-
-#ifdef CB_BLK_STAMP
-extern "C" int cbinfer_debug_blk_stamps(void* host, long bytes, int clear) {
-    if (clear) {
-        void* d = nullptr;
-        if (hipGetSymbolAddress(&d, HIP_SYMBOL(cb_blk_stamps)) != hipSuccess) return -1;
-        return (int)hipMemset(d, 0, sizeof(cb_blk_stamps));
-    }
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(cb_blk_stamps), (size_t)bytes);
-}
-#endif

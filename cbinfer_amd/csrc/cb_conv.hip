@@ -201,8 +201,6 @@ struct ConvParams {
     int32_t* listOut;                 // the list and its length are written out as a by-product
     int32_t* countOut;
     void* reluOut;                    // EPI_SCATTER_ACC: optional second plane set receiving relu(out)
-    int dbg;                          // diagnostic ablations (CBINFER_CONV_DBG): 1 no gather loads, 2 no weight loads
-    int xcdMap;                       // XCD-aware item order (CBINFER_XCD_MAP=0 switches it off)
     int seam;                         // split-K slices are summed by a second launch (cb_splitk_reduce_kernel)
     const int32_t* upstream;          // SELFC, optional: the producing layer's change count of this frame (0: skip)
 };
@@ -308,39 +306,11 @@ __device__ __forceinline__ void cb_clear_mask(const ConvParams& p) {
 //             adds, the image-bounds test and a select.  The load goes through a raw buffer descriptor
 //             over the layer state: an out-of-image tap gets an out-of-range offset, for which the
 //             hardware returns 0.
-#ifdef CB_STAMP
-// diagnostic build only (make EXTRA=-DCB_STAMP): per-workgroup phase time stamps (100 MHz constant clock)
-__device__ unsigned long long cb_stamp_buf[1024 * 8];
-__device__ unsigned long long cb_stamp_clk[1024 * 2];   // s_memtime (shader clock) at entry / exit
-// wide (MS = 2) kernel: shader-clock stamps of waves 0 (store first) and 8 (MFMA first) of workgroup 8 over
-// its first 24 stages: [wave][stage][after barrier, after first segment, after second, after third]
-__device__ unsigned long long cb_stage_clk[2 * 24 * 4];
-#define CB_STAGE_STAMP(pt)                                                                          \
-    do {                                                                                            \
-        if (blockIdx.x == 8 && (t == 0 || t == 512) && cb_stage_no < 24 && cb_stamp_first)          \
-            cb_stage_clk[((t >> 9) * 24 + cb_stage_no) * 4 + (pt)] = __builtin_amdgcn_s_memtime();  \
-    } while (0)
-#define CB_STAMP_AT(i)                                                                        \
-    do {                                                                                      \
-        if (threadIdx.x == 0 && blockIdx.x < 1024 && cb_stamp_first)                          \
-            cb_stamp_buf[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime();            \
-    } while (0)
-#else
-#define CB_STAMP_AT(i)
-#define CB_STAGE_STAMP(pt)
-#endif
 #define CB_SKMAX 8
 #define CB_SKMAX_SEAM 32   // slices per tile when a second launch sums them
-#ifndef CB_WIDE_IL
-#define CB_WIDE_IL 0
-#endif
-// diagnostic ablations of the X3 kernel are a build option (make EXTRA=-DCB_CONV_DBG): as run-time
-// branches around the stage loads they would cost the loop its counted vmcnt waits
-#ifdef CB_CONV_DBG
-#define CB_DBG(bit) (p.dbg & (bit))
-#else
-#define CB_DBG(bit) false
-#endif
+// split-K target: work items per CU (a short list is split along k until it has this many)
+#define CB_SK_TARGET 2
+static_assert(CB_SK_TARGET <= CB_CONV_GRID_PER_CU, "one slab per work item: items <= workgroups");
 // X3: the same kernel with every f32 operand split into three bf16 terms (cb_split3) and the six cross
 // products that matter -- hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi; the dropped ones are below 2^-24
 // of the product -- issued on v_mfma_f32_32x32x16_bf16 with f32 accumulation: f32-level accuracy at 16/6
@@ -382,11 +352,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
     static_assert(!X3 || (KS == 2 && MODE == CB_MODE_GATHER && B_PER_T % 4 == 0), "X3: 16 k per wave group");
     static_assert(2 * (A_STAGE + B_STAGE) >= RED, "reduce buffer");
 
-#ifdef CB_STAMP
-    bool cb_stamp_first = true;
-    if (threadIdx.x == 0 && blockIdx.x < 1024) cb_stamp_clk[blockIdx.x * 2] = __builtin_amdgcn_s_memtime();
-#endif
-    CB_STAMP_AT(0);
     const int t = threadIdx.x;
     CB_UPSTREAM_IDLE_EXIT
     // ---- SELFC: stream compaction folded into this kernel -------------------------------------------
@@ -457,10 +422,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
     // Split-K slice count (at most ~sqrt(3.4 P) <= 8: the reducer costs ~4 us of fences + ~1 us per slab)
     int SK = 1;
     const int cus = (int)gridDim.x / GPC;
-#ifndef CB_SK_TARGET
-#define CB_SK_TARGET 2
-#endif
-    static_assert(CB_SK_TARGET <= CB_CONV_GRID_PER_CU, "one slab per work item: items <= workgroups");
     // Measured in the frame (not on warm re-launches, which mislead here): a deep contraction (>= 1024 k)
     // with at least half a grid of tiles fills two workgroups per CU; everything else is only split as far
     // as every slice still gets a CU of its own -- below that the slab round trip (~8 us) costs more than
@@ -511,14 +472,13 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
     const int bj = MODE == CB_MODE_GATHER ? t % BN : t / BK;
     const int br = MODE == CB_MODE_GATHER ? __builtin_amdgcn_readfirstlane(t / BN) * B_PER_T : t % BK;
 
-    CB_STAMP_AT(1);
     // XCD-aware item order.  Workgroups are dealt round-robin over the 8 XCDs (blockIdx.x % 8 names the
     // XCD's peers; gridDim.x is a multiple of 8), and each XCD has its own 4 MB L2.  With the natural order
     // every XCD works on every output-channel tile and streams the WHOLE filter bank (3.2 MB f32 / 4.8 MB
     // split: it does not stay in one L2); here the m-tile is a function of item % 8, so an XCD only ever
     // touches the weights of 8/MT... of its own m-tile(s) and finds them in its L2.  Pure re-indexing: item
     // <-> (n-tile, m-tile, slice) stays a bijection, nothing is assumed about placement for correctness.
-    const bool xmap = p.xcdMap && (MT == 1 || MT == 2 || MT == 4 || MT == 8) && (gridDim.x & 7) == 0;
+    const bool xmap = (MT == 1 || MT == 2 || MT == 4 || MT == 8) && (gridDim.x & 7) == 0;
     const int itemsP = xmap ? (items + 7) & ~7 : items;
     for (int itemL = blockIdx.x; itemL < itemsP; itemL += gridDim.x) {
         int tile, slice;
@@ -637,9 +597,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
                 const int f = X3 ? min(t + i * NT, A_F4 - 1) : t + i * NT;   // (X3: every thread loads, the
                 if (A_F4 % NT == 0 || f < A_F4) {                            //  surplus is not stored)
                     float4 v;
-                    if (X3 && CB_DBG(2)) {
-                        v = make_float4(1.f, 1.f, 1.f, 1.f);
-                    } else if (X3) {   // 12 chunks per row and stage in the pre-split layout: the thread's
+                    if (X3) {   // 12 chunks per row and stage in the pre-split layout: the thread's
                         // byte offset is fixed per item (aoff), the stage goes in as the scalar offset
                         typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
                         typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -658,9 +616,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
             }
             if (!DOB) {
                 return;
-            } else if (X3 && CB_DBG(1)) {
-#pragma unroll
-                for (int i = 0; i < B_PER_T; ++i) breg[i] = 1.0f;
             } else if (MODE == CB_MODE_GATHER && FAST) {
 #pragma unroll
                 for (int i = 0; i < B_PER_T; ++i)
@@ -696,7 +651,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
                 // (MS == 2: the surplus threads re-write the last chunk -- same address, same value as its
                 //  owner -- so that the stage body stays one basic block for the scheduler)
                 const int f = MS == 2 ? min(t + i * NT, A_F4 - 1) : t + i * NT;
-                if (X3 && CB_DBG(256)) continue;   // (diagnostic: no weight LDS writes)
                 if (MS == 2 || A_F4 % NT == 0 || f < A_F4)
                     *(float4*)(as + (X3 ? (f / 12) * LDK + (f % 12) * 4 : (f / (BK / 4)) * LDK + (f % (BK / 4)) * 4)) =
                         make_float4(areg[4 * i], areg[4 * i + 1], areg[4 * i + 2], areg[4 * i + 3]);
@@ -709,7 +663,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
                     uint2 h2, m2, l2;
                     cb_split3t_x4(x4, h2, m2, l2);
                     char* row = (char*)(bs + bj * LDK) + (br + q * 4) * 2;
-                    if (CB_DBG(512)) continue;   // (diagnostic: split, but no pixel-operand LDS writes)
                     *(uint2*)(row) = h2;
                     *(uint2*)(row + 64) = m2;
                     *(uint2*)(row + 128) = l2;
@@ -749,7 +702,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
                 const bf16x8 bm = *(const bf16x8*)(bp + 64), am = *(const bf16x8*)(ap + 64);
                 const bf16x8 al1 = *(const bf16x8*)(ap1 + 128), ah1 = *(const bf16x8*)ap1, am1 = *(const bf16x8*)(ap1 + 64);
                 __builtin_amdgcn_sched_barrier(0);
-                if (CB_DBG(8192)) __builtin_amdgcn_s_setprio(2);   // (diagnostic: MFMA chains win issue)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
@@ -762,10 +714,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am1, bh, acc1, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah1, bm, acc1, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah1, bh, acc1, 0, 0, 0);
-                if (CB_DBG(8192)) __builtin_amdgcn_s_setprio(0);
-#if !CB_WIDE_IL
                 __builtin_amdgcn_sched_barrier(0);
-#endif
                 return;
             }
             if (X3) {
@@ -806,18 +755,9 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
         // that copy lands in the idle LDS buffer and is never multiplied).  The loop is instantiated per (interior-fast-path, wave role) so that
         // its body is branch-free: the compiler's vmcnt bookkeeping stays exact (counted waits that
         // leave the three younger stages in flight) only without control flow between the loads.
-        CB_STAMP_AT(2);
         auto main_loop = [&](auto FASTC, auto MFC) {
             constexpr bool MF = decltype(MFC)::value;
             const std::integral_constant<bool, !(BHALF && MF)> dob;   // (BHALF: the MFMA-first waves = k-group 1)
-#ifdef CB_STAMP
-            int cb_stage_no = 0;
-#define CB_STAGE_NEXT ++cb_stage_no;
-#else
-#define CB_STAGE_NEXT
-#endif
-            if (MS == 2 && MF && CB_DBG(4096)) __builtin_amdgcn_s_setprio(1);   // (diagnostic: younger half wins issue)
-            if (MS == 2 && !MF && CB_DBG(16384)) __builtin_amdgcn_s_setprio(1);  // (diagnostic: older half wins)
             if (MS == 2) {
                 // the 16-wave form keeps ONE staging set (128 registers per wave: two accumulators and nine
                 // fragment registers come first): the loads of stage s+2 are issued during stage s+1... i.e.
@@ -827,41 +767,17 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
                 store_stage(dob, 0, a0, b0);
                 load_stage(FASTC, dob, min(kBeg + BK, kLast), a0, b0);
                 __syncthreads();
-#if CB_WIDE_IL
-                // every wave: fragment reads, then the twelve MFMAs with the next stage's LDS writes, address
-                // arithmetic and loads dealt into the gaps between them
 #define CB_STAGE2(BUF, KNEXT)                                     \
-                compute(BUF);                                         \
-                store_stage(dob, (BUF) ^ 1, a0, b0);                       \
-                load_stage(FASTC, dob, min(KNEXT, kLast), a0, b0);         \
-                _Pragma("unroll") for (int g_ = 0; g_ < 12; ++g_) {   \
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);\
-                    __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);\
-                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);\
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);\
+                if (MF) {                                             \
+                    compute(BUF);                                     \
+                    store_stage(dob, (BUF) ^ 1, a0, b0);              \
+                    load_stage(FASTC, dob, min(KNEXT, kLast), a0, b0); \
+                } else {                                              \
+                    store_stage(dob, (BUF) ^ 1, a0, b0);              \
+                    load_stage(FASTC, dob, min(KNEXT, kLast), a0, b0); \
+                    compute(BUF);                                     \
                 }                                                     \
                 __syncthreads();
-#else
-#define CB_STAGE2(BUF, KNEXT)                                     \
-                CB_STAGE_STAMP(0);                                    \
-                if (MF) {   /* (diagnostic bits 1024 / 2048: these waves ONLY multiply / only stage) */ \
-                    if (!CB_DBG(8 | 2048)) compute(BUF);              \
-                    CB_STAGE_STAMP(1);                                \
-                    if (!CB_DBG(4 | 1024)) store_stage(dob, (BUF) ^ 1, a0, b0);   \
-                    CB_STAGE_STAMP(2);                                \
-                    if (!CB_DBG(16 | 1024)) load_stage(FASTC, dob, min(KNEXT, kLast), a0, b0);     \
-                    CB_STAGE_STAMP(3);                                \
-                } else {    /* (1024: these waves only stage; 2048: only multiply) */ \
-                    if (!CB_DBG(4 | 2048)) store_stage(dob, (BUF) ^ 1, a0, b0);   \
-                    CB_STAGE_STAMP(1);                                \
-                    if (!CB_DBG(16 | 2048)) load_stage(FASTC, dob, min(KNEXT, kLast), a0, b0);     \
-                    CB_STAGE_STAMP(2);                                \
-                    if (!CB_DBG(8 | 1024)) compute(BUF);              \
-                    CB_STAGE_STAMP(3);                                \
-                }                                                     \
-                CB_STAGE_NEXT                                         \
-                __syncthreads();
-#endif
                 for (int k0 = kBeg; k0 < kEnd; k0 += 2 * BK) {
                     CB_STAGE2(0, k0 + 2 * BK)
                     if (k0 + BK >= kEnd) break;
@@ -914,12 +830,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
         };
         typedef std::integral_constant<bool, true> cb_true;
         typedef std::integral_constant<bool, false> cb_false;
-        bool mfmaFirst = (KS > 1) && (__builtin_amdgcn_readfirstlane(ks) & 1);
-        if (!BHALF) {   // (BHALF ties the roles to the k-group)
-            if (CB_DBG(32)) mfmaFirst = true;                      // (diagnostic: no stagger)
-            if (CB_DBG(64)) mfmaFirst = (wave >> 2) & 1;           // (diagnostic: stagger by wave quartets)
-            if (CB_DBG(128)) mfmaFirst = wave & 1;                 // (diagnostic: stagger by wave parity)
-        }
+        const bool mfmaFirst = (KS > 1) && (__builtin_amdgcn_readfirstlane(ks) & 1);
         const bool fastU = __builtin_amdgcn_readfirstlane((int)fast) != 0;
         if (fastU) {
             if (mfmaFirst)
@@ -933,7 +844,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
                 main_loop(cb_false(), cb_false());
         }
         // (the loop ends on a barrier: all LDS stage reads are done and smem may be reused)
-        CB_STAMP_AT(3);
 
         if (KS > 1) {   // sum the wave groups' partial tiles through LDS (fixed order: deterministic)
             float* red = smem + (wq * MS * 16) * 64 + lane;
@@ -960,7 +870,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
             }
         }
 
-        CB_STAMP_AT(4);
         // one output value: bias / ReLU / the form of the store
         auto emit = [&](int m, int n, int pix, float v) {
             if (EPI != CB_EPI_SCATTER_ACC) {
@@ -1007,10 +916,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
             }
 #undef CB_PUBLISH
             if (p.seam) {   // the slices meet in the next launch: nothing to wait for here
-                CB_STAMP_AT(5);
-#ifdef CB_STAMP
-                cb_stamp_first = false;
-#endif
                 continue;
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1031,10 +936,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
             __syncthreads();
             const bool last = s_last != 0;
             __syncthreads();   // s_last may be rewritten by the next item
-            CB_STAMP_AT(5);
-#ifdef CB_STAMP
-            if (!last) cb_stamp_first = false;
-#endif
             if (!last) continue;
             // every thread: TILE / 4 / NT chunks, all slices of a chunk in flight together
 #pragma unroll
@@ -1063,10 +964,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
                     if (m + 3 < p.K) emit(m + 3, n, pix, s3);
                 }
             }
-            CB_STAMP_AT(6);
-#ifdef CB_STAMP
-            cb_stamp_first = false;
-#endif
             continue;
         }
 
@@ -1085,16 +982,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
                 emit(m, n, pix, rr < 16 ? acc[r] : acc1[r]);
             }
         }
-        CB_STAMP_AT(6);
-#ifdef CB_STAMP
-        cb_stamp_first = false;
-#endif
     }
-#ifdef CB_STAMP
-    cb_stamp_first = true;
-    if (threadIdx.x == 0 && blockIdx.x < 1024) cb_stamp_clk[blockIdx.x * 2 + 1] = __builtin_amdgcn_s_memtime();
-#endif
-    CB_STAMP_AT(7);
 
     if (SELFC && N > 0) {
         // every workgroup has read the mask: the last one to get here flips the parity for the next frame.  (An EMPTY
@@ -1261,10 +1149,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void cb_mfma_f16_kernel(ConvPara
     // ~1 us per slab, a stage pair ~1.7 us, so the best slice count is ~sqrt(1.7 P).
     int SK = 1;
     const int cus = (int)gridDim.x / CB_CONV_GRID_PER_CU;
-#ifndef CB_SK_TARGET
-#define CB_SK_TARGET 2
-#endif
-    static_assert(CB_SK_TARGET <= CB_CONV_GRID_PER_CU, "one slab per work item: items <= workgroups");
     if (p.slabs && T > 0 && T < CB_SK_TARGET * cus && P >= 8)
         SK = max(1, min(min(CB_SKMAX, (CB_SK_TARGET * cus) / T), (int)sqrtf(1.7f * (float)P)));
     const int items = T * SK;
@@ -1615,9 +1499,8 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void cb_mfma_f16_kernel(ConvPara
     }
 }
 
-// Tile configuration.  cfg = 100*WM + 10*WN + KS; the CBINFER_CONV_CFG environment variable overrides
-// the heuristic (tuning aid).  KP == 32 (K <= 32): one m-tile, 128 pixels per workgroup; otherwise
-// 64 x 64.  KS (in-block split-K): 2 unless the k-depth is a single stage.
+// Tile configuration: KP == 32 (K <= 32): one m-tile, 128 pixels per workgroup (1 x 4 waves); otherwise
+// 64 x 64 (2 x 2 waves).  KS (in-block split-K) = 2.
 int cb_num_cus() {
     static int cus = 0;
     if (cus == 0) {
@@ -1676,52 +1559,17 @@ int cb_ckkpad(int Ckk, int dtype) {
 // bf16x3 arithmetic, 16-wave forms: 2 = 256 channels x 64 pixels (output channels in multiples of 256: a
 // staged pixel row feeds all of them, and per-value work on the vector ALU -- which does NOT hide under other
 // waves' MFMAs here -- is what the stage pays for), 1 = 128 x 128 (multiples of 128), 0 = the 64 x 64 form.
-// CBINFER_X3_WIDE caps the choice.
 int cb_x3_wide(int KP) {
-    static int cap = -1;
-    if (cap < 0) {
-        const char* e = getenv("CBINFER_X3_WIDE");
-        cap = e ? atoi(e) : 2;
-    }
-    if (cap >= 2 && KP % 256 == 0) return 2;
-    if (cap >= 1 && KP % 128 == 0) return 1;
+    if (KP % 256 == 0) return 2;
+    if (KP % 128 == 0) return 1;
     return 0;
-}
-
-int conv_cfg_override() {
-    const char* e = getenv("CBINFER_CONV_CFG");
-    return e ? atoi(e) : 0;
-}
-int conv_dbg() {
-    static int d = -1;
-    if (d < 0) {
-        const char* e = getenv("CBINFER_CONV_DBG");
-        d = e ? atoi(e) : 0;
-    }
-    return d;
 }
 
 template <int MODE, int EPI>
 int launch_mfma(const ConvParams& p0, int dtype, hipStream_t s) {
     ConvParams p = p0;
-    p.dbg = conv_dbg();
-    {   // split-K slices summed by a second launch (scatter epilogues with a workspace); CBINFER_SPLITK_SEAM=0:
-        // by each tile's last workgroup inside the one launch
-        static int seam = -1;
-        if (seam < 0) {
-            const char* e = getenv("CBINFER_SPLITK_SEAM");
-            seam = e ? atoi(e) : 1;
-        }
-        p.seam = seam && p.slabs && EPI >= CB_EPI_SCATTER && (dtype == CB_F32 || dtype == CB_F32S);
-    }
-    {
-        static int xm = -1;
-        if (xm < 0) {
-            const char* e = getenv("CBINFER_XCD_MAP");
-            xm = e ? atoi(e) : 1;
-        }
-        p.xcdMap = xm;
-    }
+    // split-K slices summed by a second launch (scatter epilogues with a workspace)
+    p.seam = p.slabs && EPI >= CB_EPI_SCATTER && (dtype == CB_F32 || dtype == CB_F32S);
     const bool narrow = p.KP <= 32;
     if (dtype == CB_F32S) {   // f32 tensors, bf16x3 split products (gather modes only)
         if constexpr (MODE == CB_MODE_GATHER && EPI >= CB_EPI_SCATTER) {
@@ -1740,26 +1588,14 @@ int launch_mfma(const ConvParams& p0, int dtype, hipStream_t s) {
         }
     }
     if (dtype == CB_F32) {
-        int cfg = conv_cfg_override();
-        if (cfg == 0) cfg = narrow ? 142 : 222;
-        if (narrow && cfg / 100 != 1) cfg = 142;
-        if (p.frameMasks) {   // self-compacting frame pipeline: only the default configurations
+        if (p.frameMasks) {   // self-compacting frame pipeline
             if (MODE != CB_MODE_GATHER || EPI < CB_EPI_SCATTER) return CB_ERR_BADARG;
             constexpr int E = EPI < CB_EPI_SCATTER ? CB_EPI_SCATTER : EPI;
             if (narrow) return launch_f32<1, 4, 2, CB_MODE_GATHER, E, true>(p, s);
             return launch_f32<2, 2, 2, CB_MODE_GATHER, E, true>(p, s);
         }
-        switch (cfg) {
-            case 141: return launch_f32<1, 4, 1, MODE, EPI>(p, s);
-            case 142: return launch_f32<1, 4, 2, MODE, EPI>(p, s);
-            case 121: return launch_f32<1, 2, 1, MODE, EPI>(p, s);
-            case 122: return launch_f32<1, 2, 2, MODE, EPI>(p, s);
-            case 124: return launch_f32<1, 2, 4, MODE, EPI>(p, s);
-            case 221: return launch_f32<2, 2, 1, MODE, EPI>(p, s);
-            case 222: return launch_f32<2, 2, 2, MODE, EPI>(p, s);
-            case 224: return launch_f32<2, 2, 4, MODE, EPI>(p, s);
-            default: return CB_ERR_BADARG;
-        }
+        if (narrow) return launch_f32<1, 4, 2, MODE, EPI>(p, s);
+        return launch_f32<2, 2, 2, MODE, EPI>(p, s);
     }
     if (p.frameMasks) {
         if (MODE != CB_MODE_GATHER || EPI != CB_EPI_SCATTER) return CB_ERR_BADARG;
@@ -2000,15 +1836,3 @@ long cbinfer_frame_mask_copy_offset(int H, int W) { return 2 * cbinfer_mask_word
 int cbinfer_frame_mask_max_words(void) { return CB_SELFC_MAXW; }
 
 }  // extern "C"
-
-#ifdef CB_STAMP
-extern "C" int cbinfer_debug_stamps(void* host, long bytes) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(cb_stamp_buf), (size_t)bytes);
-}
-extern "C" int cbinfer_debug_stage_clocks(void* host, long bytes) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(cb_stage_clk), (size_t)bytes);
-}
-extern "C" int cbinfer_debug_clocks(void* host, long bytes) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(cb_stamp_clk), (size_t)bytes);
-}
-#endif

@@ -51,7 +51,6 @@ struct RowParams {
     int relu, wpr;
     int MCH, MCW;           // 16-row output-channel chunks in all / per workgroup (4 waves each)
     int halves;             // 1: one workgroup per word; 2: words with more than 32 pixels are shared by two
-    int dbg;                // diagnostic ablations (CBINFER_ROW_DBG): 1 no staging loads, 2 no k-loop, 4 no stores
     // several sequences in one launch (nSeq > 1): blockIdx.y = sequence * H + row, the per-sequence tensors
     // come from this table instead of the fields above
     int nSeq;
@@ -79,17 +78,6 @@ __device__ __forceinline__ int cb_nth_bit(unsigned long long w, int r) {
     return pos;
 }
 
-#ifdef CB_ROW_STAMP
-// diagnostic build only (make EXTRA=-DCB_ROW_STAMP): per-workgroup phase time stamps (100 MHz constant clock)
-__device__ unsigned long long cb_row_stamps[8192 * 8];
-#define CB_RSTAMP(i)                                                                              \
-    do {                                                                                          \
-        const unsigned bid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;      \
-        if (threadIdx.x == 0 && bid < 8192) cb_row_stamps[bid * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#else
-#define CB_RSTAMP(i)
-#endif
 #define CB_ROW_MAXW 16           // waves per workgroup: 4 per output-channel chunk, up to 4 chunks
 #define CB_ROW_MAXROWS 256
 #define CB_ROW_BG 3             // groups (16-byte weight loads per lane) per block
@@ -147,7 +135,6 @@ __global__ __launch_bounds__(64 * CB_ROW_MAXW) void cb_rowconv_f32_kernel(RowPar
     cb_touch_kernarg<sizeof(RowParams)>();
     extern __shared__ float lds[];   // patch [CP][CS] | red [waves][64][4]
     constexpr bool CT = KH > 0;
-    CB_RSTAMP(0);
     RowParams p = pin;
     int y = blockIdx.y;
     if (pin.nSeq > 1) {
@@ -169,7 +156,6 @@ __global__ __launch_bounds__(64 * CB_ROW_MAXW) void cb_rowconv_f32_kernel(RowPar
         if (blockIdx.z == 0 && threadIdx.x == 0) p.maskCopy[widx] = 0ull;
         return;
     }
-    CB_RSTAMP(1);
     const int pc = __popcll(word);
     const int nT = (pc + 15) >> 4;          // 16-pixel tiles in the word
     if (2 * nh >= nT) return;               // the second half exists only for words with more than 32 pixels
@@ -235,8 +221,7 @@ __global__ __launch_bounds__(64 * CB_ROW_MAXW) void cb_rowconv_f32_kernel(RowPar
     //  a 6 us workgroup)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    CB_RSTAMP(2);
-    if (!(p.dbg & 1)) {
+    {
         // the kW-1 columns beyond the 64: TW (power of two >= kW-1) slots per row, flattened over the threads
         int sh = 0;
         while ((1 << sh) < kW - 1) ++sh;
@@ -294,19 +279,11 @@ __global__ __launch_bounds__(64 * CB_ROW_MAXW) void cb_rowconv_f32_kernel(RowPar
             request(r0, e0, v, tv);
             deposit(r0, e0, v, tv);
         }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            bv[r] = p.bias ? p.bias[min(min(mc, p.MCH - 1) * 16 + 4 * (lane >> 4) + r, p.K - 1)] : 0.f;
-        loadA(qr, NB);
-        loadA(a0, min(bBeg, bLast));
-        loadA(a1, min(bBeg + 1, bLast));
     }
     floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     __syncthreads();   // patch complete
-    CB_RSTAMP(3);
 
-    if (active && !(p.dbg & 2)) {
+    if (active) {
         const float* pl = lds + base;
         // run-time shape: the walk over the k-steps in (ky, kx, channel group) order, kept in scalar
         // registers; `off` is the LDS offset of the step's tap relative to a lane's base
@@ -375,16 +352,14 @@ __global__ __launch_bounds__(64 * CB_ROW_MAXW) void cb_rowconv_f32_kernel(RowPar
         }
     }
     floatx4 acc = acc0 + acc1;
-    CB_RSTAMP(4);
 
     // ---- sum the k-parts through LDS (fixed order), then bias / ReLU / scatter -------------------------
     float* red = lds + CP * CS;
     if (active && kp > 0) *(floatx4*)(red + (wave * 64 + lane) * 4) = acc;
     __syncthreads();
-    CB_RSTAMP(5);
     if (active && kp == 0) {
         for (int q = 1; q < kparts; ++q) acc += *(const floatx4*)(red + ((wave + q * nTw) * 64 + lane) * 4);
-        if (n < pc && !(p.dbg & 4)) {
+        if (n < pc) {
             const int pix = y * p.W + tx * 64 + xl;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -403,7 +378,6 @@ __global__ __launch_bounds__(64 * CB_ROW_MAXW) void cb_rowconv_f32_kernel(RowPar
             }
         }
     }
-    CB_RSTAMP(6);
     // the last consumer of the word zeroes it (and its counter) for the next frame's detection
     if (t == 0) {
         if (consumers == 1) {
@@ -538,24 +512,8 @@ static int cb_rows_launch(const float* state, uint64_t* bits, int32_t* arrive, u
             p.seq[q].maskCopy = batch->seq[q].maskCopy;
         }
     p.wpr = cbinfer_mask_words_per_row(W);
-    {
-        static int dbg = -1;
-        if (dbg < 0) {
-            const char* e = getenv("CBINFER_ROW_DBG");
-            dbg = e ? atoi(e) : 0;
-        }
-        p.dbg = dbg;
-    }
     p.MCH = g.MCH;
     p.MCW = g.MCW;
-    {
-        static int mcw = -1;
-        if (mcw < 0) {
-            const char* e = getenv("CBINFER_ROW_MCW");   // tuning aid: chunks per workgroup
-            mcw = e ? atoi(e) : 0;
-        }
-        if (mcw > 0 && mcw <= 4) p.MCW = mcw < g.MCH ? mcw : g.MCH;
-    }
     const size_t ldsBytes = ((size_t)g.CP * g.CS + 4 * p.MCW * 64 * 4) * 4;
     // a word with all 64 pixels changed costs 4 tiles x MCW chunks x S MFMA steps on one CU: share heavy
     // words between two workgroups
@@ -606,21 +564,3 @@ int cbinfer_conv_accumulate_rows(const float* delta, uint64_t* bits, int32_t* ar
 }
 
 }  // extern "C"
-
-#ifdef CB_ROW_STAMP
-// (diagnostic build) resident workgroups per CU of the 7x7 form at `threads` threads and `ldsBytes` of dynamic LDS
-extern "C" int cbinfer_debug_row_occupancy(int threads, long ldsBytes) {
-    int n = -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, cb_rowconv_f32_kernel<7, 7, 1>, threads, (size_t)ldsBytes) != hipSuccess)
-        return -1;
-    return n;
-}
-extern "C" int cbinfer_debug_row_stamps(void* host, long bytes, int clear) {
-    if (clear) {
-        void* d = nullptr;
-        if (hipGetSymbolAddress(&d, HIP_SYMBOL(cb_row_stamps)) != hipSuccess) return -1;
-        return (int)hipMemset(d, 0, sizeof(cb_row_stamps));
-    }
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(cb_row_stamps), (size_t)bytes);
-}
-#endif

@@ -711,14 +711,6 @@ static int cbp_launch(const cbPairSeq* seqs, int nSeq, const void* prepared, con
     // are started -- one candidate unit each at 480x320: the empty ones are gone after 1.8 us -- and at most
     // CBP_MAXCAND candidates each beyond that
     long grid = 8l * cbp_num_cus();
-    {
-        static int perCU = -1;
-        if (perCU < 0) {
-            const char* e = getenv("CBINFER_PAIR_WGS_PER_CU");      // tuning aid
-            perCU = e ? atoi(e) : 0;
-        }
-        if (perCU > 0) grid = (long)perCU * cbp_num_cus();
-    }
     if (grid > total) grid = total;
     if (grid * CBP_MAXCAND < total) grid = (total + CBP_MAXCAND - 1) / CBP_MAXCAND;
     if (kH == 7)
