@@ -44,18 +44,19 @@ def _rebuild(container, rule):
     return out
 
 
-def subsitute(node, threshold=1e-1, finegrained=False):
+def subsitute(node, threshold=1e-1, finegrained=False, generalGeometry=False):
     """(module, replaced?): exactly torch.nn.Conv2d -- not a subclass -- becomes a CBConv2d sharing its
-    parameters (reference: __init__.py:10-17; the spelling of the name is the reference's)."""
+    parameters (reference: __init__.py:10-17; the spelling of the name is the reference's).  generalGeometry=True
+    also takes strided, dilated, freely padded and bias-free convolutions (CBConv2d(..., generalGeometry=True))."""
     if type(node) is not nn.Conv2d:
         return node, False
     _log('replacing conv2d')
-    cb = CBConv2d(node, threshold)
+    cb = CBConv2d(node, threshold, generalGeometry=True) if generalGeometry else CBConv2d(node, threshold)
     cb.finegrained = finegrained
     return cb, True
 
 
-def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False):
+def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False, generalGeometry=False):
     """(converted nn.Sequential, anything changed?) for the children of `m` (reference: __init__.py:20-45):
     names preserved; nn.Dropout and the types of ignoreList dropped; nested nn.Sequential containers
     converted recursively -- as in the reference (:28) WITHOUT handing `finegrained` down; every other
@@ -67,12 +68,12 @@ def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False):
 
     def rule(child, before, after):
         if type(child) is nn.Sequential:
-            child, hit = convertRecur(child, ignoreList, threshold)
+            child, hit = convertRecur(child, ignoreList, threshold, generalGeometry=generalGeometry)
         elif type(child) in dropped:
             _log('removing node %s' % (type(child),))
             child, hit = None, True
         else:
-            child, hit = subsitute(child, threshold=threshold, finegrained=finegrained)
+            child, hit = subsitute(child, threshold=threshold, finegrained=finegrained, generalGeometry=generalGeometry)
         outcomes.append(hit)
         return child
 
@@ -113,8 +114,10 @@ def propChangeIndexesOf1x1(rootModule):
     for seq in _sequentials(rootModule):
         kids = list(seq.children())
         for producer, consumer in zip(kids[:-1], kids[1:]):
+            # (a strided or padded 1x1 layer -- general geometry -- does not keep the map: it runs its own detection)
             if (type(producer) == CBConv2d and type(consumer) == CBConv2d and
-                    tuple(consumer.kernel_size) == (1, 1)):
+                    tuple(consumer.kernel_size) == (1, 1) and tuple(consumer.stride) == (1, 1) and
+                    tuple(consumer.padding) == (0, 0)):
                 _log('enabling propagation of change indexes for 1x1')
                 producer.propChangeIndexes = True
     return rootModule
@@ -160,7 +163,9 @@ def fusePoolingIntoDetection(rootModule, enabled=True):
             if type(pool) == CBPoolMax2d:
                 # (a feedback-mode layer, or -- round 4 -- a fine-grained one in its in-place form: its split-state frame
                 #  takes the pool's input as it is, cbinfer_split_forward_fg; other fine-grained frames pool first)
+                # (a general-geometry consumer has no pooled detection: the pool in front of it keeps pooling itself)
                 pool.lazy = bool(enabled and type(consumer) == CBConv2d and not pool.propChangeIndexes and
+                                 not consumer.__dict__.get('_geom') and
                                  ((consumer.feedbackLoop and not consumer.finegrained) or
                                   (consumer.finegrained and consumer.fgInPlace) or
                                   # (a layer that keeps a copy of its input: the copy-all detection of the split-state
@@ -189,7 +194,8 @@ def fuseDetectionIntoProducer(rootModule, enabled=True, windowOrder='auto'):
         kids = list(seq.children())
         for prod, pool, cons in zip(kids[:-2], kids[1:-1], kids[2:]):
             if type(prod) == CBConv2d and type(pool) == CBPoolMax2d and type(cons) == CBConv2d:
-                if enabled and getattr(pool, 'lazy', False) and cons.feedbackLoop and prod.feedbackLoop:
+                if (enabled and getattr(pool, 'lazy', False) and cons.feedbackLoop and prod.feedbackLoop and
+                        not prod.__dict__.get('_geom') and not cons.__dict__.get('_geom')):
                     prod.__dict__['_fusedNext'] = (pool, cons)      # (plain references, not children)
                     prod.__dict__['_winFold'] = windowOrder
                 else:
@@ -210,8 +216,9 @@ def linkConsumers(producer, consumers):
     last output (poseDetection/openPose/PoseModel.py:122-137).  Their change detection then rides in the producer's
     launch whenever that is exact (see fuseDetectionIntoProducer); at most two consumers per producer are folded.  An
     empty list removes the link.  Execution-level only: results do not change."""
-    consumers = [c for c in consumers if type(c) == CBConv2d]
-    if consumers:
+    # (a general-geometry layer neither folds a consumer's detection nor has its own folded)
+    consumers = [c for c in consumers if type(c) == CBConv2d and not c.__dict__.get('_geom')]
+    if consumers and not producer.__dict__.get('_geom'):
         producer.__dict__['_fusedConsumers'] = list(consumers)      # (plain references, not children)
     else:
         producer.__dict__.pop('_fusedConsumers', None)
@@ -236,10 +243,12 @@ def getStateTensors(net):
     return [t for m in _stateful(net) for t in m.getStateTensors()]
 
 
-def convert(m, ignoreList=[], threshold=1e-1):
+def convert(m, ignoreList=[], threshold=1e-1, generalGeometry=False):
     """nn.Sequential in -> nn.Sequential out with every Conv2d replaced by a CBConv2d sharing its
-    weights, ReLUs merged, Dropout removed (reference: __init__.py:91-94)."""
-    converted, _ = convertRecur(m, ignoreList=ignoreList, threshold=threshold)
+    weights, ReLUs merged, Dropout removed (reference: __init__.py:91-94).  generalGeometry=True: strided, dilated,
+    freely padded and bias-free convolutions are converted too (the default stops at them with an AssertionError, as
+    the reference does)."""
+    converted, _ = convertRecur(m, ignoreList=ignoreList, threshold=threshold, generalGeometry=generalGeometry)
     return mergeReLURecur(converted)
 
 

@@ -91,6 +91,14 @@ class HalfLayer(ctypes.Structure):
 
 _hlp = ctypes.POINTER(HalfLayer)
 
+
+class Geom(ctypes.Structure):
+    """cbGeom of include/cbinfer_hip.h: filter size, stride, padding and dilation of a general-geometry layer."""
+    _fields_ = [("kH", _i), ("kW", _i), ("sH", _i), ("sW", _i), ("pH", _i), ("pW", _i), ("dH", _i), ("dW", _i)]
+
+
+_gp, _ip = ctypes.POINTER(Geom), ctypes.POINTER(ctypes.c_int)
+
 _SIGNATURES = {
     # name: (restype, [argtypes])
     "cbinfer_abi_version": (_i, []),
@@ -216,6 +224,15 @@ _SIGNATURES = {
                                                _ndp, _vp]),
     "cbinfer_frame_mask_copy_offset": (_l, [_i, _i]),
     "cbinfer_concat_channels": (_i, [_vpp, ctypes.POINTER(ctypes.c_int32), _i, _vp, _l, _i, _vp]),
+    "cbinfer_geom_out_size": (_i, [_i, _i, _gp, _ip, _ip]),
+    "cbinfer_geom_prepared_weights_bytes": (_l, [_i, _i, _gp, _i]),
+    "cbinfer_geom_prep_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _gp, _i, _vp]),
+    "cbinfer_geom_workspace_bytes": (_l, []),
+    "cbinfer_change_detection_geom": (_i, [_vp, _vp, _vp, _i, _i, _i, _gp, _f, _i, _i, _vp]),
+    "cbinfer_conv_changed_geom": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _gp, _i, _vp, _i,
+                                       _vp]),
+    "cbinfer_cbconv2d_forward_geom": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _gp, _f, _i, _i, _i, _i,
+                                           _i, _vp, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

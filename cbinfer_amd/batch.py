@@ -35,6 +35,12 @@ class SequenceBatch(object):
         self.S = int(sequences)
         if not 1 <= self.S <= C.cbinfer_split_max_sequences():
             raise CBinferError("SequenceBatch: 1..%d sequences per launch" % C.cbinfer_split_max_sequences())
+        for name, m in (net.named_modules() if isinstance(net, torch.nn.Module) else ()):
+            if type(m) is CBConv2d and m.__dict__.get('_geom'):
+                raise CBinferError("SequenceBatch: layer %r is a general-geometry CBConv2d (kernel_size=%s stride=%s "
+                                   "padding=%s dilation=%s%s), which has no batched kernel"
+                                   % (name, tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation),
+                                      '' if m.bias is not None else ', no bias'))
         self.net = net
         self.layers = None          # built on the first frame (needs the frame size)
         self._key = None

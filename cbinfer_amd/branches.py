@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import C, check
+from ._lib import C, CBinferError, check
 from .conv2d import CBConv2d
 
 
@@ -32,6 +32,12 @@ class BranchGroup(nn.Module):
     def __init__(self, branches):
         super(BranchGroup, self).__init__()
         self.branches = nn.ModuleList(branches)
+        for name, m in self.branches.named_modules():
+            if type(m) is CBConv2d and m.__dict__.get('_geom'):
+                raise CBinferError("BranchGroup: layer %r is a general-geometry CBConv2d (kernel_size=%s stride=%s "
+                                   "padding=%s dilation=%s%s), which has no grouped launch"
+                                   % (name, tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation),
+                                      '' if m.bias is not None else ', no bias'))
         self.__dict__['_pairs'] = {}
 
     def _pair_state(self, mods, geom):

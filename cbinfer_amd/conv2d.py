@@ -235,25 +235,37 @@ class CBPoolMax2d(nn.Module):
 class CBConv2d(nn.Module):
     """Change-based 2-D convolution (reference: conv2d.py:87-304)."""
 
-    def __init__(self, m, threshold):
+    def __init__(self, m, threshold, generalGeometry=False):
         super(CBConv2d, self).__init__()
-        assert m.groups == 1 and m.transposed == False
-        assert m.output_padding == (0, 0) and m.padding == (m.kernel_size[-2] // 2,
-                                                             m.kernel_size[-1] // 2)
-        assert m.dilation == (1, 1) and m.stride == (1, 1)
+        self.generalGeometry = bool(generalGeometry)
+        if self.generalGeometry:
+            padding = self._check_general(m)
+        else:
+            assert m.groups == 1 and m.transposed == False
+            assert m.output_padding == (0, 0) and m.padding == (m.kernel_size[-2] // 2,
+                                                                 m.kernel_size[-1] // 2)
+            assert m.dilation == (1, 1) and m.stride == (1, 1)
+            padding = m.padding
         self.groups = m.groups
         self.transposed = m.transposed
         self.output_padding = m.output_padding
-        self.padding = m.padding
+        self.padding = padding
         self.dilation = m.dilation
         self.stride = m.stride
         self.kernel_size = m.kernel_size
         self.in_channels = m.in_channels
         self.out_channels = m.out_channels
 
-        assert m.weight is not None and m.bias is not None
+        assert m.weight is not None and (m.bias is not None or self.generalGeometry)
         self.weight = m.weight   # shared with the source module, as in the reference
         self.bias = m.bias
+        # a layer the unit-geometry kernels cannot take -- stride, dilation, free padding, an even filter size, no bias --
+        # runs on cb_geomconv.hip (_path: 'geom'); any other layer built with generalGeometry=True runs as it always did
+        kH, kW = self.kernel_size
+        self._geom = self.generalGeometry and (
+            tuple(self.stride) != (1, 1) or tuple(self.dilation) != (1, 1) or kH % 2 == 0 or kW % 2 == 0 or
+            tuple(padding) != (kH // 2, kW // 2) or m.bias is None)
+        self._geomC = None
 
         self.threshold = threshold
         self.clearMemory()
@@ -300,14 +312,19 @@ class CBConv2d(nn.Module):
                           ('finegrained', False), ('copyInput', True), ('feedbackLoop', False), ('syncIndexes', False),
                           ('deterministicFG', False), ('atomicFG', False), ('fgInPlace', False), ('exactF32', False),
                           ('dilatePropagatedIndexes', False), ('_work', None), ('_wprep', None),
-                          ('_inputIsLiveState', False), ('_plan', None), ('_wrows', None), ('_lastIndexes', None)):
+                          ('_inputIsLiveState', False), ('_plan', None), ('_wrows', None), ('_lastIndexes', None),
+                          ('generalGeometry', False), ('_geom', False), ('_geomC', None)):
             if name not in self.__dict__:
                 self.__dict__[name] = val
 
     def __getstate__(self):
         d = dict(self.__dict__)
-        d.update(_work=None, _wprep=None, _plan=None, _wrows=None, _lastIndexes=None)      # (transient device buffers)
+        d.update(_work=None, _wprep=None, _plan=None, _wrows=None, _lastIndexes=None, _geomC=None)      # (transient device buffers)
         return d
+
+    def __setstate__(self, state):
+        super(CBConv2d, self).__setstate__(state)
+        self._setDefaultValues()      # (a module pickled before an attribute existed loads with its default)
 
     def lastChangeIndexes(self):
         """The change list of the most recent coarse-grained frame as a ChangeIndexes (None before the first
@@ -318,6 +335,154 @@ class CBConv2d(nn.Module):
         """Forget the cached re-laid-out copies of the filter bank and the call plan -- after a write through
         `weight.data`, which bumps neither the Parameter object nor its version counter."""
         self._wprep = self._wrows = self._plan = None
+
+    # ---------------------------------------------------------------- general geometry (cb_geomconv.hip)
+    @staticmethod
+    def _check_general(m):
+        """The padding of `m` as a pair of ints if CBConv2d(m, th, generalGeometry=True) takes the module: any stride,
+        dilation and zero padding within the library's limits, with or without bias.  CBinferError otherwise."""
+        Err = _lib.CBinferError
+        if not isinstance(m, nn.Conv2d) or m.transposed or tuple(m.output_padding) != (0, 0):
+            raise Err("CBConv2d: only plain nn.Conv2d modules are converted (no transposed convolution)")
+        if m.groups != 1:
+            raise Err("CBConv2d: grouped and depthwise convolutions are not supported (groups=%d)" % m.groups)
+        if m.padding_mode != 'zeros':
+            raise Err("CBConv2d: padding_mode=%r is not supported, only 'zeros'" % (m.padding_mode,))
+        k, d = tuple(m.kernel_size), tuple(m.dilation)
+        if isinstance(m.padding, str):
+            if m.padding == 'valid':
+                padding = (0, 0)
+            elif m.padding == 'same':
+                total = tuple(d[i] * (k[i] - 1) for i in (0, 1))
+                if total[0] % 2 or total[1] % 2:
+                    raise Err("CBConv2d: padding='same' with kernel_size=%s, dilation=%s pads one side more than the "
+                              "other (torch pads %s in total); only symmetric padding is supported" % (k, d, total))
+                padding = (total[0] // 2, total[1] // 2)
+            else:
+                raise Err("CBConv2d: unknown padding %r" % (m.padding,))
+        else:
+            padding = tuple(int(v) for v in m.padding)
+        g = _lib.Geom(k[0], k[1], m.stride[0], m.stride[1], padding[0], padding[1], d[0], d[1])
+        if C.cbinfer_geom_prepared_weights_bytes(m.out_channels, m.in_channels, ctypes.byref(g), _lib.CB_F32) <= 0:
+            raise Err("CBConv2d: kernel_size=%s stride=%s padding=%s dilation=%s is beyond what the library takes "
+                      "(per axis: filter <= 7, stride <= 4, dilation <= 8, padding <= 64)"
+                      % (k, tuple(m.stride), padding, d))
+        return padding
+
+    def _geom_struct(self):
+        """(pointer to) the layer's cbGeom; transient, made again after unpickling."""
+        if self.__dict__.get('_geomC') is None:
+            k, s_, p_, d = self.kernel_size, self.stride, self.padding, self.dilation
+            self.__dict__['_geomC'] = ctypes.pointer(_lib.Geom(k[0], k[1], s_[0], s_[1], p_[0], p_[1], d[0], d[1]))
+        return self.__dict__['_geomC']
+
+    def _out_hw(self, Hi, Wi):
+        """Output map of an Hi x Wi input map (torch's formula; the input map itself for a unit-geometry layer)."""
+        if not self.__dict__.get('_geom'):
+            return Hi, Wi
+        Ho, Wo = ctypes.c_int(), ctypes.c_int()
+        if C.cbinfer_geom_out_size(Hi, Wi, self._geom_struct(), ctypes.byref(Ho), ctypes.byref(Wo)) != 0:
+            raise _lib.CBinferError("CBConv2d: a %dx%d map is smaller than the filter's reach (kernel_size=%s, dilation=%s, "
+                                    "padding=%s)" % (Hi, Wi, tuple(self.kernel_size), tuple(self.dilation),
+                                                     tuple(self.padding)))
+        return Ho.value, Wo.value
+
+    def _geom_workspace(self, input, Ho, Wo):
+        key = (input.size(-2), input.size(-1), input.device, 'geom')
+        if self._work is None or self._work['key'] != key:
+            dev = input.device
+            self._work = dict(
+                key=key, selfc=True,
+                bits=torch.zeros(C.cbinfer_frame_mask_bytes(Ho, Wo) // 8, dtype=torch.int64, device=dev),
+                idx=torch.empty(Ho * Wo, dtype=torch.int32, device=dev),
+                count=torch.zeros(1, dtype=torch.int32, device=dev),
+                conv=torch.zeros(C.cbinfer_geom_workspace_bytes(), dtype=torch.uint8, device=dev),
+                map=None, rows=None, split=None)
+        return self._work
+
+    def _geom_weights(self, Hi, Wi, arith):
+        w = self.weight
+        key = ('geom', w.data_ptr(), w._version, w.dtype, w.device, Hi, Wi, arith)
+        if self._wprep is None or self._wprep[0] != key:
+            K, Cin = w.size(0), w.size(1)
+            g = self._geom_struct()
+            wp = torch.empty(C.cbinfer_geom_prepared_weights_bytes(K, Cin, g, arith), dtype=torch.uint8, device=w.device)
+            check(C.cbinfer_geom_prep_weights(ptr(w.detach().contiguous()), ptr(wp), K, Cin, Hi, Wi, g, arith,
+                                              stream_ptr(w)))
+            self._wprep = (key, wp)
+        return self._wprep[1]
+
+    def _forward_geom(self, inp):
+        """A frame of a general-geometry layer: cbinfer_cbconv2d_forward_geom, two launches, no host sync.  Change list,
+        prevOutput and the indexes handed on live on the OUTPUT map."""
+        Err = _lib.CBinferError
+        changeIndexes = None
+        if isinstance(inp, LazyPool):      # (_path(pooled=True) == 'dense')
+            inp = inp.tensor()
+        src = inp[1] if type(inp) == tuple else inp
+        self._inputIsLiveState = bool(getattr(src, '_cbinfer_inplace_state', False))
+        input = src.detach().contiguous()
+        assert input.dim() == 4 and input.size(0) == 1 and input.size(-3) == self.in_channels
+        require_device(input)
+        assert input.dtype == self.weight.dtype, "input and weights must have the same dtype"
+        K, Cin = self.weight.size(0), self.weight.size(1)
+        Hi, Wi = input.size(-2), input.size(-1)
+        Ho, Wo = self._out_hw(Hi, Wi)
+        have = type(inp) == tuple
+        if have:
+            assert inp[0] == 'changeIndexes'
+            changeIndexes = inp[2]
+            if (Ho, Wo) != (Hi, Wi):
+                raise Err("CBConv2d: propagated change indexes address this layer's %dx%d INPUT map, its change list lives "
+                          "on the %dx%d output map (kernel_size=%s stride=%s padding=%s dilation=%s): such a layer runs "
+                          "its own change detection" % (Hi, Wi, Ho, Wo, tuple(self.kernel_size), tuple(self.stride),
+                                                        tuple(self.padding), tuple(self.dilation)))
+            if self.feedbackLoop:
+                raise Err("CBConv2d: feedbackLoop=True cannot be combined with propagated change indexes (the layer "
+                          "state would never be updated)")
+            if isinstance(changeIndexes, ChangeIndexes):
+                if changeIndexes.size not in (None, (Hi, Wi)):
+                    raise Err("CBConv2d: the propagated change indexes address a %dx%d map, this layer runs at %dx%d"
+                              % (changeIndexes.size + (Hi, Wi)))
+                idx, count = changeIndexes.buffer, changeIndexes.count
+            else:
+                idx = changeIndexes.detach().contiguous()
+                count = torch.full((1,), idx.numel(), dtype=torch.int32, device=input.device)
+            if idx.dtype != torch.int32 or not idx.is_contiguous():
+                raise Err("CBConv2d: propagated change indexes must be a contiguous int32 tensor")
+            cap = min(idx.numel(), Ho * Wo)
+        self._state_for(input.size(), input)
+        if self.gatherComputationStats:
+            self._gatherStats(input)
+        work = self._geom_workspace(input, Ho, Wo)
+        if not have:
+            idx, count, cap = work['idx'], work['count'], Ho * Wo
+        if not self.prevInput.is_contiguous():
+            self.prevInput = self.prevInput.contiguous()
+        arith = self._arith(input)
+        bias = self.bias.detach() if self.bias is not None else None
+        args = (ptr(input), ptr(self.prevInput), ptr(self.prevOutput), ptr(work['bits']), ptr(idx), ptr(count),
+                ptr(self._geom_weights(Hi, Wi, arith)), ptr(bias), Cin, Hi, Wi, K, self._geom_struct(),
+                float(self.threshold), int(bool(self.feedbackLoop)), int(bool(self.copyInput)), int(bool(self.withReLU)),
+                int(have), cap, ptr(work['conv']), arith, stream_ptr(input))
+        check(C.cbinfer_cbconv2d_forward_geom(*args))
+        result = changeIndexes if have else ChangeIndexes(idx, count, (Ho, Wo))
+        if self.saveChangeMap and not have:
+            # the frame's mask, left behind the two alternating ones, expanded to an int8 [Ho, Wo] map (list and count
+            # are written again with what they hold)
+            if work['map'] is None:
+                work['map'] = torch.zeros(Ho, Wo, dtype=torch.int8, device=input.device)
+            off = C.cbinfer_frame_mask_copy_offset(Ho, Wo) // 8
+            check(C.cbinfer_compact_bits(ptr(work['bits'][off:]), Wo, Ho, ptr(idx), ptr(count), None, ptr(work['map']),
+                                         stream_ptr(input)))
+            self.changeMap = work['map']
+        if not self.feedbackLoop and not self.copyInput:
+            self.prevInput = input.clone() if self._inputIsLiveState else input
+        elif not have and not self._inputIsLiveState:
+            self._make_plan(False, input, C.cbinfer_cbconv2d_forward_geom, args, 0)
+            if self._plan is not None:
+                self._plan['indexes'] = result
+        return self._emit(result)
 
     def _rows_path(self, dtype, H, W):
         """Which mask-driven contraction, if any, runs this layer's sync-free fp32 frame (no int8 mask copy): 'rows'
@@ -398,8 +563,8 @@ class CBConv2d(nn.Module):
         if link is None or self.__dict__.get('_noNextFold') or _switch('CBINFER_NO_NEXTFOLD'):
             return None, None
         pool, cons = link
-        if type(cons) is not CBConv2d:
-            return None, None
+        if type(cons) is not CBConv2d or cons.__dict__.get('_geom') or self.__dict__.get('_geom'):
+            return None, None      # (a general-geometry layer folds no detection and has none folded)
         # (runs every frame inside the call plans: the outcome is reused while every input of the test below is what it
         #  was -- the consumer's state and threshold by its token, everything else, both sides, by `key`)
         w, w2, prev2 = self._parameters['weight'], cons._parameters['weight'], cons._buffers.get('prevInput')
@@ -1045,8 +1210,16 @@ class CBConv2d(nn.Module):
           coarse-grained  'split' / 'hsplit' (fp32 / fp16 split-state kernels), 'pairs' (cb_rowpair.hip), 'rows' /
                           'blocks' (mask-driven, _rows_path), 'list' (cb_conv.hip), 'ops' (the reference's op sequence)
           fine-grained    'fg-split', 'fg-rows', 'fg-blocks', 'fg-list', 'fg-det' (deterministicFG), 'fg-atomic'
-          'dense'         behind a lazy pool: pool densely first."""
+          'dense'         behind a lazy pool: pool densely first.
+          'geom'          a general-geometry layer (cb_geomconv.hip; H x W is its INPUT map); 'dense' behind a lazy pool"""
         dtype = x.dtype
+        if self.__dict__.get('_geom'):
+            if self.finegrained:
+                raise _lib.CBinferError("CBConv2d: the fine-grained frame is not available on a general-geometry layer "
+                                        "(kernel_size=%s stride=%s padding=%s dilation=%s%s)"
+                                        % (tuple(self.kernel_size), tuple(self.stride), tuple(self.padding),
+                                           tuple(self.dilation), '' if self.bias is not None else ', no bias'))
+            return 'dense' if pooled else 'geom'
         if self.finegrained:
             fused = x.is_cuda and not self.atomicFG and dtype == torch.float32 and self._selfc_ok(H, W)
             if pooled:
@@ -1100,6 +1273,8 @@ class CBConv2d(nn.Module):
     def forward_normal(self, inp):
         # input parsing and checks (conv2d.py:180-190)
         changeIndexes = None
+        if self.__dict__.get('_geom'):
+            return self._forward_geom(inp)
         if isinstance(inp, LazyPool):
             path = self._path(inp.source, inp.outSize[-2], inp.outSize[-1], pooled=True)
             if path != 'dense':
@@ -1152,6 +1327,7 @@ class CBConv2d(nn.Module):
             self.prevInput = torch.full(size, float('inf'), dtype=like.dtype, device=like.device)
         outpSize = list(size)
         outpSize[-3] = self.out_channels
+        outpSize[-2], outpSize[-1] = self._out_hw(size[-2], size[-1])
         if (not _same_shape(self.prevOutput, outpSize) or self.prevOutput.dtype != like.dtype or
                 self.prevOutput.device != like.device):
             self.prevOutput = torch.full(outpSize, float('inf'), dtype=like.dtype, device=like.device)
@@ -1358,15 +1534,21 @@ class CBConv2d(nn.Module):
         changeTensor = (input - self.prevInput).abs().gt(self.threshold)
         nC = changeTensor.size(-3)
         kH, kW = self.weight.size(2), self.weight.size(3)
-        proped = F.conv2d(changeTensor.float(),
-                          torch.ones(nC, 1, kH, kW, device=input.device), groups=nC).gt(0)
+        if self.__dict__.get('_geom'):
+            # the footprint on the OUTPUT map: Ho x Wo values per feature map
+            proped = F.conv2d(changeTensor.float(), torch.ones(nC, 1, kH, kW, device=input.device), stride=self.stride,
+                              padding=tuple(self.padding), dilation=self.dilation, groups=nC).gt(0)
+        else:
+            proped = F.conv2d(changeTensor.float(),
+                              torch.ones(nC, 1, kH, kW, device=input.device), groups=nC).gt(0)
         opsPerValue = self.weight.size(0) * kH * kW * 2
         self.compStats = dict(
             numInputChangesPerFeatureMap=changeTensor.sum() * opsPerValue,
             numInputChanges=changeTensor.sum(-3).gt(0).sum() * nC * opsPerValue,
             numInputPropedChangesPerFeatureMap=proped.sum() * opsPerValue,
             numInputPropedChanges=proped.sum(-3).gt(0).sum() * nC * opsPerValue,
-            totalInputValues=changeTensor.size(-1) * changeTensor.size(-2) * nC * opsPerValue)
+            totalInputValues=proped.size(-1) * proped.size(-2) * nC * opsPerValue
+            if self.__dict__.get('_geom') else changeTensor.size(-1) * changeTensor.size(-2) * nC * opsPerValue)
 
     # ---------------------------------------------------------------- per-frame fast path
     # After a frame went through the general path, its library call is kept as a plan -- a pre-built argument list plus
@@ -1385,12 +1567,12 @@ class CBConv2d(nn.Module):
         if not (self.feedbackLoop or self.copyInput or result is not None):
             return
         w, b = self._parameters.get('weight'), self._parameters.get('bias')
-        if w is None or b is None or _switch('CBINFER_NO_FASTPATH'):
+        if w is None or (b is None and not self.__dict__.get('_geom')) or _switch('CBINFER_NO_FASTPATH'):
             return
         work = self._work
         self._plan = dict(
             pooled=pooled, shape=tuple(src.shape), dtype=src.dtype, device=src.device, flags=self._flags(),
-            w=(w.data_ptr(), w._version), b=(b.data_ptr(), b._version),
+            w=(w.data_ptr(), w._version), b=(b.data_ptr(), b._version) if b is not None else None,
             state=(self._buffers['prevInput'].data_ptr(), self._buffers['prevOutput'].data_ptr()),
             stream=args[-1], work=work, fn=fn, args=list(args), srcSlot=srcSlot, result=result, rows=rows, pmask=pmask,
             indexes=ChangeIndexes(work['idx'], work['count'], work['key'][:2]))
@@ -1411,10 +1593,11 @@ class CBConv2d(nn.Module):
             if type(inp) is not torch.Tensor:
                 return None
             src = inp
-        w, b, bufs = self._parameters['weight'], self._parameters['bias'], self._buffers
+        w, b, bufs = self._parameters['weight'], self._parameters.get('bias'), self._buffers
         if (src.shape != plan['shape'] or src.dtype != plan['dtype'] or src.device != plan['device'] or
                 not src.is_contiguous() or self._flags() != plan['flags'] or
-                (w.data_ptr(), w._version) != plan['w'] or (b.data_ptr(), b._version) != plan['b'] or
+                (w.data_ptr(), w._version) != plan['w'] or
+                (None if b is None else (b.data_ptr(), b._version)) != plan['b'] or
                 (bufs['prevInput'].data_ptr(), bufs['prevOutput'].data_ptr()) != plan['state'] or
                 self._work is not plan['work'] or raw_stream(src.device.index) != plan['stream']):
             return None
@@ -1561,6 +1744,8 @@ class CBConv2d(nn.Module):
         self.__dict__['_ranSplit'] = False
         if self.finegrained:
             assert self.feedbackLoop == False
+            if self.__dict__.get('_geom'):
+                self._path(self.weight, 1, 1)      # (raises: no fine-grained frame on general geometry)
             out = self.forward_fg(inp)
         else:
             out = self.forward_normal(inp)

@@ -59,7 +59,9 @@ typedef void* cbStream_t; /* hipStream_t */
  * weightScale == 0, cbNextDetect.arith.  9: cbinfer_hsplit_forward_group (cbHalfLayer / cbHalfNext: two layers of one
  * geometry per launch, the consumers' change detection in the producing launch); cbinfer_hsplit_* take contractions
  * of a single k-stage and up (1x1 layers on >= 64 channels).  10: cbinfer_split_*_next (a split-state layer's contraction
- * in window order carrying the pooled change detection of the layer behind the 2x2 pool). */
+ * in window order carrying the pooled change detection of the layer behind the 2x2 pool).
+ * 11 (unchanged): the general-geometry entry points (cbGeom, cbinfer_geom_*, cbinfer_*_geom) were ADDED under this
+ * number -- new symbols break no caller, every earlier symbol keeps its signature and behaviour. */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -732,6 +734,59 @@ int cbinfer_split_forward_next(const cbSplitSeq* seqs, int nSeq, int mode, int p
 #define CBINFER_CONCAT_MAX 4
 int cbinfer_concat_channels(const void* const* sources, const int32_t* channels, int n, void* output, long HW, int dtype,
                             cbStream_t stream);
+
+/* ---- general geometry: strided, dilated, freely padded, even-sized and bias-free convolutions (cb_geomconv.hip) ----
+ * The reference has no counterpart: its CBConv2d asserts stride 1, dilation 1, padding k/2 and a bias
+ * (conv2d.py:92-104).  Input map Hi x Wi, filter kH x kW, stride (sH, sW), zero padding (pH, pW), dilation (dH, dW);
+ * output map Ho = (Hi + 2 pH - dH (kH-1) - 1) / sH + 1, Wo likewise (torch's formula).  Limits per axis: k <= 7,
+ * s <= 4, d <= 8, p <= 64 -- beyond them CB_ERR_UNSUPPORTED, a non-positive entry or a filter that does not fit the
+ * padded map CB_ERR_BADARG; nothing is launched then.  The geometry travels as one HOST struct. */
+typedef struct cbGeom {
+    int kH, kW, sH, sW, pH, pW, dH, dW;
+} cbGeom;
+/* host, pure: the output size (status as above; Ho / Wo untouched on failure) */
+int cbinfer_geom_out_size(int Hi, int Wi, const cbGeom* geom, int* Ho, int* Wo);
+/* Prepared weights of a general-geometry layer: W[Kpad64][CkkPad32] in the tensors' element type (k contiguous, zero
+ * padded; dtype CB_F32S shares CB_F32's layout -- operands are split into bf16 triples on their way into LDS) followed
+ * by the k -> tap table for an Hi x Wi input map: byte offset (c Hi Wi + (ky dH - pH) Wi + (kx dW - pW)) elemSize
+ * relative to the base pixel (oy sH, ox sW), and the signed dy, dx of the border test.  0 bytes for a rejected geometry. */
+long cbinfer_geom_prepared_weights_bytes(int K, int C, const cbGeom* geom, int dtype);
+int cbinfer_geom_prep_weights(const void* weight, void* prepared, int K, int C, int Hi, int Wi, const cbGeom* geom,
+                              int dtype, cbStream_t stream);
+/* split-k workspace of cbinfer_conv_changed_geom: partial-tile slabs (scratch) followed by the tiles' arrival
+ * counters -- the last 2048 bytes, ZERO on first use and left zero by every launch.  One per layer: two launches that
+ * can run concurrently must not share one (see cbinfer_conv_changed). */
+long cbinfer_geom_workspace_bytes(void);
+/* Detection, one launch.  change(p) on the INPUT map exactly as cbinfer_change_detection (a1); updateInputState as
+ * there (1: feedback refresh at the changed pixels, 2: state <- input wherever they differ, 0: state untouched).  The
+ * EXACT footprint of the changed pixels -- output (oy, ox) iff one of its taps (oy sH - pH + ky dH, ox sW - pW + kx dW)
+ * lies inside the input map and changed; a lattice for d > 1, the reference's box for unit geometry -- is ORed into
+ * the mask the parity selects of a frame mask buffer of the OUTPUT map (cbinfer_frame_mask_bytes(Ho, Wo) bytes, zero on
+ * first use).  A changed pixel no tap reaches still refreshes the state. */
+int cbinfer_change_detection_geom(const void* input, void* state, uint64_t* frameMasks, int C, int Hi, int Wi,
+                                  const cbGeom* geom, float threshold, int updateInputState, int dtype,
+                                  cbStream_t stream);
+/* Contraction, one launch: gather -> MFMA -> bias / ReLU -> scatter at the listed OUTPUT pixels, nothing else of
+ * output [K, Ho, Wo] is written.  bias may be NULL.  dtype selects the arithmetic as in cbinfer_conv_changed (CB_F16;
+ * CB_F32S: bf16 triples, six products, f32 accumulation; CB_F32: the exact f32 MFMA).  Either
+ *   frameMasks != NULL: the list is derived from the frame mask cbinfer_change_detection_geom filled (ascending
+ *     oy Wo + ox), written to idxOut (capacity Ho Wo) / countOut, the frame's mask is copied to
+ *     cbinfer_frame_mask_copy_offset(Ho, Wo), the other mask is zeroed and the parity flipped for the next frame; or
+ *   changeList / numChanges / countDev as in cbinfer_conv_changed (entries outside the map are ignored).
+ * A short list is split along k over idle workgroups and summed in slice order (deterministic) when a workspace is
+ * given. */
+int cbinfer_conv_changed_geom(const void* input, const int32_t* changeList, int numChanges, const int32_t* countDev,
+                              uint64_t* frameMasks, int32_t* idxOut, int32_t* countOut, const void* prepared,
+                              const void* bias, void* output, int C, int Hi, int Wi, int K, const cbGeom* geom, int relu,
+                              void* workspace, int dtype, cbStream_t stream);
+/* The whole frame of a general-geometry CBConv2d enqueued without a host sync: the counterpart of
+ * cbinfer_cbconv2d_forward (same feedbackLoop / copyInput contract; prevInput [C,Hi,Wi], prevOutput [K,Ho,Wo]).
+ * haveIndexes=1 (idx / countDev produced upstream, capN their capacity) is accepted only where the output map is the
+ * input map and not in feedback mode; CB_ERR_UNSUPPORTED otherwise. */
+int cbinfer_cbconv2d_forward_geom(const void* input, void* prevInput, void* prevOutput, uint64_t* frameMasks,
+                                  int32_t* idx, int32_t* countDev, const void* prepared, const void* bias, int C, int Hi,
+                                  int Wi, int K, const cbGeom* geom, float threshold, int feedbackLoop, int copyInput,
+                                  int relu, int haveIndexes, int capN, void* workspace, int dtype, cbStream_t stream);
 
 /* replaces conv2d_fg_cpu, cbconv2d_fg_backend.cu:81-112: HOST pointers, host code, race-free. */
 void cbinfer_conv2d_fg_cpu(const float* input, const float* prevInput, float* output,
