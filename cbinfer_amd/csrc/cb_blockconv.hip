@@ -29,9 +29,6 @@
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct BlkParams {
     const float* state;     // [C,H,W]
     const uint4* wb;        // prepared weights [mtile][chunk][step][plane][lane] x 16 B
@@ -49,31 +46,6 @@ struct BlkParams {
     int accumulate;         // fine-grained frame: out += W * delta (state = delta tensor), no bias
     float* reluOut;         // ... and optionally relu(out) into a second plane set
 };
-
-__device__ __forceinline__ void cb_split3b(float x, unsigned& hi, unsigned& mid, unsigned& lo) {
-    const __bf16 h = (__bf16)x;
-    const float r1 = x - (float)h;
-    const __bf16 m = (__bf16)r1;
-    const float r2 = r1 - (float)m;
-    const __bf16 l = (__bf16)r2;
-    hi = __builtin_bit_cast(unsigned short, h);
-    mid = __builtin_bit_cast(unsigned short, m);
-    lo = __builtin_bit_cast(unsigned short, l);
-}
-
-__device__ __forceinline__ int cb_nth_bit_b(unsigned long long w, int r) {
-    int pos = 0;
-#pragma unroll
-    for (int width = 32; width >= 1; width >>= 1) {
-        const unsigned long long lowmask = ((1ull << width) - 1ull) << pos;
-        const int c = __popcll(w & lowmask);
-        if (r >= c) {
-            r -= c;
-            pos += width;
-        }
-    }
-    return pos;
-}
 
 __device__ __forceinline__ unsigned long long cb_uniform64(unsigned long long v) {
     return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
@@ -216,7 +188,7 @@ __global__ __launch_bounds__(64 * (2 * MG + 4)) void cb_blockconv_kernel(BlkPara
                 for (int j = 0; j < 4; ++j) {
                     if (j < nT[r]) {
                         const int n = 16 * j + (lane & 15);
-                        const int xl = cb_nth_bit_b(word[r], n < pc ? n : 0);
+                        const int xl = cb_select_bit(word[r], n < pc ? n : 0);
                         // tiles are stored compacted: slot i (uniform) <- (r, j)
 #pragma unroll
                         for (int s = 0; s < NTMAX; ++s)
@@ -437,7 +409,7 @@ __global__ __launch_bounds__(256) void cb_blockconv_prep_kernel(const float* __r
     const int m = 16 * mt + (lane & 15), kx = 4 * q + (lane >> 4), ch = 8 * c + e;
     const float v = (m < K && kx < kW && ch < C) ? w[(((long)m * C + ch) * kH + ky) * kW + kx] : 0.f;
     unsigned hi, mid, lo;
-    cb_split3b(v, hi, mid, lo);
+    cb_split3(v, hi, mid, lo);
     unsigned short* dst = wb + ((((long)mt * CH + c) * SPC + step) * 3 * 64 + lane) * 8 + e;
     dst[0] = (unsigned short)hi;
     dst[64 * 8] = (unsigned short)mid;

@@ -15,7 +15,28 @@ typedef _Float16 cb_half;
 #define CB_BK 16          // k-depth staged in LDS per step (fp32); fp16 uses 32
 #define CB_BK_H 32
 
+// MFMA operand / accumulator vectors and the constant address space (scalar loads), shared by every kernel file
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(4))) int cb_const_int;
+
 static inline int cb_div_up(long a, long b) { return (int)((a + b - 1) / b); }
+
+// CU count of the current device, asked once per process (256 if the runtime will not say)
+inline int cb_num_cus() {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+            cus = n;
+        else
+            cus = 256;
+    }
+    return cus;
+}
 
 static inline int cb_launch_status() {
     hipError_t e = hipGetLastError();
@@ -63,14 +84,48 @@ __device__ __forceinline__ cb_half cb_max(cb_half a, cb_half b) { return a < b ?
 __device__ __forceinline__ float cb_threshold(float th, float*) { return th; }
 __device__ __forceinline__ cb_half cb_threshold(float th, cb_half*) { return (cb_half)th; }  // RNE
 
+// r-th (0-based) set bit of w, r < popcount(w)
+__device__ __forceinline__ int cb_select_bit(unsigned long long w, int r) {
+    int pos = 0;
+#pragma unroll
+    for (int width = 32; width >= 1; width >>= 1) {
+        const unsigned long long lowmask = ((1ull << width) - 1ull) << pos;
+        const int c = __popcll(w & lowmask);
+        if (r >= c) {
+            r -= c;
+            pos += width;
+        }
+    }
+    return pos;
+}
+
+// the bits of word `tile` of a row's change mask that are pixels of a W-wide image
+__device__ __forceinline__ unsigned long long cb_valid_mask(int W, int tile) {
+    const int rem = W - tile * 64;
+    return rem >= 64 ? ~0ull : ((1ull << rem) - 1ull);
+}
+
+// x = hi + mid + lo with three bf16 terms (24 significant bits): hi = bf16(x), mid = bf16(x - hi),
+// lo = bf16(x - hi - mid); both differences are exact in f32.  Returned as the raw 16-bit patterns.
+// (cbs_split3 in cb_split_common.h is NOT a copy: it carries non-finite inputs and truncates near FLT_MAX.)
+__device__ __forceinline__ void cb_split3(float x, unsigned& hi, unsigned& mid, unsigned& lo) {
+    const __bf16 h = (__bf16)x;
+    const float r1 = x - (float)h;
+    const __bf16 m = (__bf16)r1;
+    const float r2 = r1 - (float)m;
+    const __bf16 l = (__bf16)r2;
+    hi = __builtin_bit_cast(unsigned short, h);
+    mid = __builtin_bit_cast(unsigned short, m);
+    lo = __builtin_bit_cast(unsigned short, l);
+}
+
 // A kernel whose arguments are a struct of several hundred bytes reads them where it needs them: a handful of
 // scalar loads at a time, each group a round trip to the kernel-argument memory (which misses the scalar cache
 // the first time a 64-byte line is touched), one after the other along the kernel's critical path.  This touches
 // every line of the first BYTES argument bytes in ONE burst at kernel entry, so that all later reads hit.
 template <int BYTES>
 __device__ __forceinline__ void cb_touch_kernarg() {
-    typedef __attribute__((address_space(4))) const int cb_kint;
-    cb_kint* ka = (cb_kint*)__builtin_amdgcn_kernarg_segment_ptr();
+    const cb_const_int* ka = (const cb_const_int*)__builtin_amdgcn_kernarg_segment_ptr();
     int acc = 0;
 #pragma unroll
     for (int o = 0; o < BYTES; o += 64) acc |= ka[o / 4];

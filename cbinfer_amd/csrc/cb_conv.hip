@@ -17,23 +17,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// x = hi + mid + lo with three bf16 terms (24 significant bits): hi = bf16(x), mid = bf16(x - hi),
-// lo = bf16(x - hi - mid); both differences are exact in f32.  Returned as the raw 16-bit patterns.
-__device__ __forceinline__ void cb_split3(float x, unsigned& hi, unsigned& mid, unsigned& lo) {
-    const __bf16 h = (__bf16)x;
-    const float r1 = x - (float)h;
-    const __bf16 m = (__bf16)r1;
-    const float r2 = r1 - (float)m;
-    const __bf16 l = (__bf16)r2;
-    hi = __builtin_bit_cast(unsigned short, h);
-    mid = __builtin_bit_cast(unsigned short, m);
-    lo = __builtin_bit_cast(unsigned short, l);
-}
-// The same decomposition for the inner loops, cheaper: hi and mid by truncation (a mask instead of a
+// cb_split3's decomposition (cb_common.h) for the inner loops, cheaper: hi and mid by truncation (a mask instead of a
 // conversion and a shift each), lo rounded to nearest; |x - (hi + mid + lo)| <= 2^-24 |x| still.  The terms
 // are returned as f32 bit patterns with the bf16 in the TOP half, so two of them pack with one shift-or.
 __device__ __forceinline__ void cb_split3t(float x, unsigned& hi, unsigned& mid, unsigned& lo) {
@@ -70,8 +54,6 @@ __device__ __forceinline__ void cb_split3t_x4(const float (&x)[4], uint2& hi, ui
     lo = make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(p0, bf16x2)),
                     __builtin_bit_cast(unsigned, __builtin_convertvector(p1, bf16x2)));
 }
-typedef __attribute__((address_space(4))) int cb_const_int;   // constant address space: scalar loads
-
 __device__ __forceinline__ float cb_relu(float v) { return v <= 0.f ? 0.f : v; }
 __device__ __forceinline__ cb_half cb_relu(cb_half v) { return v <= (cb_half)0 ? (cb_half)0 : v; }
 
@@ -228,7 +210,14 @@ struct ConvParams {
 // workgroups count themselves on SHARDED counters (a top counter behind them): a returning atomic on ONE word is
 // served every 11 ns, so the 512 workgroups of a launch that finds nothing to do -- the common case of a deep layer
 // of a network whose change has died out further up -- spent 5.6 us of their 7.3 queueing for their tickets (round 4).
-__device__ __forceinline__ void cb_arrive_and_flip(unsigned long long* frameMasks, int maskWords, int* tickets, int par) {
+// (An EMPTY mask, N == 0 -- every workgroup sees that alike -- needs neither: the next detection finds the mask the
+// parity selects as clean as this one left it, and the other one is zeroed by the next launch that has work; the
+// arrival tickets were 1.7 of the 5.2 us of a launch with nothing to do.)  Called by all threads at the kernel's end.
+__device__ __forceinline__ void cb_arrive_and_flip(unsigned long long* frameMasks, int maskWords, int* tickets, int par,
+                                                   int N) {
+    if (N <= 0) return;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
     int* ctl = (int*)(frameMasks + 2 * (long)maskWords);
     bool last;
     if (tickets == nullptr) {
@@ -249,21 +238,6 @@ __device__ __forceinline__ void cb_arrive_and_flip(unsigned long long* frameMask
     }
 }
 
-// r-th (0-based) set bit of w, r < popcount(w)
-__device__ __forceinline__ int cb_select_bit(unsigned long long w, int r) {
-    int pos = 0;
-#pragma unroll
-    for (int width = 32; width >= 1; width >>= 1) {
-        const unsigned long long lowmask = ((1ull << width) - 1ull) << pos;
-        const int c = __popcll(w & lowmask);
-        if (r >= c) {
-            r -= c;
-            pos += width;
-        }
-    }
-    return pos;
-}
-
 // The fused kernel is the last consumer of the frame's change mask, so it re-zeroes it (before any
 // early exit): the next frame's detection can atomicOr into a clean mask without a memset node.
 __device__ __forceinline__ void cb_clear_mask(const ConvParams& p) {
@@ -280,6 +254,278 @@ __device__ __forceinline__ void cb_clear_mask(const ConvParams& p) {
 #define CB_EPI_YT 1
 #define CB_EPI_SCATTER 2
 #define CB_EPI_SCATTER_ACC 3
+
+// ---------------------------------------------------------------------------------------------
+// what cb_mfma_f32_kernel and cb_mfma_f16_kernel share: in-kernel compaction, the pixel a thread gathers for,
+// the k-group reduction, split-K and the epilogue.  The LDS arrays are the kernels', handed in as pointers.
+// ---------------------------------------------------------------------------------------------
+// ---- SELFC: stream compaction folded into the contraction -----------------------------------------
+// Every workgroup rebuilds the exclusive popcount prefix of the frame's change mask (<= 32 KB, L2
+// resident) in LDS; a tile's pixels are then found by rank (binary search over the prefix + select
+// of the r-th set bit).  No compaction launch, and no hand-off between workgroups.  Two masks
+// alternate by a device-side parity so that this launch can zero the one the NEXT frame's detection
+// will fill while every workgroup still reads the current one; the last workgroup to finish flips
+// the parity (cb_arrive_and_flip).
+//
+// The frame's mask by that parity (which goes out through par); zeroes the other mask for the next frame
+// (+ round 6: a copy of THIS frame's mask at a fixed address behind the two masks and the control words -- which
+//  of the two masks is the frame's is a device-side matter (the parity); the copy is what a chained consumer's
+//  detection reads as its producer mask: segments this layer did not rewrite are skipped)
+template <int NT>
+__device__ __forceinline__ const unsigned long long* cb_selfc_frame_mask(unsigned long long* frameMasks, int maskWords,
+                                                                        int& par) {
+    const int t = threadIdx.x;
+    int* ctl = (int*)(frameMasks + 2 * (long)maskWords);   // {parity, done}
+    par = ctl[0];
+    const unsigned long long* mask = frameMasks + (par ? maskWords : 0);
+    unsigned long long* other = frameMasks + (par ? 0 : maskWords);
+    unsigned long long* copy = frameMasks + 2 * (long)maskWords + 2;
+    for (int i = blockIdx.x * NT + t; i < maskWords; i += gridDim.x * NT) other[i] = 0ull, copy[i] = mask[i];
+    return mask;
+}
+
+// Exclusive prefix of the per-word popcounts of the mask into s_pre[maskWords + 1] (s_wsum[NT / 64]: scratch); returns
+// the total.  Pass 1: coalesced, independent loads (word t, t+NT, ...) -> counts in LDS; pass 2 (LDS only): thread t
+// owns CH consecutive words.  (The mask selection above stays a function of its own: as one function with this
+// scan, two of the 1024-thread kernels spilled 4 and 8 bytes more than before.)
+template <int NT>
+__device__ __forceinline__ int cb_mask_prefix(const unsigned long long* mask, int maskWords, int* s_pre, int* s_wsum) {
+    const int t = threadIdx.x;
+    const int CH = (maskWords + NT - 1) / NT;
+#pragma unroll 4
+    for (int w = t; w < maskWords; w += NT) s_pre[w] = __popcll(mask[w]);
+    __syncthreads();
+    const int wb = t * CH;
+    int loc = 0;
+    for (int u = 0; u < CH; ++u) {
+        const int w = wb + u;
+        if (w < maskWords) loc += s_pre[w];
+    }
+    int incl = loc;   // inclusive scan over the wave, then over the waves
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if ((t & 63) >= o) incl += v;
+    }
+    if ((t & 63) == 63) s_wsum[t >> 6] = incl;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < (t >> 6); ++w) base += s_wsum[w];
+    int run = base + incl - loc;
+    for (int u = 0; u < CH; ++u) {
+        const int w = wb + u;
+        if (w < maskWords) {
+            const int c = s_pre[w];   // count -> exclusive prefix, in place (this thread's chunk only)
+            s_pre[w] = run;
+            run += c;
+        }
+    }
+    if (t == NT - 1) s_pre[maskWords] = base + incl;   // the last thread's chunk ends the mask
+    __syncthreads();
+    return s_pre[maskWords];
+}
+
+// SELFC: pixel of slot j of the tile at n0 = the (n0+j)-th set bit of the mask -> s_tilePix[j] (-1 past the list),
+// and into the change list when this item is the one that owns the tile's list entries
+template <int BN>
+__device__ __forceinline__ void cb_selfc_tile_pixels(const int* s_pre, int* s_tilePix, const unsigned long long* mask,
+                                                     int maskWords, int wpr, int W, int n0, int N, int32_t* listOut,
+                                                     bool ownsList) {
+    const int t = threadIdx.x;
+    __syncthreads();   // s_tilePix of the previous item is no longer read
+    if (t < BN) {
+        const int r = n0 + t;
+        int pos = -1;
+        if (r < N) {
+            int lo = 0, hi = maskWords;   // largest w with s_pre[w] <= r
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (s_pre[mid] <= r)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            const int bit = cb_select_bit(mask[lo], r - s_pre[lo]);
+            const int row = lo / wpr;
+            pos = row * W + (lo - row * wpr) * 64 + bit;
+            if (ownsList) listOut[r] = pos;
+        }
+        s_tilePix[t] = pos;
+    }
+    __syncthreads();
+}
+
+// per-thread B-load coordinates of the pixel at index pos of a [C,H,W] tensor of ELEM-byte values
+template <int ELEM>
+__device__ __forceinline__ void cb_pixel_coords(int pos, int W, int& py, int& px, int& pbase) {
+    py = pos / W;
+    px = pos - py * W;
+    pbase = pos * ELEM;
+}
+
+// The pieces below are macros, not functions.  They expand in the kernels' item loops and use the kernels' names
+// (p, t, ks, wm, wn, l31, h, acc, n0, m0, N, SK, tile, HW, emit, s_last, s_tilePix, the template parameters and tile
+// constants); `continue` is the item loop's.  As functions -- arguments by value or by reference, inlining forced or
+// left to the inliner -- every one of them changed the instruction schedule, some the register count and occupancy,
+// of kernels that sit on the register limit of their launch bounds; as macros they leave every kernel's instruction
+// stream as it was with the text written out twice (tools/isa_diff.py).
+
+// wave-uniform: every tap of every pixel of this wave lies inside the image -> no bounds test
+// ... and no padded k in this slice: then the pixel's byte offset (minus the most negative tap's) is
+// the load's vector offset for the whole item and the tap goes in as the SCALAR offset -- no per-tap
+// address arithmetic at all.  (The scalar offset is not range-checked by the hardware, hence the
+// conditions; it is unsigned, hence the bias.)  ELEM: bytes per value.  Declares fast, tapBias, pfast.
+#define CB_GATHER_FAST(ELEM)                                                           \
+    bool fast = false;                                                                 \
+    int tapBias = 0, pfast = 0;                                                        \
+    if (MODE == CB_MODE_GATHER) {                                                      \
+        const int phh = (p.kH - 1) / 2, pww = (p.kW - 1) / 2;                          \
+        fast = __all(py >= phh && py + (p.kH - 1 - phh) < p.H && px >= pww &&          \
+                     px + (p.kW - 1 - pww) < p.W) &&                                   \
+               kEnd <= (p.Ckk / BK) * BK;                                              \
+        tapBias = (phh * p.W + pww) * (ELEM);                                          \
+        pfast = pbase4 - tapBias;                                                      \
+    }
+
+// sum the wave groups' partial tiles through LDS (fixed order: deterministic).  ACC1: the second row tile's
+// accumulator (MS == 2; any floatx16 otherwise, not touched)
+#define CB_KGROUP_REDUCE(MS, ACC1)                                                     \
+    if (KS > 1) {                                                                      \
+        float* red = smem + (wq * (MS) * 16) * 64 + lane;                              \
+        _Pragma("unroll") for (int g = 1; g < KS; ++g) {                               \
+            if (ks == g) {                                                             \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) red[r * 64] = acc[r];   \
+                if ((MS) == 2) {                                                       \
+                    _Pragma("unroll") for (int r = 0; r < 16; ++r) red[(16 + r) * 64] = ACC1[r]; \
+                }                                                                      \
+            }                                                                          \
+            __syncthreads();                                                           \
+            if (ks == 0) {                                                             \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[r] += red[r * 64];  \
+                if ((MS) == 2) {                                                       \
+                    _Pragma("unroll") for (int r = 0; r < 16; ++r) ACC1[r] += red[(16 + r) * 64]; \
+                }                                                                      \
+            }                                                                          \
+            __syncthreads();                                                           \
+        }                                                                              \
+    }
+
+// one output value (the body of the kernels' emit(m, n, pix, v)): bias / ReLU / the form of the store.  T: the output
+// element type; RELU_OUT: the accumulate form keeps relu(out) in a second plane set (f32 only: fp16 has no
+// fine-grained frame)
+#define CB_EMIT(T, RELU_OUT)                                                           \
+    if (EPI != CB_EPI_SCATTER_ACC) {                                                   \
+        if (bias) v += (float)bias[m];                                                 \
+        if (p.relu) v = cb_relu(v);                                                    \
+    }                                                                                  \
+    if (EPI == CB_EPI_Y)                                                               \
+        out[(long)n * p.K + m] = (T)v;                                                 \
+    else if (EPI == CB_EPI_YT)                                                         \
+        out[(long)m * p.nHost + n] = (T)v;                                             \
+    else if (EPI == CB_EPI_SCATTER)                                                    \
+        out[(long)m * HW + pix] = (T)v;                                                \
+    else {                                                                             \
+        const float nv = (float)out[(long)m * HW + pix] + v;                           \
+        out[(long)m * HW + pix] = (T)nv;                                               \
+        if ((RELU_OUT) && p.reluOut) ((float*)p.reluOut)[(long)m * HW + pix] = cb_relu(nv); \
+    }
+
+// Split-K (SK > 1): publish this slice's partial tile, take a ticket; the last arriver sums the slices and stores.
+// Slab = [BM/4][BN] float4: four consecutive output channels of one pixel -- the registers
+// 4q..4q+3 of a lane's 32x32 accumulator as they stand -- so both sides move 16 bytes per lane in
+// 512-byte runs.  The stores are write-through (sc1) and drained before the workgroup's ticket,
+// which replaces the agent-scope release (an L2 write-back per workgroup); with one workgroup
+// per CU the reducer's sc1 loads also replace the acquire (MI355X_MICROARCH.md, "Inter-workgroup
+// visibility": publish-large / splitk-seam), otherwise (ACQUIRE) it invalidates its L1 first.
+// SEAM: this kernel has the form whose slices meet in the next launch (p.seam: nothing to wait for here).
+// The slab slot is `item`.  Ends the item (`continue`).
+#define CB_PUBLISH(A, J, MS)                                                           \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                    \
+        const floatx4 f = {A[4 * q], A[4 * q + 1], A[4 * q + 2], A[4 * q + 3]};        \
+        const u32x4 v = __builtin_bit_cast(u32x4, f);                                  \
+        const int mq = (wm * (MS) + (J)) * 8 + 2 * q + h;                              \
+        __builtin_amdgcn_raw_buffer_store_b128(                                        \
+            v, srsrc, (item * (TILE / 4) + mq * BN + wn * 32 + l31) * 16, 0, 16 /* sc1 */);     \
+    }
+#define CB_SPLITK_TILE(MS, ACC1, SEAM, ACQUIRE)                                        \
+    {                                                                                  \
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));                \
+        const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(        \
+            (void*)p.slabs, 0, (int)min((long)gridDim.x * TILE * 4, (long)0x7fffffff), 0x00020000); \
+        if (ks == 0) {                                                                 \
+            CB_PUBLISH(acc, 0, MS)                                                     \
+            if ((MS) == 2) {                                                           \
+                CB_PUBLISH(ACC1, 1, MS)                                                \
+            }                                                                          \
+        }                                                                              \
+        if ((SEAM) && p.seam) {                                                        \
+            continue;                                                                  \
+        }                                                                              \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                               \
+        __syncthreads();                                                               \
+        if (t == 0) {                                                                  \
+            const int ticket = __hip_atomic_fetch_add(p.tickets + tile, 1, __ATOMIC_RELAXED, \
+                                                      __HIP_MEMORY_SCOPE_AGENT);       \
+            const int last = ticket == SK - 1;                                         \
+            if (last) {                                                                \
+                if (ACQUIRE) {                                                         \
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                 \
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   \
+                }                                                                      \
+                __hip_atomic_store(p.tickets + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+            }                                                                          \
+            s_last = last;                                                             \
+        }                                                                              \
+        __syncthreads();                                                               \
+        const bool last = s_last != 0;                                                 \
+        __syncthreads(); /* s_last may be rewritten by the next item */                \
+        if (!last) continue;                                                           \
+        /* every thread: TILE / 4 / NT chunks, all slices of a chunk in flight together */ \
+        _Pragma("unroll") for (int c0 = 0; c0 < TILE / 4; c0 += NT) {                  \
+            const int c = c0 + t;                                                      \
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;                              \
+            _Pragma("unroll 4") for (int j = 0; j < SK; ++j) {                         \
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(                 \
+                    srsrc, ((tile * SK + j) * (TILE / 4) + c) * 16, 0, 16 /* sc1 */);  \
+                /* (whole-vector casts: element-wise ones on these types came out as splats) */ \
+                const floatx4 f = __builtin_bit_cast(floatx4, v);                      \
+                s0 += f.x;                                                             \
+                s1 += f.y;                                                             \
+                s2 += f.z;                                                             \
+                s3 += f.w;                                                             \
+            }                                                                          \
+            const int nl = c % BN, mq = c / BN;                                        \
+            const int n = n0 + nl;                                                     \
+            int pix = 0;                                                               \
+            if (EPI >= CB_EPI_SCATTER && n < N) pix = SELFC ? s_tilePix[nl] : p.list[n]; \
+            if (n < N && (unsigned)pix < (unsigned)HW) {                               \
+                const int m = m0 + 4 * mq;                                             \
+                if (m < p.K) emit(m, n, pix, s0);                                      \
+                if (m + 1 < p.K) emit(m + 1, n, pix, s1);                              \
+                if (m + 2 < p.K) emit(m + 2, n, pix, s2);                              \
+                if (m + 3 < p.K) emit(m + 3, n, pix, s3);                              \
+            }                                                                          \
+        }                                                                              \
+        continue;                                                                      \
+    }
+
+// plain epilogue (SK == 1): C/D map of the 32x32 tile: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
+// (a list entry outside the map -- a propagated list of another resolution -- is dropped, never
+// written through: the reference's scatter would corrupt a neighbouring plane, .cu:187)
+#define CB_STORE_TILE(MS, ACC1)                                                        \
+    {                                                                                  \
+        const int n = n0 + wn * 32 + l31;                                              \
+        int pix = 0;                                                                   \
+        if (EPI >= CB_EPI_SCATTER && ks == 0 && n < N) pix = SELFC ? s_tilePix[wn * 32 + l31] : p.list[n]; \
+        if (ks == 0 && n < N && (unsigned)pix < (unsigned)HW) {                        \
+            _Pragma("unroll") for (int rr = 0; rr < 16 * (MS); ++rr) {                 \
+                const int r = rr & 15;                                                 \
+                const int m = m0 + (wm * (MS) + (rr >> 4)) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h; \
+                if (m >= p.K) continue;                                                \
+                emit(m, n, pix, rr < 16 ? acc[r] : ACC1[r]);                           \
+            }                                                                          \
+        }                                                                              \
+    }
 
 // fp32 contraction kernel (persistent, load-balanced).
 //   tile      BM x BN = (32*WM) x (32*WN) outputs, one 32x32 MFMA tile per wave; KS wave groups split the
@@ -354,13 +600,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
 
     const int t = threadIdx.x;
     CB_UPSTREAM_IDLE_EXIT
-    // ---- SELFC: stream compaction folded into this kernel -------------------------------------------
-    // Every workgroup rebuilds the exclusive popcount prefix of the frame's change mask (<= 32 KB, L2
-    // resident) in LDS; a tile's pixels are then found by rank (binary search over the prefix + select
-    // of the r-th set bit).  No compaction launch, and no hand-off between workgroups.  Two masks
-    // alternate by a device-side parity so that this launch can zero the one the NEXT frame's detection
-    // will fill while every workgroup still reads the current one; the last workgroup to finish flips
-    // the parity.
+    // SELFC: stream compaction folded into this kernel (see cb_selfc_frame_mask)
     __shared__ int s_pre[SELFC ? CB_SELFC_MAXW + 1 : 1];
     __shared__ int s_wsum[SELFC ? NT / 64 : 1];
     __shared__ int s_tilePix[SELFC ? BN : 1];
@@ -368,49 +608,8 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
     int par = 0;
     int N;
     if (SELFC) {
-        int* ctl = (int*)(p.frameMasks + 2 * (long)p.maskWords);   // {parity, done}
-        par = ctl[0];
-        mask = p.frameMasks + (par ? p.maskWords : 0);
-        unsigned long long* other = p.frameMasks + (par ? 0 : p.maskWords);
-        // (+ round 6: a copy of THIS frame's mask at a fixed address behind the two masks and the control words -- which
-        //  of the two masks is the frame's is a device-side matter (the parity); the copy is what a chained consumer's
-        //  detection reads as its producer mask: segments this layer did not rewrite are skipped)
-        unsigned long long* copy = p.frameMasks + 2 * (long)p.maskWords + 2;
-        for (int i = blockIdx.x * NT + t; i < p.maskWords; i += gridDim.x * NT) other[i] = 0ull, copy[i] = mask[i];
-        // Exclusive prefix of the per-word popcounts.  Pass 1: coalesced, independent loads (word t,
-        // t+NT, ...) -> counts in LDS; pass 2 (LDS only): thread t owns CH consecutive words.
-        const int CH = (p.maskWords + NT - 1) / NT;
-#pragma unroll 4
-        for (int w = t; w < p.maskWords; w += NT) s_pre[w] = __popcll(mask[w]);
-        __syncthreads();
-        const int wb = t * CH;
-        int loc = 0;
-        for (int u = 0; u < CH; ++u) {
-            const int w = wb + u;
-            if (w < p.maskWords) loc += s_pre[w];
-        }
-        int incl = loc;   // inclusive scan over the wave, then over the waves
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o);
-            if ((t & 63) >= o) incl += v;
-        }
-        if ((t & 63) == 63) s_wsum[t >> 6] = incl;
-        __syncthreads();
-        int base = 0;
-        for (int w = 0; w < (t >> 6); ++w) base += s_wsum[w];
-        int run = base + incl - loc;
-        for (int u = 0; u < CH; ++u) {
-            const int w = wb + u;
-            if (w < p.maskWords) {
-                const int c = s_pre[w];   // count -> exclusive prefix, in place (this thread's chunk only)
-                s_pre[w] = run;
-                run += c;
-            }
-        }
-        if (t == NT - 1) s_pre[p.maskWords] = base + incl;   // the last thread's chunk ends the mask
-        __syncthreads();
-        N = min(s_pre[p.maskWords], p.nHost);
+        mask = cb_selfc_frame_mask<NT>(p.frameMasks, p.maskWords, par);
+        N = min(cb_mask_prefix<NT>(mask, p.maskWords, s_pre, s_wsum), p.nHost);
         if (blockIdx.x == 0 && t == 0) p.countOut[0] = N;
     } else {
         if (MODE == CB_MODE_GATHER) cb_clear_mask(p);
@@ -504,58 +703,15 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
         // per-thread B-load coordinates; a slot past the list is "outside the image"
         int py = -(1 << 20), px = 0, pbase4 = 0;
         if (SELFC) {
-            // pixel of slot j of this tile = the (n0+j)-th set bit of the mask
-            __syncthreads();   // s_tilePix of the previous item is no longer read
-            if (t < BN) {
-                const int r = n0 + t;
-                int pos = -1;
-                if (r < N) {
-                    int lo = 0, hi = p.maskWords;   // largest w with s_pre[w] <= r
-                    while (hi - lo > 1) {
-                        const int mid = (lo + hi) >> 1;
-                        if (s_pre[mid] <= r)
-                            lo = mid;
-                        else
-                            hi = mid;
-                    }
-                    const int bit = cb_select_bit(mask[lo], r - s_pre[lo]);
-                    const int row = lo / p.wpr;
-                    pos = row * p.W + (lo - row * p.wpr) * 64 + bit;
-                    if (m0 == 0 && slice == 0) p.listOut[r] = pos;
-                }
-                s_tilePix[t] = pos;
-            }
-            __syncthreads();
+            cb_selfc_tile_pixels<BN>(s_pre, s_tilePix, mask, p.maskWords, p.wpr, p.W, n0, N, p.listOut,
+                                     m0 == 0 && slice == 0);
             const int pos = s_tilePix[bj];
-            if (pos >= 0) {
-                py = pos / p.W;
-                px = pos - py * p.W;
-                pbase4 = pos * 4;
-            }
+            if (pos >= 0) cb_pixel_coords<4>(pos, p.W, py, px, pbase4);
         } else if (MODE == CB_MODE_GATHER) {
             const int n = n0 + bj;
-            if (n < N) {
-                const int pos = p.list[n];
-                py = pos / p.W;
-                px = pos - py * p.W;
-                pbase4 = pos * 4;
-            }
+            if (n < N) cb_pixel_coords<4>(p.list[n], p.W, py, px, pbase4);
         }
-        // wave-uniform: every tap of every pixel of this wave lies inside the image -> no bounds test
-        // ... and no padded k in this slice: then the pixel's byte offset (minus the most negative tap's) is
-        // the load's vector offset for the whole item and the tap goes in as the SCALAR offset -- no per-tap
-        // address arithmetic at all.  (The scalar offset is not range-checked by the hardware, hence the
-        // conditions; it is unsigned, hence the bias.)
-        bool fast = false;
-        int tapBias = 0, pfast = 0;
-        if (MODE == CB_MODE_GATHER) {
-            const int phh = (p.kH - 1) / 2, pww = (p.kW - 1) / 2;
-            fast = __all(py >= phh && py + (p.kH - 1 - phh) < p.H && px >= pww &&
-                         px + (p.kW - 1 - pww) < p.W) &&
-                   kEnd <= (p.Ckk / BK) * BK;
-            tapBias = (phh * p.W + pww) * 4;
-            pfast = pbase4 - tapBias;
-        }
+        CB_GATHER_FAST(4)   // the interior fast path: no bounds test, the tap as the load's scalar offset
         // taps of the NEXT stage to load, B_PER_T consecutive table entries per array: ONE scalar load
         // each (s_load_dwordx4), kept in scalar registers across the stage
         typedef int ivec __attribute__((ext_vector_type(B_PER_T)));
@@ -845,153 +1001,15 @@ __global__ __launch_bounds__(64 * WM * WN * KS)
         }
         // (the loop ends on a barrier: all LDS stage reads are done and smem may be reused)
 
-        if (KS > 1) {   // sum the wave groups' partial tiles through LDS (fixed order: deterministic)
-            float* red = smem + (wq * MS * 16) * 64 + lane;
-#pragma unroll
-            for (int g = 1; g < KS; ++g) {
-                if (ks == g) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) red[r * 64] = acc[r];
-                    if (MS == 2) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) red[(16 + r) * 64] = acc1[r];
-                    }
-                }
-                __syncthreads();
-                if (ks == 0) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] += red[r * 64];
-                    if (MS == 2) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc1[r] += red[(16 + r) * 64];
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        CB_KGROUP_REDUCE(MS, acc1)
 
-        // one output value: bias / ReLU / the form of the store
-        auto emit = [&](int m, int n, int pix, float v) {
-            if (EPI != CB_EPI_SCATTER_ACC) {
-                if (bias) v += bias[m];
-                if (p.relu) v = cb_relu(v);
-            }
-            if (EPI == CB_EPI_Y)
-                out[(long)n * p.K + m] = v;
-            else if (EPI == CB_EPI_YT)
-                out[(long)m * p.nHost + n] = v;
-            else if (EPI == CB_EPI_SCATTER)
-                out[(long)m * HW + pix] = v;
-            else {
-                const float nv = out[(long)m * HW + pix] + v;
-                out[(long)m * HW + pix] = nv;
-                if (p.reluOut) ((float*)p.reluOut)[(long)m * HW + pix] = cb_relu(nv);
-            }
-        };
-        if (SK > 1) {
-            // Publish this slice's partial tile, take a ticket; the last arriver sums the slices and stores.
-            // Slab = [BM/4][BN] float4: four consecutive output channels of one pixel -- the registers
-            // 4q..4q+3 of a lane's 32x32 accumulator as they stand -- so both sides move 16 bytes per lane in
-            // 512-byte runs.  The stores are write-through (sc1) and drained before the workgroup's ticket,
-            // which replaces the agent-scope release (an L2 write-back per workgroup); with one workgroup
-            // per CU the reducer's sc1 loads also replace the acquire (MI355X_MICROARCH.md, "Inter-workgroup
-            // visibility": publish-large / splitk-seam), otherwise it invalidates its L1 first.
-            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
-            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)p.slabs, 0, (int)min((long)gridDim.x * TILE * 4, (long)0x7fffffff), 0x00020000);
-#define CB_PUBLISH(A, J)                                                                            \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                            \
-                const f32x4 f = {A[4 * q], A[4 * q + 1], A[4 * q + 2], A[4 * q + 3]};                   \
-                const u32x4 v = __builtin_bit_cast(u32x4, f);                                           \
-                const int mq = (wm * MS + (J)) * 8 + 2 * q + h;                                         \
-                __builtin_amdgcn_raw_buffer_store_b128(                                                 \
-                    v, srsrc, (item * (TILE / 4) + mq * BN + wn * 32 + l31) * 16, 0, 16 /* sc1 */);     \
-            }
-            if (ks == 0) {
-                CB_PUBLISH(acc, 0)
-                if (MS == 2) {
-                    CB_PUBLISH(acc1, 1)
-                }
-            }
-#undef CB_PUBLISH
-            if (p.seam) {   // the slices meet in the next launch: nothing to wait for here
-                continue;
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (t == 0) {
-                const int ticket = __hip_atomic_fetch_add(p.tickets + tile, 1, __ATOMIC_RELAXED,
-                                                          __HIP_MEMORY_SCOPE_AGENT);
-                const int last = ticket == SK - 1;
-                if (last) {
-                    if (GPC != 1) {
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    }
-                    __hip_atomic_store(p.tickets + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                s_last = last;
-            }
-            __syncthreads();
-            const bool last = s_last != 0;
-            __syncthreads();   // s_last may be rewritten by the next item
-            if (!last) continue;
-            // every thread: TILE / 4 / NT chunks, all slices of a chunk in flight together
-#pragma unroll
-            for (int c0 = 0; c0 < TILE / 4; c0 += NT) {
-                const int c = c0 + t;
-                float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll 4
-                for (int j = 0; j < SK; ++j) {
-                    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
-                        srsrc, ((tile * SK + j) * (TILE / 4) + c) * 16, 0, 16 /* sc1 */);
-                    const f32x4 f = __builtin_bit_cast(f32x4, v);   // (whole-vector casts: element-wise
-                    s0 += f.x;                                     //  ones on these types came out as splats)
-                    s1 += f.y;
-                    s2 += f.z;
-                    s3 += f.w;
-                }
-                const int nl = c % BN, mq = c / BN;
-                const int n = n0 + nl;
-                int pix = 0;
-                if (EPI >= CB_EPI_SCATTER && n < N) pix = SELFC ? s_tilePix[nl] : p.list[n];
-                if (n < N && (unsigned)pix < (unsigned)HW) {
-                    const int m = m0 + 4 * mq;
-                    if (m < p.K) emit(m, n, pix, s0);
-                    if (m + 1 < p.K) emit(m + 1, n, pix, s1);
-                    if (m + 2 < p.K) emit(m + 2, n, pix, s2);
-                    if (m + 3 < p.K) emit(m + 3, n, pix, s3);
-                }
-            }
-            continue;
-        }
+        auto emit = [&](int m, int n, int pix, float v) { CB_EMIT(float, true) };
+        if (SK > 1) CB_SPLITK_TILE(MS, acc1, true, GPC != 1)
 
-        // epilogue: C/D map of the 32x32 tile: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-        const int n = n0 + wn * 32 + l31;
-        int pix = 0;
-        if (EPI >= CB_EPI_SCATTER && ks == 0 && n < N) pix = SELFC ? s_tilePix[wn * 32 + l31] : p.list[n];
-        // (a list entry outside the map -- a propagated list of another resolution -- is dropped, never
-        // written through: the reference's scatter would corrupt a neighbouring plane, .cu:187)
-        if (ks == 0 && n < N && (unsigned)pix < (unsigned)HW) {
-#pragma unroll
-            for (int rr = 0; rr < 16 * MS; ++rr) {
-                const int r = rr & 15;
-                const int m = m0 + (wm * MS + (rr >> 4)) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (m >= p.K) continue;
-                emit(m, n, pix, rr < 16 ? acc[r] : acc1[r]);
-            }
-        }
+        CB_STORE_TILE(MS, acc1)
     }
 
-    if (SELFC && N > 0) {
-        // every workgroup has read the mask: the last one to get here flips the parity for the next frame.  (An EMPTY
-        // mask -- every workgroup sees that alike -- needs neither: the next detection finds the mask the parity
-        // selects as clean as this one left it, and the other one is zeroed by the next launch that has work; the
-        // arrival tickets were 1.7 of the 5.2 us of a launch with nothing to do.)
-        __syncthreads();
-        if (t == 0) cb_arrive_and_flip(p.frameMasks, p.maskWords, p.tickets, par);
-    }
+    if (SELFC) cb_arrive_and_flip(p.frameMasks, p.maskWords, p.tickets, par, N);
 }
 
 // Second launch of a split-K contraction ("cut the seam"): every thread sums one float4 of a tile over its SK
@@ -1079,13 +1097,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void cb_mfma_f16_kernel(ConvPara
 
     const int t = threadIdx.x;
     CB_UPSTREAM_IDLE_EXIT
-    // ---- SELFC: stream compaction folded into this kernel -------------------------------------------
-    // Every workgroup rebuilds the exclusive popcount prefix of the frame's change mask (<= 32 KB, L2
-    // resident) in LDS; a tile's pixels are then found by rank (binary search over the prefix + select
-    // of the r-th set bit).  No compaction launch, and no hand-off between workgroups.  Two masks
-    // alternate by a device-side parity so that this launch can zero the one the NEXT frame's detection
-    // will fill while every workgroup still reads the current one; the last workgroup to finish flips
-    // the parity.
+    // SELFC: stream compaction folded into this kernel (see cb_selfc_frame_mask)
     __shared__ int s_pre[SELFC ? CB_SELFC_MAXW + 1 : 1];
     __shared__ int s_wsum[SELFC ? NT / 64 : 1];
     __shared__ int s_tilePix[SELFC ? BN : 1];
@@ -1093,49 +1105,8 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void cb_mfma_f16_kernel(ConvPara
     int par = 0;
     int N;
     if (SELFC) {
-        int* ctl = (int*)(p.frameMasks + 2 * (long)p.maskWords);   // {parity, done}
-        par = ctl[0];
-        mask = p.frameMasks + (par ? p.maskWords : 0);
-        unsigned long long* other = p.frameMasks + (par ? 0 : p.maskWords);
-        // (+ round 6: a copy of THIS frame's mask at a fixed address behind the two masks and the control words -- which
-        //  of the two masks is the frame's is a device-side matter (the parity); the copy is what a chained consumer's
-        //  detection reads as its producer mask: segments this layer did not rewrite are skipped)
-        unsigned long long* copy = p.frameMasks + 2 * (long)p.maskWords + 2;
-        for (int i = blockIdx.x * NT + t; i < p.maskWords; i += gridDim.x * NT) other[i] = 0ull, copy[i] = mask[i];
-        // Exclusive prefix of the per-word popcounts.  Pass 1: coalesced, independent loads (word t,
-        // t+NT, ...) -> counts in LDS; pass 2 (LDS only): thread t owns CH consecutive words.
-        const int CH = (p.maskWords + NT - 1) / NT;
-#pragma unroll 4
-        for (int w = t; w < p.maskWords; w += NT) s_pre[w] = __popcll(mask[w]);
-        __syncthreads();
-        const int wb = t * CH;
-        int loc = 0;
-        for (int u = 0; u < CH; ++u) {
-            const int w = wb + u;
-            if (w < p.maskWords) loc += s_pre[w];
-        }
-        int incl = loc;   // inclusive scan over the wave, then over the waves
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o);
-            if ((t & 63) >= o) incl += v;
-        }
-        if ((t & 63) == 63) s_wsum[t >> 6] = incl;
-        __syncthreads();
-        int base = 0;
-        for (int w = 0; w < (t >> 6); ++w) base += s_wsum[w];
-        int run = base + incl - loc;
-        for (int u = 0; u < CH; ++u) {
-            const int w = wb + u;
-            if (w < p.maskWords) {
-                const int c = s_pre[w];   // count -> exclusive prefix, in place (this thread's chunk only)
-                s_pre[w] = run;
-                run += c;
-            }
-        }
-        if (t == NT - 1) s_pre[p.maskWords] = base + incl;   // the last thread's chunk ends the mask
-        __syncthreads();
-        N = min(s_pre[p.maskWords], p.nHost);
+        mask = cb_selfc_frame_mask<NT>(p.frameMasks, p.maskWords, par);
+        N = min(cb_mask_prefix<NT>(mask, p.maskWords, s_pre, s_wsum), p.nHost);
         if (blockIdx.x == 0 && t == 0) p.countOut[0] = N;
     } else {
         if (MODE == CB_MODE_GATHER) cb_clear_mask(p);
@@ -1192,56 +1163,15 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void cb_mfma_f16_kernel(ConvPara
         // per-thread B-load coordinates; a slot past the list is "outside the image"
         int py = -(1 << 20), px = 0, pbase4 = 0;
         if (SELFC) {
-            // pixel of slot j of this tile = the (n0+j)-th set bit of the mask
-            __syncthreads();   // s_tilePix of the previous item is no longer read
-            if (t < BN) {
-                const int r = n0 + t;
-                int pos = -1;
-                if (r < N) {
-                    int lo = 0, hi = p.maskWords;   // largest w with s_pre[w] <= r
-                    while (hi - lo > 1) {
-                        const int mid = (lo + hi) >> 1;
-                        if (s_pre[mid] <= r)
-                            lo = mid;
-                        else
-                            hi = mid;
-                    }
-                    const int bit = cb_select_bit(mask[lo], r - s_pre[lo]);
-                    const int row = lo / p.wpr;
-                    pos = row * p.W + (lo - row * p.wpr) * 64 + bit;
-                    if (m0 == 0 && slice == 0) p.listOut[r] = pos;
-                }
-                s_tilePix[t] = pos;
-            }
-            __syncthreads();
+            cb_selfc_tile_pixels<BN>(s_pre, s_tilePix, mask, p.maskWords, p.wpr, p.W, n0, N, p.listOut,
+                                     m0 == 0 && slice == 0);
             const int pos = s_tilePix[bj];
-            if (pos >= 0) {
-                py = pos / p.W;
-                px = pos - py * p.W;
-                pbase4 = pos * 2;
-            }
+            if (pos >= 0) cb_pixel_coords<2>(pos, p.W, py, px, pbase4);
         } else if (MODE == CB_MODE_GATHER) {
             const int n = n0 + bj;
-            if (n < N) {
-                const int pos = p.list[n];
-                py = pos / p.W;
-                px = pos - py * p.W;
-                pbase4 = pos * 2;
-            }
+            if (n < N) cb_pixel_coords<2>(p.list[n], p.W, py, px, pbase4);
         }
-        // wave-uniform: every tap of every pixel of this wave lies inside the image -> no bounds test
-        // ... and no padded k in this slice: the tap then goes in as the load's (unsigned, unchecked) scalar
-        // offset, biased by the most negative tap, and the pixel's byte offset serves the whole item
-        bool fast = false;
-        int tapBias = 0, pfast = 0;
-        if (MODE == CB_MODE_GATHER) {
-            const int phh = (p.kH - 1) / 2, pww = (p.kW - 1) / 2;
-            fast = __all(py >= phh && py + (p.kH - 1 - phh) < p.H && px >= pww &&
-                         px + (p.kW - 1 - pww) < p.W) &&
-                   kEnd <= (p.Ckk / BK) * BK;
-            tapBias = (phh * p.W + pww) * 2;
-            pfast = pbase4 - tapBias;
-        }
+        CB_GATHER_FAST(2)   // the interior fast path: no bounds test, the tap as the load's scalar offset
         int aoff[A_PER_T];
 #pragma unroll
         for (int i = 0; i < A_PER_T; ++i) {
@@ -1378,150 +1308,32 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void cb_mfma_f16_kernel(ConvPara
         }
         __syncthreads();   // all LDS stage reads done: smem may be reused
 
-        if (KS > 1) {   // sum the wave groups' partial tiles through LDS (fixed order: deterministic)
-            float* red = smem + (wq * 16) * 64 + lane;
-#pragma unroll
-            for (int g = 1; g < KS; ++g) {
-                if (ks == g) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) red[r * 64] = acc[r];
-                }
-                __syncthreads();
-                if (ks == 0) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] += red[r * 64];
-                }
-                __syncthreads();
-            }
-        }
+        CB_KGROUP_REDUCE(1, acc)   // (one row tile per wave: no second accumulator)
 
-        auto emit = [&](int m, int n, int pix, float v) {
-            if (EPI != CB_EPI_SCATTER_ACC) {
-                if (bias) v += (float)bias[m];
-                if (p.relu) v = cb_relu(v);
-            }
-            if (EPI == CB_EPI_Y)
-                out[(long)n * p.K + m] = (cb_half)v;
-            else if (EPI == CB_EPI_YT)
-                out[(long)m * p.nHost + n] = (cb_half)v;
-            else if (EPI == CB_EPI_SCATTER)
-                out[(long)m * HW + pix] = (cb_half)v;
-            else
-                out[(long)m * HW + pix] = (cb_half)((float)out[(long)m * HW + pix] + v);
-        };
-        if (SK > 1) {
-            // publish this slice's partial tile, take a ticket; the last arriver sums and stores -- the
-            // protocol and slab layout of cb_mfma_f32_kernel ([BM/4][BN] float4, write-through stores, no
-            // release; two workgroups per CU: the reducer invalidates its L1 before its sc1 loads)
-            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
-            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)p.slabs, 0, (int)min((long)gridDim.x * TILE * 4, (long)0x7fffffff), 0x00020000);
-            if (ks == 0) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 f = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-                    const u32x4 v = __builtin_bit_cast(u32x4, f);
-                    const int mq = wm * 8 + 2 * q + h;
-                    __builtin_amdgcn_raw_buffer_store_b128(
-                        v, srsrc, (item * (TILE / 4) + mq * BN + wn * 32 + l31) * 16, 0, 16 /* sc1 */);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (t == 0) {
-                const int ticket = __hip_atomic_fetch_add(p.tickets + tile, 1, __ATOMIC_RELAXED,
-                                                          __HIP_MEMORY_SCOPE_AGENT);
-                const int last = ticket == SK - 1;
-                if (last) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(p.tickets + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                s_last = last;
-            }
-            __syncthreads();
-            const bool last = s_last != 0;
-            __syncthreads();   // s_last may be rewritten by the next item
-            if (!last) continue;
-#pragma unroll
-            for (int c0 = 0; c0 < TILE / 4; c0 += NT) {
-                const int c = c0 + t;
-                float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll 4
-                for (int j = 0; j < SK; ++j) {
-                    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
-                        srsrc, ((tile * SK + j) * (TILE / 4) + c) * 16, 0, 16 /* sc1 */);
-                    const f32x4 f = __builtin_bit_cast(f32x4, v);
-                    s0 += f.x;
-                    s1 += f.y;
-                    s2 += f.z;
-                    s3 += f.w;
-                }
-                const int nl = c % BN, mq = c / BN;
-                const int n = n0 + nl;
-                int pix = 0;
-                if (EPI >= CB_EPI_SCATTER && n < N) pix = SELFC ? s_tilePix[nl] : p.list[n];
-                if (n < N && (unsigned)pix < (unsigned)HW) {
-                    const int m = m0 + 4 * mq;
-                    if (m < p.K) emit(m, n, pix, s0);
-                    if (m + 1 < p.K) emit(m + 1, n, pix, s1);
-                    if (m + 2 < p.K) emit(m + 2, n, pix, s2);
-                    if (m + 3 < p.K) emit(m + 3, n, pix, s3);
-                }
-            }
-            continue;
-        }
+        auto emit = [&](int m, int n, int pix, float v) { CB_EMIT(cb_half, false) };
+        if (SK > 1) CB_SPLITK_TILE(1, acc, false, true)   // (two workgroups per CU: the summing one acquires)
 
-        // epilogue: C/D map of the 32x32 tile: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-        const int n = n0 + wn * 32 + l31;
-        int pix = 0;
-        if (EPI >= CB_EPI_SCATTER && ks == 0 && n < N) pix = SELFC ? s_tilePix[wn * 32 + l31] : p.list[n];
-        // (a list entry outside the map -- a propagated list of another resolution -- is dropped, never
-        // written through: the reference's scatter would corrupt a neighbouring plane, .cu:187)
-        if (ks == 0 && n < N && (unsigned)pix < (unsigned)HW) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (m >= p.K) continue;
-                emit(m, n, pix, acc[r]);
-            }
-        }
+        CB_STORE_TILE(1, acc)
     }
 
-    if (SELFC && N > 0) {
-        // every workgroup has read the mask: the last one to get here flips the parity for the next frame.  (An EMPTY
-        // mask -- every workgroup sees that alike -- needs neither: the next detection finds the mask the parity
-        // selects as clean as this one left it, and the other one is zeroed by the next launch that has work; the
-        // arrival tickets were 1.7 of the 5.2 us of a launch with nothing to do.)
-        __syncthreads();
-        if (t == 0) cb_arrive_and_flip(p.frameMasks, p.maskWords, p.tickets, par);
-    }
+    if (SELFC) cb_arrive_and_flip(p.frameMasks, p.maskWords, p.tickets, par, N);
 }
 
-// Tile configuration: KP == 32 (K <= 32): one m-tile, 128 pixels per workgroup (1 x 4 waves); otherwise
-// 64 x 64 (2 x 2 waves).  KS (in-block split-K) = 2.
-int cb_num_cus() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            cus = n;
-        else
-            cus = 256;
-    }
-    return cus;
+// Persistent grid of a contraction with BM x BN tiles: perCU workgroups per CU -- fewer only if the tile capacity of
+// the list itself is smaller and there is no split-K workspace (or in-kernel compaction) to spread it with; 0: no tile.
+long cb_conv_grid(const ConvParams& p, int BM, int BN, int perCU, bool selfc) {
+    const long tilesCap = (long)cb_div_up(p.nHost, BN) * (p.KP / BM);
+    if (tilesCap == 0) return 0;
+    long g = perCU * (long)cb_num_cus();
+    if (!p.slabs && tilesCap < g && !selfc) g = tilesCap;
+    return g;
 }
 
 template <int WM, int WN, int KS, int MODE, int EPI, bool SELFC = false, bool X3 = false, int MS = 1, bool BHALF = false>
 int launch_f32(const ConvParams& p, hipStream_t s) {
-    const long tilesCap = (long)cb_div_up(p.nHost, 32 * WN) * (p.KP / (32 * WM * MS));
-    if (tilesCap == 0) return CB_OK;
-    // persistent grid: 2 workgroups per CU, 1 of the 1024-thread form (fewer only if the capacity itself is
-    // smaller and there is no split-K workspace to spread it with)
-    long g = (WM * WN * KS > 8 ? 1 : CB_CONV_GRID_PER_CU) * (long)cb_num_cus();
-    if (!p.slabs && tilesCap < g && !SELFC) g = tilesCap;
+    // 2 workgroups per CU, 1 of the 1024-thread form
+    const long g = cb_conv_grid(p, 32 * WM * MS, 32 * WN, WM * WN * KS > 8 ? 1 : CB_CONV_GRID_PER_CU, SELFC);
+    if (g == 0) return CB_OK;
     dim3 grid((unsigned)g), block(64 * WM * WN * KS);
     // (the second launch pays where a tile's slices are 64 KB each -- the 16-wave forms; with 16 KB slabs the
     //  last workgroup's reduce is cheaper than a launch boundary: OpenPose's 36 small layers lost 5 % to it)
@@ -1541,10 +1353,8 @@ int launch_f32(const ConvParams& p, hipStream_t s) {
 
 template <int WM, int WN, int KS, int MODE, int EPI, bool SELFC = false>
 int launch_f16(const ConvParams& p, hipStream_t s) {
-    const long tilesCap = (long)cb_div_up(p.nHost, 32 * WN) * (p.KP / (32 * WM));
-    if (tilesCap == 0) return CB_OK;
-    long g = CB_CONV_GRID_PER_CU * (long)cb_num_cus();
-    if (!p.slabs && tilesCap < g && !SELFC) g = tilesCap;
+    const long g = cb_conv_grid(p, 32 * WM, 32 * WN, CB_CONV_GRID_PER_CU, SELFC);
+    if (g == 0) return CB_OK;
     dim3 grid((unsigned)g), block(64 * WM * WN * KS);
     hipLaunchKernelGGL((cb_mfma_f16_kernel<WM, WN, KS, MODE, EPI, SELFC>), grid, block, 0, s, p);
     return cb_launch_status();
@@ -1565,45 +1375,78 @@ int cb_x3_wide(int KP) {
     return 0;
 }
 
+// Calls launch(SELFC) with the SELFC bit taken from p.frameMasks.  A frame mask with a form that has no in-kernel
+// compaction (HAS_SELFC false: a matrix mode or a non-scatter epilogue) is a bad argument.
+template <bool HAS_SELFC, typename Launch>
+int cb_launch_selfc(const ConvParams& p, Launch launch) {
+    if (!p.frameMasks) return launch(std::false_type());
+    if constexpr (HAS_SELFC)
+        return launch(std::true_type());   // self-compacting frame pipeline
+    else
+        return CB_ERR_BADARG;
+}
+
+// Tile configuration: KP == 32 (K <= 32): one m-tile, 128 pixels per workgroup (1 x 4 waves); otherwise
+// 64 x 64 (2 x 2 waves), or one of the 16-wave forms of the bf16x3 arithmetic (cb_x3_wide).  KS (in-block split-K) = 2.
 template <int MODE, int EPI>
 int launch_mfma(const ConvParams& p0, int dtype, hipStream_t s) {
     ConvParams p = p0;
     // split-K slices summed by a second launch (scatter epilogues with a workspace)
     p.seam = p.slabs && EPI >= CB_EPI_SCATTER && (dtype == CB_F32 || dtype == CB_F32S);
     const bool narrow = p.KP <= 32;
-    if (dtype == CB_F32S) {   // f32 tensors, bf16x3 split products (gather modes only)
-        if constexpr (MODE == CB_MODE_GATHER && EPI >= CB_EPI_SCATTER) {
-            if (p.frameMasks) {
-                if (narrow) return launch_f32<1, 4, 2, CB_MODE_GATHER, EPI, true, true>(p, s);
-                if (cb_x3_wide(p.KP) == 2) return launch_f32<4, 2, 2, CB_MODE_GATHER, EPI, true, true, 2, true>(p, s);
-                if (cb_x3_wide(p.KP) >= 1) return launch_f32<2, 4, 2, CB_MODE_GATHER, EPI, true, true, 2>(p, s);
-                return launch_f32<2, 2, 2, CB_MODE_GATHER, EPI, true, true>(p, s);
-            }
-            if (narrow) return launch_f32<1, 4, 2, CB_MODE_GATHER, EPI, false, true>(p, s);
-            if (cb_x3_wide(p.KP) == 2) return launch_f32<4, 2, 2, CB_MODE_GATHER, EPI, false, true, 2, true>(p, s);
-            if (cb_x3_wide(p.KP) >= 1) return launch_f32<2, 4, 2, CB_MODE_GATHER, EPI, false, true, 2>(p, s);
-            return launch_f32<2, 2, 2, CB_MODE_GATHER, EPI, false, true>(p, s);
+    constexpr bool scatters = MODE == CB_MODE_GATHER && EPI >= CB_EPI_SCATTER;
+    if (dtype == CB_F32S) {   // f32 tensors, bf16x3 split products (gather + scatter only)
+        if constexpr (scatters) {
+            return cb_launch_selfc<true>(p, [&](auto selfc) {
+                constexpr bool SC = decltype(selfc)::value;
+                if (narrow) return launch_f32<1, 4, 2, MODE, EPI, SC, true>(p, s);
+                if (cb_x3_wide(p.KP) == 2) return launch_f32<4, 2, 2, MODE, EPI, SC, true, 2, true>(p, s);
+                if (cb_x3_wide(p.KP) >= 1) return launch_f32<2, 4, 2, MODE, EPI, SC, true, 2>(p, s);
+                return launch_f32<2, 2, 2, MODE, EPI, SC, true>(p, s);
+            });
         } else {
             return CB_ERR_UNSUPPORTED;
         }
     }
-    if (dtype == CB_F32) {
-        if (p.frameMasks) {   // self-compacting frame pipeline
-            if (MODE != CB_MODE_GATHER || EPI < CB_EPI_SCATTER) return CB_ERR_BADARG;
-            constexpr int E = EPI < CB_EPI_SCATTER ? CB_EPI_SCATTER : EPI;
-            if (narrow) return launch_f32<1, 4, 2, CB_MODE_GATHER, E, true>(p, s);
-            return launch_f32<2, 2, 2, CB_MODE_GATHER, E, true>(p, s);
-        }
-        if (narrow) return launch_f32<1, 4, 2, MODE, EPI>(p, s);
-        return launch_f32<2, 2, 2, MODE, EPI>(p, s);
+    if (dtype == CB_F32)
+        return cb_launch_selfc<scatters>(p, [&](auto selfc) {
+            constexpr bool SC = decltype(selfc)::value;
+            if (narrow) return launch_f32<1, 4, 2, MODE, EPI, SC>(p, s);
+            return launch_f32<2, 2, 2, MODE, EPI, SC>(p, s);
+        });
+    // fp16: in-kernel compaction with the plain scatter only (no fine-grained frame in fp16)
+    return cb_launch_selfc<scatters && EPI == CB_EPI_SCATTER>(p, [&](auto selfc) {
+        constexpr bool SC = decltype(selfc)::value;
+        if (narrow) return launch_f16<1, 4, 2, MODE, EPI, SC>(p, s);
+        return launch_f16<2, 2, 2, MODE, EPI, SC>(p, s);
+    });
+}
+
+// The ConvParams of a fused gather -> contraction -> scatter over the layer state `input` [C,H,W], for up to nHost
+// pixels; workspace (optional): [tickets: grid ints, padded to 4 KB][slabs: one partial tile per workgroup of the grid]
+ConvParams cb_gather_params(const void* input, const void* weightsPrepared, const void* bias, void* output, int nHost,
+                            int C, int H, int W, int K, int kH, int kW, int relu, void* workspace, int dtype) {
+    ConvParams p = {};
+    p.A = weightsPrepared;
+    p.B = input;
+    p.bias = bias;
+    p.out = output;
+    p.nHost = nHost;
+    p.K = K;
+    p.KP = cbinfer_weights_kpad(K);
+    p.Ckk = C * kH * kW;
+    p.CkkP = cb_ckkpad(p.Ckk, dtype);
+    p.C = C;
+    p.H = H;
+    p.W = W;
+    p.kH = kH;
+    p.kW = kW;
+    p.relu = relu;
+    if (workspace) {
+        p.tickets = (int*)workspace;
+        p.slabs = (float*)((char*)workspace + 4096);
     }
-    if (p.frameMasks) {
-        if (MODE != CB_MODE_GATHER || EPI != CB_EPI_SCATTER) return CB_ERR_BADARG;
-        if (narrow) return launch_f16<1, 4, 2, CB_MODE_GATHER, CB_EPI_SCATTER, true>(p, s);
-        return launch_f16<2, 2, 2, CB_MODE_GATHER, CB_EPI_SCATTER, true>(p, s);
-    }
-    if (narrow) return launch_f16<1, 4, 2, MODE, EPI>(p, s);
-    return launch_f16<2, 2, 2, MODE, EPI>(p, s);
+    return p;
 }
 
 }  // namespace
@@ -1723,30 +1566,12 @@ int cbinfer_conv_changed(const void* input, const int32_t* changeList, int numCh
     CB_REQUIRE(dtype == CB_F32 || dtype == CB_F16 || dtype == CB_F32S);
     if ((long)C * kH * kW > 65535 || (long)C * H * W * 4 >= (1l << 30)) return CB_ERR_UNSUPPORTED;
     if (numChanges == 0) return CB_OK;
-    ConvParams p = {};
-    p.A = weightsPrepared;
-    p.B = input;
-    p.bias = bias;
-    p.out = output;
+    ConvParams p = cb_gather_params(input, weightsPrepared, bias, output, numChanges, C, H, W, K, kH, kW, relu, workspace,
+                                    dtype);
     p.list = changeList;
     p.countDev = countDev;
-    p.nHost = numChanges;
-    p.K = K;
-    p.KP = cbinfer_weights_kpad(K);
-    p.Ckk = C * kH * kW;
-    p.CkkP = cb_ckkpad(p.Ckk, dtype);
-    p.C = C;
-    p.H = H;
-    p.W = W;
-    p.kH = kH;
-    p.kW = kW;
-    p.relu = relu;
     p.clearBits = (unsigned long long*)clearBits;
     p.clearWords = clearBits ? clearWords : 0;
-    if (workspace) {   // [tickets: grid ints, padded to 4 KB][slabs: one partial tile per workgroup of the grid]
-        p.tickets = (int*)workspace;
-        p.slabs = (float*)((char*)workspace + 4096);
-    }
     if (accumulate)
         return launch_mfma<CB_MODE_GATHER, CB_EPI_SCATTER_ACC>(p, dtype, (hipStream_t)stream);
     return launch_mfma<CB_MODE_GATHER, CB_EPI_SCATTER>(p, dtype, (hipStream_t)stream);
@@ -1765,32 +1590,13 @@ static int cb_conv_from_mask(const void* input, uint64_t* frameMasks, int32_t* i
     const long words = cbinfer_mask_words(H, W);
     if (words > CB_SELFC_MAXW || (long)C * kH * kW > 65535 || (long)C * H * W * 4 >= (1l << 30))
         return CB_ERR_UNSUPPORTED;
-    ConvParams p = {};
-    p.A = weightsPrepared;
-    p.B = input;
-    p.bias = bias;
-    p.out = output;
-    p.nHost = H * W;
-    p.K = K;
-    p.KP = cbinfer_weights_kpad(K);
-    p.Ckk = C * kH * kW;
-    p.CkkP = cb_ckkpad(p.Ckk, dtype);
-    p.C = C;
-    p.H = H;
-    p.W = W;
-    p.kH = kH;
-    p.kW = kW;
-    p.relu = relu;
+    ConvParams p = cb_gather_params(input, weightsPrepared, bias, output, H * W, C, H, W, K, kH, kW, relu, workspace, dtype);
     p.frameMasks = (unsigned long long*)frameMasks;
     p.maskWords = (int)words;
     p.wpr = cbinfer_mask_words_per_row(W);
     p.listOut = idxOut;
     p.countOut = countOut;
     p.upstream = upstream;
-    if (workspace) {
-        p.tickets = (int*)workspace;
-        p.slabs = (float*)((char*)workspace + 4096);
-    }
     if (accumulate) {
         if (dtype != CB_F32 && dtype != CB_F32S) return CB_ERR_UNSUPPORTED;
         p.reluOut = reluOut;

@@ -7,11 +7,6 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned long long cb_valid_mask(int W, int tile) {
-    const int rem = W - tile * 64;
-    return rem >= 64 ? ~0ull : ((1ull << rem) - 1ull);
-}
-
 // One workgroup = one 64-pixel row segment x all channels.  blockDim.x = 64*G: wave g scans channels
 // g, g+G, ... (each wave-load is one coalesced 256-B (fp32) / 128-B (fp16) segment of a channel row),
 // the per-wave ballots are OR-reduced through LDS, and the resulting 64-bit word is dilated with

@@ -18,9 +18,6 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short ushortx8 __attribute__((ext_vector_type(8)));
 
 #define CBG_MAX_K 7      // filter size per axis
@@ -185,28 +182,6 @@ struct GeomConvParams {
     int K, KP, CkkP, Hi, Wi, Ho, Wo, sH, sW, relu;
 };
 
-// r-th (0-based) set bit of w, r < popcount(w)
-__device__ __forceinline__ int cbg_select_bit(unsigned long long w, int r) {
-    int pos = 0;
-#pragma unroll
-    for (int width = 32; width >= 1; width >>= 1) {
-        const int c = __popcll(w & (((1ull << width) - 1ull) << pos));
-        if (r >= c) r -= c, pos += width;
-    }
-    return pos;
-}
-
-// x = hi + mid + lo, three bf16 terms (24 significant bits; both differences are exact in f32)
-__device__ __forceinline__ void cbg_split3(float x, unsigned short& hi, unsigned short& mid, unsigned short& lo) {
-    const __bf16 h = (__bf16)x;
-    const float r1 = x - (float)h;
-    const __bf16 m = (__bf16)r1;
-    const __bf16 l = (__bf16)(r1 - (float)m);
-    hi = __builtin_bit_cast(unsigned short, h);
-    mid = __builtin_bit_cast(unsigned short, m);
-    lo = __builtin_bit_cast(unsigned short, l);
-}
-
 #define CBG_ROW16 40      // LDS row of 32 16-bit k-slots + 16 bytes (16-byte fragment reads free of conflicts)
 #define CBG_ROW32 33
 
@@ -230,9 +205,9 @@ struct CbgStage<CB_F32S> {
         ushortx8 h, m, l;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            unsigned short a, b, c;
-            cbg_split3(x[i], a, b, c);
-            h[i] = a, m[i] = b, l[i] = c;
+            unsigned a, b, c;
+            cb_split3(x[i], a, b, c);
+            h[i] = (unsigned short)a, m[i] = (unsigned short)b, l[i] = (unsigned short)c;
         }
         *(ushortx8*)&v[0][row][k0] = h;
         *(ushortx8*)&v[1][row][k0] = m;
@@ -394,7 +369,7 @@ __global__ __launch_bounds__(256) void cbg_conv_kernel(GeomConvParams p) {
                         if (r < c) break;
                         r -= c;
                     }
-                    if (w < wEnd) pix = (int)(w / p.wpr) * p.Wo + (int)(w % p.wpr) * 64 + cbg_select_bit(mw, r);
+                    if (w < wEnd) pix = (int)(w / p.wpr) * p.Wo + (int)(w % p.wpr) * 64 + cb_select_bit(mw, r);
                 } else {
                     pix = p.list[q];
                 }

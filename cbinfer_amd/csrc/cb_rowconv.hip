@@ -33,8 +33,6 @@
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 struct RowParams {
     const float* state;     // [C,H,W] layer state the gather reads (conv2d.py:242)
     const float* wq;        // prepared weights (fragment order)
@@ -62,21 +60,6 @@ struct RowParams {
         unsigned long long* maskCopy;
     } seq[CBINFER_SPLIT_MAX_SEQUENCES];
 };
-
-// r-th (0-based) set bit of w, r < popcount(w)
-__device__ __forceinline__ int cb_nth_bit(unsigned long long w, int r) {
-    int pos = 0;
-#pragma unroll
-    for (int width = 32; width >= 1; width >>= 1) {
-        const unsigned long long lowmask = ((1ull << width) - 1ull) << pos;
-        const int c = __popcll(w & lowmask);
-        if (r >= c) {
-            r -= c;
-            pos += width;
-        }
-    }
-    return pos;
-}
 
 #define CB_ROW_MAXW 16           // waves per workgroup: 4 per output-channel chunk, up to 4 chunks
 #define CB_ROW_MAXROWS 256
@@ -181,7 +164,7 @@ __global__ __launch_bounds__(64 * CB_ROW_MAXW) void cb_rowconv_f32_kernel(RowPar
     const int nt = 2 * nh + sub % nTw, kp = sub / nTw;
     const bool active = mc < p.MCH && nt < nT;
     const int n = nt * 16 + (lane & 15);
-    const int xl = cb_nth_bit(word, n < pc ? n : 0);
+    const int xl = cb_select_bit(word, n < pc ? n : 0);
     const int base = (lane >> 4) * CS + xl;   // + tap offset (ky*RS + kx + 4 g CS) = LDS float index
     const int bBeg = NB * kp / kparts, bEnd = NB * (kp + 1) / kparts, bLast = max(bEnd - 1, bBeg);
 

@@ -35,9 +35,6 @@
 
 namespace cbp {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-using cbs::halfx8;
-
 #define CBP_NT 256
 #define CBP_NW 4
 #define CBP_MAXCAND 4               // candidate units per workgroup: the grid is at least units / 4
@@ -72,21 +69,6 @@ __host__ __device__ constexpr int cbp_plane_stride(int kH, int kW) {
     int cs = (kH + 1) * (64 + kW - 1);
     while (cs % 32 != 16) ++cs;     // lane quarters q and q+1 hit disjoint bank halves
     return cs;
-}
-
-// r-th (0-based) set bit of w, r < popcount(w)
-__device__ __forceinline__ int cbp_nth_bit(unsigned long long w, int r) {
-    int pos = 0;
-#pragma unroll
-    for (int width = 32; width >= 1; width >>= 1) {
-        const unsigned long long lowmask = ((1ull << width) - 1ull) << pos;
-        const int c = __popcll(w & lowmask);
-        if (r >= c) {
-            r -= c;
-            pos += width;
-        }
-    }
-    return pos;
 }
 
 #ifdef CBP_STAMP
@@ -453,7 +435,7 @@ __global__ __launch_bounds__(CBP_NT, 4) void cbp_rowpair_kernel(PairParams p) {
         int xl0 = 0, xl1 = 0;
         floatx4 accA = {0.f, 0.f, 0.f, 0.f}, accB = accA;
         if (tile0 * 16 < pc) {
-            xl0 = cbp_nth_bit(word, n0 < pc ? n0 : 0), xl1 = cbp_nth_bit(word, n1 < pc ? n1 : 0);
+            xl0 = cb_select_bit(word, n0 < pc ? n0 : 0), xl1 = cb_select_bit(word, n1 < pc ? n1 : 0);
             const float* pl0 = s_patch + (lane >> 4) * CS + row * RS + xl0;
             const float* pl1 = s_patch + (lane >> 4) * CS + row * RS + xl1;
             // (the second tile is multiplied whether it exists or not -- its lanes then read the first changed pixel's
@@ -624,19 +606,6 @@ __global__ __launch_bounds__(CBP_NT, 4) void cbp_rowpair_kernel(PairParams p) {
     CBP_STAMP_AT(7);
 }
 
-static int cbp_num_cus() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            cus = n;
-        else
-            cus = 256;
-    }
-    return cus;
-}
-
 }  // namespace cbp
 using namespace cbp;
 
@@ -710,7 +679,7 @@ static int cbp_launch(const cbPairSeq* seqs, int nSeq, const void* prepared, con
     // worked through one after the other (8 us each, mostly round trips to memory), so up to eight workgroups per CU
     // are started -- one candidate unit each at 480x320: the empty ones are gone after 1.8 us -- and at most
     // CBP_MAXCAND candidates each beyond that
-    long grid = 8l * cbp_num_cus();
+    long grid = 8l * cb_num_cus();
     if (grid > total) grid = total;
     if (grid * CBP_MAXCAND < total) grid = (total + CBP_MAXCAND - 1) / CBP_MAXCAND;
     if (kH == 7)

@@ -56,7 +56,6 @@ __device__ unsigned long long cbs_stamp_buf[4 * 2048 * 16];
 namespace cbs {
 
 typedef __attribute__((address_space(3))) void* cb_lds_ptr;
-typedef __attribute__((address_space(4))) const int cbs_const_int;
 
 // ---------------------------------------------------------------------------------------------------
 // weights: [stage][row tile of 32][k-step][plane][lane][8 f16] (MFMA A-fragment order) + the stage table
@@ -193,11 +192,6 @@ struct CbsDetArgs {
                       // operand of out += W * delta -- and so does the f32 delta tensor (the exact path's operand)
 };
 
-__device__ __forceinline__ unsigned long long cbs_valid_mask(int W, int tile) {
-    const int rem = W - tile * 64;
-    return rem >= 64 ? ~0ull : ((1ull << rem) - 1ull);
-}
-
 // One workgroup = one 64-pixel row segment x all channels of one sequence (blockIdx.z); wave g owns channels
 // g, g+G, g+2G, g+3G (G = C/4 waves).  Decomposition, predicate (strict >, cbconv2d_cg_backend.cu:56), dilation
 // and producer-mask shortcut are cb_detect_kernel's (cb_detect.hip); what is new is the second state: the new
@@ -286,7 +280,7 @@ __global__ __launch_bounds__(1024) void cbs_detect_kernel(CbsDetArgs a) {
     // the pixels whose states take the new values: the changed ones (feedback mode), or -- copy-all -- those of the
     // segment that hold a value that differs from the state bit for bit (behind another change-based layer the frame is
     // bit-identical to the last one wherever that layer recomputed nothing); fine-grained: all (the records hold deltas)
-    const unsigned long long upd = a.fg ? cbs_valid_mask(W, tx) : (a.copyAll ? md : m);
+    const unsigned long long upd = a.fg ? cb_valid_mask(W, tx) : (a.copyAll ? md : m);
     if (upd == 0) return;               // (copy-all, nothing differs: nothing above the threshold either)
 
     // feedback: refresh the f32 state at the (pre-dilation) changed pixels only (.cu:74-80) ...
@@ -329,8 +323,8 @@ __global__ __launch_bounds__(1024) void cbs_detect_kernel(CbsDetArgs a) {
         SR |= m >> (64 - d);
         SL |= m << (64 - d);
     }
-    D &= cbs_valid_mask(W, tx);
-    SR = (tx + 1 < a.wpr) ? (SR & cbs_valid_mask(W, tx + 1)) : 0ull;
+    D &= cb_valid_mask(W, tx);
+    SR = (tx + 1 < a.wpr) ? (SR & cb_valid_mask(W, tx + 1)) : 0ull;
     if (tx == 0) SL = 0;
     if (g == 0) {
         const int items = 3 * (2 * a.kHH + 1);
@@ -853,7 +847,7 @@ __global__ __launch_bounds__(64 * WM * WN) void cbs_conv_kernel(CbsParams p, typ
     }
 
     const int aRecords = (int)min(p.aBytes, (long)0x7fffffff);
-    cbs_const_int* stageOff = (cbs_const_int*)p.stageOff;
+    const cb_const_int* stageOff = (const cb_const_int*)p.stageOff;
     const int HW = p.H * p.W;
     const float lo2 = 1.0f / CBS_LO;
 
@@ -1690,8 +1684,8 @@ __global__ __launch_bounds__(64 * WM * WN) void cbs_conv_kernel(CbsParams p, typ
                             SR |= acc >> (64 - d);
                             SL |= acc << (64 - d);
                         }
-                        D &= cbs_valid_mask(ext.W2, wi);
-                        SR = (wi + 1 < ext.wpr2) ? (SR & cbs_valid_mask(ext.W2, wi + 1)) : 0ull;
+                        D &= cb_valid_mask(ext.W2, wi);
+                        SR = (wi + 1 < ext.wpr2) ? (SR & cb_valid_mask(ext.W2, wi + 1)) : 0ull;
                         if (wi == 0) SL = 0ull;
                         for (int yy = max(y2 - ext.kHH, 0); yy <= min(y2 + ext.kHH, ext.H2 - 1); ++yy) {
                             unsigned long long* row = ext.nmasks + (long)yy * ext.wpr2 + wi;
@@ -2224,43 +2218,30 @@ __global__ __launch_bounds__(64 * CB_TAIL_MAXW) void cbs_reduce_tail_kernel(CbsP
     }
 }
 
-int cbs_num_cus() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            cus = n;
-        else
-            cus = 256;
-    }
-    return cus;
-}
-
 template <int BM, int BN, int WM, int WN, int PRE_CAP, bool MASK_LDS, int RING, int AR = 0>
 int cbs_launch_conv(const CbsParams& p, int perCU, const CbsTailArgs* tail, hipStream_t s,
                     const typename CbsExtOf<AR>::type& ext = typename CbsExtOf<AR>::type()) {
     if ((long)p.nSeq * p.maskWords > PRE_CAP) return CB_ERR_UNSUPPORTED;
     const bool second = p.slabs && (p.nStages >= 48 || p.forceSK > 0);
     if (tail && !second) return CB_ERR_UNSUPPORTED;      // (the fused tail reads the launch info of a deep contraction)
-    dim3 grid((unsigned)(perCU * cbs_num_cus())), block(64 * WM * WN);
+    dim3 grid((unsigned)(perCU * cb_num_cus())), block(64 * WM * WN);
     hipLaunchKernelGGL((cbs_conv_kernel<BM, BN, WM, WN, PRE_CAP, MASK_LDS, RING, AR>), grid, block, 0, s, p, ext);
     int st = cb_launch_status();
     if (st != CB_OK) return st;
     if constexpr (AR == 1) {
         if (second) {      // (fp16: the group-aware second launch, which also runs the consumers' detection)
-            hipLaunchKernelGGL((cbh_reduce_kernel<BM, BN>), dim3(2 * cbs_num_cus()), dim3(256), 0, s, p, ext);
+            hipLaunchKernelGGL((cbh_reduce_kernel<BM, BN>), dim3(2 * cb_num_cus()), dim3(256), 0, s, p, ext);
             st = cb_launch_status();
         }
         return st;
     }
     if (tail) {
         const int waves = (tail->C1 + 15) / 16;
-        hipLaunchKernelGGL((cbs_reduce_tail_kernel<BM, BN>), dim3(2 * cbs_num_cus()), dim3(64 * waves),
+        hipLaunchKernelGGL((cbs_reduce_tail_kernel<BM, BN>), dim3(2 * cb_num_cus()), dim3(64 * waves),
                            cb_tail_lds_bytes(p.K, tail->C1, tail->C2), s, p, *tail);
         st = cb_launch_status();
     } else if (second) {
-        hipLaunchKernelGGL(cbs_reduce_kernel, dim3(4 * cbs_num_cus()), dim3(256), 0, s, p, BM, BN);
+        hipLaunchKernelGGL(cbs_reduce_kernel, dim3(4 * cb_num_cus()), dim3(256), 0, s, p, BM, BN);
         st = cb_launch_status();
     }
     return st;
@@ -2314,7 +2295,7 @@ long cbinfer_split3_prepared_bytes(int C, int K, int kH, int kW) {
 static long cbs_slab_capacity(int nSeq, int H, int W, int K) {
     const int bm = cbs_bm(K), bn = bm >= 128 ? 128 : 64;
     const long tiles = (long)nSeq * (((long)H * W + bn - 1) / bn) * (cbs_kp(K) / bm);
-    return tiles > 2l * cbs_num_cus() ? tiles : 2l * cbs_num_cus();
+    return tiles > 2l * cb_num_cus() ? tiles : 2l * cb_num_cus();
 }
 long cbinfer_split_workspace_bytes(int nSeq, int C, int H, int W, int K, int kH, int kW) {
     if (!cbs_supported(C, K, kH, kW)) return 0;
@@ -2896,7 +2877,7 @@ __global__ __launch_bounds__(512) void cbh_detect_kernel(CbhDetGroup grp) {
     };
     __shared__ unsigned long long sm[8];
     __shared__ _Float16 T[64][66];
-    const unsigned long long vm = cbs_valid_mask(W, tx);
+    const unsigned long long vm = cb_valid_mask(W, tx);
     char* const recRow = a.S + CBS_SPAD + ((long)(y + a.padY) * a.Wp + (tx * 64 + a.padXL)) * a.rec;
 
     // one channel group: [compare] -> [state <- input at the lanes of upd] -> [records of the pixels of upd]
@@ -2984,7 +2965,7 @@ __global__ __launch_bounds__(512) void cbh_detect_kernel(CbhDetGroup grp) {
         SL |= m << (64 - d);
     }
     D &= vm;
-    SR = (tx + 1 < a.wpr) ? (SR & cbs_valid_mask(W, tx + 1)) : 0ull;
+    SR = (tx + 1 < a.wpr) ? (SR & cb_valid_mask(W, tx + 1)) : 0ull;
     if (tx == 0) SL = 0;
     if (g == 0) {
         const int items = 3 * (2 * a.kHH + 1);
@@ -3087,7 +3068,7 @@ int cbinfer_hsplit_forward_group(const cbHalfLayer* layers, int nLayers, int poo
     // tile height reads them): OpenPose's 128->128 @184x327 at 24 % change 21 -> 12 us, 128->256 @92x163 19 -> 10 us.
     {
         const long full128 = (((long)H * W + 127) / 128) * (KP / 128);
-        if (BM == 128 && g.nStages < 48 && full128 < 4l * cbs_num_cus()) BM = 64;
+        if (BM == 128 && g.nStages < 48 && full128 < 4l * cb_num_cus()) BM = 64;
     }
     hipStream_t s = (hipStream_t)stream;
     const int wpr = cbinfer_mask_words_per_row(W);

@@ -7,10 +7,6 @@
 
 namespace cbs {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #define CBS_MAXSEQ CBINFER_SPLIT_MAX_SEQUENCES
 #define CBS_XSCALE 0.0625f            // activations are stored as x * 2^-4 (range up to 2^20, see header)
 #define CBS_XSCALE_INV 16.f

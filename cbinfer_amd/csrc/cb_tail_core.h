@@ -3,8 +3,7 @@
 // and cbs_reduce_tail_kernel (cb_split.hip), which makes them from the partial tiles of a split contraction: one
 // body, so both give the same bits.
 #pragma once
-
-typedef float cb_tail_floatx4 __attribute__((ext_vector_type(4)));
+#include "cb_common.h"
 
 #ifndef CB_TAIL_STAMP
 #define CB_TAIL_STAMP(i)
@@ -35,14 +34,14 @@ __host__ __device__ inline size_t cb_tail_lds_bytes(int C0, int C1, int C2) {
 // of its 16 rows of W1 (all of them up to 256 input channels) and its rows' biases.  Loaded ONCE per workgroup, at
 // the top of the kernel, so that the request travels together with everything else the kernel asks for first.
 struct CbTailPre {
-    cb_tail_floatx4 a[16];
+    floatx4 a[16];
     float b1v[4];
 };
 __device__ __forceinline__ void cb_tail_preload(CbTailPre& P, const float* __restrict__ w1p,
                                                 const float* __restrict__ b1, int C0P, int C1) {
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int groups = C0P / 16;
-    const cb_tail_floatx4* ap = (const cb_tail_floatx4*)w1p + ((long)wave * groups) * 64 + lane;
+    const floatx4* ap = (const floatx4*)w1p + ((long)wave * groups) * 64 + lane;
 #pragma unroll
     for (int i = 0; i < 16; ++i) P.a[i] = ap[(long)min(i, groups - 1) * 64];
 #pragma unroll
@@ -57,7 +56,6 @@ __device__ __forceinline__ void cb_tail_preload(CbTailPre& P, const float* __res
 __device__ __forceinline__ void cb_tail_tile(const CbTailLds& l, const int* s_pix, const CbTailPre& P,
                                              const float* __restrict__ w1p, float* out, int C0P, int C1, int C2, int HW,
                                              int relu1, int relu2) {
-    typedef cb_tail_floatx4 floatx4;
     const int t = threadIdx.x, NT = blockDim.x;
     const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     float* Xs = l.Xs;
