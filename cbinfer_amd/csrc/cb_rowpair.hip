@@ -92,8 +92,13 @@ __device__ unsigned long long cbp_stamp_buf[4096 * 8];
 // REFRESHED values (frame where the pixel changed, state elsewhere: .cu:74-80).  It does not write the state: a neighbour
 // that starts later must still see the old one -- the refresh is left to a launch behind this one (cbs_conv_kernel's idle
 // workgroups: cbinfer_refresh_state's loop).  No global mask, no mask round trip in front of the patch's, no detection launch.
+// FIVE workgroups per CU are resident (the other instances: four), so the 1280 units of a 480x320 frame = 5 x 256 CUs all
+// start at once instead of a fifth of them behind the first empty units: 30.6 KB of static LDS (a fifth of 160 KB is 32 KB;
+// the pooled values share the patch's space) and <= 96 registers -- what kept the instance at 127 were the invariants of the
+// candidate-unit loop hoisted in front of it and spilled or held through the unit; with its ONE candidate (NCAND) there is no
+// loop, and the instance needs 64.
 template <int KH, int KW, bool DET = false>
-__global__ __launch_bounds__(CBP_NT, 4) void cbp_rowpair_kernel(PairParams p) {
+__global__ __launch_bounds__(CBP_NT, DET ? 5 : 4) void cbp_rowpair_kernel(PairParams p) {
     cb_touch_kernarg<sizeof(PairParams)>();
 #ifdef CBP_STAMP
     bool cbp_first = true;
@@ -101,10 +106,15 @@ __global__ __launch_bounds__(CBP_NT, 4) void cbp_rowpair_kernel(PairParams p) {
     CBP_STAMP_AT(0);
     constexpr int RS = 64 + KW - 1, PR = KH + 1, CS = cbp_plane_stride(KH, KW), S = KH * KW, G = (S + 3) / 4;
     constexpr int PH = (KH - 1) / 2, PW = (KW - 1) / 2;
+    constexpr int NCAND = DET ? 1 : CBP_MAXCAND;      // candidate units of a workgroup (DET: the grid is the units)
     __shared__ float s_patch[4 * CS];
+    // pooled values [channel][xo]: in the patch's place -- the patch is dead behind the k-loop, and the barrier in front of
+    // the pooled detection stands between its last reader and the first pooled value (the next unit stages its patch
+    // behind that unit's first barrier)
+    static_assert(4 * CS >= 16 * 33, "the pooled values take the patch's place");
+    float* const s_P = s_patch;
     __shared__ __attribute__((aligned(16))) float s_w[G * 256];     // the weights, MFMA fragment order: [group][lane][4]
     __shared__ __attribute__((aligned(16))) float s_out[2 * 16 * 64];          // [row][channel][x]: the pair's outputs after this frame
-    __shared__ float s_P[16 * 33];                // pooled values [channel][xo]
     __shared__ unsigned s_chg[CBP_NW];
     __shared__ unsigned long long s_rb[DET ? 2 * (KH + 1) : 1];      // DET: changed pixels of the patch, [row][64 + KW - 1 bits]
 
@@ -126,7 +136,7 @@ __global__ __launch_bounds__(CBP_NT, 4) void cbp_rowpair_kernel(PairParams p) {
 
     // ---- this workgroup's candidate units: blockIdx.x, + gridDim.x, ... (neighbouring units go to different
     //      workgroups); their mask words are requested in one burst and are the same for every lane ---------------
-    unsigned long long cwA[CBP_MAXCAND], cwB[CBP_MAXCAND];
+    unsigned long long cwA[NCAND], cwB[NCAND];
     constexpr int PROWS = 4 * PR;                       // patch rows: plane x row
     constexpr int PX4 = (PROWS * 16 + CBP_NT - 1) / CBP_NT, PED = (PROWS * (KW - 1) + CBP_NT - 1) / CBP_NT;
     floatx4 xv4[DET ? PX4 : 1], sv4[DET ? PX4 : 1];
@@ -163,7 +173,7 @@ __global__ __launch_bounds__(CBP_NT, 4) void cbp_rowpair_kernel(PairParams p) {
         }
     }
 #pragma unroll
-    for (int k = 0; k < CBP_MAXCAND; ++k) {
+    for (int k = 0; k < NCAND; ++k) {
         if constexpr (DET) {
             cwA[k] = 0ull, cwB[k] = 0ull;
             continue;
@@ -246,9 +256,9 @@ __global__ __launch_bounds__(CBP_NT, 4) void cbp_rowpair_kernel(PairParams p) {
     };
     bool any = false;
 #pragma unroll
-    for (int k = 0; k < CBP_MAXCAND; ++k) {
+    for (int k = 0; k < NCAND; ++k) {
         cwA[k] = uniform64(cwA[k]), cwB[k] = uniform64(cwB[k]);
-        if (k == CBP_MAXCAND - 1) CBP_STAMP_AT(1);
+        if (k == NCAND - 1) CBP_STAMP_AT(1);
         any |= (cwA[k] | cwB[k]) != 0ull;
     }
     // A unit's two mask words belong to this workgroup alone: it leaves the frame's copy at its fixed address and zeroes
@@ -262,7 +272,7 @@ __global__ __launch_bounds__(CBP_NT, 4) void cbp_rowpair_kernel(PairParams p) {
     auto finish = [&]() {
         if (t == 0) {
 #pragma unroll
-            for (int k = 0; k < CBP_MAXCAND; ++k) {
+            for (int k = 0; k < NCAND; ++k) {
                 const int u = blockIdx.x + k * gridDim.x;
                 if (u < units) {
                     const int q = u / unitsSeq, ul = u - q * unitsSeq;
@@ -294,10 +304,10 @@ __global__ __launch_bounds__(CBP_NT, 4) void cbp_rowpair_kernel(PairParams p) {
     }
 
 #pragma unroll 1
-    for (int k = 0; k < CBP_MAXCAND; ++k) {
+    for (int k = 0; k < NCAND; ++k) {
         unsigned long long wordA = cwA[0], wordB = cwB[0];
 #pragma unroll
-        for (int j = 1; j < CBP_MAXCAND; ++j)
+        for (int j = 1; j < NCAND; ++j)
             if (j == k) wordA = cwA[j], wordB = cwB[j];
         if ((wordA | wordB) == 0ull) continue;      // (uniform)
         const int u = blockIdx.x + k * gridDim.x;
@@ -671,8 +681,11 @@ static int cbp_launch(const cbPairSeq* seqs, int nSeq, const void* prepared, con
     }
     const long total = (long)p.units * nSeq;
     if (frame) {      // DET: one unit per workgroup, the layer's own detection inside (one sequence, 7x7)
-        if (nSeq != 1 || kH != 7) return CB_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL((cbp_rowpair_kernel<7, 7, true>), dim3((unsigned)total), dim3(CBP_NT), 0, (hipStream_t)stream, p);
+        // (the instance looks at the unit blockIdx.x of sequence 0 and at no other: grid == units, one sequence -- anything
+        //  else is refused here, not computed wrongly there)
+        const long grid = total;
+        if (nSeq != 1 || kH != 7 || grid != (long)p.units) return CB_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL((cbp_rowpair_kernel<7, 7, true>), dim3((unsigned)grid), dim3(CBP_NT), 0, (hipStream_t)stream, p);
         return cb_launch_status();
     }
     // four workgroups of four waves per CU are resident (<= 128 registers, 32 KB of LDS each); a workgroup's units are

@@ -605,16 +605,34 @@ __global__ __launch_bounds__(64 * WM * WN) void cbs_conv_kernel(CbsParams p, typ
     // LDS and never looks at the mask again.  On its way OUT of the kernel each workgroup counts itself on an
     // arrival counter behind the mask, and the one that learns it was the last zeroes the masks for the next
     // frame's detection.  Nobody waits for anybody; the next launch finds them clean.
-    for (int q = t; q < p.nSeq; q += NT) s_maskPtr[q] = p.seq[q].masks;
     // the layer's range flag (set by the detection when a state value left the f16 pair's range, sticky): requested
     // here, looked at behind the scan -- such a sequence's tiles are then computed by plain f32 arithmetic from the
-    // f32 state (cbs_exact_tile below): slow, right, in this very frame
+    // f32 state (cbs_exact_tile below): slow, right, in this very frame.  Thread q < nSeq: the pointers of sequence q by
+    // a select per sequence out of the kernel arguments (indexed by the thread they are loads from the argument block,
+    // a round trip each in front of the scan's)
     int flagv = 0;
-    if (t < p.nSeq) {
-        const int* rf = p.seq[t].rangeFlag;
-        if (rf) flagv = *rf;
+    static_assert(NT >= CBS_MAXSEQ, "one thread per sequence");
+    if (p.nSeq == 1) {
+        if (t == 0) {
+            const int* rf = p.seq[0].rangeFlag;
+            s_maskPtr[0] = p.seq[0].masks;
+            if (rf) flagv = *rf;
+        }
+    } else if (t < CBS_MAXSEQ) {
+        // (cbs_uniform_ptr: the compiler otherwise turns the selects back into one load at a selected address)
+        const void *mp = nullptr, *rf = nullptr;
+#pragma unroll
+        for (int j = 0; j < CBS_MAXSEQ; ++j) {
+            const void* mj = cbs_uniform_ptr(p.seq[j].masks);
+            const void* rj = cbs_uniform_ptr(p.seq[j].rangeFlag);
+            if (t == j) mp = mj, rf = rj;
+        }
+        if (t < p.nSeq) {
+            s_maskPtr[t] = (const unsigned long long*)mp;
+            if (rf) flagv = *(const __attribute__((address_space(1))) int*)rf;      // (a global load, not a flat one)
+        }
     }
-    __syncthreads();
+    // (s_maskPtr is read behind the scan's barriers: none is needed here)
     const int E = p.nSeq * MW;
     // Thread t owns the CH consecutive words [t CH, (t+1) CH) of the concatenated masks: their popcounts stay in
     // registers, one wave scan + one exchange of the wave totals gives every thread its base, and the exclusive
@@ -632,27 +650,46 @@ __global__ __launch_bounds__(64 * WM * WN) void cbs_conv_kernel(CbsParams p, typ
         const int CHU = (EU + NT - 1) / NT, ub = t * CHU;
         unsigned long long cntU[CUMAX], wA[CUMAX], wB[CUMAX];
         unsigned long long locU = 0ull;
-        const unsigned long long* mk = s_maskPtr[0];
+        // the words of ALL of this thread's units in one burst, in front of one wait: never predicated (a predicated load
+        // is a branch, and the chunks then cost a round trip each) -- clamped addresses, predicated uses; global loads
+        // through the pointer of the kernel arguments (out of LDS it is a generic one: flat loads, LDS counter and all)
+        const unsigned long long* mk = p.seq[0].masks;
+#pragma unroll
+        for (int u = 0; u < CUMAX; ++u) {
+            const int i = min(ub + u, EU - 1);
+            const int yo = cbs_div(i, p.magicWpr), tx = i - yo * p.wpr, ya = 2 * yo;
+            wA[u] = mk[ya * p.wpr + tx];
+            wB[u] = mk[min(ya + 1, p.H - 1) * p.wpr + tx];
+        }
+#pragma unroll
+        for (int u = 0; u < CUMAX; ++u) asm volatile("" ::"v"(wA[u]), "v"(wB[u]));      // (every load is issued: none sinks into a use's branch)
 #pragma unroll
         for (int u = 0; u < CUMAX; ++u) {
             const int i = ub + u;
-            cntU[u] = 0ull, wA[u] = 0ull, wB[u] = 0ull;
-            if (u < CHU && i < EU) {
-                const int yo = cbs_div(i, p.magicWpr), tx = i - yo * p.wpr, ya = 2 * yo;
-                const unsigned long long a = mk[ya * p.wpr + tx];
-                const unsigned long long b0 = mk[min(ya + 1, p.H - 1) * p.wpr + tx];      // (clamped, not predicated)
-                const unsigned long long b = ya + 1 < p.H ? b0 : 0ull;
-                const unsigned long long v = a | b;
-                wA[u] = a, wB[u] = b;
-                cntU[u] = (unsigned long long)__popcll(a) | ((unsigned long long)__popcll(b) << 20) |
-                          ((unsigned long long)__popcll((v | (v >> 1)) & 0x5555555555555555ull) << 40);
-            }
+            const bool own = u < CHU && i < EU;
+            const int ic = min(i, EU - 1);
+            const int yo = cbs_div(ic, p.magicWpr), ya = 2 * yo;
+            const unsigned long long a = own ? wA[u] : 0ull;
+            const unsigned long long b = own && ya + 1 < p.H ? wB[u] : 0ull;
+            const unsigned long long v = a | b;
+            wA[u] = a, wB[u] = b;
+            cntU[u] = (unsigned long long)__popcll(a) | ((unsigned long long)__popcll(b) << 20) |
+                      ((unsigned long long)__popcll((v | (v >> 1)) & 0x5555555555555555ull) << 40);
             locU += cntU[u];
         }
-        {
+        {      // the frame's copy of the mask: the first workgroup, every thread the words it holds
             unsigned long long* copy = p.seq[0].maskCopy;
-            if (copy)
-                for (int i = blockIdx.x * NT + t; i < MW; i += gridDim.x * NT) copy[i] = mk[i];
+            if (copy && blockIdx.x == 0) {
+#pragma unroll
+                for (int u = 0; u < CUMAX; ++u) {
+                    const int i = ub + u;
+                    if (u < CHU && i < EU) {
+                        const int yo = cbs_div(i, p.magicWpr), tx = i - yo * p.wpr, ya = 2 * yo;
+                        copy[ya * p.wpr + tx] = wA[u];
+                        if (ya + 1 < p.H) copy[(ya + 1) * p.wpr + tx] = wB[u];
+                    }
+                }
+            }
         }
         unsigned long long incl = locU;
 #pragma unroll
@@ -698,24 +735,55 @@ __global__ __launch_bounds__(64 * WM * WN) void cbs_conv_kernel(CbsParams p, typ
         constexpr int CHMAX = (PRE_CAP + NT - 1) / NT;
         const int CHW = (E + NT - 1) / NT, wb = t * CHW;
         int cnt[CHMAX];
-        unsigned long long wordReg[MASK_LDS ? CHMAX : 1];
+        unsigned long long wordReg[CHMAX];
         int loc = 0;
+        // the words of ALL of this thread's chunks in one burst, in front of one wait (see the window-order scan): clamped
+        // addresses, predicated uses, global loads; several sequences: the pointer by the word's sequence index out of
+        // the kernel arguments (scalar registers, a select per sequence)
+        if (p.nSeq == 1) {
+            const unsigned long long* mk = p.seq[0].masks;
+    #pragma unroll
+            for (int u = 0; u < CHMAX; ++u) wordReg[u] = mk[min(wb + u, E - 1)];
+        } else {
+    #pragma unroll
+            for (int u = 0; u < CHMAX; ++u) {
+                const int i = min(wb + u, E - 1);
+                const int q = cbs_div(i, p.magicMW), w = i - q * MW;
+                const unsigned long long* mk = p.seq[0].masks;
+    #pragma unroll
+                for (int j = 1; j < CBS_MAXSEQ; ++j) mk = q == j ? p.seq[j].masks : mk;
+                wordReg[u] = mk[w];
+            }
+        }
+    #pragma unroll
+        for (int u = 0; u < CHMAX; ++u) asm volatile("" ::"v"(wordReg[u]));      // (every load is issued: none sinks into a use's branch)
     #pragma unroll
         for (int u = 0; u < CHMAX; ++u) {
             const int i = wb + u;
-            cnt[u] = 0;
-            if (u < CHW && i < E) {
-                const int q = cbs_div(i, p.magicMW), w = i - q * MW;
-                const unsigned long long word = s_maskPtr[q][w];
-                cnt[u] = __popcll(word);
-                if (MASK_LDS) wordReg[u] = word;
-            }
+            if (!(u < CHW && i < E)) wordReg[u] = 0ull;
+            cnt[u] = __popcll(wordReg[u]);
             loc += cnt[u];
         }
-        for (int q = 0; q < p.nSeq; ++q) {      // this launch also leaves a copy of the frame's masks at a fixed address
-            unsigned long long* copy = p.seq[q].maskCopy;
-            if (copy)
-                for (int i = blockIdx.x * NT + t; i < MW; i += gridDim.x * NT) copy[i] = s_maskPtr[q][i];
+        if (blockIdx.x == 0) {      // this launch also leaves a copy of the frame's masks at a fixed address: the first
+                                    // workgroup, every thread the words it holds
+            if (p.nSeq == 1) {
+                unsigned long long* copy = p.seq[0].maskCopy;
+                if (copy) {
+    #pragma unroll
+                    for (int u = 0; u < CHMAX; ++u)
+                        if (u < CHW && wb + u < E) copy[wb + u] = wordReg[u];
+                }
+            } else {
+    #pragma unroll
+                for (int u = 0; u < CHMAX; ++u) {
+                    const int i = wb + u;
+                    const int q = cbs_div(min(i, E - 1), p.magicMW), w = i - q * MW;
+                    unsigned long long* copy = p.seq[0].maskCopy;
+    #pragma unroll
+                    for (int j = 1; j < CBS_MAXSEQ; ++j) copy = q == j ? p.seq[j].maskCopy : copy;
+                    if (u < CHW && i < E && copy) copy[w] = wordReg[u];
+                }
+            }
         }
         {
             int incl = loc;
