@@ -12,6 +12,7 @@ import torch.nn as nn
 from . import _lib                      # loads libcbinfer_hip.so; raises ImportError if not built
 from .conv2d import CBConv2d
 from .conv2d import CBPoolMax2d
+from .conv2d import CBPoolAvg2d
 from .conv2d import CBTail1x1
 from .conv2d_cg import ChangeIndexes, ChannelConcat
 from .pipeline import FramePipeline
@@ -123,24 +124,41 @@ def propChangeIndexesOf1x1(rootModule):
     return rootModule
 
 
-def insertCBPooling(rootModule, cloneOutput=True):
+def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
     """what sceneLabeling/modelLoader.py:62-78 does by hand for experiments 5/6, for any
     converted network: every 2x2/stride-2 nn.MaxPool2d that directly follows a CBConv2d inside an
     nn.Sequential becomes a CBPoolMax2d fed by that layer's change indexes (propChangeIndexes on the
     conv), so only the windows holding a changed pixel are pooled again.  A CBConv2d consuming the pool
-    then needs its own input copy (copyInput) unless it runs in feedback mode.  Returns rootModule."""
+    then needs its own input copy (copyInput) unless it runs in feedback mode.  generalGeometry=True: every
+    nn.MaxPool2d and nn.AvgPool2d within the library's limits (CBPoolMax2d(m, generalGeometry=True), CBPoolAvg2d) is
+    converted; a pool beyond them stays the dense torch operator.  Returns rootModule."""
     def _pair(v):
         return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+    def _converted(pool):
+        if generalGeometry:
+            try:
+                if type(pool) == torch.nn.MaxPool2d:
+                    return CBPoolMax2d(pool, generalGeometry=True)
+                if type(pool) == torch.nn.AvgPool2d:
+                    return CBPoolAvg2d(pool)
+            except _lib.CBinferError:
+                pass      # (beyond the limits: stays dense)
+            return None
+        if (type(pool) == torch.nn.MaxPool2d and
+                _pair(pool.kernel_size) == (2, 2) and _pair(pool.stride) == (2, 2) and
+                _pair(pool.padding) == (0, 0) and _pair(pool.dilation) == (1, 1)):
+            return CBPoolMax2d(pool)
+        return None
+
     for seq in _sequentials(rootModule):
         names = list(seq._modules.keys())
         for a, b in zip(names[:-1], names[1:]):
             conv, pool = seq._modules[a], seq._modules[b]
-            if (type(conv) == CBConv2d and type(pool) == torch.nn.MaxPool2d and
-                    _pair(pool.kernel_size) == (2, 2) and _pair(pool.stride) == (2, 2) and
-                    _pair(pool.padding) == (0, 0) and _pair(pool.dilation) == (1, 1)):
+            cb = _converted(pool) if type(conv) == CBConv2d else None
+            if cb is not None:
                 _log('change-based pooling after %s' % a)
                 conv.propChangeIndexes = True
-                cb = CBPoolMax2d(pool)
                 cb.cloneOutput = cloneOutput
                 seq._modules[b] = cb
                 nxt = names.index(b) + 1
@@ -164,8 +182,9 @@ def fusePoolingIntoDetection(rootModule, enabled=True):
                 # (a feedback-mode layer, or -- round 4 -- a fine-grained one in its in-place form: its split-state frame
                 #  takes the pool's input as it is, cbinfer_split_forward_fg; other fine-grained frames pool first)
                 # (a general-geometry consumer has no pooled detection: the pool in front of it keeps pooling itself)
+                # (a pool of any other window than 2x2/s2/p0 -- cb_pool2d.hip -- is never folded: it pools itself)
                 pool.lazy = bool(enabled and type(consumer) == CBConv2d and not pool.propChangeIndexes and
-                                 not consumer.__dict__.get('_geom') and
+                                 not pool.__dict__.get('_general') and not consumer.__dict__.get('_geom') and
                                  ((consumer.feedbackLoop and not consumer.finegrained) or
                                   (consumer.finegrained and consumer.fgInPlace) or
                                   # (a layer that keeps a copy of its input: the copy-all detection of the split-state
@@ -225,7 +244,7 @@ def linkConsumers(producer, consumers):
     return producer
 
 
-_STATEFUL = (CBConv2d, CBPoolMax2d, CBTail1x1)
+_STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1)
 
 
 def _stateful(net):
@@ -342,7 +361,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBTail1x1', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

@@ -99,6 +99,16 @@ class Geom(ctypes.Structure):
 
 _gp, _ip = ctypes.POINTER(Geom), ctypes.POINTER(ctypes.c_int)
 
+POOL_MAX, POOL_AVG_PAD, POOL_AVG_NOPAD = 0, 1, 2      # CB_POOL_*
+
+
+class Pool(ctypes.Structure):
+    """cbPool of include/cbinfer_hip.h: window, stride, padding, ceil_mode and operation of a change-based pool."""
+    _fields_ = [("kH", _i), ("kW", _i), ("sH", _i), ("sW", _i), ("pH", _i), ("pW", _i), ("ceilMode", _i), ("op", _i)]
+
+
+_pp = ctypes.POINTER(Pool)
+
 _SIGNATURES = {
     # name: (restype, [argtypes])
     "cbinfer_abi_version": (_i, []),
@@ -233,6 +243,11 @@ _SIGNATURES = {
                                        _vp]),
     "cbinfer_cbconv2d_forward_geom": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _gp, _f, _i, _i, _i, _i,
                                            _i, _vp, _i, _vp]),
+    "cbinfer_pool_supported": (_i, [_pp]),
+    "cbinfer_pool_out_size": (_i, [_i, _i, _pp, _ip, _ip]),
+    "cbinfer_pool_footprint": (_i, [_vp, _i, _vp, _vp, _i, _i, _pp, _vp, _vp]),
+    "cbinfer_pool_changed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _pp, _i, _vp]),
+    "cbinfer_cbpool2d_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _pp, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, stream_ptr
-from .conv2d import CBConv2d, CBPoolMax2d, CBTail1x1, _switch
+from .conv2d import CBConv2d, CBPoolAvg2d, CBPoolMax2d, CBTail1x1, _switch
 
 
 def _ptr_array(tensors):
@@ -41,6 +41,9 @@ class SequenceBatch(object):
                                    "padding=%s dilation=%s%s), which has no batched kernel"
                                    % (name, tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation),
                                       '' if m.bias is not None else ', no bias'))
+            if type(m) in (CBPoolMax2d, CBPoolAvg2d) and m.__dict__.get('_general'):
+                raise CBinferError("SequenceBatch: layer %r is %r, a pool that is never folded into the next detection "
+                                   "(only 2x2/stride 2 without padding is) and has no batched kernel" % (name, m))
         self.net = net
         self.layers = None          # built on the first frame (needs the frame size)
         self._key = None
@@ -69,12 +72,12 @@ class SequenceBatch(object):
         if len(_lib.SplitTail().output) != C.cbinfer_split_max_sequences():
             raise CBinferError("SequenceBatch: cbSplitTail.output[] and cbinfer_split_max_sequences() disagree")
         for pos, m in enumerate(kids):
-            if type(m) is CBPoolMax2d:
+            if type(m) in (CBPoolMax2d, CBPoolAvg2d):
                 if not layers:
                     raise CBinferError("SequenceBatch: a CBPoolMax2d needs a producing CBConv2d in front of it")
                 if not getattr(m, 'lazy', False) or m.propChangeIndexes:
                     raise CBinferError("SequenceBatch: CBPoolMax2d must be folded into the next detection "
-                                       "(pycbinfer.fusePoolingIntoDetection)")
+                                       "(pycbinfer.fusePoolingIntoDetection): child %d, %r, is not" % (pos, m))
                 _, c, h, w = shape
                 oh, ow = ((h - 1) // 2 + 1, (w - 1) // 2 + 1) if m.ceil_mode else (h // 2, w // 2)
                 pooledFrom = (len(layers) - 1, h, w)

@@ -163,14 +163,65 @@ class LazyPool(object):
         return F.max_pool2d(self.source, 2, 2, ceil_mode=self.ceil_mode)
 
 
-class CBPoolMax2d(nn.Module):
-    """Change-based 2x2/stride-2 max pooling (reference: conv2d.py:24-84)."""
+def _pool_pair(v, what):
+    """An int or a pair of ints of a pooling module as a pair; CBinferError for anything else (a string, a triple)."""
+    if isinstance(v, int) and not isinstance(v, bool):
+        return (v, v)
+    if isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in v):
+        return tuple(v)
+    raise _lib.CBinferError("change-based pooling: %s=%r is not supported, only an int or a pair of ints" % (what, v))
 
-    def __init__(self, m):
+
+def _check_general_pool(m, kind):
+    """(kernel_size, stride, padding, cbPool operation) if the general change-based pool takes `m`, an nn.MaxPool2d
+    (kind 'max') or nn.AvgPool2d ('avg'): per axis window <= 8, stride <= 8, padding <= window / 2, dilation 1, no
+    return_indices, no divisor_override.  CBinferError with a sentence otherwise."""
+    Err = _lib.CBinferError
+    if kind == 'max':
+        name, op = 'CBPoolMax2d', _lib.POOL_MAX
+        if not isinstance(m, nn.MaxPool2d):
+            raise Err("CBPoolMax2d: only nn.MaxPool2d modules are converted")
+        if _pool_pair(m.dilation, 'dilation') != (1, 1):
+            raise Err("CBPoolMax2d: dilated max pooling is not supported (dilation=%s)" % (m.dilation,))
+        if m.return_indices:
+            raise Err("CBPoolMax2d: return_indices=True is not supported (the change-based pool keeps no argmax)")
+    else:
+        name = 'CBPoolAvg2d'
+        if not isinstance(m, nn.AvgPool2d):
+            raise Err("CBPoolAvg2d: only nn.AvgPool2d modules are converted")
+        if m.divisor_override is not None:
+            raise Err("CBPoolAvg2d: divisor_override=%r is not supported" % (m.divisor_override,))
+        op = _lib.POOL_AVG_PAD if m.count_include_pad else _lib.POOL_AVG_NOPAD
+    k = _pool_pair(m.kernel_size, 'kernel_size')
+    s = _pool_pair(m.stride if m.stride is not None else m.kernel_size, 'stride')
+    p = _pool_pair(m.padding, 'padding')
+    g = _lib.Pool(k[0], k[1], s[0], s[1], p[0], p[1], int(bool(m.ceil_mode)), op)
+    if not C.cbinfer_pool_supported(ctypes.byref(g)):
+        raise Err("%s: kernel_size=%s stride=%s padding=%s is beyond what the library takes (per axis: window <= 8, "
+                  "stride <= 8, padding <= window / 2)" % (name, k, s, p))
+    return k, s, p, op
+
+
+class CBPoolMax2d(nn.Module):
+    """Change-based max pooling: 2x2/stride-2 (reference: conv2d.py:24-84) and, with generalGeometry=True, any window,
+    stride, zero padding and ceil_mode within the library's limits (cb_pool2d.hip)."""
+    _KIND = 'max'
+
+    def __init__(self, m, generalGeometry=False):
         super(CBPoolMax2d, self).__init__()
-        ks = m.kernel_size if isinstance(m.kernel_size, tuple) else (m.kernel_size,) * 2
-        st = m.stride if isinstance(m.stride, tuple) else (m.stride,) * 2
-        assert ks == (2, 2) and st == (2, 2)
+        self.generalGeometry = bool(generalGeometry)
+        if self.generalGeometry:
+            ks, st, pd, self._op = _check_general_pool(m, self._KIND)
+        else:
+            ks = m.kernel_size if isinstance(m.kernel_size, tuple) else (m.kernel_size,) * 2
+            st = m.stride if isinstance(m.stride, tuple) else (m.stride,) * 2
+            assert ks == (2, 2) and st == (2, 2)
+            pd, self._op = (0, 0), _lib.POOL_MAX
+        # a window the 2x2 kernel cannot take runs on cb_pool2d.hip; a 2x2/s2/p0 max pool runs as it always did
+        self._general = self.generalGeometry and (self._KIND != 'max' or (ks, st, pd) != ((2, 2), (2, 2), (0, 0)))
+        self.padding = pd
+        self._poolC = None
+        self._poolWork = None
         self.stride = st
         self.kernel_size = ks
         self.ceil_mode = m.ceil_mode
@@ -189,15 +240,111 @@ class CBPoolMax2d(nn.Module):
         if not hasattr(self, 'outputState') or 'outputState' not in self._buffers:
             self.register_buffer('outputState', torch.zeros(0))
         self.outputState = self.outputState.new_zeros(0)
+        self.__dict__['_poolWork'] = None      # (device work buffers of the general path, not part of the state)
 
     def getStateTensors(self):
         return [self.outputState] if hasattr(self, 'outputState') else []
+
+    def _setDefaultValues(self):
+        # back-fill attributes missing in modules pickled by older versions
+        for name, val in (('generalGeometry', False), ('_general', False), ('padding', (0, 0)), ('_op', _lib.POOL_MAX),
+                          ('_poolC', None), ('_poolWork', None)):
+            if name not in self.__dict__:
+                self.__dict__[name] = val
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d.update(_poolC=None, _poolWork=None)      # (transient: the ctypes struct and the device work buffers)
+        return d
+
+    def __setstate__(self, state):
+        super(CBPoolMax2d, self).__setstate__(state)
+        self._setDefaultValues()
+
+    # ---------------------------------------------------------------- any window (cb_pool2d.hip)
+    def _pool_struct(self):
+        """(pointer to) the module's cbPool; transient, made again after unpickling."""
+        if self.__dict__.get('_poolC') is None:
+            k, s_, p_ = self.kernel_size, self.stride, self.padding
+            self.__dict__['_poolC'] = ctypes.pointer(_lib.Pool(k[0], k[1], s_[0], s_[1], p_[0], p_[1],
+                                                               int(bool(self.ceil_mode)), self._op))
+        return self.__dict__['_poolC']
+
+    def _out_hw(self, Hi, Wi):
+        Ho, Wo = ctypes.c_int(), ctypes.c_int()
+        if C.cbinfer_pool_out_size(Hi, Wi, self._pool_struct(), ctypes.byref(Ho), ctypes.byref(Wo)) != 0:
+            raise _lib.CBinferError("%s: a %dx%d map is smaller than the window (kernel_size=%s, padding=%s)"
+                                    % (self.__class__.__name__, Hi, Wi, tuple(self.kernel_size), tuple(self.padding)))
+        return Ho.value, Wo.value
+
+    def _pool_workspace(self, Hi, Wi, dev):
+        """Working mask (zero between frames), the frame's mask copy, index buffer and count: once per map size."""
+        key = (Hi, Wi, dev)
+        work = self.__dict__.get('_poolWork')
+        if work is None or work['key'] != key:
+            Ho, Wo = self._out_hw(Hi, Wi)
+            words = C.cbinfer_mask_words(Ho, Wo)
+            work = self.__dict__['_poolWork'] = dict(
+                key=key, size=(Ho, Wo),
+                bits=torch.zeros(words, dtype=torch.int64, device=dev),
+                copy=torch.zeros(words, dtype=torch.int64, device=dev),
+                idx=torch.empty(Ho * Wo, dtype=torch.int32, device=dev),
+                count=torch.zeros(1, dtype=torch.int32, device=dev))
+        return work
+
+    def _forward_general(self, input, changeIndexes):
+        """A frame on cb_pool2d.hip: cbinfer_cbpool2d_forward, two launches, no host sync.  The output pixels whose
+        window holds a listed input pixel are pooled again; the list handed on lives on the OUTPUT map."""
+        Err = _lib.CBinferError
+        name = self.__class__.__name__
+        nc, Hi, Wi = input.size(-3), input.size(-2), input.size(-1)
+        assert input.dim() == 4 and input.size(0) == 1
+        work = self._pool_workspace(Hi, Wi, input.device)
+        Ho, Wo = work['size']
+        idx, count, mask, cap = None, None, None, 0
+        if isinstance(changeIndexes, ChangeIndexes):
+            if changeIndexes.size not in (None, (Hi, Wi)):
+                raise Err("%s: the propagated change indexes address a %dx%d map, this pool's input map is %dx%d"
+                          % ((name,) + tuple(changeIndexes.size) + (Hi, Wi)))
+            if (isinstance(changeIndexes, MaskChangeIndexes) and not changeIndexes._made and
+                    changeIndexes._mask is not None and changeIndexes.size == (Hi, Wi)):
+                mask = changeIndexes._mask      # (the producer's list is never made)
+            else:
+                idx, count = changeIndexes.buffer, changeIndexes.count
+        elif isinstance(changeIndexes, torch.Tensor):
+            idx = changeIndexes.detach().contiguous()
+            assert idx.dim() == 1
+        else:
+            raise Err("%s: change indexes must be an int32 tensor or a ChangeIndexes" % name)
+        if mask is None:
+            if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.device != input.device:
+                raise Err("%s: propagated change indexes must be a contiguous int32 tensor on the input's device" % name)
+            cap = idx.numel()
+            if cap == 0:
+                idx = work['idx']      # (an empty tensor has no address: any buffer stands for the empty list)
+        if (not _same_shape(self.outputState, (1, nc, Ho, Wo)) or self.outputState.dtype != input.dtype or
+                self.outputState.device != input.device):
+            self.outputState = torch.full((1, nc, Ho, Wo), float('inf'), dtype=input.dtype, device=input.device)
+        check(C.cbinfer_cbpool2d_forward(ptr(input), ptr(self.outputState), ptr(idx), cap, ptr(count), ptr(mask),
+                                         ptr(work['bits']), ptr(work['copy']), nc, Hi, Wi, self._pool_struct(),
+                                         dtype_code(input), stream_ptr(input)))
+        if getattr(self, 'cloneOutput', True):
+            output = self.outputState.clone()
+        else:
+            output = self.outputState
+            output._cbinfer_inplace_state = True
+        if self.propChangeIndexes:
+            # (an input-resolution list means nothing behind such a pool: downsampleIndexes is ignored)
+            return 'changeIndexes', output, MaskChangeIndexes(work['copy'], (Ho, Wo), work['idx'], work['count'])
+        return output
 
     def forward(self, inp):
         assert type(inp) == tuple and inp[0] == 'changeIndexes'
         input = inp[1].detach().contiguous()
         changeIndexes = inp[2]
         require_device(input)
+        if self.__dict__.get('_general'):
+            return self._forward_general(input, changeIndexes)
         nc, h, w = input.size(-3), input.size(-2), input.size(-1)
         oh, ow = ((h - 1) // 2 + 1, (w - 1) // 2 + 1) if self.ceil_mode else (h // 2, w // 2)
         if getattr(self, 'lazy', False) and not self.propChangeIndexes:
@@ -227,9 +374,34 @@ class CBPoolMax2d(nn.Module):
         return output
 
     def __repr__(self):
+        if self.__dict__.get('generalGeometry'):
+            return ('%s (k=%s, s=%s, p=%s, ceil_mode=%s, propChgIdxs=%s)' %
+                    (self.__class__.__name__, self.kernel_size, self.stride, self.padding, self.ceil_mode,
+                     self.propChangeIndexes))
         return ('%s (k=%s, s=%s, ceil_mode=%s, propChgIdxs=%s)' %
                 (self.__class__.__name__, self.kernel_size, self.stride, self.ceil_mode,
                  self.propChangeIndexes))
+
+
+class CBPoolAvg2d(CBPoolMax2d):
+    """Change-based average pooling of an nn.AvgPool2d (no counterpart in the reference): any window, stride, zero
+    padding, ceil_mode and count_include_pad within the library's limits, 2x2 included (cb_pool2d.hip).
+    The surface is CBPoolMax2d's: propChangeIndexes, cloneOutput, outputState, clearMemory, getStateTensors.  Never
+    folded into a consumer's detection (lazy stays False)."""
+    _KIND = 'avg'
+
+    def __init__(self, m):
+        super(CBPoolAvg2d, self).__init__(m, generalGeometry=True)
+        self.count_include_pad = bool(m.count_include_pad)
+
+    def __setstate__(self, state):
+        super(CBPoolAvg2d, self).__setstate__(state)
+        self.__dict__['generalGeometry'] = self.__dict__['_general'] = True
+
+    def __repr__(self):
+        return ('%s (k=%s, s=%s, p=%s, ceil_mode=%s, count_include_pad=%s, propChgIdxs=%s)' %
+                (self.__class__.__name__, self.kernel_size, self.stride, self.padding, self.ceil_mode,
+                 self.count_include_pad, self.propChangeIndexes))
 
 
 class CBConv2d(nn.Module):

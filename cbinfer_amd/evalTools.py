@@ -11,7 +11,7 @@ import time
 
 import torch
 
-from . import CBConv2d, CBPoolMax2d, clearMemory
+from . import CBConv2d, CBPoolAvg2d, CBPoolMax2d, clearMemory
 
 
 def _staged(frameset, cuda, preprocessor):
@@ -168,7 +168,7 @@ def getCBpoolLayers(model):
     for sub in _submodels(model):
         mods = sub if isinstance(sub, torch.nn.Sequential) else [sub]
         for m in mods:
-            if type(m) is CBPoolMax2d:
+            if type(m) in (CBPoolMax2d, CBPoolAvg2d):
                 out.append(m)
     return out
 

@@ -61,7 +61,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * of a single k-stage and up (1x1 layers on >= 64 channels).  10: cbinfer_split_*_next (a split-state layer's contraction
  * in window order carrying the pooled change detection of the layer behind the 2x2 pool).
  * 11 (unchanged): the general-geometry entry points (cbGeom, cbinfer_geom_*, cbinfer_*_geom) were ADDED under this
- * number -- new symbols break no caller, every earlier symbol keeps its signature and behaviour. */
+ * number -- new symbols break no caller, every earlier symbol keeps its signature and behaviour.  Likewise the
+ * general pooling entry points (cbPool, cbinfer_pool_*, cbinfer_cbpool2d_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -787,6 +788,53 @@ int cbinfer_cbconv2d_forward_geom(const void* input, void* prevInput, void* prev
                                   int32_t* idx, int32_t* countDev, const void* prepared, const void* bias, int C, int Hi,
                                   int Wi, int K, const cbGeom* geom, float threshold, int feedbackLoop, int copyInput,
                                   int relu, int haveIndexes, int capN, void* workspace, int dtype, cbStream_t stream);
+
+/* ---- change-based pooling for any window: max and average (cb_pool2d.hip) ----------------------------
+ * The reference pools 2x2 / stride 2 only (a9, cbinfer_max_pool2d above).  Input map Hi x Wi, window kH x kW, stride
+ * (sH, sW), zero padding (pH, pW), ceilMode 0 / 1, dilation 1.  Limits per axis: 1 <= k <= 8, 1 <= s <= 8,
+ * 0 <= p <= k / 2 (torch's own rule); beyond them CB_ERR_UNSUPPORTED.  Bad arguments and out-of-limit windows return
+ * a status and launch nothing.  The window travels as one HOST struct.
+ *   output size per axis: o = floor_or_ceil((n + 2 p - k) / s) + 1, and in ceil mode o -= 1 if (o - 1) s >= n + p
+ *     (torch's rule); a map with n + 2 p < k on an axis is refused (CB_ERR_BADARG).
+ *   listed output pixels: (oy, ox) iff its window -- rows oy sH - pH ... + kH - 1, columns likewise --, clipped to the
+ *     input map, holds a changed input pixel.  With s > k an input pixel between two windows lists nothing.
+ *   values: listed pixels are recomputed for all channels from the input tensor, every other output pixel keeps its
+ *     bits.  CB_POOL_MAX: the maximum over the window's in-map pixels (padding never wins; a NaN wins, as in torch).
+ *     Average: the in-map values summed in f32 in row-major window order (ky outer, kx inner), divided by ONE IEEE f32
+ *     division, rounded to f16 once for CB_F16; the divisor is
+ *     (min(y0 + kH, Hi + pH) - y0) (min(x0 + kW, Wi + pW) - x0) with y0 = oy sH - pH, x0 = ox sW - pW for
+ *     CB_POOL_AVG_PAD (torch's count_include_pad=True) and the number of in-map pixels for CB_POOL_AVG_NOPAD. */
+#define CB_POOL_MAX 0
+#define CB_POOL_AVG_PAD 1
+#define CB_POOL_AVG_NOPAD 2
+typedef struct cbPool {
+    int kH, kW, sH, sW, pH, pW, ceilMode, op;
+} cbPool;
+/* host, pure: 1 if the window is within the limits above, else 0 */
+int cbinfer_pool_supported(const cbPool* pool);
+/* host, pure: the output size (CB_OK; CB_ERR_UNSUPPORTED beyond the limits, CB_ERR_BADARG for a map smaller than the
+ * window; Ho / Wo untouched on failure) */
+int cbinfer_pool_out_size(int Hi, int Wi, const cbPool* pool, int* Ho, int* Wo);
+/* Launch 1: the listed output pixels ORed into `bits`, a row-padded mask of the OUTPUT map (cbinfer_mask_words(Ho, Wo)
+ * words, zero on entry).  Exactly ONE of the producer's changes is given, else CB_ERR_BADARG:
+ *   changeIndexes (int32 flat indexes y Wi + x; capN entries at most, countDev the device-side length or NULL: capN
+ *     is the length): one thread per (entry, output row it reaches), at most two 64-bit atomicOr per row; an entry
+ *     outside the map is dropped; capN == 0 launches nothing; or
+ *   inputMask (the producer's row-padded change mask of the INPUT map, cbinfer_mask_words(Hi, Wi) words; countDev
+ *     must be NULL): one wave per output mask word, one ballot, no atomics -- the producer's list is never made. */
+int cbinfer_pool_footprint(const int32_t* changeIndexes, int capN, const int32_t* countDev, const uint64_t* inputMask,
+                           int Hi, int Wi, const cbPool* pool, uint64_t* bits, cbStream_t stream);
+/* Launch 2: pooling at the pixels of `bits` -- input [C, Hi, Wi], output [C, Ho, Wo], dtype CB_F32 or CB_F16.  Every
+ * word of `bits` is copied to maskCopy (the frame's mask, cbinfer_compact_bits makes the list from it on demand) and
+ * zeroed in `bits`, which is thus ready for the next frame's launch 1.  No atomics; bits != maskCopy. */
+int cbinfer_pool_changed(const void* input, void* output, uint64_t* bits, uint64_t* maskCopy, int C, int Hi, int Wi,
+                         const cbPool* pool, int dtype, cbStream_t stream);
+/* The whole frame of a change-based pool enqueued without a host sync: cbinfer_pool_footprint, then
+ * cbinfer_pool_changed (the latter also for an empty list: the mask copy is written every frame).  All arguments are
+ * checked before the first launch. */
+int cbinfer_cbpool2d_forward(const void* input, void* outputState, const int32_t* changeIndexes, int capN,
+                             const int32_t* countDev, const uint64_t* inputMask, uint64_t* bits, uint64_t* maskCopy,
+                             int C, int Hi, int Wi, const cbPool* pool, int dtype, cbStream_t stream);
 
 /* replaces conv2d_fg_cpu, cbconv2d_fg_backend.cu:81-112: HOST pointers, host code, race-free. */
 void cbinfer_conv2d_fg_cpu(const float* input, const float* prevInput, float* output,
