@@ -105,6 +105,66 @@ __device__ __forceinline__ unsigned long long cb_valid_mask(int W, int tile) {
     return rem >= 64 ? ~0ull : ((1ull << rem) - 1ull);
 }
 
+// Horizontal dilation by kWH pixels of word `tile` of a row's change mask (wpr words, W pixels): D the word's own bits,
+// SR / SL what spills into the next / the previous word, all three cut to the pixels of the row.
+struct cb_dilated {
+    unsigned long long D, SR, SL;
+};
+__device__ __forceinline__ cb_dilated cb_dilate_word(unsigned long long m, int kWH, int W, int tile, int wpr) {
+    cb_dilated r = {m, 0ull, 0ull};
+    for (int d = 1; d <= kWH; ++d) {
+        r.D |= (m << d) | (m >> d);
+        r.SR |= m >> (64 - d);
+        r.SL |= m << (64 - d);
+    }
+    r.D &= cb_valid_mask(W, tile);
+    r.SR = (tile + 1 < wpr) ? (r.SR & cb_valid_mask(W, tile + 1)) : 0ull;
+    if (tile == 0) r.SL = 0ull;
+    return r;
+}
+// ... ORed by one wave into the rows y - kHH .. y + kHH of an H-row mask: lane = (row, word).  The three words BY VALUE:
+// handed over as a reference to the struct, the compiler keeps them in LDS (or scratch) for the indexed read below.
+__device__ __forceinline__ void cb_or_dilated_rows(unsigned long long* bits, unsigned long long D, unsigned long long SR,
+                                                   unsigned long long SL, int y, int kHH, int H, int tile, int wpr,
+                                                   int lane) {
+    const int items = 3 * (2 * kHH + 1);
+    for (int i = lane; i < items; i += 64) {
+        const int yy = y + i / 3 - kHH;
+        const int which = i % 3;
+        if (yy < 0 || yy >= H) continue;
+        const unsigned long long v = which == 0 ? D : (which == 1 ? SR : SL);
+        const int t2 = which == 0 ? tile : (which == 1 ? tile + 1 : tile - 1);
+        if (v) atomicOr(&bits[(long)yy * wpr + t2], v);
+    }
+}
+
+// Pooled detection with the producer's change mask (pH x pW, this frame): a pooled pixel none of whose window pixels the
+// producing layer rewrote compares exactly as it did last frame, i.e. not above the threshold.  The 64 pooled pixels of
+// word `tile` of row y lie under four words of that mask: false if none of them has a bit set (wave-uniform).
+__device__ __forceinline__ bool cb_producer_touched(const unsigned long long* __restrict__ prodMask, int pH, int pW, int y,
+                                                    int tile) {
+    const int pwpr = (pW + 63) >> 6;
+    unsigned long long any = 0ull;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {      // (clamped, not predicated: one round trip for the four)
+            const int yy = 2 * y + j, ww = 2 * tile + i;
+            const unsigned long long v = prodMask[(long)min(yy, pH - 1) * pwpr + min(ww, pwpr - 1)];
+            any |= (yy < pH && ww < pwpr) ? v : 0ull;
+        }
+    return __builtin_amdgcn_readfirstlane((int)(any != 0ull)) != 0;
+}
+
+// The 2x2 max of the pool's input at window corner q by four UNCONDITIONAL loads: px1 / py1 are the offsets of the
+// window's second column / row, 0 where the map's edge cuts it off (min(x0 + 1, pW - 1) - x0 and the like) -- such a
+// window reads a pixel twice, max(a, a) = a.  A per-lane `if (inside)` around the loads is a branch region of its own for
+// every channel, and the compiler then waits for one channel's window before it requests the next.
+template <typename T>
+__device__ __forceinline__ T cb_pooled_load(const T* q, int px1, int py1) {
+    return cb_max(cb_max(q[0], q[px1]), cb_max(q[py1], q[py1 + px1]));
+}
+
 // x = hi + mid + lo with three bf16 terms (24 significant bits): hi = bf16(x), mid = bf16(x - hi),
 // lo = bf16(x - hi - mid); both differences are exact in f32.  Returned as the raw 16-bit patterns.
 // (cbs_split3 in cb_split_common.h is NOT a copy: it carries non-finite inputs and truncates near FLT_MAX.)

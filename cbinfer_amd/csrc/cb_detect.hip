@@ -49,22 +49,7 @@ __global__ __launch_bounds__(1024) void cb_detect_kernel(const T* __restrict__ i
         yb -= q * H;
         in = (const T*)batch.seq[q].in, state = (T*)batch.seq[q].state, bits = batch.seq[q].bits;
     }
-    // POOL with the producer's change mask (pre-pool resolution, this frame): a pooled pixel none of whose
-    // window pixels was rewritten by the producing layer compares exactly as it did last frame, i.e. not
-    // above the threshold -- the 64 pooled pixels of this workgroup lie under four words of that mask
-    if (POOL && prodMask) {
-        const int pwpr = (pW + 63) >> 6;
-        unsigned long long any = 0ull;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int yy = 2 * yb + j, ww = 2 * (int)blockIdx.x + i;
-                const unsigned long long v = prodMask[(long)min(yy, pH - 1) * pwpr + min(ww, pwpr - 1)];
-                any |= (yy < pH && ww < pwpr) ? v : 0ull;      // (clamped, not predicated: one round trip for the four)
-            }
-        if (__builtin_amdgcn_readfirstlane((int)(any != 0ull)) == 0) return;
-    }
+    if (POOL && prodMask && !cb_producer_touched(prodMask, pH, pW, yb, (int)blockIdx.x)) return;
     // frame pipeline: two masks alternate by a device-side parity (flipped by the consumer kernel)
     if (BITS && parity && *parity) bits += altWords;
     const int lane = threadIdx.x & 63;
@@ -81,14 +66,10 @@ __global__ __launch_bounds__(1024) void cb_detect_kernel(const T* __restrict__ i
     // input value of channel c at this lane's pixel
     const long pHW = (long)pH * pW;
     const int py0 = 2 * y, px0 = 2 * x;
-    // (four unconditional loads with clamped coordinates -- a window cut off by the map's edge reads a pixel twice,
-    //  max(a, a) = a: a per-lane branch around the loads makes the compiler wait for one channel's window before it
-    //  requests the next)
     const int px1 = min(px0 + 1, pW - 1) - px0, py1 = (min(py0 + 1, pH - 1) - py0) * pW;
     auto ldin = [&](int c) -> T {
         if (!POOL) return in[(long)c * HW + p];
-        const T* q = in + (long)c * pHW + (long)py0 * pW + px0;
-        return cb_max(cb_max(q[0], q[px1]), cb_max(q[py1], q[py1 + px1]));
+        return cb_pooled_load(in + (long)c * pHW + (long)py0 * pW + px0, px1, py1);
     };
 
     bool chg = false;
@@ -161,29 +142,11 @@ __global__ __launch_bounds__(1024) void cb_detect_kernel(const T* __restrict__ i
     }
 
     // horizontal dilation of the 64-pixel word, with the parts spilling into the neighbour words
-    unsigned long long D = m, SR = 0, SL = 0;
-    for (int d = 1; d <= kWH; ++d) {
-        D |= (m << d) | (m >> d);
-        SR |= m >> (64 - d);
-        SL |= m << (64 - d);
-    }
-    D &= cb_valid_mask(W, tx);
-    SR = (tx + 1 < wpr) ? (SR & cb_valid_mask(W, tx + 1)) : 0ull;
-    if (tx == 0) SL = 0;
-
+    const cb_dilated dl = cb_dilate_word(m, kWH, W, tx, wpr);
     if (BITS) {
-        if (g == 0) {
-            const int items = 3 * (2 * kHH + 1);
-            for (int i = lane; i < items; i += 64) {
-                const int yy = y + i / 3 - kHH;
-                const int which = i % 3;
-                if (yy < 0 || yy >= H) continue;
-                const unsigned long long v = which == 0 ? D : (which == 1 ? SR : SL);
-                const int t2 = which == 0 ? tx : (which == 1 ? tx + 1 : tx - 1);
-                if (v) atomicOr(&bits[(long)yy * wpr + t2], v);
-            }
-        }
+        if (g == 0) cb_or_dilated_rows(bits, dl.D, dl.SR, dl.SL, y, kHH, H, tx, wpr, lane);
     } else {
+        const unsigned long long D = dl.D, SR = dl.SR, SL = dl.SL;
         for (int r = g; r <= 2 * kHH; r += G) {
             const int yy = y + r - kHH;
             if (yy < 0 || yy >= H) continue;
@@ -254,24 +217,8 @@ __global__ __launch_bounds__(1024) void cb_detect_fg_frame_kernel(
     unsigned long long m = 0;
     for (int i = 0; i < G; ++i) m |= sm[i];
     if (m == 0) return;
-    unsigned long long D = m, SR = 0, SL = 0;
-    for (int d = 1; d <= kWH; ++d) {
-        D |= (m << d) | (m >> d);
-        SR |= m >> (64 - d);
-        SL |= m << (64 - d);
-    }
-    D &= cb_valid_mask(W, tx);
-    SR = (tx + 1 < wpr) ? (SR & cb_valid_mask(W, tx + 1)) : 0ull;
-    if (tx == 0) SL = 0;
-    const int items = 3 * (2 * kHH + 1);
-    for (int i = lane; i < items; i += 64) {
-        const int yy = y + i / 3 - kHH;
-        const int which = i % 3;
-        if (yy < 0 || yy >= H) continue;
-        const unsigned long long v = which == 0 ? D : (which == 1 ? SR : SL);
-        const int t2 = which == 0 ? tx : (which == 1 ? tx + 1 : tx - 1);
-        if (v) atomicOr(&bits[(long)yy * wpr + t2], v);
-    }
+    const cb_dilated dl = cb_dilate_word(m, kWH, W, tx, wpr);
+    cb_or_dilated_rows(bits, dl.D, dl.SR, dl.SL, y, kHH, H, tx, wpr, lane);
 }
 
 // Stand-alone gather-form dilation of a byte map (cbconv2d_cg_backend.cu:101-124).

@@ -583,28 +583,10 @@ __global__ __launch_bounds__(CBP_NT, DET ? 5 : 4) void cbp_rowpair_kernel(PairPa
         if (wave == 1) {
             const int w2 = tx >> 1, wpr2 = p.next.wpr2;
             const unsigned long long M = (unsigned long long)m32 << ((tx & 1) * 32);
-            unsigned long long D = M, SR = 0ull, SL = 0ull;
-            for (int d = 1; d <= p.next.kWH; ++d) {
-                D |= (M << d) | (M >> d);
-                SR |= M >> (64 - d);
-                SL |= M << (64 - d);
-            }
-            auto validMask = [&](int tile) -> unsigned long long {
-                const int rem = p.next.W2 - tile * 64;
-                return rem >= 64 ? ~0ull : (rem <= 0 ? 0ull : ((1ull << rem) - 1ull));
-            };
-            D &= validMask(w2);
-            SR = (w2 + 1 < wpr2) ? (SR & validMask(w2 + 1)) : 0ull;
-            if (w2 == 0) SL = 0ull;
-            const int items = 3 * (2 * p.next.kHH + 1);
-            for (int i = lane; i < items; i += 64) {
-                const int yy = yo + i / 3 - p.next.kHH;
-                const int which = i % 3;
-                if (yy < 0 || yy >= p.next.H2) continue;
-                const unsigned long long v = which == 0 ? D : (which == 1 ? SR : SL);
-                const int t2 = which == 0 ? w2 : (which == 1 ? w2 + 1 : w2 - 1);
-                if (v) atomicOr(&sq.nmasks[(long)yy * wpr2 + t2], v);
-            }
+            // (w2 < wpr2: the unit holds a pooled pixel of the map, and the next word is asked for behind w2 + 1 < wpr2 --
+            //  cb_valid_mask never sees a word beyond the row)
+            const cb_dilated dl = cb_dilate_word(M, p.next.kWH, p.next.W2, w2, wpr2);
+            cb_or_dilated_rows(sq.nmasks, dl.D, dl.SR, dl.SL, yo, p.next.kHH, p.next.H2, w2, wpr2, lane);
         }
         CBP_STAMP_AT(6);
 #ifdef CBP_STAMP

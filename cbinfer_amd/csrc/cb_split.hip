@@ -203,19 +203,7 @@ __global__ __launch_bounds__(1024) void cbs_detect_kernel(CbsDetArgs a) {
     const CbsDetSeq sq = a.seq[blockIdx.z];
     const int W = a.W, H = a.H, C = a.C, pH = a.pH, pW = a.pW;
     CBS_DET_STAMP(0);
-    if (POOL && sq.prodMask) {
-        const int pwpr = (pW + 63) >> 6;
-        unsigned long long any = 0ull;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {      // (clamped, not predicated: four loads in one round trip)
-                const int yy = 2 * (int)blockIdx.y + j, ww = 2 * (int)blockIdx.x + i;
-                const unsigned long long v = sq.prodMask[(long)min(yy, pH - 1) * pwpr + min(ww, pwpr - 1)];
-                any |= (yy < pH && ww < pwpr) ? v : 0ull;
-            }
-        if (__builtin_amdgcn_readfirstlane((int)(any != 0ull)) == 0) return;
-    }
+    if (POOL && sq.prodMask && !cb_producer_touched(sq.prodMask, pH, pW, (int)blockIdx.y, (int)blockIdx.x)) return;
     CBS_DET_STAMP(1);
     unsigned long long* bits = sq.masks;      // (single mask: the contraction zeroes it once every workgroup has it)
     const int lane = threadIdx.x & 63;
@@ -231,15 +219,12 @@ __global__ __launch_bounds__(1024) void cbs_detect_kernel(CbsDetArgs a) {
 
     const long pHW = (long)pH * pW;
     const int py0 = 2 * y, px0 = 2 * x;
-    // The 2x2 window by four UNCONDITIONAL loads with clamped coordinates (a window cut off by the map's edge reads a
-    // pixel twice: max(a, a) = a).  A per-lane `if (inside) ... else ...` around the loads is a branch region of its
-    // own for every channel, and the compiler then waits for one channel's loads before it requests the next: four
-    // round trips instead of one (2.6 of the 4.5 us of this kernel's per-workgroup chain, round 3 stamps).
+    // (cb_pooled_load's unconditional loads: four round trips became one, 2.6 of the 4.5 us of this kernel's per-workgroup
+    //  chain, round 3 stamps)
     const int px1 = min(px0 + 1, pW - 1) - px0, py1 = (min(py0 + 1, pH - 1) - py0) * pW;
     auto ldin = [&](int c) -> float {
         if (!POOL) return in[(long)c * HW + p];
-        const float* q = in + (long)c * pHW + (long)py0 * pW + px0;
-        return fmaxf(fmaxf(q[0], q[px1]), fmaxf(q[py1], q[py1 + px1]));
+        return cb_pooled_load(in + (long)c * pHW + (long)py0 * pW + px0, px1, py1);
     };
 
     // C == 4 G: four channels per wave, eight independent loads in flight per lane
@@ -317,26 +302,8 @@ __global__ __launch_bounds__(1024) void cbs_detect_kernel(CbsDetArgs a) {
     CBS_DET_STAMP(4);
     if (m == 0) return;
     // dilation of the 64-pixel word (+ the parts spilling into the neighbour words), ORed into the frame mask
-    unsigned long long D = m, SR = 0, SL = 0;
-    for (int d = 1; d <= a.kWH; ++d) {
-        D |= (m << d) | (m >> d);
-        SR |= m >> (64 - d);
-        SL |= m << (64 - d);
-    }
-    D &= cb_valid_mask(W, tx);
-    SR = (tx + 1 < a.wpr) ? (SR & cb_valid_mask(W, tx + 1)) : 0ull;
-    if (tx == 0) SL = 0;
-    if (g == 0) {
-        const int items = 3 * (2 * a.kHH + 1);
-        for (int i = lane; i < items; i += 64) {
-            const int yy = y + i / 3 - a.kHH;
-            const int which = i % 3;
-            if (yy < 0 || yy >= H) continue;
-            const unsigned long long v = which == 0 ? D : (which == 1 ? SR : SL);
-            const int t2 = which == 0 ? tx : (which == 1 ? tx + 1 : tx - 1);
-            if (v) atomicOr(&bits[(long)yy * a.wpr + t2], v);
-        }
-    }
+    const cb_dilated dl = cb_dilate_word(m, a.kWH, W, tx, a.wpr);
+    if (g == 0) cb_or_dilated_rows(bits, dl.D, dl.SR, dl.SL, y, a.kHH, H, tx, a.wpr, lane);
     CBS_DET_STAMP(5);
 }
 
@@ -1746,15 +1713,8 @@ __global__ __launch_bounds__(64 * WM * WN) void cbs_conv_kernel(CbsParams p, typ
                         }
                     }
                     if (leader) {
-                        unsigned long long D = acc, SR = 0ull, SL = 0ull;
-                        for (int d = 1; d <= ext.kWH; ++d) {
-                            D |= (acc << d) | (acc >> d);
-                            SR |= acc >> (64 - d);
-                            SL |= acc << (64 - d);
-                        }
-                        D &= cb_valid_mask(ext.W2, wi);
-                        SR = (wi + 1 < ext.wpr2) ? (SR & cb_valid_mask(ext.W2, wi + 1)) : 0ull;
-                        if (wi == 0) SL = 0ull;
+                        const cb_dilated dl = cb_dilate_word(acc, ext.kWH, ext.W2, wi, ext.wpr2);
+                        const unsigned long long D = dl.D, SR = dl.SR, SL = dl.SL;
                         for (int yy = max(y2 - ext.kHH, 0); yy <= min(y2 + ext.kHH, ext.H2 - 1); ++yy) {
                             unsigned long long* row = ext.nmasks + (long)yy * ext.wpr2 + wi;
                             atomicOr(row, D);
@@ -1917,6 +1877,18 @@ __global__ __launch_bounds__(64 * WM * WN) void cbs_conv_kernel(CbsParams p, typ
     }
 }
 
+// The tiles of a launch are numbered through its sequences (launch info: tiles per sequence at CBS_INFO_TP).
+// CBS_TILES_BEFORE declares tilesBefore[q]: the tiles of the sequences in front of q; CBS_TILE_SEQUENCE declares q: the
+// sequence that tile ptg belongs to.  (Macros: as functions taking the array they cost cbs_reduce_kernel its register
+// figure -- 79 instead of 82 VGPRs, another occupancy -- and the generated code is to stay what was measured.)
+#define CBS_TILES_BEFORE(tilesBefore, info) \
+    int tilesBefore[CBS_MAXSEQ + 1];        \
+    tilesBefore[0] = 0;                     \
+    _Pragma("unroll") for (int q_ = 0; q_ < CBS_MAXSEQ; ++q_) tilesBefore[q_ + 1] = tilesBefore[q_] + (info)[CBS_INFO_TP + q_]
+#define CBS_TILE_SEQUENCE(q, tilesBefore, nSeq, ptg)  \
+    int q = 0;                                        \
+    _Pragma("unroll") for (int u_ = 1; u_ < CBS_MAXSEQ; ++u_) if (u_ < (nSeq) && (ptg) >= tilesBefore[u_]) q = u_
+
 // Second launch of a split contraction: sums the SK slabs of every tile in slice order, scales, adds the bias,
 // applies the ReLU and scatters (all CUs, one float4 of four output channels per thread and step).
 __global__ __launch_bounds__(256) void cbs_reduce_kernel(CbsParams p, int BM, int BN) {
@@ -1924,10 +1896,7 @@ __global__ __launch_bounds__(256) void cbs_reduce_kernel(CbsParams p, int BM, in
     const int SK = p.info[CBS_INFO_SK];
     if (SK <= 1) return;
     const int MT = p.info[CBS_INFO_MT], CMB = MT * SK, TILE4 = BM * BN / 4, HW = p.H * p.W;
-    int tilesBefore[CBS_MAXSEQ + 1];
-    tilesBefore[0] = 0;
-#pragma unroll
-    for (int q = 0; q < CBS_MAXSEQ; ++q) tilesBefore[q + 1] = tilesBefore[q] + p.info[CBS_INFO_TP + q];
+    CBS_TILES_BEFORE(tilesBefore, p.info);
     const int TP = tilesBefore[CBS_MAXSEQ];
     const float4* __restrict__ slabs = (const float4*)p.slabs;
     const long total = (long)TP * MT * TILE4;
@@ -1935,10 +1904,7 @@ __global__ __launch_bounds__(256) void cbs_reduce_kernel(CbsParams p, int BM, in
         const int tile = (int)(g / TILE4), c = (int)(g - (long)tile * TILE4);
         const int ptg = tile / MT, mt = tile % MT;
         const int nl = c % BN, mq = c / BN;
-        int q = 0;
-#pragma unroll
-        for (int u = 1; u < CBS_MAXSEQ; ++u)
-            if (u < p.nSeq && ptg >= tilesBefore[u]) q = u;
+        CBS_TILE_SEQUENCE(q, tilesBefore, p.nSeq, ptg);
         const int n = (ptg - tilesBefore[q]) * BN + nl;
         const int N = p.info[CBS_INFO_TP + CBS_MAXSEQ + q];
         const float4* sl = slabs + ((long)ptg * CMB + mt) * TILE4 + c;      // slice j: + j * MT * TILE4
@@ -2167,10 +2133,7 @@ __global__ __launch_bounds__(64 * CB_TAIL_MAXW) void cbs_reduce_tail_kernel(CbsP
     // their address needs no pixel index -- and the 16 pixel indices.  Third: this wave's rows of W1.
     CB_TAIL_STAMP(0);
     const int SK = p.info[CBS_INFO_SK], MT = p.info[CBS_INFO_MT], CMB = MT * SK, TILE4 = BM * BN / 4;
-    int tilesBefore[CBS_MAXSEQ + 1];
-    tilesBefore[0] = 0;
-#pragma unroll
-    for (int q = 0; q < CBS_MAXSEQ; ++q) tilesBefore[q + 1] = tilesBefore[q] + p.info[CBS_INFO_TP + q];
+    CBS_TILES_BEFORE(tilesBefore, p.info);
     const int GP = BN / CB_TAIL_PX, groups = tilesBefore[CBS_MAXSEQ] * GP;
     if ((int)blockIdx.x >= groups) return;
     CB_TAIL_STAMP(1);
@@ -2184,10 +2147,7 @@ __global__ __launch_bounds__(64 * CB_TAIL_MAXW) void cbs_reduce_tail_kernel(CbsP
     const int px = t & 15, cstep = NT >> 4;
     for (int g = blockIdx.x; g < groups; g += gridDim.x) {
         const int ptg = g / GP, gi = g - ptg * GP;
-        int q = 0;
-#pragma unroll
-        for (int u = 1; u < CBS_MAXSEQ; ++u)
-            if (u < p.nSeq && ptg >= tilesBefore[u]) q = u;
+        CBS_TILE_SEQUENCE(q, tilesBefore, p.nSeq, ptg);
         const int nl0 = gi * CB_TAIL_PX, n0 = (ptg - tilesBefore[q]) * BN + nl0;
         const int N = p.info[CBS_INFO_TP + CBS_MAXSEQ + q];
         if (n0 >= N) continue;      // (uniform: a tile's last groups may be empty)
@@ -2329,6 +2289,16 @@ extern "C" int cbinfer_debug_split_stamps(void* host, long bytes, int clear) {
 }
 #endif
 
+// (a template: outside the extern "C" block its callers live in)
+// The side job of a contraction launch (CbsSideExt, or the same five fields of CbsWinExt): another layer's feedback refresh
+template <typename Ext>
+static int cbs_fill_side(Ext& e, const cbSideRefresh* side) {
+    CB_REQUIRE(side->state && side->C >= 1 && side->H >= 1 && side->W >= 1 && (long)side->H * side->W < (1l << 30));
+    e.sideFrame = side->frame, e.sideState = side->state, e.sideC = side->C, e.sideHW = side->H * side->W;
+    e.sideTh = side->threshold;
+    return CB_OK;
+}
+
 extern "C" {
 
 int cbinfer_split_supported(int C, int K, int kH, int kW) { return cbs_supported(C, K, kH, kW) ? 1 : 0; }
@@ -2365,42 +2335,65 @@ static long cbs_slab_capacity(int nSeq, int H, int W, int K) {
     const long tiles = (long)nSeq * (((long)H * W + bn - 1) / bn) * (cbs_kp(K) / bm);
     return tiles > 2l * cb_num_cus() ? tiles : 2l * cb_num_cus();
 }
-long cbinfer_split_workspace_bytes(int nSeq, int C, int H, int W, int K, int kH, int kW) {
-    if (!cbs_supported(C, K, kH, kW)) return 0;
-    const CbsGeom g = cbs_geom(C, H, W, kH, kW);
-    if (g.nStages < 48) return 0;
+static long cbs_workspace_bytes(int nSeq, int H, int W, int K) {
     const int bm = cbs_bm(K), bn = bm >= 128 ? 128 : 64;
     return 256 + cbs_slab_capacity(nSeq, H, W, K) * bm * bn * 4;
 }
+long cbinfer_split_workspace_bytes(int nSeq, int C, int H, int W, int K, int kH, int kW) {
+    if (!cbs_supported(C, K, kH, kW)) return 0;
+    if (cbs_geom(C, H, W, kH, kW).nStages < 48) return 0;
+    return cbs_workspace_bytes(nSeq, H, W, K);
+}
 
+// What the geometry decides of a contraction's CbsParams, for the f32 layers and the fp16 group alike: sizes, the
+// workspace's two parts, the division constants.  g: cbs_geom / cbh_geom of the layer, BM: the tile height the launch
+// runs with, MW: cbinfer_mask_words(H, W), cap: cbs_slab_capacity.  The sequences, weights, bias, relu, aBytes and what
+// differs between the two callers (outScale, halfOut, maxChunks, upstream, forceSK, accumulate) stay with them.
+static void cbs_fill_params(CbsParams& p, const CbsGeom& g, int K, int KP, int BM, int H, int W, long MW, void* workspace,
+                            long cap) {
+    p.info = workspace ? (int*)workspace : nullptr;
+    p.slabs = workspace ? (float*)((char*)workspace + 256) : nullptr;
+    p.K = K, p.KP = KP, p.H = H, p.W = W, p.Wp = g.Wp, p.rec = g.rec, p.nStages = g.nStages, p.kH = g.kH, p.kW = g.kW;
+    p.maskWords = (int)MW, p.wpr = cbinfer_mask_words_per_row(W), p.dummyBase = g.dummyBase;
+    p.stateBytes = (long)g.Hp * g.Wp * g.rec;
+    p.magicMW = (1ull << 32) / (unsigned long long)MW + 1ull;
+    p.magicWpr = (1ull << 32) / (unsigned long long)p.wpr + 1ull;
+    p.magicW = (1ull << 32) / (unsigned long long)W + 1ull;
+    p.magicMT = (1ull << 32) / (unsigned long long)(KP / BM) + 1ull;
+    p.arriveShards = (int)(MW / 16 < 8 ? MW / 16 : 8);
+    // the workspace was sized by cbinfer_[h]split[_group]_workspace_bytes for this very geometry: a split the kernel
+    // decides on itself (items <= grid <= 2 CUs) always fits, a forced one (forceSplit: tests, tuning) is refused beyond it
+    p.slabCap = (int)(cap > 0x7fffffffl ? 0x7fffffffl : cap);
+    p.splitRounds = 2;
+    p.dbg = 0;
+}
+
+// planes == 2: f16 pairs (4 KB of fragments per stage and 32-row tile, the plain filter bank behind the stage table);
+// 3: bf16 triples (6 KB, no plain bank, no scale)
+static int cbs_prep_weights(const float* weight, void* prepared, int K, int C, int kH, int kW, int H, int W, int planes,
+                            float weightScale, cbStream_t stream) {
+    if (!cbs_supported(C, K, kH, kW)) return CB_ERR_UNSUPPORTED;
+    const CbsGeom g = cbs_geom(C, H, W, kH, kW, planes);
+    if ((long)g.Hp * g.Wp * g.rec >= (1l << 31)) return CB_ERR_UNSUPPORTED;
+    const int KP = cbs_kp(K);
+    const long total = (long)g.nStages * (KP / 32) * (2 * planes) * 64;      // threads: one 16-byte piece each
+    const long aBytes = total * 16;
+    int* stageOff = (int*)((char*)prepared + aBytes);
+    float* wPlain = planes == 3 ? nullptr : (float*)((char*)prepared + cbs_plain_offset(aBytes, g.nStages));
+    // (a thread per entry of the stage table too: total > nStages whatever the form)
+    hipLaunchKernelGGL(cbs_prep_kernel, dim3(cb_div_up(total > g.nStages ? total : g.nStages, 256)), dim3(256), 0,
+                       (hipStream_t)stream, weight, (halfx8*)prepared, stageOff, wPlain, g, K, KP, weightScale);
+    return cb_launch_status();
+}
 int cbinfer_split_prep_weights(const float* weight, void* prepared, int K, int C, int kH, int kW, int H, int W,
                                float weightScale, cbStream_t stream) {
     CB_REQUIRE(weight && prepared && H > 0 && W > 0 && weightScale > 0.f);
-    if (!cbs_supported(C, K, kH, kW)) return CB_ERR_UNSUPPORTED;
-    const CbsGeom g = cbs_geom(C, H, W, kH, kW);
-    if ((long)g.Hp * g.Wp * g.rec >= (1l << 31)) return CB_ERR_UNSUPPORTED;
-    const int KP = cbs_kp(K);
-    const long total = (long)g.nStages * (KP / 32) * 4 * 64;
-    const long aBytes = (long)g.nStages * (KP / 32) * 4096;
-    int* stageOff = (int*)((char*)prepared + aBytes);
-    float* wPlain = (float*)((char*)prepared + cbs_plain_offset(aBytes, g.nStages));
-    hipLaunchKernelGGL(cbs_prep_kernel, dim3(cb_div_up(total, 256)), dim3(256), 0, (hipStream_t)stream, weight,
-                       (halfx8*)prepared, stageOff, wPlain, g, K, KP, weightScale);
-    return cb_launch_status();
+    return cbs_prep_weights(weight, prepared, K, C, kH, kW, H, W, 2, weightScale, stream);
 }
 int cbinfer_split3_prep_weights(const float* weight, void* prepared, int K, int C, int kH, int kW, int H, int W,
                                 cbStream_t stream) {
     CB_REQUIRE(weight && prepared && H > 0 && W > 0);
-    if (!cbs_supported(C, K, kH, kW)) return CB_ERR_UNSUPPORTED;
-    const CbsGeom g = cbs_geom(C, H, W, kH, kW, 3);
-    if ((long)g.Hp * g.Wp * g.rec >= (1l << 31)) return CB_ERR_UNSUPPORTED;
-    const int KP = cbs_kp(K);
-    const long total = (long)g.nStages * (KP / 32) * 6 * 64;
-    const long aBytes = (long)g.nStages * (KP / 32) * 6144;
-    int* stageOff = (int*)((char*)prepared + aBytes);
-    hipLaunchKernelGGL(cbs_prep_kernel, dim3(cb_div_up(total > g.nStages ? total : g.nStages, 256)), dim3(256), 0,
-                       (hipStream_t)stream, weight, (halfx8*)prepared, stageOff, (float*)nullptr, g, K, KP, 1.0f);
-    return cb_launch_status();
+    return cbs_prep_weights(weight, prepared, K, C, kH, kW, H, W, 3, 1.0f, stream);
 }
 
 static int cbs_state_init(void* splitState, int C, int H, int W, int kH, int kW, int planes, cbStream_t stream) {
@@ -2419,23 +2412,22 @@ int cbinfer_split3_state_init(void* splitState, int C, int H, int W, int kH, int
 
 // splitState <- split(state): for a state the caller wrote itself (restored states); the zero border must exist
 // already (cbinfer_split_state_init)
-int cbinfer_split_state_rebuild(const float* state, void* splitState, int C, int H, int W, int kH, int kW,
-                                int32_t* rangeFlag, cbStream_t stream) {
+static int cbs_state_rebuild(const float* state, void* splitState, int C, int H, int W, int kH, int kW, int planes,
+                             int32_t* rangeFlag, cbStream_t stream) {
     CB_REQUIRE(state && splitState && H > 0 && W > 0);
     if (!cbs_supported(C, 1, kH, kW)) return CB_ERR_UNSUPPORTED;
-    const CbsGeom g = cbs_geom(C, H, W, kH, kW);
+    const CbsGeom g = cbs_geom(C, H, W, kH, kW, planes);
     hipLaunchKernelGGL(cbs_state_rebuild_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, state,
                        (char*)splitState, g, rangeFlag);
     return cb_launch_status();
 }
+int cbinfer_split_state_rebuild(const float* state, void* splitState, int C, int H, int W, int kH, int kW,
+                                int32_t* rangeFlag, cbStream_t stream) {
+    return cbs_state_rebuild(state, splitState, C, H, W, kH, kW, 2, rangeFlag, stream);
+}
 int cbinfer_split3_state_rebuild(const float* state, void* splitState, int C, int H, int W, int kH, int kW,
                                  cbStream_t stream) {
-    CB_REQUIRE(state && splitState && H > 0 && W > 0);
-    if (!cbs_supported(C, 1, kH, kW)) return CB_ERR_UNSUPPORTED;
-    const CbsGeom g = cbs_geom(C, H, W, kH, kW, 3);
-    hipLaunchKernelGGL(cbs_state_rebuild_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, state,
-                       (char*)splitState, g, (int*)nullptr);
-    return cb_launch_status();
+    return cbs_state_rebuild(state, splitState, C, H, W, kH, kW, 3, nullptr, stream);      // (bf16 triples: f32's range)
 }
 
 // Detection of up to CBS_MAXSEQ sequences in one launch (see cbSplitSeq in the header).  pooled != 0: `input` is
@@ -2477,6 +2469,12 @@ int cbinfer_split_detect(const cbSplitSeq* seqs, int nSeq, int mode, int pH, int
     else
         hipLaunchKernelGGL(cbs_detect_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
     return cb_launch_status();
+}
+
+// The detection's mode word of a frame function: the caller's bits, CBINFER_SPLIT_X3 from the arithmetic (weightScale == 0:
+// bf16 triples)
+static int cbs_detect_mode(int mode, float weightScale) {
+    return (mode & ~CBINFER_SPLIT_X3) | (weightScale == 0.f ? CBINFER_SPLIT_X3 : 0);
 }
 
 // The contraction of up to CBS_MAXSEQ sequences in one launch (+ the reduce launch of a split contraction).
@@ -2539,39 +2537,24 @@ static int cbs_split_conv(const cbSplitSeq* seqs, int nSeq, const void* prepared
     p.stageOff = (const int*)((const char*)prepared + p.aBytes);
     p.wPlain = x3 ? nullptr : (const float*)((const char*)prepared + cbs_plain_offset(p.aBytes, g.nStages));
     p.bias = bias;
-    p.info = workspace ? (int*)workspace : nullptr;
-    p.slabs = workspace ? (float*)((char*)workspace + 256) : nullptr;
-    p.K = K, p.KP = KP, p.H = H, p.W = W, p.Wp = g.Wp, p.rec = g.rec, p.nStages = g.nStages, p.kH = kH, p.kW = kW;
-    p.maskWords = (int)MW, p.wpr = cbinfer_mask_words_per_row(W), p.relu = relu, p.dummyBase = g.dummyBase;
-    p.stateBytes = (long)g.Hp * g.Wp * g.rec;
+    p.relu = relu;
+    cbs_fill_params(p, g, K, KP, BM, H, W, MW, workspace, cbs_slab_capacity(nSeq, H, W, K));
     p.outScale = x3 ? 1.0f : 1.0f / (weightScale * CBS_XSCALE);
-    p.magicMW = (1ull << 32) / (unsigned long long)MW + 1ull;
-    p.magicWpr = (1ull << 32) / (unsigned long long)p.wpr + 1ull;
-    p.magicW = (1ull << 32) / (unsigned long long)W + 1ull;
-    p.magicMT = (1ull << 32) / (unsigned long long)(KP / BM) + 1ull;
     p.forceSK = forceSplit;
     p.accumulate = accumulate;
     p.halfOut = 0;
     p.upstream = nullptr;
-    p.splitRounds = 2;
-    p.arriveShards = (int)(MW / 16 < 8 ? MW / 16 : 8);
-    p.dbg = 0;
     p.maxChunks = CBS_CHUNKS;
 #ifdef CBS_DBG
     if (const char* e = getenv("CBINFER_SPLIT_DBG")) p.dbg = atoi(e);
 #endif
     hipStream_t s = (hipStream_t)stream;
-    // the workspace was sized by cbinfer_split_workspace_bytes for this very geometry: a split the kernel decides on
-    // itself (items <= grid <= 2 CUs) always fits, a forced one (forceSplit: tests, tuning) is refused beyond it
-    const long cap = cbs_slab_capacity(nSeq, H, W, K);
-    p.slabCap = (int)(cap > 0x7fffffffl ? 0x7fffffffl : cap);
     if (side && side->frame && !next) {
         // pixel order + another layer's state refresh on the idle workgroups (AR = 4)
         if (!cbs_refresh_supported(C, K, kH, kW, H, W) || nSeq != 1 || !x3 || accumulate || tail) return CB_ERR_UNSUPPORTED;
-        CB_REQUIRE(side->state && side->C >= 1 && side->H >= 1 && side->W >= 1 && (long)side->H * side->W < (1l << 30));
         CbsSideExt e;
-        e.sideFrame = side->frame, e.sideState = side->state, e.sideC = side->C, e.sideHW = side->H * side->W;
-        e.sideTh = side->threshold;
+        const int st = cbs_fill_side(e, side);
+        if (st != CB_OK) return st;
         return cbs_launch_conv<64, 64, 2, 2, CBS_PRE_SMALL, true, 5, 4>(p, 1, nullptr, s, e);
     }
     if (next) {
@@ -2589,9 +2572,8 @@ static int cbs_split_conv(const cbSplitSeq* seqs, int nSeq, const void* prepared
         e.magicW2 = (1ull << 32) / (unsigned long long)next->W + 1ull;
         e.sideFrame = nullptr, e.sideState = nullptr, e.sideC = 0, e.sideHW = 0, e.sideTh = 0.f;
         if (side && side->frame) {
-            CB_REQUIRE(side->state && side->C >= 1 && side->H >= 1 && side->W >= 1 && (long)side->H * side->W < (1l << 30));
-            e.sideFrame = side->frame, e.sideState = side->state, e.sideC = side->C, e.sideHW = side->H * side->W;
-            e.sideTh = side->threshold;
+            const int st = cbs_fill_side(e, side);
+            if (st != CB_OK) return st;
         }
         return cbs_launch_conv<64, 64, 2, 2, CBS_PRE_SMALL, true, 5, 3>(p, 1, nullptr, s, e);
     }
@@ -2634,22 +2616,30 @@ int cbinfer_split_tail_supported(int C, int K, int kH, int kW, int C1, int C2) {
            C1 <= 16 * CB_TAIL_MAXW && cb_tail_lds_bytes(K, C1, C2) <= 60 * 1024;
 }
 
-// cbinfer_split_conv with the fused 1x1 tail in the second launch (the two launches of cbinfer_split_forward_tail behind
-// its detection)
-int cbinfer_split_conv_tail(const cbSplitSeq* seqs, int nSeq, const void* prepared, const float* bias, int C, int H,
-                            int W, int K, int kH, int kW, float weightScale, int relu, void* workspace, int forceSplit,
-                            const cbSplitTail* tail, cbStream_t stream) {
+// The second launch's view of a fused 1x1 tail, with the argument checks of the entry points that take one
+// (bias: the layer's, or NULL -- the second launch reads it, and without one the tail's first, four values at a time)
+static int cbs_tail_args(CbsTailArgs& ta, const cbSplitTail* tail, int nSeq, const float* bias, int C, int K, int kH,
+                         int kW) {
     CB_REQUIRE(tail && tail->w1Prepared && tail->b1 && tail->w2 && tail->b2 && nSeq >= 1 && nSeq <= CBS_MAXSEQ);
-    // (the second launch reads the layer's bias -- and, without one, the tail's first -- four values at a time)
     CB_REQUIRE((((size_t)bias | (size_t)tail->b1) & 15) == 0);
     if (!cbinfer_split_tail_supported(C, K, kH, kW, tail->C1, tail->C2)) return CB_ERR_UNSUPPORTED;
-    CbsTailArgs ta;
     ta.w1p = tail->w1Prepared, ta.b1 = tail->b1, ta.w2 = tail->w2, ta.b2 = tail->b2;
     ta.C1 = tail->C1, ta.C2 = tail->C2, ta.relu1 = tail->relu1, ta.relu2 = tail->relu2;
     for (int q = 0; q < CBS_MAXSEQ; ++q) {
         if (q < nSeq) CB_REQUIRE(tail->output[q]);
         ta.out[q] = q < nSeq ? tail->output[q] : nullptr;
     }
+    return CB_OK;
+}
+
+// cbinfer_split_conv with the fused 1x1 tail in the second launch (the two launches of cbinfer_split_forward_tail behind
+// its detection)
+int cbinfer_split_conv_tail(const cbSplitSeq* seqs, int nSeq, const void* prepared, const float* bias, int C, int H,
+                            int W, int K, int kH, int kW, float weightScale, int relu, void* workspace, int forceSplit,
+                            const cbSplitTail* tail, cbStream_t stream) {
+    CbsTailArgs ta;
+    const int st = cbs_tail_args(ta, tail, nSeq, bias, C, K, kH, kW);
+    if (st != CB_OK) return st;
     return cbs_split_conv(seqs, nSeq, prepared, bias, C, H, W, K, kH, kW, weightScale, relu, workspace, forceSplit, &ta,
                           stream);
 }
@@ -2663,8 +2653,8 @@ int cbinfer_split_forward_tail(const cbSplitSeq* seqs, int nSeq, int mode, int p
                                cbStream_t stream) {
     CB_REQUIRE(tail);
     if (!cbinfer_split_tail_supported(C, K, kH, kW, tail->C1, tail->C2)) return CB_ERR_UNSUPPORTED;
-    mode = (mode & ~CBINFER_SPLIT_X3) | (weightScale == 0.f ? CBINFER_SPLIT_X3 : 0);
-    const int st = cbinfer_split_detect(seqs, nSeq, mode, pH, pW, C, H, W, kH, kW, threshold, stream);
+    const int st = cbinfer_split_detect(seqs, nSeq, cbs_detect_mode(mode, weightScale), pH, pW, C, H, W, kH, kW, threshold,
+                                        stream);
     if (st != CB_OK) return st;
     return cbinfer_split_conv_tail(seqs, nSeq, prepared, bias, C, H, W, K, kH, kW, weightScale, relu, workspace,
                                    forceSplit, tail, stream);
@@ -2680,9 +2670,9 @@ int cbinfer_split_forward_tail(const cbSplitSeq* seqs, int nSeq, int mode, int p
 int cbinfer_split_forward_fg(const cbSplitSeq* seqs, int nSeq, int pooled, int pH, int pW, const void* prepared, int C,
                              int H, int W, int K, int kH, int kW, float threshold, float weightScale, void* workspace,
                              cbStream_t stream) {
-    const int st = cbinfer_split_detect(seqs, nSeq, CBINFER_SPLIT_FG | (pooled ? CBINFER_SPLIT_POOLED : 0) |
-                                        (weightScale == 0.f ? CBINFER_SPLIT_X3 : 0), pH, pW, C, H, W,
-                                        kH, kW, threshold, stream);
+    const int st = cbinfer_split_detect(seqs, nSeq,
+                                        cbs_detect_mode(CBINFER_SPLIT_FG | (pooled ? CBINFER_SPLIT_POOLED : 0), weightScale),
+                                        pH, pW, C, H, W, kH, kW, threshold, stream);
     if (st != CB_OK) return st;
     return cbs_split_conv(seqs, nSeq, prepared, nullptr, C, H, W, K, kH, kW, weightScale, 0, workspace, 0, nullptr,
                           stream, 1);
@@ -2695,19 +2685,11 @@ int cbinfer_split_forward_fg(const cbSplitSeq* seqs, int nSeq, int pooled, int p
 int cbinfer_split_forward_fg_tail(const cbSplitSeq* seqs, int nSeq, int pooled, int pH, int pW, const void* prepared,
                                   int C, int H, int W, int K, int kH, int kW, float threshold, float weightScale,
                                   void* workspace, const cbSplitTail* tail, cbStream_t stream) {
-    CB_REQUIRE(tail && tail->w1Prepared && tail->b1 && tail->w2 && tail->b2 && nSeq >= 1 && nSeq <= CBS_MAXSEQ);
-    CB_REQUIRE(((size_t)tail->b1 & 15) == 0);
-    if (!cbinfer_split_tail_supported(C, K, kH, kW, tail->C1, tail->C2)) return CB_ERR_UNSUPPORTED;
     CbsTailArgs ta;
-    ta.w1p = tail->w1Prepared, ta.b1 = tail->b1, ta.w2 = tail->w2, ta.b2 = tail->b2;
-    ta.C1 = tail->C1, ta.C2 = tail->C2, ta.relu1 = tail->relu1, ta.relu2 = tail->relu2;
-    for (int q = 0; q < CBS_MAXSEQ; ++q) {
-        if (q < nSeq) CB_REQUIRE(tail->output[q]);
-        ta.out[q] = q < nSeq ? tail->output[q] : nullptr;
-    }
-    const int st = cbinfer_split_detect(seqs, nSeq, CBINFER_SPLIT_FG | (pooled ? CBINFER_SPLIT_POOLED : 0) |
-                                        (weightScale == 0.f ? CBINFER_SPLIT_X3 : 0), pH, pW, C, H, W,
-                                        kH, kW, threshold, stream);
+    int st = cbs_tail_args(ta, tail, nSeq, nullptr, C, K, kH, kW);
+    if (st != CB_OK) return st;
+    st = cbinfer_split_detect(seqs, nSeq, cbs_detect_mode(CBINFER_SPLIT_FG | (pooled ? CBINFER_SPLIT_POOLED : 0), weightScale),
+                              pH, pW, C, H, W, kH, kW, threshold, stream);
     if (st != CB_OK) return st;
     return cbs_split_conv(seqs, nSeq, prepared, nullptr, C, H, W, K, kH, kW, weightScale, 0, workspace, 0, &ta,
                           stream, 1);
@@ -2756,8 +2738,8 @@ int cbinfer_split_forward_next(const cbSplitSeq* seqs, int nSeq, int mode, int p
                                cbStream_t stream) {
     CB_REQUIRE(next);
     if (!cbs_next_supported(C, K, kH, kW, H, W, next) || nSeq != 1 || weightScale != 0.f) return CB_ERR_UNSUPPORTED;
-    mode = (mode & ~CBINFER_SPLIT_X3) | CBINFER_SPLIT_X3;
-    const int st = cbinfer_split_detect(seqs, nSeq, mode, pH, pW, C, H, W, kH, kW, threshold, stream);
+    const int st = cbinfer_split_detect(seqs, nSeq, cbs_detect_mode(mode, weightScale), pH, pW, C, H, W, kH, kW, threshold,
+                                        stream);
     if (st != CB_OK) return st;
     return cbinfer_split_conv_next(seqs, nSeq, prepared, bias, C, H, W, K, kH, kW, weightScale, relu, workspace, next,
                                    stream);
@@ -2766,8 +2748,8 @@ int cbinfer_split_forward_next(const cbSplitSeq* seqs, int nSeq, int mode, int p
 int cbinfer_split_forward(const cbSplitSeq* seqs, int nSeq, int mode, int pH, int pW, const void* prepared,
                           const float* bias, int C, int H, int W, int K, int kH, int kW, float threshold,
                           float weightScale, int relu, void* workspace, cbStream_t stream) {
-    mode = (mode & ~CBINFER_SPLIT_X3) | (weightScale == 0.f ? CBINFER_SPLIT_X3 : 0);
-    const int st = cbinfer_split_detect(seqs, nSeq, mode, pH, pW, C, H, W, kH, kW, threshold, stream);
+    const int st = cbinfer_split_detect(seqs, nSeq, cbs_detect_mode(mode, weightScale), pH, pW, C, H, W, kH, kW, threshold,
+                                        stream);
     if (st != CB_OK) return st;
     return cbs_split_conv(seqs, nSeq, prepared, bias, C, H, W, K, kH, kW, weightScale, relu, workspace, 0, nullptr,
                           stream);
@@ -2907,19 +2889,7 @@ __global__ __launch_bounds__(512) void cbh_detect_kernel(CbhDetGroup grp) {
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6, t = threadIdx.x;
     const int tx = blockIdx.x, y = blockIdx.y;
     const int W = a.W, H = a.H, C = a.C;
-    if (POOL && a.prodMask) {
-        const int pwpr = (a.pW + 63) >> 6;
-        unsigned long long any = 0ull;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int yy = 2 * y + j, ww = 2 * tx + i;
-                const unsigned long long v = a.prodMask[(long)min(yy, a.pH - 1) * pwpr + min(ww, pwpr - 1)];
-                any |= (yy < a.pH && ww < pwpr) ? v : 0ull;
-            }
-        if (__builtin_amdgcn_readfirstlane((int)(any != 0ull)) == 0) return;
-    }
+    if (POOL && a.prodMask && !cb_producer_touched(a.prodMask, a.pH, a.pW, y, tx)) return;
     if (!POOL && a.prodMask) {
         // round 5: the layer is handed the OUTPUT BUFFER of another change-based layer of the same resolution (a chain,
         // CBConv2d._note_upstream) and that layer's change mask of this frame: a 64-pixel segment none of whose pixels
@@ -2940,8 +2910,7 @@ __global__ __launch_bounds__(512) void cbh_detect_kernel(CbhDetGroup grp) {
     auto ldin = [&](int c) -> _Float16 {      // (a channel beyond C -- the padding of the last group -- reads channel C-1:
         c = min(c, C - 1);                    //  never used, see `real` below)
         if (!POOL) return in[(long)c * HW + p];
-        const _Float16* q = in + (long)c * pHW + (long)py0 * a.pW + px0;
-        return cb_max(cb_max(q[0], q[px1]), cb_max(q[py1], q[py1 + px1]));
+        return cb_pooled_load(in + (long)c * pHW + (long)py0 * a.pW + px0, px1, py1);
     };
     __shared__ unsigned long long sm[8];
     __shared__ _Float16 T[64][66];
@@ -3026,26 +2995,8 @@ __global__ __launch_bounds__(512) void cbh_detect_kernel(CbhDetGroup grp) {
         for (int cg = 0; cg < NG; ++cg) group(cg, false, true, m, dummy);
     }
 
-    unsigned long long D = m, SR = 0, SL = 0;
-    for (int d = 1; d <= a.kWH; ++d) {
-        D |= (m << d) | (m >> d);
-        SR |= m >> (64 - d);
-        SL |= m << (64 - d);
-    }
-    D &= vm;
-    SR = (tx + 1 < a.wpr) ? (SR & cb_valid_mask(W, tx + 1)) : 0ull;
-    if (tx == 0) SL = 0;
-    if (g == 0) {
-        const int items = 3 * (2 * a.kHH + 1);
-        for (int i = lane; i < items; i += 64) {
-            const int yy = y + i / 3 - a.kHH;
-            const int which = i % 3;
-            if (yy < 0 || yy >= H) continue;
-            const unsigned long long v = which == 0 ? D : (which == 1 ? SR : SL);
-            const int t2 = which == 0 ? tx : (which == 1 ? tx + 1 : tx - 1);
-            if (v) atomicOr(&a.masks[(long)yy * a.wpr + t2], v);
-        }
-    }
+    const cb_dilated dl = cb_dilate_word(m, a.kWH, W, tx, a.wpr);
+    if (g == 0) cb_or_dilated_rows(a.masks, dl.D, dl.SR, dl.SL, y, a.kHH, H, tx, a.wpr, lane);
 }
 
 }  // namespace cbs
@@ -3066,8 +3017,7 @@ long cbinfer_hsplit_prepared_bytes(int C, int K, int kH, int kW) {
 long cbinfer_hsplit_workspace_bytes(int C, int H, int W, int K, int kH, int kW) {
     if (!cbh_supported(C, K, kH, kW)) return 0;
     if (cbh_geom(C, H, W, kH, kW).nStages < 48) return 0;
-    const int bm = cbs_bm(K), bn = bm >= 128 ? 128 : 64;
-    return 256 + cbs_slab_capacity(1, H, W, K) * bm * bn * 4;
+    return cbs_workspace_bytes(1, H, W, K);
 }
 int cbinfer_hsplit_prep_weights(const void* weight, void* prepared, int K, int C, int kH, int kW, int H, int W,
                                 cbStream_t stream) {
@@ -3200,22 +3150,13 @@ int cbinfer_hsplit_forward_group(const cbHalfLayer* layers, int nLayers, int poo
     p.stageOff = (const int*)((const char*)layers[0].prepared + p.aBytes);      // (the geometry's: one table for the group)
     p.wPlain = nullptr;
     p.bias = (const float*)layers[0].bias;      // (f16 values; the fp16 kernels read the per-layer pointers of CbhExt)
-    p.info = workspace ? (int*)workspace : nullptr;
-    p.slabs = workspace ? (float*)((char*)workspace + 256) : nullptr;
-    p.K = K0, p.KP = KP, p.H = H, p.W = W, p.Wp = g.Wp, p.rec = g.rec, p.nStages = g.nStages, p.kH = kH, p.kW = kW;
-    p.maskWords = (int)MW, p.wpr = wpr, p.relu = layers[0].relu, p.dummyBase = g.dummyBase;
-    p.stateBytes = (long)g.Hp * g.Wp * g.rec;
+    p.relu = layers[0].relu;
+    cbs_fill_params(p, g, K0, KP, BM, H, W, MW, workspace, cbs_slab_capacity(nLayers, H, W, K0));
     p.outScale = 1.0f;
-    p.magicMW = (1ull << 32) / (unsigned long long)MW + 1ull;
-    p.magicWpr = (1ull << 32) / (unsigned long long)p.wpr + 1ull;
-    p.magicW = (1ull << 32) / (unsigned long long)W + 1ull;
-    p.magicMT = (1ull << 32) / (unsigned long long)(KP / BM) + 1ull;
-    p.forceSK = 0, p.accumulate = 0, p.halfOut = 1, p.splitRounds = 2, p.dbg = 0;
+    p.forceSK = 0, p.accumulate = 0, p.halfOut = 1;
     p.maxChunks = 16;      // (the device picks 4, 8 or 16 chunks by the tile count)
     p.upstream = nLayers == 1 ? layers[0].upstreamCount : nullptr;
-    p.arriveShards = (int)(MW / 16 < 8 ? MW / 16 : 8);
-    const long cap = cbs_slab_capacity(nLayers, H, W, K0), cap1 = cbs_slab_capacity(1, H, W, K0);
-    p.slabCap = (int)(cap > 0x7fffffffl ? 0x7fffffffl : cap);
+    const long cap1 = cbs_slab_capacity(1, H, W, K0);
     x.slabCap1 = (int)(cap1 > 0x7fffffffl ? 0x7fffffffl : cap1);
     x.pad_ = 0;
     const long E = (long)nLayers * MW;
@@ -3257,8 +3198,7 @@ int cbinfer_hsplit_forward(const int32_t* upstreamCount, const void* input, int 
 long cbinfer_hsplit_group_workspace_bytes(int nLayers, int C, int H, int W, int K, int kH, int kW) {
     if (nLayers < 1 || nLayers > CBH_GROUP || !cbh_supported(C, K, kH, kW)) return 0;
     if (cbh_geom(C, H, W, kH, kW).nStages < 48) return 0;
-    const int bm = cbs_bm(K), bn = bm >= 128 ? 128 : 64;
-    return 256 + cbs_slab_capacity(nLayers, H, W, K) * bm * bn * 4;
+    return cbs_workspace_bytes(nLayers, H, W, K);
 }
 
 }  // extern "C"
