@@ -19,6 +19,7 @@ from .pipeline import FramePipeline
 from .batch import SequenceBatch
 from .branches import BranchGroup
 from .program import FrameProgram
+from .residual import CBAdd2d, CBResidual, foldBatchNorm
 
 __version__ = "0.1.0"
 
@@ -244,7 +245,7 @@ def linkConsumers(producer, consumers):
     return producer
 
 
-_STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1)
+_STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d)
 
 
 def _stateful(net):
@@ -361,7 +362,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

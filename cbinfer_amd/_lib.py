@@ -248,6 +248,8 @@ _SIGNATURES = {
     "cbinfer_pool_footprint": (_i, [_vp, _i, _vp, _vp, _i, _i, _pp, _vp, _vp]),
     "cbinfer_pool_changed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _pp, _i, _vp]),
     "cbinfer_cbpool2d_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _pp, _i, _vp]),
+    "cbinfer_add_changed": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "cbinfer_cbadd_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

@@ -24,6 +24,7 @@ import torch
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, stream_ptr
 from .conv2d import CBConv2d, CBPoolAvg2d, CBPoolMax2d, CBTail1x1, _switch
+from .residual import CBAdd2d
 
 
 def _ptr_array(tensors):
@@ -44,6 +45,9 @@ class SequenceBatch(object):
             if type(m) in (CBPoolMax2d, CBPoolAvg2d) and m.__dict__.get('_general'):
                 raise CBinferError("SequenceBatch: layer %r is %r, a pool that is never folded into the next detection "
                                    "(only 2x2/stride 2 without padding is) and has no batched kernel" % (name, m))
+            if type(m) is CBAdd2d:
+                raise CBinferError("SequenceBatch: layer %r is %r, a change-based sum, which has no batched kernel: run "
+                                   "residual networks one sequence per stream" % (name, m))
         self.net = net
         self.layers = None          # built on the first frame (needs the frame size)
         self._key = None

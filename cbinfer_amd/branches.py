@@ -19,6 +19,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check
 from .conv2d import CBConv2d
+from .residual import CBAdd2d
 
 
 def _kp(K):
@@ -38,6 +39,9 @@ class BranchGroup(nn.Module):
                                    "padding=%s dilation=%s%s), which has no grouped launch"
                                    % (name, tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation),
                                       '' if m.bias is not None else ', no bias'))
+            if type(m) is CBAdd2d:
+                raise CBinferError("BranchGroup: layer %r is %r, a change-based sum, which has no grouped launch"
+                                   % (name, m))
         self.__dict__['_pairs'] = {}
 
     def _pair_state(self, mods, geom):

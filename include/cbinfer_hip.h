@@ -836,6 +836,40 @@ int cbinfer_cbpool2d_forward(const void* input, void* outputState, const int32_t
                              const int32_t* countDev, const uint64_t* inputMask, uint64_t* bits, uint64_t* maskCopy,
                              int C, int Hi, int Wi, const cbPool* pool, int dtype, cbStream_t stream);
 
+/* ---- change-based element-wise sum: out = a + b [, ReLU] (cb_add.hip) ---------------------------------
+ * No counterpart in the reference.  a, b and the state `out` are [C, H, W], contiguous, one dtype (CB_F32 or CB_F16).
+ * Every producer of this library leaves the pixels outside its change list bit for bit as they were, so a + b can
+ * differ from last frame's only at the union of the operands' changes; recomputing there is the dense sum, exactly.
+ *   listed pixels: the union of the two operands' changes.  Per operand the changes come as its row-padded change
+ *     MASK (cbinfer_mask_words(H, W) words), as an int32 LIST (flat indexes y W + x; entries outside the map are
+ *     dropped), or not at all: every pixel is listed then.  Bits of the row padding are never set.
+ *   values: at listed pixels, every channel, out = a + b -- CB_F32: one IEEE addition; CB_F16: the sum formed in f32
+ *     and rounded to f16 once (the correctly rounded f16 sum).  relu != 0: v > 0 ? v : 0, and a NaN stays a NaN.  Every
+ *     other pixel of `out` keeps its bits.
+ *   hand-on: maskCopy receives the frame's union mask every frame (all zeros for an empty frame: cbinfer_compact_bits
+ *     makes the ascending list from it on demand); `bits`, the working mask (cbinfer_mask_words(H, W) words, zero on
+ *     first use), is zero again when the launch ends.
+ * Bad arguments (a null tensor or mask, C / H / W < 1, an unknown dtype, a negative list capacity, bits == maskCopy,
+ * H W or 64 C beyond an int32) return CB_ERR_BADARG and launch nothing.
+ *
+ * The mask-driven launch.  maskA / maskB: the operand's change mask, or NULL; allA / allB != 0: the operand lists every
+ * pixel.  The kernel ORs `bits`, maskA and maskB word by word itself (or forms the full row word); an operand with
+ * neither contributes what `bits` holds on entry.  No atomics. */
+int cbinfer_add_changed(const void* a, const void* b, void* out, const uint64_t* maskA, int allA, const uint64_t* maskB,
+                        int allB, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int relu, int dtype,
+                        cbStream_t stream);
+/* The whole frame of a change-based sum enqueued without a host sync.  Per operand X: maskX != NULL: mask form;
+ * listX != NULL: list form (capX entries at most, countX the device-side length or NULL: capX is the length; capX == 0
+ * launches nothing); both NULL: no change information, every pixel is listed; both set: CB_ERR_BADARG.  With both
+ * operands in mask or all form the frame is ONE launch (cbinfer_add_changed); an operand in list form costs one launch
+ * in front, which ORs its bits into `bits` (cbinfer_pool_footprint with a 1x1 / stride-1 window: one 64-bit atomicOr
+ * per entry) -- skipped when the other operand lists every pixel anyway.  All arguments are checked before the first
+ * launch. */
+int cbinfer_cbadd_forward(const void* a, const void* b, void* outputState, const uint64_t* maskA, const int32_t* listA,
+                          int capA, const int32_t* countA, const uint64_t* maskB, const int32_t* listB, int capB,
+                          const int32_t* countB, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int relu,
+                          int dtype, cbStream_t stream);
+
 /* replaces conv2d_fg_cpu, cbconv2d_fg_backend.cu:81-112: HOST pointers, host code, race-free. */
 void cbinfer_conv2d_fg_cpu(const float* input, const float* prevInput, float* output,
                            const float* weight, float threshold, int no, int ni, int h, int w,
