@@ -1492,7 +1492,8 @@ class CBConv2d(nn.Module):
         return self._emit(changeIndexes, last=False)
 
     def _state_for(self, size, like):
-        """(Re)allocate the state, +inf: a first frame is 100 % change (conv2d.py:192-199).  -> prevInput is new"""
+        """(Re)allocate the state, +inf: a first frame is 100 % change (conv2d.py:192-199).  -> prevInput is new
+        (prevOutput of a general-geometry layer with output pixels no tap reaches: _bias_map)"""
         fresh = (tuple(self.prevInput.size()) != tuple(size) or self.prevInput.dtype != like.dtype or
                  self.prevInput.device != like.device)
         if fresh:
@@ -1502,8 +1503,31 @@ class CBConv2d(nn.Module):
         outpSize[-2], outpSize[-1] = self._out_hw(size[-2], size[-1])
         if (not _same_shape(self.prevOutput, outpSize) or self.prevOutput.dtype != like.dtype or
                 self.prevOutput.device != like.device):
-            self.prevOutput = torch.full(outpSize, float('inf'), dtype=like.dtype, device=like.device)
+            if self._has_unreached_outputs():
+                self.prevOutput = self._bias_map(outpSize, like)
+            else:
+                self.prevOutput = torch.full(outpSize, float('inf'), dtype=like.dtype, device=like.device)
         return fresh
+
+    def _has_unreached_outputs(self):
+        """Padding beyond the dilated filter's reach on an axis (p > d (k-1), nn.Conv2d(3, 8, 3, padding=3)): the outer
+        output pixels have no tap inside the input map, so no frame ever lists or writes them."""
+        if not self.__dict__.get('_geom'):
+            return False
+        k, p, d = self.kernel_size, self.padding, self.dilation
+        return any(p[i] > d[i] * (k[i] - 1) for i in (0, 1))
+
+    def _bias_map(self, size, like):
+        """The dense value of an output pixel without an in-map tap, broadcast over the map: the bias (0 without one),
+        after the ReLU when withReLU -- exact in fp32 and fp16.  Made when the state is (re)allocated, with the flags of
+        that moment: the first frame overwrites every reachable pixel, the others keep this value until the next
+        clearMemory() or change of resolution / dtype / device -- so a withReLU toggled in the middle of a sequence
+        reaches them as it reaches any unlisted pixel, not at all."""
+        fill = torch.zeros(size, dtype=like.dtype, device=like.device)
+        if self.bias is not None:
+            b = self.bias.detach().to(device=like.device, dtype=like.dtype)
+            fill += (F.relu(b) if self.withReLU else b).view(1, -1, 1, 1)
+        return fill
 
     def _forward_pooled(self, lazy, path):
         """A layer behind a lazy CBPoolMax2d (pycbinfer.fusePoolingIntoDetection) on `path` (_path): its change detection

@@ -59,7 +59,9 @@ int cbg_ckkpad(int Ckk) { return (Ckk + CBG_BK - 1) / CBG_BK * CBG_BK; }
 // weight preparation: W[KP][CkkP] in the tensors' element type (k contiguous, zero padded), then the k -> tap table:
 //   off[k]  = byte offset of tap (c, ky, kx) relative to the BASE pixel (oy sH, ox sW) of the input map
 //   dydx[k] = (dx << 16) | (dy & 0xffff) with dy = ky dH - pH, dx = kx dW - pW (the border test against Hi, Wi)
-// The padded tail k >= Ckk gets dy = -32768: outside every map.
+// The padded tail k >= Ckk gets dy = dx = -32768: outside every map (either one alone is not -- a base pixel at row
+// 32768 or beyond brings the tap back inside a map that tall; both at once would need 2^30 pixels, which
+// cbinfer_geom_prep_weights refuses).
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void cbg_prep_kernel(const T* __restrict__ w, T* __restrict__ wp, int K, int Ckk,
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void cbg_prep_kernel(const T* __restrict__ w, 
         const int k = (int)e;
         if (k >= Ckk) {
             tab[k] = 0;
-            tab[CkkP + k] = 0x8000;
+            tab[CkkP + k] = (int)0x80008000u;
         } else {
             const int c = k / (g.kH * g.kW), r = k % (g.kH * g.kW);
             const int dy = (r / g.kW) * g.dH - g.pH, dx = (r % g.kW) * g.dW - g.pW;

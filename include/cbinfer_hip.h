@@ -741,7 +741,12 @@ int cbinfer_concat_channels(const void* const* sources, const int32_t* channels,
  * (conv2d.py:92-104).  Input map Hi x Wi, filter kH x kW, stride (sH, sW), zero padding (pH, pW), dilation (dH, dW);
  * output map Ho = (Hi + 2 pH - dH (kH-1) - 1) / sH + 1, Wo likewise (torch's formula).  Limits per axis: k <= 7,
  * s <= 4, d <= 8, p <= 64 -- beyond them CB_ERR_UNSUPPORTED, a non-positive entry or a filter that does not fit the
- * padded map CB_ERR_BADARG; nothing is launched then.  The geometry travels as one HOST struct. */
+ * padded map CB_ERR_BADARG; nothing is launched then.  The geometry travels as one HOST struct.
+ * Output pixels no tap reaches: with p > d (k-1) on an axis (nn.Conv2d(3, 8, 3, padding=3)) the output pixels with
+ * o s - p + (k-1) d < 0, and their mirror at the far edge, have no tap inside the input map.  The detection never
+ * lists them, so NO entry point below ever writes them (cbinfer_conv_changed_geom does when a caller's own list names
+ * one: bias, ReLU applied).  Their dense value is the bias (after the ReLU), 0 without one, in every frame: the caller
+ * initialises prevOutput / output with it -- CBConv2d does when it allocates the state. */
 typedef struct cbGeom {
     int kH, kW, sH, sW, pH, pW, dH, dW;
 } cbGeom;

@@ -6,7 +6,9 @@ specification (DESIGN.md, "General geometry"):
   rule 2      the change list on the OUTPUT map: output (oy, ox) iff one of its taps is a changed input pixel -- written
               twice (tap loop, and conv2d(changed, ones) > 0) and asserted equal;
   rule 4      torch.nn.functional.conv2d in float64 on the twin's state, compared at the listed pixels; every other
-              output pixel must keep its bits.
+              output pixel must keep its bits.  An output pixel no tap reaches (padding beyond the dilated filter's
+              reach) is never listed, so the C entry points never write it: the caller initialises it -- CBConv2d with
+              the bias (after the ReLU), its dense value.
 The twin is teacher-forced: it and the module see the same frames.  Bars: fp32 1e-4 absolute, fp16
 4 * 2^-10 * max(1, |ref|max) -- those of tests/test_gpu_modules.py::test_fuzz_shapes_track_dense; inputs in [0, 1),
 torch's default initialisation."""
@@ -37,8 +39,13 @@ GEOMS = {
     "2x2s2p0": ((2, 2), (2, 2), (0, 0), (1, 1)),
     "4x4s4p0": ((4, 4), (4, 4), (0, 0), (1, 1)),
     "aniso": ((3, 5), (2, 1), (0, 3), (1, 2)),
+    # padding beyond the dilated filter's reach: the outer output pixels have no tap inside the input map
+    "3x3p3": ((3, 3), (1, 1), (3, 3), (1, 1)),
+    "2x2s2p2": ((2, 2), (2, 2), (2, 2), (1, 1)),
+    "1x1p64": ((1, 1), (1, 1), (64, 64), (1, 1)),
 }
 NAMES = list(GEOMS)
+RING = ("3x3p3", "2x2s2p2", "1x1p64")      # geometries with unreachable output pixels
 DTYPES = [torch.float32, torch.float16]
 
 
@@ -60,6 +67,20 @@ def in_size_for(target, k, s, p, d):
         n += 1
     assert out_size(n, k, s, p, d) == target
     return n
+
+
+def sizes_for(name, geom, Ho, Wo):
+    """Input size of a test map: the smallest with the output size asked for; '1x1p64' (Wo = Wi + 128) on a 1..3-pixel
+    map instead."""
+    (kH, kW), s, p, d = geom
+    if name == "1x1p64":
+        return 1 + Ho % 3, 1 + Wo % 3
+    return in_size_for(Ho, kH, s[0], p[0], d[0]), in_size_for(Wo, kW, s[1], p[1], d[1])
+
+
+def reachable(geom, Hi, Wi, Ho, Wo):
+    """The output pixels with a tap inside the input map: all of them unless p > d (k-1) on an axis."""
+    return footprint(np.ones((Hi, Wi), dtype=bool), geom, Ho, Wo)
 
 
 def footprint(changed, geom, Ho, Wo):
@@ -163,9 +184,9 @@ def test_geometries_track_the_twin(pkg, oracle, name, dtype):
         Wo = (63, 64, 65)[(c + gi) % 3]
         K = (32, 33, 64, 70)[(c + gi) % 4]
         Cin = (3, 16, 5, 32)[c % 4]
-        Wi = in_size_for(Wo, kW, s[1], p[1], d[1])
-        Hi = in_size_for(5 + c, kH, s[0], p[0], d[0]) + (c % s[0])
-        Ho = out_size(Hi, kH, s[0], p[0], d[0])
+        Hi, Wi = sizes_for(name, geom, 5 + c, Wo)
+        Hi += c % s[0]
+        Ho, Wo = out_size(Hi, kH, s[0], p[0], d[0]), out_size(Wi, kW, s[1], p[1], d[1])
         conv = make_conv(geom, Cin, K, bias, dtype)
         m = pkg.CBConv2d(conv, TH, generalGeometry=True)
         m.feedbackLoop, m.withReLU = feedback, relu
@@ -179,7 +200,10 @@ def test_geometries_track_the_twin(pkg, oracle, name, dtype):
                 assert tuple(y.shape) == (1, K, Ho, Wo), tag
                 got = m.lastChangeIndexes().tensor().cpu().numpy()
                 assert np.array_equal(got, idx), tag
-                assert t > 0 or idx.size == Ho * Wo, tag
+                if name in RING:      # the first frame lists every pixel a tap reaches, and those are not all
+                    assert t > 0 or Ho * Wo > idx.size == int(reachable(geom, Hi, Wi, Ho, Wo).sum()), tag
+                else:
+                    assert t > 0 or idx.size == Ho * Wo, tag
                 assert np.array_equal(bits_of(m.prevInput.cpu().numpy()), bits_of(twin.state)), tag
                 out = y.cpu().numpy()[0]
                 if idx.size:
@@ -187,6 +211,8 @@ def test_geometries_track_the_twin(pkg, oracle, name, dtype):
                     assert err <= bound_for(dtype, ref), tag + (err,)
                 if prev is not None:
                     assert np.array_equal(bits_of(out)[:, ~listed], bits_of(prev)[:, ~listed]), tag
+                elif name in RING:    # never written: the dense value there is the bias and nothing else
+                    assert np.array_equal(out[:, ~listed], ref[:, ~listed].astype(npdtype)), tag
                 prev = out.copy()
 
 
@@ -194,7 +220,9 @@ def test_geometries_track_the_twin(pkg, oracle, name, dtype):
 @pytest.mark.parametrize("name", NAMES + ["wide"])
 def test_threshold_zero_equals_dense(pkg, name, dtype):
     """With threshold 0 the layer equals conv(x) densely after every frame.  'wide': 256 output channels at 161 x 241,
-    where the list fills more tiles than the grid has workgroups (no k-split, several tiles per workgroup)."""
+    where the list fills more tiles than the grid has workgroups (no k-split, several tiles per workgroup).  The
+    geometries of RING (output pixels without a tap inside the map, whose dense value is the bias) run with and
+    without bias, with and without ReLU."""
     rng = np.random.default_rng(7)
     if name == "wide":
         geom, Cin, K, Hi, Wi = GEOMS["3x3s2p1"], 3, 256, 161, 241
@@ -202,26 +230,30 @@ def test_threshold_zero_equals_dense(pkg, name, dtype):
         geom = GEOMS[name]
         gi = NAMES.index(name)
         Cin, K = (3, 16, 5, 32)[gi % 4], (32, 33, 64, 70)[gi % 4]
-        Wi = in_size_for((63, 64, 65)[gi % 3], geom[0][1], geom[1][1], geom[2][1], geom[3][1])
-        Hi = in_size_for(9, geom[0][0], geom[1][0], geom[2][0], geom[3][0])
-    conv = make_conv(geom, Cin, K, name != "7x7s2p3", dtype)
-    m = pkg.CBConv2d(conv, 0.0, generalGeometry=True)
-    m.withReLU = NAMES.index(name) % 2 == 0 if name != "wide" else True
-    m.feedbackLoop = name in ("3x3d2p2", "4x4s4p0", "wide")
-    x = torch.rand(1, Cin, Hi, Wi, device="cuda").to(dtype)
-    with torch.no_grad():
-        for t in range(4):
-            if t:
-                x = x.clone()
-                for _ in range(3):
-                    y0, x0 = int(rng.integers(0, Hi)), int(rng.integers(0, Wi))
-                    x[:, :, y0:y0 + 4, x0:x0 + 7] = torch.rand_like(x[:, :, y0:y0 + 4, x0:x0 + 7])
-            y = m(x.clone())
-            ref = dense_f64(conv, x)
-            if m.withReLU:
-                ref = torch.relu(ref)
-            err = (y.cpu().double() - ref).abs().max().item()
-            assert err <= bound_for(dtype, ref.numpy()), (name, t, err)
+        Hi, Wi = sizes_for(name, geom, 9, (63, 64, 65)[gi % 3])
+    if name in RING:
+        combos = [(b, r) for b in (True, False) for r in (False, True)]
+    else:
+        combos = [(name != "7x7s2p3", NAMES.index(name) % 2 == 0 if name != "wide" else True)]
+    for bias, relu in combos:
+        conv = make_conv(geom, Cin, K, bias, dtype)
+        m = pkg.CBConv2d(conv, 0.0, generalGeometry=True)
+        m.withReLU = relu
+        m.feedbackLoop = name in ("3x3d2p2", "4x4s4p0", "wide")
+        x = torch.rand(1, Cin, Hi, Wi, device="cuda").to(dtype)
+        with torch.no_grad():
+            for t in range(4):
+                if t:
+                    x = x.clone()
+                    for _ in range(3):
+                        y0, x0 = int(rng.integers(0, Hi)), int(rng.integers(0, Wi))
+                        x[:, :, y0:y0 + 4, x0:x0 + 7] = torch.rand_like(x[:, :, y0:y0 + 4, x0:x0 + 7])
+                y = m(x.clone())
+                ref = dense_f64(conv, x)
+                if m.withReLU:
+                    ref = torch.relu(ref)
+                err = (y.cpu().double() - ref).abs().max().item()
+                assert err <= bound_for(dtype, ref.numpy()), (name, bias, relu, t, err)
 
 
 def test_beyond_the_limits_is_a_cbinfer_error(pkg):

@@ -216,3 +216,50 @@ def test_new_kernels_use_mfma_and_no_scratch():
     for word in ("s_" + "store", "s_buffer_" + "store", "s_scratch_" + "store", "s_" + "atomic", "s_buffer_" + "atomic",
                  "s_dcache_" + "wb", "s_dcache_" + "discard", "getenv"):
         assert word not in src, word
+
+
+def test_state_of_a_layer_with_unreachable_output_pixels_starts_as_their_dense_value():
+    """Padding beyond the dilated filter's reach (p > d (k-1) on an axis): the outer output pixels have no tap inside
+    the input map, are never listed and never written.  Their dense value is the bias (after the ReLU), so prevOutput
+    is allocated holding it instead of +inf -- bit for bit torch's dense result there --, again after clearMemory(), a
+    change of resolution or dtype, with the flags of that moment; every other layer still allocates +inf."""
+    import pycbinfer
+    torch.manual_seed(3)
+    ring = [nn.Conv2d(3, 4, 3, padding=3), nn.Conv2d(3, 4, 2, stride=2, padding=2, bias=False),
+            nn.Conv2d(3, 4, 1, padding=64), nn.Conv2d(3, 4, (3, 3), padding=(1, 3)),
+            nn.Conv2d(3, 4, 3, stride=2, padding=5, dilation=2)]
+    for conv in ring:
+        for relu in (False, True):
+            m = pycbinfer.CBConv2d(conv, 0.1, generalGeometry=True)
+            m.withReLU = relu
+            assert m._has_unreached_outputs()
+            for size, dtype in (((1, 3, 5, 6), torch.float32), ((1, 3, 7, 4), torch.float32), ((1, 3, 7, 4), torch.float16)):
+                x = torch.rand(size)
+                m._state_for(size, x.to(dtype))
+                with torch.no_grad():
+                    dense = conv(x)
+                    if relu:
+                        dense = F.relu(dense)
+                    reach = F.conv2d(torch.ones(1, 1, *size[2:]), torch.ones(1, 1, *conv.kernel_size), stride=conv.stride,
+                                     padding=conv.padding, dilation=conv.dilation)[0, 0] > 0
+                assert not reach.all() and reach.any()
+                assert m.prevOutput.dtype == dtype and tuple(m.prevOutput.shape) == tuple(dense.shape)
+                assert torch.isinf(m.prevInput).all()
+                assert torch.equal(m.prevOutput[0][:, ~reach], dense[0][:, ~reach].to(dtype))
+            # a flag toggled later reaches these pixels when the state is allocated again
+            m.withReLU = not relu
+            m.clearMemory()
+            m._state_for((1, 3, 5, 6), torch.zeros(1, 3, 5, 6))
+            want = torch.zeros(4) if conv.bias is None else conv.bias.detach()
+            want = F.relu(want) if m.withReLU else want
+            assert torch.equal(m.prevOutput, want.view(1, 4, 1, 1).expand(1, 4, *m._out_hw(5, 6)))
+            back = pickle.loads(pickle.dumps(m))
+            assert torch.equal(back.prevOutput, m.prevOutput) and back._has_unreached_outputs()
+    for conv in (nn.Conv2d(3, 4, 3, padding=2, dilation=2), nn.Conv2d(3, 4, 3, stride=2, padding=2),
+                 nn.Conv2d(3, 4, 7, stride=2, padding=3, bias=False)):
+        m = pycbinfer.CBConv2d(conv, 0.1, generalGeometry=True)
+        assert not m._has_unreached_outputs()
+        m._state_for((1, 3, 9, 9), torch.zeros(1, 3, 9, 9))
+        assert torch.isinf(m.prevOutput).all()
+    unit = pycbinfer.CBConv2d(nn.Conv2d(3, 4, 3, padding=1), 0.1)
+    assert not unit._has_unreached_outputs()
