@@ -109,6 +109,16 @@ class Pool(ctypes.Structure):
 
 _pp = ctypes.POINTER(Pool)
 
+UPSAMPLE_NEAREST, UPSAMPLE_BILINEAR = 0, 1      # CB_UPSAMPLE_*
+
+
+class Upsample(ctypes.Structure):
+    """cbUpsample of include/cbinfer_hip.h: integer scales, mode and align_corners of a change-based upsampling."""
+    _fields_ = [("sH", _i), ("sW", _i), ("mode", _i), ("alignCorners", _i)]
+
+
+_up, _i32p = ctypes.POINTER(Upsample), ctypes.POINTER(ctypes.c_int32)
+
 _SIGNATURES = {
     # name: (restype, [argtypes])
     "cbinfer_abi_version": (_i, []),
@@ -250,6 +260,9 @@ _SIGNATURES = {
     "cbinfer_cbpool2d_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _pp, _i, _vp]),
     "cbinfer_add_changed": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "cbinfer_cbadd_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "cbinfer_upsample_supported": (_i, [_up]),
+    "cbinfer_cbupsample_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _up, _i, _vp]),
+    "cbinfer_cbconcat_forward": (_i, [_vpp, _i32p, _i, _vp, _vpp, _vpp, _i32p, _vpp, _vp, _vp, _i, _i, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

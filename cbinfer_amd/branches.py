@@ -20,6 +20,7 @@ from . import _lib
 from ._lib import C, CBinferError, check
 from .conv2d import CBConv2d
 from .residual import CBAdd2d
+from .decoder import CBConcat2d, CBUpsample2d
 
 
 def _kp(K):
@@ -42,6 +43,9 @@ class BranchGroup(nn.Module):
             if type(m) is CBAdd2d:
                 raise CBinferError("BranchGroup: layer %r is %r, a change-based sum, which has no grouped launch"
                                    % (name, m))
+            if type(m) in (CBUpsample2d, CBConcat2d):
+                raise CBinferError("BranchGroup: layer %r is %r, a change-based decoder operator, which has no grouped "
+                                   "launch" % (name, m))
         self.__dict__['_pairs'] = {}
 
     def _pair_state(self, mods, geom):

@@ -1,0 +1,315 @@
+"""Change-based decoder operators: CBUpsample2d, CBConcat2d and insertCBUpsampling (cb_decoder.hip).
+
+The reference has neither operator: an nn.Upsample or a torch.cat(dim=1) -- what every dense-prediction decoder (FCN and
+DeepLab heads, U-Net, the top-down path of an FPN) is built from -- ends a change-based chain: torch recomputes the whole
+map at the largest resolutions of the network, drops the producers' change masks and cannot be recorded by a
+FrameProgram.  Every producer of this package leaves the pixels outside its change list bit for bit as they were, so the
+output of either operator can differ from last frame's only at the FOOTPRINT of the operands' changes: both modules
+recompute there and are the dense result exactly, without a threshold.
+
+Bilinear upsampling derives its source coordinates in INTEGERS (include/cbinfer_hip.h); torch derives them from a float
+scale and its weights drift by about o 2^-24 along a row, so the bilinear values are pinned against float64 math and are
+not bit-identical to F.interpolate.  Nearest is bit-identical to torch.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
+from .conv2d import CBConv2d, CBPoolAvg2d, CBPoolMax2d, _same_shape
+from .conv2d_cg import ChangeIndexes, MaskChangeIndexes
+from .residual import CBAdd2d, CBResidual
+
+MAX_SCALE = 8
+
+
+def _split(name, x, which):
+    """(contiguous tensor, change indexes or None) of an operand: a tensor or ('changeIndexes', tensor, indexes)."""
+    if type(x) == tuple:
+        if len(x) != 3 or x[0] != 'changeIndexes':
+            raise CBinferError("%s: %s is a tuple, but not ('changeIndexes', tensor, indexes)" % (name, which))
+        x, indexes = x[1], x[2]
+    else:
+        indexes = None
+    if not torch.is_tensor(x):
+        raise CBinferError("%s: %s must be a tensor or the ('changeIndexes', tensor, indexes) tuple, got %s"
+                           % (name, which, type(x).__name__))
+    return x.detach().contiguous(), indexes
+
+
+def _form(name, which, indexes, H, W, dev, spare):
+    """(mask, list, capacity, device count) of an operand's changes on its H x W map; all None / 0: every pixel is
+    listed.  `spare`: any int32 device buffer, which stands for the empty list (an empty tensor has no address)."""
+    if indexes is None:
+        return None, None, 0, None
+    if isinstance(indexes, ChangeIndexes):
+        if indexes.size is not None and tuple(indexes.size) != (H, W):
+            raise CBinferError("%s: the change indexes of %s address a %dx%d map, the tensor is a %dx%d map"
+                               % ((name, which) + tuple(indexes.size) + (H, W)))
+        if isinstance(indexes, MaskChangeIndexes) and indexes._mask is not None:
+            return indexes._mask, None, 0, None      # (the producer's list is not needed)
+        idx, count = indexes.buffer, indexes.count
+    elif torch.is_tensor(indexes):
+        idx, count = indexes.detach(), None
+    else:
+        raise CBinferError("%s: the change indexes of %s must be an int32 tensor or a ChangeIndexes, got %s"
+                           % (name, which, type(indexes).__name__))
+    if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != dev:
+        raise CBinferError("%s: the change indexes of %s must be a contiguous one-dimensional int32 tensor on the "
+                           "tensor's device" % (name, which))
+    cap = idx.numel()
+    return None, (idx if cap else spare), cap, count
+
+
+def _integer_scale(v):
+    """An int or an integer-valued float as an int, else None."""
+    if isinstance(v, bool):
+        return None
+    if isinstance(v, int):
+        return v
+    if isinstance(v, float) and v == int(v):
+        return int(v)
+    return None
+
+
+def _check_upsample(m):
+    """(sH, sW, mode, align_corners) if the library takes the upsampling module `m`; CBinferError with a sentence naming
+    the setting otherwise."""
+    Err = CBinferError
+    if not isinstance(m, nn.Upsample):
+        raise Err("CBUpsample2d: only nn.Upsample, nn.UpsamplingNearest2d and nn.UpsamplingBilinear2d modules are "
+                  "converted, got %s" % type(m).__name__)
+    if m.size is not None:
+        raise Err("CBUpsample2d: size=%r is not supported, only an integer scale_factor" % (m.size,))
+    sf = m.scale_factor
+    if isinstance(sf, (tuple, list)):
+        if len(sf) != 2:
+            raise Err("CBUpsample2d: scale_factor=%r is not supported, only a number or a pair (2-d maps)" % (sf,))
+        pair = tuple(_integer_scale(v) for v in sf)
+    else:
+        pair = (_integer_scale(sf),) * 2
+    if any(v is None for v in pair):
+        raise Err("CBUpsample2d: scale_factor=%r is not supported, only integer scales" % (sf,))
+    if any(v < 1 or v > MAX_SCALE for v in pair):
+        raise Err("CBUpsample2d: scale_factor=%r is beyond what the library takes (1..%d per axis)" % (sf, MAX_SCALE))
+    if m.mode not in ('nearest', 'bilinear'):
+        raise Err("CBUpsample2d: mode=%r is not supported, only 'nearest' and 'bilinear'" % (m.mode,))
+    if getattr(m, 'recompute_scale_factor', None):
+        raise Err("CBUpsample2d: recompute_scale_factor=%r is not supported" % (m.recompute_scale_factor,))
+    if m.mode == 'nearest' and m.align_corners is not None:
+        raise Err("CBUpsample2d: align_corners=%r has no meaning with mode='nearest'" % (m.align_corners,))
+    return pair[0], pair[1], m.mode, bool(m.align_corners)
+
+
+class _CBDecoderModule(nn.Module):
+    """What the two modules share: the state buffer, the flags of CBAdd2d, transient work buffers."""
+
+    def __init__(self):
+        super(_CBDecoderModule, self).__init__()
+        self.propChangeIndexes = False
+        self.cloneOutput = True
+        self.register_buffer('outputState', torch.zeros(0))
+        self.clearMemory()
+
+    def clearMemory(self):
+        if 'outputState' not in self._buffers:
+            self.register_buffer('outputState', torch.zeros(0))
+        self.outputState = self.outputState.new_zeros(0)
+        self.__dict__['_work'] = None      # (device work buffers and ctypes arguments, not part of the state)
+
+    def getStateTensors(self):
+        return [self.outputState]
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        for name in ('_work', '_upC'):      # (transient: device work buffers, ctypes arguments)
+            if name in d:
+                d[name] = None
+        return d
+
+    def _result(self, work, H, W):
+        if self.cloneOutput:
+            output = self.outputState.clone()
+        else:
+            output = self.outputState
+            output._cbinfer_inplace_state = True
+        if self.propChangeIndexes:
+            return 'changeIndexes', output, MaskChangeIndexes(work['copy'], (H, W), work['idx'], work['count'])
+        return output
+
+
+class CBUpsample2d(_CBDecoderModule):
+    """nn.Upsample with an integer scale_factor (1..8 per axis), mode 'nearest' or 'bilinear' (align_corners False or
+    True), recomputed at the output pixels that read a changed input pixel.
+
+    forward(x): a [1, C, Hi, Wi] tensor -- no change information, every pixel is recomputed -- or the
+    ('changeIndexes', tensor, indexes) tuple of a producer with propChangeIndexes.  A MaskChangeIndexes is taken as its
+    mask (one launch, the list is not needed); any other ChangeIndexes, or an exact int32 tensor, as a list (one launch
+    in front).  The flags are CBAdd2d's: propChangeIndexes hands on the frame's footprint as a MaskChangeIndexes on the
+    OUTPUT map; cloneOutput=False hands out the state itself, tagged, and the frame is then free of torch operators."""
+
+    def __init__(self, m):
+        super(CBUpsample2d, self).__init__()
+        sH, sW, self.mode, self.align_corners = _check_upsample(m)
+        self.scale_factor = (sH, sW)
+        self.__dict__['_upC'] = None
+
+    def _struct(self):
+        """(pointer to) the module's cbUpsample; transient, made again after unpickling."""
+        if self.__dict__.get('_upC') is None:
+            mode = _lib.UPSAMPLE_NEAREST if self.mode == 'nearest' else _lib.UPSAMPLE_BILINEAR
+            self.__dict__['_upC'] = ctypes.pointer(_lib.Upsample(self.scale_factor[0], self.scale_factor[1], mode,
+                                                                 int(self.align_corners)))
+        return self.__dict__['_upC']
+
+    def _workspace(self, Hi, Wi, dev):
+        """Working mask (zero between frames), the frame's mask copy, index buffer and count: once per map size."""
+        key = (Hi, Wi, dev)
+        work = self.__dict__.get('_work')
+        if work is None or work['key'] != key:
+            Ho, Wo = Hi * self.scale_factor[0], Wi * self.scale_factor[1]
+            words = C.cbinfer_mask_words(Ho, Wo)
+            work = self.__dict__['_work'] = dict(
+                key=key, size=(Ho, Wo),
+                bits=torch.zeros(words, dtype=torch.int64, device=dev),
+                copy=torch.zeros(words, dtype=torch.int64, device=dev),
+                idx=torch.empty(Ho * Wo, dtype=torch.int32, device=dev),
+                count=torch.zeros(1, dtype=torch.int32, device=dev))
+        return work
+
+    def forward(self, inp):
+        x, indexes = _split('CBUpsample2d', inp, 'the input')
+        if x.dim() != 4 or x.size(0) != 1:
+            raise CBinferError("CBUpsample2d: the input must be a [1, C, H, W] tensor, got %s" % (tuple(x.shape),))
+        if x.dtype not in (torch.float32, torch.float16):
+            raise CBinferError("CBUpsample2d: float32 and float16 tensors only, got %s" % x.dtype)
+        require_device(x)
+        nc, Hi, Wi = x.size(1), x.size(2), x.size(3)
+        work = self._workspace(Hi, Wi, x.device)
+        Ho, Wo = work['size']
+        form = _form('CBUpsample2d', 'the input', indexes, Hi, Wi, x.device, work['idx'])
+        if (not _same_shape(self.outputState, (1, nc, Ho, Wo)) or self.outputState.dtype != x.dtype or
+                self.outputState.device != x.device):
+            # a new state is written completely: the change information is not used
+            self.outputState = torch.empty((1, nc, Ho, Wo), dtype=x.dtype, device=x.device)
+            form = (None, None, 0, None)
+        check(C.cbinfer_cbupsample_forward(ptr(x), ptr(self.outputState), ptr(form[0]), ptr(form[1]), form[2],
+                                           ptr(form[3]), ptr(work['bits']), ptr(work['copy']), nc, Hi, Wi,
+                                           self._struct(), dtype_code(x), stream_ptr(x)))
+        return self._result(work, Ho, Wo)
+
+    def __repr__(self):
+        return ('CBUpsample2d (scale_factor=%s, mode=%s, align_corners=%s, propChgIdxs=%s)'
+                % (self.scale_factor, self.mode, self.align_corners, self.propChangeIndexes))
+
+
+class CBConcat2d(_CBDecoderModule):
+    """torch.cat(operands, dim=1) of 2..4 [1, Ck, H, W] maps: operand k's channels are copied at operand k's changed
+    pixels only -- a skip connection that did not change is not touched -- and the union of the operands' changes is
+    handed on.
+
+    forward(operands): a list of tensors or ('changeIndexes', tensor, indexes) tuples, each in the forms CBUpsample2d
+    takes; the flags are the same.  (pycbinfer.ChannelConcat is the dense concat: it copies every pixel every frame and
+    hands nothing on.)"""
+
+    def __init__(self):
+        super(CBConcat2d, self).__init__()
+        self._channels = None      # (the channel split the state was written with)
+
+    def clearMemory(self):
+        super(CBConcat2d, self).clearMemory()
+        self.__dict__['_channels'] = None
+
+    def _workspace(self, n, H, W, dev):
+        """n working masks (zero between frames), the frame's mask copy, index buffer, count and the host argument
+        arrays: once per operand count and map size."""
+        key = (n, H, W, dev)
+        work = self.__dict__.get('_work')
+        if work is None or work['key'] != key:
+            words = C.cbinfer_mask_words(H, W)
+            work = self.__dict__['_work'] = dict(
+                key=key,
+                bits=torch.zeros(n * words, dtype=torch.int64, device=dev),
+                copy=torch.zeros(words, dtype=torch.int64, device=dev),
+                idx=torch.empty(H * W, dtype=torch.int32, device=dev),
+                count=torch.zeros(1, dtype=torch.int32, device=dev),
+                srcs=(ctypes.c_void_p * n)(), chans=(ctypes.c_int32 * n)(), masks=(ctypes.c_void_p * n)(),
+                lists=(ctypes.c_void_p * n)(), caps=(ctypes.c_int32 * n)(), counts=(ctypes.c_void_p * n)())
+        return work
+
+    def forward(self, operands):
+        if not isinstance(operands, (list, tuple)) or (type(operands) == tuple and operands[:1] == ('changeIndexes',)):
+            raise CBinferError("CBConcat2d: forward takes a LIST of operands (tensors or ('changeIndexes', tensor, "
+                               "indexes) tuples), got %s" % type(operands).__name__)
+        n = len(operands)
+        if not 2 <= n <= 4:
+            raise CBinferError("CBConcat2d: 2..4 operands, got %d" % n)
+        split = [_split('CBConcat2d', x, 'operand %d' % k) for k, x in enumerate(operands)]
+        t0 = split[0][0]
+        for k, (t, _) in enumerate(split):
+            if t.dim() != 4 or t.size(0) != 1:
+                raise CBinferError("CBConcat2d: operands must be [1, C, H, W] tensors, operand %d is %s"
+                                   % (k, tuple(t.shape)))
+            if t.shape[2:] != t0.shape[2:] or t.dtype != t0.dtype or t.device != t0.device:
+                raise CBinferError("CBConcat2d: the operands differ: operand 0 is %s %s on %s, operand %d is %s %s on %s"
+                                   % (tuple(t0.shape), t0.dtype, t0.device, k, tuple(t.shape), t.dtype, t.device))
+        if t0.dtype not in (torch.float32, torch.float16):
+            raise CBinferError("CBConcat2d: float32 and float16 tensors only, got %s" % t0.dtype)
+        require_device(*[t for t, _ in split])
+        H, W = t0.size(2), t0.size(3)
+        chans = tuple(t.size(1) for t, _ in split)
+        work = self._workspace(n, H, W, t0.device)
+        forms = [_form('CBConcat2d', 'operand %d' % k, ix, H, W, t0.device, work['idx'])
+                 for k, (_, ix) in enumerate(split)]
+        if (not _same_shape(self.outputState, (1, sum(chans), H, W)) or self.outputState.dtype != t0.dtype or
+                self.outputState.device != t0.device or self.__dict__.get('_channels') != chans):
+            # a new state is written completely: no operand's change information is used
+            self.outputState = torch.empty((1, sum(chans), H, W), dtype=t0.dtype, device=t0.device)
+            self.__dict__['_channels'] = chans
+            forms = [(None, None, 0, None)] * n
+        for k, ((t, _), f) in enumerate(zip(split, forms)):
+            work['srcs'][k], work['chans'][k] = t.data_ptr(), chans[k]
+            work['masks'][k], work['lists'][k], work['caps'][k], work['counts'][k] = ptr(f[0]), ptr(f[1]), f[2], ptr(f[3])
+        check(C.cbinfer_cbconcat_forward(work['srcs'], work['chans'], n, ptr(self.outputState), work['masks'],
+                                         work['lists'], work['caps'], work['counts'], ptr(work['bits']),
+                                         ptr(work['copy']), H, W, dtype_code(t0), stream_ptr(t0)))
+        return self._result(work, H, W)
+
+    def __repr__(self):
+        return 'CBConcat2d (propChgIdxs=%s)' % self.propChangeIndexes
+
+
+_UPSAMPLERS = (nn.Upsample, nn.UpsamplingNearest2d, nn.UpsamplingBilinear2d)
+_PRODUCERS = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d)
+
+
+def insertCBUpsampling(rootModule, cloneOutput=True):
+    """Inside every nn.Sequential of rootModule, an nn.Upsample / nn.UpsamplingNearest2d / nn.UpsamplingBilinear2d within
+    the library's limits that directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual or another
+    CBUpsample2d becomes a CBUpsample2d fed by that producer's changes: propChangeIndexes is switched on at the producer
+    (a CBResidual's `.add`; a 2x2 CBPoolMax2d of the reference's kind also hands on the OUTPUT-resolution list,
+    downsampleIndexes).  A CBConv2d consuming the upsampled map then needs its own input copy (copyInput) unless it runs
+    in feedback mode, as behind a pool of insertCBPooling.  An upsampling beyond the limits stays the dense torch
+    operator.  Returns rootModule."""
+    for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
+        names = list(seq._modules.keys())
+        for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
+            prod, up = seq._modules[a], seq._modules[b]
+            if type(prod) not in _PRODUCERS or type(up) not in _UPSAMPLERS:
+                continue
+            try:
+                cb = CBUpsample2d(up)
+            except CBinferError:
+                continue      # (beyond the limits: stays dense)
+            (prod.add if type(prod) is CBResidual else prod).propChangeIndexes = True
+            if type(prod) is CBPoolMax2d and not prod.__dict__.get('_general'):
+                prod.downsampleIndexes = True      # (the list of the pool's input addresses another map)
+            cb.cloneOutput = cloneOutput
+            seq._modules[b] = cb
+            if pos + 2 < len(names):
+                consumer = seq._modules[names[pos + 2]]
+                if type(consumer) == CBConv2d and not consumer.feedbackLoop:
+                    consumer.copyInput = True
+    return rootModule

@@ -62,7 +62,9 @@ typedef void* cbStream_t; /* hipStream_t */
  * in window order carrying the pooled change detection of the layer behind the 2x2 pool).
  * 11 (unchanged): the general-geometry entry points (cbGeom, cbinfer_geom_*, cbinfer_*_geom) were ADDED under this
  * number -- new symbols break no caller, every earlier symbol keeps its signature and behaviour.  Likewise the
- * general pooling entry points (cbPool, cbinfer_pool_*, cbinfer_cbpool2d_forward). */
+ * general pooling entry points (cbPool, cbinfer_pool_*, cbinfer_cbpool2d_forward), the sum (cbinfer_add_changed,
+ * cbinfer_cbadd_forward) and the decoder operators (cbUpsample, cbinfer_upsample_supported,
+ * cbinfer_cbupsample_forward, cbinfer_cbconcat_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -874,6 +876,59 @@ int cbinfer_cbadd_forward(const void* a, const void* b, void* outputState, const
                           int capA, const int32_t* countA, const uint64_t* maskB, const int32_t* listB, int capB,
                           const int32_t* countB, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int relu,
                           int dtype, cbStream_t stream);
+
+/* ---- change-based upsampling and channel concatenation for decoders (cb_decoder.hip) -------------------
+ * No counterpart in the reference.  Both operators are exact for the reason the sum is: every producer leaves the pixels
+ * outside its change list bit for bit as they were, so the output can differ from last frame's only at the footprint of
+ * the operands' changes.  Tensors are contiguous, CB_F32 or CB_F16; masks are row-padded (cbinfer_mask_words); an
+ * int32 list holds flat indexes y W + x, entries outside the map are dropped; bits of the row padding are never set.
+ *
+ * Upsample.  input [C, Hi, Wi], the state `out` [C, Ho, Wo] with Ho = Hi sH, Wo = Wi sW; 1 <= sH, sW <= 8.
+ *   source coordinates per axis (n input, N = n s output pixels, o the output coordinate), ALL IN INTEGERS:
+ *     CB_UPSAMPLE_NEAREST: i0 = o / s.  The value is copied bit for bit; (oy, ox) is listed iff its source pixel is.
+ *     CB_UPSAMPLE_BILINEAR: alignCorners == 0: num = max(2 o + 1 - s, 0), den = 2 s;  alignCorners == 1:
+ *       num = o (n - 1), den = N - 1 (N == 1: num = 0, den = 1).  i0 = num / den, rho = num - i0 den,
+ *       i1 = min(i0 + 1, n - 1), lambda = (float)rho / (float)den -- one IEEE division of two integers (exactly
+ *       representable for extents below 2^24).  With a, b, c, d the values at (y0,x0), (y0,x1), (y1,x0), (y1,x1):
+ *         out = (1 - ly) ((1 - lx) a + lx b) + ly ((1 - lx) c + lx d)
+ *       evaluated in f32 (the compiler may contract to FMAs) and rounded to the dtype once.  (oy, ox) is listed iff any of
+ *       its four source pixels is -- a zero weight does not matter, the mask handed on is a function of the input's
+ *       mask alone.  torch derives the source coordinate from a float scale; its lambda drifts by about o 2^-24, so
+ *       bilinear is pinned against float64 math, not bit-compared with torch.
+ *   the input's changes: inputMask (over the INPUT map; one launch, the footprint gathered inside it), list (capN
+ *     entries at most, countDev the device-side length or NULL: capN is the length; one launch in front, which ORs the
+ *     footprint into `bits`; capN == 0 launches nothing in front), or neither: every output pixel is listed.
+ *   hand-on: maskCopy (cbinfer_mask_words(Ho, Wo) words) receives the frame's mask every frame; `bits`, the working
+ *     mask of the OUTPUT map (zero on first use), is zero again when the frame ends.  Unlisted pixels keep their bits.
+ * Bad arguments (a null tensor or mask, C / Hi / Wi < 1, an unknown dtype or mode, a scale outside 1..8, capN < 0, both
+ * a mask and a list, a count without a list, inputMask == bits or maskCopy, bits == maskCopy, Ho Wo or 64 C beyond an
+ * int32) return CB_ERR_BADARG and launch nothing. */
+#define CB_UPSAMPLE_NEAREST 0
+#define CB_UPSAMPLE_BILINEAR 1
+typedef struct cbUpsample {
+    int sH, sW, mode, alignCorners;
+} cbUpsample;
+/* host, pure: 1 if scales, mode and alignCorners (0 / 1) are within the limits above, else 0 */
+int cbinfer_upsample_supported(const cbUpsample* up);
+/* The whole frame of a change-based upsampling enqueued without a host sync. */
+int cbinfer_cbupsample_forward(const void* input, void* outputState, const uint64_t* inputMask, const int32_t* list,
+                               int capN, const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int Hi,
+                               int Wi, const cbUpsample* up, int dtype, cbStream_t stream);
+/* Concat.  n = 2..4 operands sources[k] of [channels[k], H, W], the state `out` [sum channels, H, W].  The arrays are
+ * HOST arrays of n entries; masks / lists / caps / counts may be NULL (no operand has one).  Per operand k: masks[k]:
+ * mask form; lists[k]: list form (caps[k] entries at most, counts[k] the device-side length or NULL); neither: every
+ * pixel is listed.  Operand k's channels are copied bit for bit at operand k's listed pixels ONLY -- an operand that
+ * did not change is not touched --; every other value of `out` keeps its bits.  maskCopy receives the UNION of the
+ * operands' masks every frame.  `bits` holds n working masks (n cbinfer_mask_words(H, W) words, operand k's at
+ * bits + k words; zero on first use, zero again when the frame ends).  With every operand in mask or all form the
+ * frame is ONE launch; an operand in list form costs one launch in front (cbinfer_pool_footprint with a 1x1 window).
+ * Bad arguments (a null tensor or array, n outside 2..4, channels / H / W < 1, an unknown dtype, a capacity < 0, both a
+ * mask and a list for one operand, a count without a list, an operand mask or maskCopy inside `bits`, an operand mask
+ * == maskCopy, H W or 64 sum channels beyond an int32) return CB_ERR_BADARG and launch nothing. */
+int cbinfer_cbconcat_forward(const void* const* sources, const int32_t* channels, int n, void* outputState,
+                             const uint64_t* const* masks, const int32_t* const* lists, const int32_t* caps,
+                             const int32_t* const* counts, uint64_t* bits, uint64_t* maskCopy, int H, int W, int dtype,
+                             cbStream_t stream);
 
 /* replaces conv2d_fg_cpu, cbconv2d_fg_backend.cu:81-112: HOST pointers, host code, race-free. */
 void cbinfer_conv2d_fg_cpu(const float* input, const float* prevInput, float* output,
