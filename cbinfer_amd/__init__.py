@@ -21,6 +21,7 @@ from .branches import BranchGroup
 from .program import FrameProgram
 from .residual import CBAdd2d, CBResidual, foldBatchNorm
 from .decoder import CBUpsample2d, CBConcat2d, insertCBUpsampling
+from .tconv import CBConvTranspose2d, insertCBTransposedConv
 
 __version__ = "0.1.0"
 
@@ -246,7 +247,7 @@ def linkConsumers(producer, consumers):
     return producer
 
 
-_STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d)
+_STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d)
 
 
 def _stateful(net):
@@ -363,7 +364,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

@@ -119,6 +119,16 @@ class Upsample(ctypes.Structure):
 
 _up, _i32p = ctypes.POINTER(Upsample), ctypes.POINTER(ctypes.c_int32)
 
+
+class TGeom(ctypes.Structure):
+    """cbTGeom of include/cbinfer_hip.h: filter size, stride, padding, dilation and output padding of a transposed
+    convolution."""
+    _fields_ = [("kH", _i), ("kW", _i), ("sH", _i), ("sW", _i), ("pH", _i), ("pW", _i), ("dH", _i), ("dW", _i),
+                ("opH", _i), ("opW", _i)]
+
+
+_tgp = ctypes.POINTER(TGeom)
+
 _SIGNATURES = {
     # name: (restype, [argtypes])
     "cbinfer_abi_version": (_i, []),
@@ -263,6 +273,14 @@ _SIGNATURES = {
     "cbinfer_upsample_supported": (_i, [_up]),
     "cbinfer_cbupsample_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _up, _i, _vp]),
     "cbinfer_cbconcat_forward": (_i, [_vpp, _i32p, _i, _vp, _vpp, _vpp, _i32p, _vpp, _vp, _vp, _i, _i, _i, _vp]),
+    "cbinfer_tconv_out_size": (_i, [_i, _i, _tgp, _ip, _ip]),
+    "cbinfer_tconv_prepared_weights_bytes": (_l, [_i, _i, _tgp, _i]),
+    "cbinfer_tconv_prep_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _tgp, _i, _vp]),
+    "cbinfer_tconv_workspace_bytes": (_l, []),
+    "cbinfer_change_detection_tconv": (_i, [_vp, _vp, _vp, _i, _i, _i, _tgp, _f, _i, _i, _vp]),
+    "cbinfer_conv_changed_tconv": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _tgp, _i, _vp, _i, _vp]),
+    "cbinfer_cbconvtranspose2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _tgp, _f, _i, _i, _i, _vp,
+                                               _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

@@ -21,6 +21,7 @@ from ._lib import C, CBinferError, check
 from .conv2d import CBConv2d
 from .residual import CBAdd2d
 from .decoder import CBConcat2d, CBUpsample2d
+from .tconv import CBConvTranspose2d
 
 
 def _kp(K):
@@ -46,6 +47,9 @@ class BranchGroup(nn.Module):
             if type(m) in (CBUpsample2d, CBConcat2d):
                 raise CBinferError("BranchGroup: layer %r is %r, a change-based decoder operator, which has no grouped "
                                    "launch" % (name, m))
+            if type(m) is CBConvTranspose2d:
+                raise CBinferError("BranchGroup: layer %r is %r, a change-based transposed convolution, which has no "
+                                   "grouped launch" % (name, m))
         self.__dict__['_pairs'] = {}
 
     def _pair_state(self, mods, geom):

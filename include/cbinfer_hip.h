@@ -64,7 +64,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * number -- new symbols break no caller, every earlier symbol keeps its signature and behaviour.  Likewise the
  * general pooling entry points (cbPool, cbinfer_pool_*, cbinfer_cbpool2d_forward), the sum (cbinfer_add_changed,
  * cbinfer_cbadd_forward) and the decoder operators (cbUpsample, cbinfer_upsample_supported,
- * cbinfer_cbupsample_forward, cbinfer_cbconcat_forward). */
+ * cbinfer_cbupsample_forward, cbinfer_cbconcat_forward) and the transposed convolution (cbTGeom, cbinfer_tconv_*,
+ * cbinfer_*_tconv, cbinfer_cbconvtranspose2d_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -929,6 +930,70 @@ int cbinfer_cbconcat_forward(const void* const* sources, const int32_t* channels
                              const uint64_t* const* masks, const int32_t* const* lists, const int32_t* caps,
                              const int32_t* const* counts, uint64_t* bits, uint64_t* maskCopy, int H, int W, int dtype,
                              cbStream_t stream);
+
+/* ---- transposed convolution (cb_tconv.hip) ------------------------------------------------------------
+ * The reference has no counterpart: its CBConv2d asserts transposed == False (conv2d.py:92-104).  Input map Hi x Wi,
+ * weight [C, K, kH, kW] (torch's layout for nn.ConvTranspose2d), stride (sH, sW), padding (pH, pW), dilation (dH, dW),
+ * output padding (opH, opW); output map Ho = (Hi - 1) sH - 2 pH + dH (kH - 1) + opH + 1, Wo likewise.
+ *   out[co, oy, ox] = bias[co] + sum over c and the taps (ky, kx) for which ny = oy + pH - ky dH is divisible by sH,
+ *     nx = ox + pW - kx dW by sW and (ny / sH, nx / sW) lies inside the input map, of in[c, ny/sH, nx/sW] w[c, co, ky, kx].
+ *   The PHASE of an output pixel is ((oy + pH) mod sH, (ox + pW) mod sW); tap ky belongs to row phase ry iff
+ *     (ry - ky dH) mod sH == 0, columns likewise.  A phase may own no tap (k < s; 1x1 stride 2; 3x3 s2 d2), and rows or
+ *     columns added by the output padding may be out of reach: such pixels are never listed and NO entry point below
+ *     writes them.  Their dense value is the bias (after the ReLU), 0 without one, in every frame: the caller
+ *     initialises prevOutput / output with it -- CBConvTranspose2d does when it allocates the state.
+ * Limits per axis: k <= 8, s <= 4, d <= 4, 0 <= p <= d (k-1), 0 <= op < max(s, d) (torch's own rule); groups 1, batch 1.
+ * Beyond them CB_ERR_UNSUPPORTED.  A null geometry, tensor or mask, a non-positive k / s / d, a negative p / op, C, K,
+ * Hi or Wi < 1, an input map so small that Ho or Wo < 1, an unknown dtype, Ho Wo, C Hi Wi or K Ho Wo beyond an int32, or a capacity < 0: CB_ERR_BADARG.  Nothing
+ * is launched in either case.  The geometry travels as one HOST struct. */
+typedef struct cbTGeom {
+    int kH, kW, sH, sW, pH, pW, dH, dW, opH, opW;
+} cbTGeom;
+/* host, pure: the output size (status as above; Ho / Wo untouched on failure).  No counterpart in the reference. */
+int cbinfer_tconv_out_size(int Hi, int Wi, const cbTGeom* geom, int* Ho, int* Wo);
+/* Prepared weights (no counterpart in the reference): per phase ph = ry sW + rx with at least one tap, in phase order,
+ * W_ph[Kpad64][CkkP_ph] in the tensors' element type (Ckk_ph = C taps(ph) padded to 32, k = c taps(ph) + tap, zero
+ * padded; CB_F32S shares CB_F32's layout) followed by that phase's k -> tap table for an Hi x Wi input map: byte
+ * offset relative to the pixel's base input pixel ((oy + pH) / sH, (ox + pW) / sW) and the signed dy, dx of the border
+ * test.  cbinfer_tconv_prepared_weights_bytes: the total, 0 for a rejected geometry. */
+long cbinfer_tconv_prepared_weights_bytes(int K, int C, const cbTGeom* geom, int dtype);
+int cbinfer_tconv_prep_weights(const void* weight, void* prepared, int K, int C, int Hi, int Wi, const cbTGeom* geom,
+                               int dtype, cbStream_t stream);
+/* split-k workspace of cbinfer_conv_changed_tconv (no counterpart in the reference): partial-tile slabs followed by
+ * the tiles' arrival counters -- the last 2048 bytes, ZERO on first use and left zero by every launch.  One per layer. */
+long cbinfer_tconv_workspace_bytes(void);
+/* Detection, one launch (no counterpart in the reference).  change(p) on the INPUT map exactly as
+ * cbinfer_change_detection (a1); updateInputState as there (1: feedback refresh at the changed pixels, 2: state <-
+ * input wherever they differ, 0: state untouched).  The EXACT footprint -- output (oy, ox) iff for some tap ny and nx
+ * divide and (ny / sH, nx / sW) is inside the input map and changed -- is ORed into the mask the parity selects of a
+ * frame mask buffer of the OUTPUT map (cbinfer_frame_mask_bytes(Ho, Wo) bytes, zero on first use).  A changed pixel
+ * that reaches no output pixel still refreshes the state. */
+int cbinfer_change_detection_tconv(const void* input, void* state, uint64_t* frameMasks, int C, int Hi, int Wi,
+                                   const cbTGeom* geom, float threshold, int updateInputState, int dtype,
+                                   cbStream_t stream);
+/* Contraction, one launch (no counterpart in the reference): per phase, gather -> MFMA -> bias / ReLU -> scatter at
+ * the listed OUTPUT pixels with at least one tap; nothing else of output [K, Ho, Wo] is written.  Tiles hold pixels of
+ * one phase and spend CkkP_ph / 32 stages.  bias may be NULL; dtype selects the arithmetic as in
+ * cbinfer_conv_changed_geom.  Either
+ *   frameMasks != NULL: the listed pixels are those of the frame mask cbinfer_change_detection_tconv filled; the
+ *     frame's mask is copied to cbinfer_frame_mask_copy_offset(Ho, Wo), the other mask is zeroed and the parity flipped
+ *     for the next frame (no list is written: cbinfer_compact_bits makes one from the copy); or
+ *   changeList (ascending flat output pixels) / numChanges (0 <= numChanges <= Ho Wo) / countDev (device-side length or
+ *     NULL): entries outside the map and entries of a phase without a tap are dropped; the kernel buckets the rest by
+ *     phase itself.
+ * A short list is split along k over idle workgroups (per phase, capped by the phase's stage count) and summed in
+ * slice order (deterministic) when a workspace is given. */
+int cbinfer_conv_changed_tconv(const void* input, const int32_t* changeList, int numChanges, const int32_t* countDev,
+                               uint64_t* frameMasks, const void* prepared, const void* bias, void* output, int C, int Hi,
+                               int Wi, int K, const cbTGeom* geom, int relu, void* workspace, int dtype,
+                               cbStream_t stream);
+/* The whole frame of a CBConvTranspose2d enqueued without a host sync: detection + contraction (no counterpart in the
+ * reference; feedbackLoop / copyInput contract of cbinfer_cbconv2d_forward; prevInput [C,Hi,Wi], prevOutput [K,Ho,Wo]).
+ * The frame's change mask on the OUTPUT map is left at cbinfer_frame_mask_copy_offset(Ho, Wo) of frameMasks. */
+int cbinfer_cbconvtranspose2d_forward(const void* input, void* prevInput, void* prevOutput, uint64_t* frameMasks,
+                                      const void* prepared, const void* bias, int C, int Hi, int Wi, int K,
+                                      const cbTGeom* geom, float threshold, int feedbackLoop, int copyInput, int relu,
+                                      void* workspace, int dtype, cbStream_t stream);
 
 /* replaces conv2d_fg_cpu, cbconv2d_fg_backend.cu:81-112: HOST pointers, host code, race-free. */
 void cbinfer_conv2d_fg_cpu(const float* input, const float* prevInput, float* output,

@@ -8,12 +8,13 @@ import sys
 
 import cbinfer_amd
 from cbinfer_amd import *            # noqa: F401,F403
-from cbinfer_amd import conv2d, conv2d_cg, conv2d_fg, decoder, residual
+from cbinfer_amd import conv2d, conv2d_cg, conv2d_fg, decoder, residual, tconv
 
 sys.modules[__name__ + '.conv2d'] = conv2d
 sys.modules[__name__ + '.conv2d_cg'] = conv2d_cg
 sys.modules[__name__ + '.conv2d_fg'] = conv2d_fg
 sys.modules[__name__ + '.residual'] = residual
 sys.modules[__name__ + '.decoder'] = decoder
+sys.modules[__name__ + '.tconv'] = tconv
 
 __all__ = cbinfer_amd.__all__
