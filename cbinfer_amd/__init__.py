@@ -22,6 +22,7 @@ from .program import FrameProgram
 from .residual import CBAdd2d, CBResidual, foldBatchNorm
 from .decoder import CBUpsample2d, CBConcat2d, insertCBUpsampling
 from .tconv import CBConvTranspose2d, insertCBTransposedConv
+from .dwconv import CBDepthwiseConv2d, linkDepthwise
 
 __version__ = "0.1.0"
 
@@ -48,19 +49,24 @@ def _rebuild(container, rule):
     return out
 
 
-def subsitute(node, threshold=1e-1, finegrained=False, generalGeometry=False):
+def subsitute(node, threshold=1e-1, finegrained=False, generalGeometry=False, depthwise=False):
     """(module, replaced?): exactly torch.nn.Conv2d -- not a subclass -- becomes a CBConv2d sharing its
     parameters (reference: __init__.py:10-17; the spelling of the name is the reference's).  generalGeometry=True
-    also takes strided, dilated, freely padded and bias-free convolutions (CBConv2d(..., generalGeometry=True))."""
+    also takes strided, dilated, freely padded and bias-free convolutions (CBConv2d(..., generalGeometry=True)).
+    depthwise=True: a depthwise convolution (groups == in_channels > 1) becomes a CBDepthwiseConv2d; with the default it
+    is refused as every grouped convolution is."""
     if type(node) is not nn.Conv2d:
         return node, False
+    if depthwise and node.groups == node.in_channels > 1:
+        _log('replacing depthwise conv2d')
+        return CBDepthwiseConv2d(node, threshold), True
     _log('replacing conv2d')
     cb = CBConv2d(node, threshold, generalGeometry=True) if generalGeometry else CBConv2d(node, threshold)
     cb.finegrained = finegrained
     return cb, True
 
 
-def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False, generalGeometry=False):
+def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False, generalGeometry=False, depthwise=False):
     """(converted nn.Sequential, anything changed?) for the children of `m` (reference: __init__.py:20-45):
     names preserved; nn.Dropout and the types of ignoreList dropped; nested nn.Sequential containers
     converted recursively -- as in the reference (:28) WITHOUT handing `finegrained` down; every other
@@ -72,12 +78,14 @@ def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False, generalGeo
 
     def rule(child, before, after):
         if type(child) is nn.Sequential:
-            child, hit = convertRecur(child, ignoreList, threshold, generalGeometry=generalGeometry)
+            child, hit = convertRecur(child, ignoreList, threshold, generalGeometry=generalGeometry,
+                                      depthwise=depthwise)
         elif type(child) in dropped:
             _log('removing node %s' % (type(child),))
             child, hit = None, True
         else:
-            child, hit = subsitute(child, threshold=threshold, finegrained=finegrained, generalGeometry=generalGeometry)
+            child, hit = subsitute(child, threshold=threshold, finegrained=finegrained, generalGeometry=generalGeometry,
+                                   depthwise=depthwise)
         outcomes.append(hit)
         return child
 
@@ -90,12 +98,19 @@ def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False, generalGeo
 
 def mergeReLURecur(m):
     """An nn.ReLU right behind a CBConv2d is absorbed into it (withReLU=True) and leaves the container,
-    nested nn.Sequential containers included (reference: __init__.py:47-66)."""
+    nested nn.Sequential containers included (reference: __init__.py:47-66).  A CBDepthwiseConv2d absorbs an nn.ReLU
+    and an nn.ReLU6 (reluCap = 6.0); an nn.ReLU6 behind a CBConv2d stays the dense module it is."""
     def rule(child, before, after):
         if type(child) is nn.Sequential:
             return mergeReLURecur(child)
         if type(child) is CBConv2d and type(after) is nn.ReLU:
             child.withReLU = True
+        if type(child) is CBDepthwiseConv2d and type(after) in (nn.ReLU, nn.ReLU6):
+            child.withReLU = True
+            child.reluCap = 6.0 if type(after) is nn.ReLU6 else None
+        if type(child) in (nn.ReLU, nn.ReLU6) and type(before) is CBDepthwiseConv2d:
+            _log('merging ReLU layer')
+            return None
         if type(child) is nn.ReLU and type(before) is CBConv2d:
             _log('merging ReLU layer')
             return None
@@ -247,7 +262,8 @@ def linkConsumers(producer, consumers):
     return producer
 
 
-_STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d)
+_STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d,
+             CBDepthwiseConv2d)
 
 
 def _stateful(net):
@@ -265,12 +281,14 @@ def getStateTensors(net):
     return [t for m in _stateful(net) for t in m.getStateTensors()]
 
 
-def convert(m, ignoreList=[], threshold=1e-1, generalGeometry=False):
+def convert(m, ignoreList=[], threshold=1e-1, generalGeometry=False, depthwise=False):
     """nn.Sequential in -> nn.Sequential out with every Conv2d replaced by a CBConv2d sharing its
     weights, ReLUs merged, Dropout removed (reference: __init__.py:91-94).  generalGeometry=True: strided, dilated,
     freely padded and bias-free convolutions are converted too (the default stops at them with an AssertionError, as
-    the reference does)."""
-    converted, _ = convertRecur(m, ignoreList=ignoreList, threshold=threshold, generalGeometry=generalGeometry)
+    the reference does).  depthwise=True: depthwise convolutions (groups == in_channels > 1) become CBDepthwiseConv2d
+    modules, an nn.ReLU or nn.ReLU6 behind one is absorbed; other grouped convolutions are refused as before."""
+    converted, _ = convertRecur(m, ignoreList=ignoreList, threshold=threshold, generalGeometry=generalGeometry,
+                                depthwise=depthwise)
     return mergeReLURecur(converted)
 
 
@@ -364,7 +382,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

@@ -110,6 +110,7 @@ class Pool(ctypes.Structure):
 _pp = ctypes.POINTER(Pool)
 
 UPSAMPLE_NEAREST, UPSAMPLE_BILINEAR = 0, 1      # CB_UPSAMPLE_*
+ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2      # CB_ACT_*
 
 
 class Upsample(ctypes.Structure):
@@ -281,6 +282,11 @@ _SIGNATURES = {
     "cbinfer_conv_changed_tconv": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _tgp, _i, _vp, _i, _vp]),
     "cbinfer_cbconvtranspose2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _tgp, _f, _i, _i, _i, _vp,
                                                _i, _vp]),
+    "cbinfer_dwconv_supported": (_i, [_i, _i, _gp]),
+    "cbinfer_dwconv_changed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _gp, _i, _i, _vp]),
+    "cbinfer_cbdwconv2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _gp, _f, _i, _i, _i, _i, _vp]),
+    "cbinfer_cbdwconv2d_forward_propagated": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
+                                                   _gp, _i, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

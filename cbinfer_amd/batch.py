@@ -27,6 +27,7 @@ from .conv2d import CBConv2d, CBPoolAvg2d, CBPoolMax2d, CBTail1x1, _switch
 from .residual import CBAdd2d
 from .decoder import CBConcat2d, CBUpsample2d
 from .tconv import CBConvTranspose2d
+from .dwconv import CBDepthwiseConv2d
 
 
 def _ptr_array(tensors):
@@ -56,6 +57,9 @@ class SequenceBatch(object):
             if type(m) is CBConvTranspose2d:
                 raise CBinferError("SequenceBatch: layer %r is %r, a change-based transposed convolution, which has no "
                                    "batched kernel: run decoder networks one sequence per stream" % (name, m))
+            if type(m) is CBDepthwiseConv2d:
+                raise CBinferError("SequenceBatch: layer %r is %r, a change-based depthwise convolution, which has no "
+                                   "batched kernel: run separable networks one sequence per stream" % (name, m))
         self.net = net
         self.layers = None          # built on the first frame (needs the frame size)
         self._key = None

@@ -22,6 +22,7 @@ from .conv2d import CBConv2d
 from .residual import CBAdd2d
 from .decoder import CBConcat2d, CBUpsample2d
 from .tconv import CBConvTranspose2d
+from .dwconv import CBDepthwiseConv2d
 
 
 def _kp(K):
@@ -49,6 +50,9 @@ class BranchGroup(nn.Module):
                                    "launch" % (name, m))
             if type(m) is CBConvTranspose2d:
                 raise CBinferError("BranchGroup: layer %r is %r, a change-based transposed convolution, which has no "
+                                   "grouped launch" % (name, m))
+            if type(m) is CBDepthwiseConv2d:
+                raise CBinferError("BranchGroup: layer %r is %r, a change-based depthwise convolution, which has no "
                                    "grouped launch" % (name, m))
         self.__dict__['_pairs'] = {}
 

@@ -172,6 +172,24 @@ def _pool_pair(v, what):
     raise _lib.CBinferError("change-based pooling: %s=%r is not supported, only an int or a pair of ints" % (what, v))
 
 
+def _padding_pair(m, who):
+    """The padding of the nn.Conv2d `m` as a pair of ints: ints as they are, 'valid', or a symmetric 'same'.
+    CBinferError in the name of `who` otherwise."""
+    Err = _lib.CBinferError
+    k, d = tuple(m.kernel_size), tuple(m.dilation)
+    if isinstance(m.padding, str):
+        if m.padding == 'valid':
+            return (0, 0)
+        if m.padding == 'same':
+            total = tuple(d[i] * (k[i] - 1) for i in (0, 1))
+            if total[0] % 2 or total[1] % 2:
+                raise Err("%s: padding='same' with kernel_size=%s, dilation=%s pads one side more than the "
+                          "other (torch pads %s in total); only symmetric padding is supported" % (who, k, d, total))
+            return (total[0] // 2, total[1] // 2)
+        raise Err("%s: unknown padding %r" % (who, m.padding,))
+    return tuple(int(v) for v in m.padding)
+
+
 def _check_general_pool(m, kind):
     """(kernel_size, stride, padding, cbPool operation) if the general change-based pool takes `m`, an nn.MaxPool2d
     (kind 'max') or nn.AvgPool2d ('avg'): per axis window <= 8, stride <= 8, padding <= window / 2, dilation 1, no
@@ -521,19 +539,7 @@ class CBConv2d(nn.Module):
         if m.padding_mode != 'zeros':
             raise Err("CBConv2d: padding_mode=%r is not supported, only 'zeros'" % (m.padding_mode,))
         k, d = tuple(m.kernel_size), tuple(m.dilation)
-        if isinstance(m.padding, str):
-            if m.padding == 'valid':
-                padding = (0, 0)
-            elif m.padding == 'same':
-                total = tuple(d[i] * (k[i] - 1) for i in (0, 1))
-                if total[0] % 2 or total[1] % 2:
-                    raise Err("CBConv2d: padding='same' with kernel_size=%s, dilation=%s pads one side more than the "
-                              "other (torch pads %s in total); only symmetric padding is supported" % (k, d, total))
-                padding = (total[0] // 2, total[1] // 2)
-            else:
-                raise Err("CBConv2d: unknown padding %r" % (m.padding,))
-        else:
-            padding = tuple(int(v) for v in m.padding)
+        padding = _padding_pair(m, 'CBConv2d')
         g = _lib.Geom(k[0], k[1], m.stride[0], m.stride[1], padding[0], padding[1], d[0], d[1])
         if C.cbinfer_geom_prepared_weights_bytes(m.out_channels, m.in_channels, ctypes.byref(g), _lib.CB_F32) <= 0:
             raise Err("CBConv2d: kernel_size=%s stride=%s padding=%s dilation=%s is beyond what the library takes "

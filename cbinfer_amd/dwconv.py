@@ -1,0 +1,301 @@
+"""Change-based depthwise convolution: CBDepthwiseConv2d and linkDepthwise (cb_dwconv.hip).
+
+The reference has no such operator.  A depthwise nn.Conv2d (groups == in_channels, with a channel multiplier) -- the 3x3
+layer of MobileNet / EfficientNet-type blocks, the separable convolutions of Xception / DeepLabv3+, the 7x7 stage of
+ConvNeXt-type blocks -- ends a change-based chain: CBConv2d refuses groups, torch recomputes the whole map, drops the
+producer's change mask and cannot be recorded by a FrameProgram.  The module either runs the layer's own change
+detection on its input (component a1's rule with `threshold`) or, behind a producer that hands on its changes
+(propagatedChanges), takes the footprint of the producer's list or mask; it recomputes exactly the listed output pixels
+and leaves every other output pixel bit for bit as it was.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
+from . import decoder, tconv
+from .conv2d import CBConv2d, CBPoolMax2d, _padding_pair, _same_shape
+from .conv2d_cg import ChangeIndexes, MaskChangeIndexes
+from .residual import CBResidual
+from .tconv import CBConvTranspose2d
+
+MAX_K, MAX_S, MAX_D, MAX_P = 7, 4, 8, 64
+
+
+def _check_depthwise(m):
+    """(kernel_size, stride, padding, dilation) as pairs of ints if the library takes the module `m`; CBinferError with
+    a sentence naming the setting otherwise."""
+    Err = CBinferError
+    if not isinstance(m, nn.Conv2d) or m.transposed or tuple(m.output_padding) != (0, 0):
+        raise Err("CBDepthwiseConv2d: only plain nn.Conv2d modules are converted, got %s" % type(m).__name__)
+    if m.groups != m.in_channels:
+        raise Err("CBDepthwiseConv2d: groups=%d with in_channels=%d is not a depthwise convolution (groups == "
+                  "in_channels); general grouped convolutions are not supported" % (m.groups, m.in_channels))
+    if m.out_channels % m.in_channels:
+        raise Err("CBDepthwiseConv2d: out_channels=%d is not a multiple of in_channels=%d"
+                  % (m.out_channels, m.in_channels))
+    if m.padding_mode != 'zeros':
+        raise Err("CBDepthwiseConv2d: padding_mode=%r is not supported, only 'zeros'" % (m.padding_mode,))
+    p = _padding_pair(m, 'CBDepthwiseConv2d')
+    k, s, d = (tuple(int(v) for v in t) for t in (m.kernel_size, m.stride, m.dilation))
+    for i in (0, 1):
+        if k[i] > MAX_K:
+            raise Err("CBDepthwiseConv2d: kernel_size=%s is beyond what the library takes (<= %d per axis)" % (k, MAX_K))
+        if s[i] > MAX_S:
+            raise Err("CBDepthwiseConv2d: stride=%s is beyond what the library takes (<= %d per axis)" % (s, MAX_S))
+        if d[i] > MAX_D:
+            raise Err("CBDepthwiseConv2d: dilation=%s is beyond what the library takes (<= %d per axis)" % (d, MAX_D))
+        if p[i] > MAX_P:
+            raise Err("CBDepthwiseConv2d: padding=%s is beyond what the library takes (<= %d per axis)" % (p, MAX_P))
+    g = _lib.Geom(k[0], k[1], s[0], s[1], p[0], p[1], d[0], d[1])
+    if not C.cbinfer_dwconv_supported(m.in_channels, m.out_channels // m.in_channels, ctypes.byref(g)):
+        raise Err("CBDepthwiseConv2d: kernel_size=%s stride=%s padding=%s dilation=%s is beyond what the library takes"
+                  % (k, s, p, d))
+    return k, s, p, d
+
+
+def _propagated_ok(k, p, d):
+    """The footprint of a producer's changes is the filter's window: dilation 1 and padding <= kernel_size / 2."""
+    return all(d[i] == 1 and 2 * p[i] <= k[i] for i in (0, 1))
+
+
+class CBDepthwiseConv2d(nn.Module):
+    """Change-based depthwise nn.Conv2d (no counterpart in the reference): groups == in_channels, out_channels a
+    multiple of it; per axis kernel_size <= 7, stride <= 4, dilation <= 8, padding <= 64 (ints, 'valid' or a symmetric
+    'same'); with or without bias, batch 1, fp32 or fp16.  The parameters are shared with the source module.
+
+    forward(x): a [1, C, Hi, Wi] tensor or the ('changeIndexes', tensor, indexes) tuple of a producer.  Flags:
+    threshold, feedbackLoop, copyInput as on CBConv2d; withReLU, and reluCap (None, or 6.0 for ReLU6); propChangeIndexes
+    hands on the frame's change mask on the OUTPUT map as a MaskChangeIndexes; cloneOutput=False hands out prevOutput
+    itself, tagged, and the frame is then free of torch operators.  propagatedChanges=False: the indexes of a tuple are
+    ignored, the layer detects for itself.  propagatedChanges=True (dilation 1, padding <= kernel_size / 2): the output
+    pixels whose filter window holds a pixel of the producer's list or mask are recomputed from the input tensor itself;
+    no detection runs, prevInput is not kept, `threshold` is not used, and the frame on which prevOutput was
+    (re)allocated -- or a bare tensor, which carries no change information -- lists every pixel.  Output pixels no tap
+    reaches (padding > dilation (kernel_size - 1)) hold act(bias) from the moment the state is allocated and are never
+    written."""
+
+    def __init__(self, m, threshold):
+        super(CBDepthwiseConv2d, self).__init__()
+        self.kernel_size, self.stride, self.padding, self.dilation = _check_depthwise(m)
+        self.groups = m.groups
+        self.transposed = False
+        self.in_channels = m.in_channels
+        self.out_channels = m.out_channels
+        self.weight = m.weight      # shared with the source module
+        self.bias = m.bias
+        self.threshold = threshold
+        self.withReLU = False
+        self.reluCap = None
+        self.propChangeIndexes = False
+        self.propagatedChanges = False
+        self.copyInput = True
+        self.feedbackLoop = False
+        self.cloneOutput = True
+        self.clearMemory()
+
+    # ---------------------------------------------------------------- state
+    def clearMemory(self):
+        for name in ('prevInput', 'prevOutput'):
+            if name not in self._buffers:
+                self.register_buffer(name, self.weight.detach().new_zeros(0))
+        self.prevInput = self.weight.detach().new_zeros(0)
+        self.prevOutput = self.weight.detach().new_zeros(0)
+        for name in ('_work', '_geomC'):      # (transient: device work buffers, ctypes arguments)
+            self.__dict__[name] = None
+
+    def getStateTensors(self):
+        return [self.prevInput, self.prevOutput]
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d.update(_work=None, _geomC=None)
+        return d
+
+    def _struct(self):
+        """(pointer to) the layer's cbGeom; transient, made again after unpickling."""
+        if self.__dict__.get('_geomC') is None:
+            k, s, p, d = self.kernel_size, self.stride, self.padding, self.dilation
+            self.__dict__['_geomC'] = ctypes.pointer(_lib.Geom(k[0], k[1], s[0], s[1], p[0], p[1], d[0], d[1]))
+        return self.__dict__['_geomC']
+
+    def _out_hw(self, Hi, Wi):
+        Ho, Wo = ctypes.c_int(), ctypes.c_int()
+        if C.cbinfer_geom_out_size(Hi, Wi, self._struct(), ctypes.byref(Ho), ctypes.byref(Wo)) != 0:
+            raise CBinferError("CBDepthwiseConv2d: a %dx%d map is smaller than the filter's reach (kernel_size=%s, "
+                               "dilation=%s, padding=%s)" % (Hi, Wi, self.kernel_size, self.dilation, self.padding))
+        return Ho.value, Wo.value
+
+    def _act(self):
+        if not self.withReLU:
+            return _lib.ACT_NONE
+        if self.reluCap is None:
+            return _lib.ACT_RELU
+        if float(self.reluCap) != 6.0:
+            raise CBinferError("CBDepthwiseConv2d: reluCap=%r is not supported, only None or 6.0" % (self.reluCap,))
+        return _lib.ACT_RELU6
+
+    def _bias_map(self, size, like):
+        """The dense value of an output pixel no tap reaches, broadcast over the map: the bias (0 without one), after
+        the activation.  The first frame overwrites every reachable pixel."""
+        fill = torch.zeros(size, dtype=like.dtype, device=like.device)
+        if self.bias is not None:
+            b = self.bias.detach().to(device=like.device, dtype=like.dtype)
+            act = self._act()
+            if act != _lib.ACT_NONE:
+                b = torch.relu(b) if act == _lib.ACT_RELU else torch.clamp(b, 0.0, 6.0)
+            fill += b.view(1, -1, 1, 1)
+        return fill
+
+    def _state_for(self, input, Ho, Wo, keepInput):
+        """(Re)allocate the state on a new resolution, dtype or device: prevInput +inf -- the first frame of a sequence
+        is dense through the same kernel, every input pixel changed.  True if prevOutput was (re)allocated."""
+        if not keepInput:
+            if self.prevInput.numel():
+                self.prevInput = input.new_zeros(0)
+        elif (not _same_shape(self.prevInput, input.size()) or self.prevInput.dtype != input.dtype or
+                self.prevInput.device != input.device):
+            self.prevInput = torch.full(input.size(), float('inf'), dtype=input.dtype, device=input.device)
+        size = (1, self.out_channels, Ho, Wo)
+        if (not _same_shape(self.prevOutput, size) or self.prevOutput.dtype != input.dtype or
+                self.prevOutput.device != input.device):
+            self.prevOutput = self._bias_map(size, input)
+            return True
+        return False
+
+    def _workspace(self, Hi, Wi, dev):
+        """Frame masks (zero once) and their mask-copy view for the layer's own detection, working mask and mask copy
+        for propagated changes, index buffer and count for a consumer that wants the list: once per map size."""
+        key = (Hi, Wi, dev)
+        work = self.__dict__.get('_work')
+        if work is None or work['key'] != key:
+            Ho, Wo = self._out_hw(Hi, Wi)
+            words = C.cbinfer_mask_words(Ho, Wo)
+            frame = torch.zeros(C.cbinfer_frame_mask_bytes(Ho, Wo) // 8, dtype=torch.int64, device=dev)
+            off = C.cbinfer_frame_mask_copy_offset(Ho, Wo) // 8
+            work = self.__dict__['_work'] = dict(
+                key=key, size=(Ho, Wo), frame=frame, frameCopy=frame[off:off + words],
+                bits=torch.zeros(words, dtype=torch.int64, device=dev),
+                copy=torch.zeros(words, dtype=torch.int64, device=dev),
+                idx=torch.empty(Ho * Wo, dtype=torch.int32, device=dev),
+                count=torch.zeros(1, dtype=torch.int32, device=dev))
+        return work
+
+    # ---------------------------------------------------------------- frame
+    def _producer_changes(self, indexes, Hi, Wi, x, work):
+        """(list, capacity, device count, mask) of a producer's changes for cbinfer_cbdwconv2d_forward_propagated."""
+        Err = CBinferError
+        if isinstance(indexes, ChangeIndexes):
+            if indexes.size not in (None, (Hi, Wi)):
+                raise Err("CBDepthwiseConv2d: the propagated change indexes address a %dx%d map, this layer's input map "
+                          "is %dx%d" % (tuple(indexes.size) + (Hi, Wi)))
+            if (isinstance(indexes, MaskChangeIndexes) and not indexes._made and indexes._mask is not None and
+                    indexes.size == (Hi, Wi)):
+                return None, 0, None, indexes._mask      # (the producer's list is never made)
+            idx, count = indexes.buffer, indexes.count
+        elif isinstance(indexes, torch.Tensor):
+            idx, count = indexes.detach().contiguous(), None
+        else:
+            raise Err("CBDepthwiseConv2d: change indexes must be an int32 tensor or a ChangeIndexes")
+        if idx.dim() != 1 or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.device != x.device:
+            raise Err("CBDepthwiseConv2d: propagated change indexes must be a contiguous int32 tensor on the input's "
+                      "device")
+        cap = idx.numel()
+        if cap == 0:
+            idx = work['idx']      # (an empty tensor has no address: any buffer stands for the empty list)
+        return idx, cap, count, None
+
+    def forward(self, inp):
+        indexes = None
+        if type(inp) == tuple:
+            if len(inp) != 3 or inp[0] != 'changeIndexes':
+                raise CBinferError("CBDepthwiseConv2d: the input is a tuple, but not ('changeIndexes', tensor, indexes)")
+            inp, indexes = inp[1], inp[2]
+        if not torch.is_tensor(inp):
+            raise CBinferError("CBDepthwiseConv2d: the input must be a tensor or the ('changeIndexes', tensor, indexes) "
+                               "tuple, got %s" % type(inp).__name__)
+        live = bool(getattr(inp, '_cbinfer_inplace_state', False))
+        x = inp.detach().contiguous()
+        if x.dim() != 4 or x.size(0) != 1 or x.size(1) != self.in_channels:
+            raise CBinferError("CBDepthwiseConv2d: the input must be a [1, %d, H, W] tensor, got %s"
+                               % (self.in_channels, tuple(x.shape)))
+        require_device(x)
+        if x.dtype != self.weight.dtype or x.device != self.weight.device:
+            raise CBinferError("CBDepthwiseConv2d: input (%s on %s) and weights (%s on %s) differ in dtype or device"
+                               % (x.dtype, x.device, self.weight.dtype, self.weight.device))
+        Cin, mult, Hi, Wi = self.in_channels, self.out_channels // self.in_channels, x.size(2), x.size(3)
+        act, dt = self._act(), dtype_code(x)
+        work = self._workspace(Hi, Wi, x.device)
+        Ho, Wo = work['size']
+        weight = self.weight.detach().contiguous()
+        bias = self.bias.detach() if self.bias is not None else None
+        if self.propagatedChanges:
+            if not _propagated_ok(self.kernel_size, self.padding, self.dilation):
+                raise CBinferError("CBDepthwiseConv2d: propagatedChanges needs dilation 1 and padding <= kernel_size / 2 "
+                                   "per axis (kernel_size=%s padding=%s dilation=%s): the layer must detect for itself"
+                                   % (self.kernel_size, self.padding, self.dilation))
+            fresh = self._state_for(x, Ho, Wo, keepInput=False)
+            idx, cap, count, mask = None, 0, None, None
+            every = fresh or indexes is None
+            if indexes is not None:      # (checked on every frame, read on all but the first)
+                idx, cap, count, mask = self._producer_changes(indexes, Hi, Wi, x, work)
+            if every:
+                idx, cap, count, mask = None, 0, None, None
+            check(C.cbinfer_cbdwconv2d_forward_propagated(
+                ptr(x), ptr(self.prevOutput), ptr(idx), cap, ptr(count), ptr(mask), int(every), ptr(work['bits']),
+                ptr(work['copy']), ptr(weight), ptr(bias), Cin, mult, Hi, Wi, self._struct(), act, dt, stream_ptr(x)))
+            copy = work['copy']
+        else:
+            self._state_for(x, Ho, Wo, keepInput=True)
+            if not self.prevInput.is_contiguous():
+                self.prevInput = self.prevInput.contiguous()
+            check(C.cbinfer_cbdwconv2d_forward(
+                ptr(x), ptr(self.prevInput), ptr(self.prevOutput), ptr(work['frame']), ptr(weight), ptr(bias), Cin, mult,
+                Hi, Wi, self._struct(), float(self.threshold), int(bool(self.feedbackLoop)), int(bool(self.copyInput)),
+                act, dt, stream_ptr(x)))
+            if not self.feedbackLoop and not self.copyInput:
+                self.prevInput = x.clone() if live else x
+            copy = work['frameCopy']
+        if self.cloneOutput:
+            output = self.prevOutput.clone()
+        else:
+            output = self.prevOutput
+            output._cbinfer_inplace_state = True
+        if self.propChangeIndexes:
+            return 'changeIndexes', output, MaskChangeIndexes(copy, (Ho, Wo), work['idx'], work['count'])
+        return output
+
+    def __repr__(self):
+        return ('CBDepthwiseConv2d (%d, %d, k=%s, s=%s, p=%s, d=%s, th=%s, withReLU=%s, reluCap=%s, propChgIdxs=%s, '
+                'propagated=%s)' % (self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding,
+                                    self.dilation, self.threshold, self.withReLU, self.reluCap, self.propChangeIndexes,
+                                    self.propagatedChanges))
+
+
+_DW_PRODUCERS = tconv._TCONV_PRODUCERS + (CBDepthwiseConv2d,)
+# the layer hands on its changes like every producer: insertCBUpsampling and insertCBTransposedConv take it as one
+decoder._PRODUCERS = decoder._PRODUCERS + (CBDepthwiseConv2d,)
+tconv._TCONV_PRODUCERS = tconv._TCONV_PRODUCERS + (CBDepthwiseConv2d,)
+
+
+def linkDepthwise(rootModule):
+    """Inside every nn.Sequential of rootModule: a CBDepthwiseConv2d with dilation 1 and padding <= kernel_size / 2 that
+    directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBConvTranspose2d or another
+    CBDepthwiseConv2d takes that producer's changes (propagatedChanges on the layer, propChangeIndexes on the producer)
+    and runs no detection; a CBDepthwiseConv2d directly in front of a 1x1 / stride-1 / padding-0 CBConv2d hands its
+    changes on (propChangeIndexes).  Returns rootModule."""
+    for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
+        kids = list(seq.children())
+        for prod, cons in zip(kids[:-1], kids[1:]):
+            if (type(cons) is CBDepthwiseConv2d and type(prod) in _DW_PRODUCERS and
+                    _propagated_ok(cons.kernel_size, cons.padding, cons.dilation)):
+                cons.propagatedChanges = True
+                (prod.add if type(prod) is CBResidual else prod).propChangeIndexes = True
+                if type(prod) is CBPoolMax2d and not prod.__dict__.get('_general'):
+                    prod.downsampleIndexes = True      # (the list of the pool's input addresses another map)
+            if (type(prod) is CBDepthwiseConv2d and type(cons) is CBConv2d and tuple(cons.kernel_size) == (1, 1) and
+                    tuple(cons.stride) == (1, 1) and tuple(cons.padding) == (0, 0)):
+                prod.propChangeIndexes = True
+    return rootModule

@@ -995,6 +995,56 @@ int cbinfer_cbconvtranspose2d_forward(const void* input, void* prevInput, void* 
                                       const cbTGeom* geom, float threshold, int feedbackLoop, int copyInput, int relu,
                                       void* workspace, int dtype, cbStream_t stream);
 
+/* ---- depthwise convolution (cb_dwconv.hip) ------------------------------------------------------------
+ * The reference has no counterpart: its CBConv2d asserts groups == 1 (conv2d.py:92-104).  groups == in_channels with a
+ * channel multiplier: input [C, Hi, Wi], weight [K, 1, kH, kW] (torch's layout, read as it is: no preparation, no
+ * workspace), K = C mult, mult >= 1, a cbGeom within the general-geometry limits, output [K, Ho, Wo] by
+ * cbinfer_geom_out_size.  At a listed output pixel, for every k:
+ *   out[k, oy, ox] = act(bias[k] + sum over the taps (ky, kx) inside the input map of
+ *                        w[k, 0, ky, kx] in[k / mult, oy sH - pH + ky dH, ox sW - pW + kx dW])
+ *   evaluated in f32 in ONE fixed order: start from the bias (0 without one), taps row-major (ky outer, kx inner), one FMA
+ *   per tap, out-of-map taps skipped, rounded to f16 once for CB_F16.  A pixel's bits depend neither on which other
+ *   pixels are listed nor on the launch form.  act: CB_ACT_NONE; CB_ACT_RELU: v > 0 ? v : 0; CB_ACT_RELU6: additionally
+ *   v < 6 ? v : 6; a NaN stays a NaN.  Every unlisted output value keeps its bits.  Output pixels no tap reaches (see the
+ *   general geometry above) are NEVER written, listed or not: the caller initialises them to act(bias).
+ * dtype CB_F32 or CB_F16 (no CB_F32S: f32 FMAs on exact operands need no bf16 triples).  All arguments are checked
+ * before the first launch: a null geometry, tensor or mask, C, mult, Hi or Wi < 1, an unknown dtype or act, 64 C mult
+ * beyond an int32: CB_ERR_BADARG; a geometry beyond the limits, K Ho Wo beyond an int32 or C Hi Wi 4 >= 2^30:
+ * CB_ERR_UNSUPPORTED.  Nothing is launched in either case. */
+#define CB_ACT_NONE 0
+#define CB_ACT_RELU 1
+#define CB_ACT_RELU6 2
+/* host, pure: 1 if C, mult and the geometry are within the limits above, else 0.  No counterpart in the reference. */
+int cbinfer_dwconv_supported(int C, int mult, const cbGeom* geom);
+/* The stencil at the listed pixels (no counterpart in the reference).  Exactly ONE form is given, else CB_ERR_BADARG:
+ *   frameMasks: the frame mask buffer of the OUTPUT map as cbinfer_change_detection_geom fills it; the protocol of
+ *     cbinfer_conv_changed_tconv -- the frame's mask is copied to cbinfer_frame_mask_copy_offset(Ho, Wo), the other
+ *     mask is zeroed, the last workgroup to arrive flips the parity; no list is written; one launch; or
+ *   bits / maskCopy: the contract of cbinfer_pool_changed -- every word of `bits` is copied to maskCopy and zeroed;
+ *     bits != maskCopy; a small launch in front moves the mask, the stencil launch reads maskCopy only. */
+int cbinfer_dwconv_changed(const void* input, const void* weight, const void* bias, void* output, uint64_t* frameMasks,
+                           uint64_t* bits, uint64_t* maskCopy, int C, int mult, int Hi, int Wi, const cbGeom* geom,
+                           int act, int dtype, cbStream_t stream);
+/* The whole frame with the layer's own detection, enqueued without a host sync (no counterpart in the reference):
+ * cbinfer_change_detection_geom (unchanged, called as it is) + cbinfer_dwconv_changed.  feedbackLoop / copyInput contract
+ * and the updateInputState mapping exactly as cbinfer_cbconv2d_forward_geom; prevInput [C,Hi,Wi], prevOutput [K,Ho,Wo].
+ * The frame's change mask on the OUTPUT map is left at cbinfer_frame_mask_copy_offset(Ho, Wo) of frameMasks. */
+int cbinfer_cbdwconv2d_forward(const void* input, void* prevInput, void* prevOutput, uint64_t* frameMasks,
+                               const void* weight, const void* bias, int C, int mult, int Hi, int Wi, const cbGeom* geom,
+                               float threshold, int feedbackLoop, int copyInput, int act, int dtype, cbStream_t stream);
+/* The whole frame from propagated changes (no counterpart in the reference): cbinfer_pool_footprint (the producer's
+ * list -- changeIndexes / capN / countDev -- or its mask of the INPUT map, inputMask; window = the filter) +
+ * cbinfer_dwconv_changed in the bits / maskCopy form on the INPUT tensor itself: no detection runs and no state of the
+ * input is kept.  Only where the pool footprint is the filter's: dilation 1 and p <= k / 2 per axis (and the pool
+ * limits); CB_ERR_UNSUPPORTED otherwise.  allPixels != 0: every pixel is listed (the frame after the output state was
+ * allocated) and the producer's changes are not read.  `bits`: the working mask of the OUTPUT map (zero on first use,
+ * zero again when the frame ends); maskCopy receives the frame's mask every frame. */
+int cbinfer_cbdwconv2d_forward_propagated(const void* input, void* outputState, const int32_t* changeIndexes, int capN,
+                                          const int32_t* countDev, const uint64_t* inputMask, int allPixels,
+                                          uint64_t* bits, uint64_t* maskCopy, const void* weight, const void* bias, int C,
+                                          int mult, int Hi, int Wi, const cbGeom* geom, int act, int dtype,
+                                          cbStream_t stream);
+
 /* replaces conv2d_fg_cpu, cbconv2d_fg_backend.cu:81-112: HOST pointers, host code, race-free. */
 void cbinfer_conv2d_fg_cpu(const float* input, const float* prevInput, float* output,
                            const float* weight, float threshold, int no, int ni, int h, int w,
