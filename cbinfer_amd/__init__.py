@@ -23,6 +23,7 @@ from .residual import CBAdd2d, CBResidual, foldBatchNorm
 from .decoder import CBUpsample2d, CBConcat2d, insertCBUpsampling
 from .tconv import CBConvTranspose2d, insertCBTransposedConv
 from .dwconv import CBDepthwiseConv2d, linkDepthwise
+from .pointwise import CBPointwise2d, insertCBPointwise
 
 __version__ = "0.1.0"
 
@@ -149,7 +150,8 @@ def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
     conv), so only the windows holding a changed pixel are pooled again.  A CBConv2d consuming the pool
     then needs its own input copy (copyInput) unless it runs in feedback mode.  generalGeometry=True: every
     nn.MaxPool2d and nn.AvgPool2d within the library's limits (CBPoolMax2d(m, generalGeometry=True), CBPoolAvg2d) is
-    converted; a pool beyond them stays the dense torch operator.  Returns rootModule."""
+    converted, also directly behind a CBPointwise2d (the general pools take its mask); a pool beyond them stays the dense
+    torch operator.  Returns rootModule."""
     def _pair(v):
         return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
@@ -173,7 +175,8 @@ def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
         names = list(seq._modules.keys())
         for a, b in zip(names[:-1], names[1:]):
             conv, pool = seq._modules[a], seq._modules[b]
-            cb = _converted(pool) if type(conv) == CBConv2d else None
+            cb = _converted(pool) if (type(conv) == CBConv2d or
+                                      (generalGeometry and type(conv) is CBPointwise2d)) else None
             if cb is not None:
                 _log('change-based pooling after %s' % a)
                 conv.propChangeIndexes = True
@@ -263,7 +266,7 @@ def linkConsumers(producer, consumers):
 
 
 _STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d,
-             CBDepthwiseConv2d)
+             CBDepthwiseConv2d, CBPointwise2d)
 
 
 def _stateful(net):
@@ -382,7 +385,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

@@ -111,6 +111,9 @@ _pp = ctypes.POINTER(Pool)
 
 UPSAMPLE_NEAREST, UPSAMPLE_BILINEAR = 0, 1      # CB_UPSAMPLE_*
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2      # CB_ACT_*
+# CB_PW_*
+(PW_IDENTITY, PW_RELU, PW_HARDTANH, PW_LEAKY, PW_PRELU, PW_HARDSWISH, PW_HARDSIGMOID, PW_SIGMOID, PW_SILU,
+ PW_TANH) = range(10)
 
 
 class Upsample(ctypes.Structure):
@@ -287,6 +290,10 @@ _SIGNATURES = {
     "cbinfer_cbdwconv2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _gp, _f, _i, _i, _i, _i, _vp]),
     "cbinfer_cbdwconv2d_forward_propagated": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
                                                    _gp, _i, _i, _vp]),
+    "cbinfer_pointwise_supported": (_i, [_i, _f, _f]),
+    "cbinfer_pointwise_changed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i, _vp]),
+    "cbinfer_cbpointwise_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i,
+                                         _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

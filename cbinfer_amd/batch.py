@@ -28,6 +28,7 @@ from .residual import CBAdd2d
 from .decoder import CBConcat2d, CBUpsample2d
 from .tconv import CBConvTranspose2d
 from .dwconv import CBDepthwiseConv2d
+from .pointwise import CBPointwise2d
 
 
 def _ptr_array(tensors):
@@ -60,6 +61,9 @@ class SequenceBatch(object):
             if type(m) is CBDepthwiseConv2d:
                 raise CBinferError("SequenceBatch: layer %r is %r, a change-based depthwise convolution, which has no "
                                    "batched kernel: run separable networks one sequence per stream" % (name, m))
+            if type(m) is CBPointwise2d:
+                raise CBinferError("SequenceBatch: layer %r is %r, a change-based element-wise function, which has no "
+                                   "batched kernel: run such networks one sequence per stream" % (name, m))
         self.net = net
         self.layers = None          # built on the first frame (needs the frame size)
         self._key = None

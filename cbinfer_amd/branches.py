@@ -23,6 +23,7 @@ from .residual import CBAdd2d
 from .decoder import CBConcat2d, CBUpsample2d
 from .tconv import CBConvTranspose2d
 from .dwconv import CBDepthwiseConv2d
+from .pointwise import CBPointwise2d
 
 
 def _kp(K):
@@ -53,6 +54,9 @@ class BranchGroup(nn.Module):
                                    "grouped launch" % (name, m))
             if type(m) is CBDepthwiseConv2d:
                 raise CBinferError("BranchGroup: layer %r is %r, a change-based depthwise convolution, which has no "
+                                   "grouped launch" % (name, m))
+            if type(m) is CBPointwise2d:
+                raise CBinferError("BranchGroup: layer %r is %r, a change-based element-wise function, which has no "
                                    "grouped launch" % (name, m))
         self.__dict__['_pairs'] = {}
 

@@ -1,0 +1,167 @@
+// Change-based element-wise function of one map, out = act(x scale[c] + shift[c]), on gfx950.  The
+// reference has no such operator; contracts of the entry points in include/cbinfer_hip.h.  Every producer of this library
+// leaves the pixels outside its change list bit for bit as they were, so f(x) can differ from last frame's only at the
+// operand's changed pixels: recomputing there gives the dense result exactly, without a threshold.  A frame is
+//   for an operand in LIST form, one launch in front: the list's bits ORed into the zeroed working mask
+//              (cbinfer_pool_footprint of cb_pool2d.hip with a 1x1 / stride-1 window: one 64-bit atomicOr per entry);
+//   one launch, mask-driven in cba_add_kernel's form: workgroups of four waves stride over the mask words, OR the
+//              operand's change mask (or the full row word of an operand without change information) into the working
+//              word themselves, and spread the (set bit, channel) items of a non-empty word over the 256 threads, set bit
+//              fastest.  The word's owner copies it to the frame's mask copy and zeroes the working word.
+// The function is a template parameter (one kernel per kind and dtype); the affine and its per-channel operands are
+// decided by a pointer that is uniform over the launch.  No LDS, host sync, memset, allocation, data atomics or inline
+// assembly.
+#include "cb_common.h"
+
+// hipcc contracts a * b + c to an FMA by default -- also through __fmul_rn / __fadd_rn, which are plain operators compiled
+// under the header's own setting --, so the arithmetic below is written with operators under this file's pragma:
+// everything is evaluated as written, one rounding per operation.
+#pragma clang fp contract(off)
+
+namespace {
+
+__device__ __forceinline__ float cbw_load(const float* p) { return *p; }
+__device__ __forceinline__ float cbw_load(const cb_half* p) { return (float)*p; }
+
+// lo <= t <= hi by comparisons: a NaN stays a NaN (fminf / fmaxf would drop it)
+__device__ __forceinline__ float cbw_clamp(float t, float lo, float hi) { return t < lo ? lo : (t > hi ? hi : t); }
+
+// One value, all in f32; every operation is a correctly rounded IEEE one in the order written (nothing is contracted to
+// an FMA), so a float32 twin on the host reproduces the bits of the seven kinds without a transcendental function.
+template <int KIND>
+__device__ __forceinline__ float cbw_act(float v, float p0, float p1, float slope) {
+    switch (KIND) {
+        case CB_PW_RELU: return v < 0.f ? 0.f : v;      // (-0 and a NaN stay, as torch.relu)
+        case CB_PW_HARDTANH: return cbw_clamp(v, p0, p1);
+        case CB_PW_LEAKY: return v > 0.f ? v : v * p0;
+        case CB_PW_PRELU: return v > 0.f ? v : slope * v;
+        case CB_PW_HARDSWISH: return v * cbw_clamp(v + 3.f, 0.f, 6.f) / 6.f;
+        case CB_PW_HARDSIGMOID: return cbw_clamp(v + 3.f, 0.f, 6.f) / 6.f;
+        case CB_PW_SIGMOID: return 1.f / (1.f + expf(-v));
+        case CB_PW_SILU: return v / (1.f + expf(-v));
+        case CB_PW_TANH: return tanhf(v);
+        default: return v;      // CB_PW_IDENTITY: the affine alone
+    }
+}
+
+// x, out [C, H, W].  mask: the operand's change mask of this frame, or NULL; all: every pixel is listed.  An operand
+// without a mask has its bits in `bits` already (list form) -- or did not change.  scale / shift [C] (both or neither),
+// slope [C] (CB_PW_PRELU only).
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void cbw_pointwise_kernel(const T* __restrict__ x, T* __restrict__ out,
+                                                           const unsigned long long* __restrict__ mask, int all,
+                                                           unsigned long long* bits,
+                                                           unsigned long long* __restrict__ maskCopy,
+                                                           const float* __restrict__ scale,
+                                                           const float* __restrict__ shift,
+                                                           const float* __restrict__ slope, float p0, float p1,
+                                                           long words, int C, int H, int W, int wpr) {
+    const long HW = (long)H * W;
+    for (long w = blockIdx.x; w < words; w += gridDim.x) {
+        // (uniform over the workgroup: the working word is zeroed only behind the barrier below)
+        const unsigned long long own = bits[w];
+        const int y = (int)(w / wpr), tile = (int)(w - (long)y * wpr);
+        const unsigned long long valid = cb_valid_mask(W, tile);
+        unsigned long long word = own;
+        if (mask) word |= mask[w];
+        word = all ? valid : (word & valid);      // (the bits of the row padding are never set)
+        if (threadIdx.x == 0) maskCopy[w] = word;
+        if (word != 0) {
+            const int n = __popcll(word);
+            const long rowBase = (long)y * W + tile * 64;
+            const int total = n * C;
+            for (int e = threadIdx.x; e < total; e += 256) {
+                const int c = e / n, i = e - c * n;
+                const long o = (long)c * HW + rowBase + (n == 64 ? i : cb_select_bit(word, i));
+                float v = cbw_load(x + o);
+                // two roundings, never one FMA
+                if (scale) v = v * scale[c] + shift[c];
+                v = cbw_act<KIND>(v, p0, p1, KIND == CB_PW_PRELU ? slope[c] : 0.f);
+                out[o] = (T)v;      // fp16: rounded once
+            }
+        }
+        if (own != 0) {
+            __syncthreads();      // every wave has read the word
+            if (threadIdx.x == 0) bits[w] = 0;
+        }
+    }
+}
+
+template <typename T>
+void cbw_launch(const void* x, void* out, const uint64_t* mask, int all, uint64_t* bits, uint64_t* maskCopy, int C, int H,
+                int W, int kind, float p0, float p1, const float* scale, const float* shift, const float* slope,
+                hipStream_t s) {
+    const int wpr = (W + 63) / 64;
+    const long words = (long)H * wpr;
+    long blocks = words;
+    const long cap = (long)cb_num_cus() * 8;
+    if (blocks > cap) blocks = cap;
+    const dim3 grid((unsigned)blocks), block(256);
+#define CBW_GO(KIND)                                                                                                  \
+    case KIND:                                                                                                        \
+        hipLaunchKernelGGL((cbw_pointwise_kernel<T, KIND>), grid, block, 0, s, (const T*)x, (T*)out,                  \
+                           (const unsigned long long*)mask, all, (unsigned long long*)bits,                          \
+                           (unsigned long long*)maskCopy, scale, shift, slope, p0, p1, words, C, H, W, wpr);         \
+        break
+    switch (kind) {
+        CBW_GO(CB_PW_IDENTITY);
+        CBW_GO(CB_PW_RELU);
+        CBW_GO(CB_PW_HARDTANH);
+        CBW_GO(CB_PW_LEAKY);
+        CBW_GO(CB_PW_PRELU);
+        CBW_GO(CB_PW_HARDSWISH);
+        CBW_GO(CB_PW_HARDSIGMOID);
+        CBW_GO(CB_PW_SIGMOID);
+        CBW_GO(CB_PW_SILU);
+        CBW_GO(CB_PW_TANH);
+    }
+#undef CBW_GO
+}
+
+// what both entry points ask of the tensors, the module's two masks and the function
+bool cbw_args_ok(const void* x, const void* out, const uint64_t* mask, const uint64_t* bits, const uint64_t* maskCopy,
+                 int C, int H, int W, int kind, float p0, float p1, const float* scale, const float* shift,
+                 const float* slope, int dtype) {
+    return x && out && x != out && bits && maskCopy && bits != maskCopy && mask != bits && mask != maskCopy && C >= 1 &&
+           H >= 1 && W >= 1 && (dtype == CB_F32 || dtype == CB_F16) && cbinfer_pointwise_supported(kind, p0, p1) &&
+           (kind != CB_PW_PRELU || slope) && !scale == !shift &&
+           // (a list addresses a pixel with an int32; the kernel numbers a word's items with an int)
+           (long)H * W < (1l << 31) && (long)C * 64 < (1l << 31);
+}
+
+}  // namespace
+
+int cbinfer_pointwise_supported(int kind, float p0, float p1) {
+    if (kind < CB_PW_IDENTITY || kind > CB_PW_TANH) return 0;
+    if (kind == CB_PW_HARDTANH && !(p0 <= p1)) return 0;      // (also a NaN bound)
+    return 1;
+}
+
+int cbinfer_pointwise_changed(const void* x, void* out, const uint64_t* mask, int all, uint64_t* bits, uint64_t* maskCopy,
+                              int C, int H, int W, int kind, float p0, float p1, const float* scale, const float* shift,
+                              const float* slope, int dtype, cbStream_t stream) {
+    CB_REQUIRE(cbw_args_ok(x, out, mask, bits, maskCopy, C, H, W, kind, p0, p1, scale, shift, slope, dtype));
+    if (dtype == CB_F32)
+        cbw_launch<float>(x, out, mask, all, bits, maskCopy, C, H, W, kind, p0, p1, scale, shift, slope,
+                          (hipStream_t)stream);
+    else
+        cbw_launch<cb_half>(x, out, mask, all, bits, maskCopy, C, H, W, kind, p0, p1, scale, shift, slope,
+                            (hipStream_t)stream);
+    return cb_launch_status();
+}
+
+int cbinfer_cbpointwise_forward(const void* x, void* outputState, const uint64_t* mask, const int32_t* list, int capN,
+                                const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int kind,
+                                float p0, float p1, const float* scale, const float* shift, const float* slope, int dtype,
+                                cbStream_t stream) {
+    // (every argument is checked before the first launch)
+    CB_REQUIRE(cbw_args_ok(x, outputState, mask, bits, maskCopy, C, H, W, kind, p0, p1, scale, shift, slope, dtype));
+    CB_REQUIRE(capN >= 0 && !(mask && list) && (list || !countDev));
+    if (list) {
+        const cbPool one = {1, 1, 1, 1, 0, 0, 0, CB_POOL_MAX};      // a 1x1 / stride-1 window reaches its own pixel only
+        const int st = cbinfer_pool_footprint(list, capN, countDev, nullptr, H, W, &one, bits, stream);
+        if (st != CB_OK) return st;
+    }
+    return cbinfer_pointwise_changed(x, outputState, mask, !mask && !list, bits, maskCopy, C, H, W, kind, p0, p1, scale,
+                                     shift, slope, dtype, stream);
+}

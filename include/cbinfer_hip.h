@@ -65,7 +65,9 @@ typedef void* cbStream_t; /* hipStream_t */
  * general pooling entry points (cbPool, cbinfer_pool_*, cbinfer_cbpool2d_forward), the sum (cbinfer_add_changed,
  * cbinfer_cbadd_forward) and the decoder operators (cbUpsample, cbinfer_upsample_supported,
  * cbinfer_cbupsample_forward, cbinfer_cbconcat_forward) and the transposed convolution (cbTGeom, cbinfer_tconv_*,
- * cbinfer_*_tconv, cbinfer_cbconvtranspose2d_forward). */
+ * cbinfer_*_tconv, cbinfer_cbconvtranspose2d_forward), the depthwise convolution (cbinfer_dwconv_*,
+ * cbinfer_cbdwconv2d_forward*) and the element-wise functions (CB_PW_*, cbinfer_pointwise_supported,
+ * cbinfer_pointwise_changed, cbinfer_cbpointwise_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -877,6 +879,65 @@ int cbinfer_cbadd_forward(const void* a, const void* b, void* outputState, const
                           int capA, const int32_t* countA, const uint64_t* maskB, const int32_t* listB, int capB,
                           const int32_t* countB, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int relu,
                           int dtype, cbStream_t stream);
+
+/* ---- change-based element-wise function: out = act(x scale[c] + shift[c]) (cb_pointwise.hip) ------------
+ * No counterpart in the reference.  x and the state `out` are [C, H, W], contiguous, one dtype (CB_F32 or CB_F16), two
+ * different tensors.  Every producer of this library leaves the pixels outside its change list bit for bit as they were,
+ * so f(x) can differ from last frame's only at the operand's changed pixels; recomputing there is the dense result.
+ *   listed pixels: the operand's changes, as its row-padded change MASK (cbinfer_mask_words(H, W) words), as an int32
+ *     LIST (flat indexes y W + x; entries outside the map are dropped), or not at all: every pixel is listed then.  Bits
+ *     of the row padding are never set.
+ *   values: at listed pixels, every channel c, all in f32 and rounded to f16 once at the end for CB_F16:
+ *     affine (scale != NULL; scale, shift f32 [C], also for CB_F16): v = fl(fl(x scale[c]) + shift[c]) -- two correctly
+ *       rounded operations, never one FMA;
+ *     then `kind` with the f32 parameters p0, p1, every operation correctly rounded in the order written, comparisons
+ *     instead of fmin / fmax (a NaN stays a NaN), clamp(t, lo, hi) = t < lo ? lo : (t > hi ? hi : t):
+ *       CB_PW_IDENTITY     v
+ *       CB_PW_RELU         v < 0 ? 0 : v                      (-0 and a NaN stay)
+ *       CB_PW_HARDTANH     clamp(v, p0, p1)                   (ReLU6: p0 = 0, p1 = 6)
+ *       CB_PW_LEAKY        v > 0 ? v : v p0
+ *       CB_PW_PRELU        v > 0 ? v : slope[c] v             (slope f32 [C])
+ *       CB_PW_HARDSWISH    v clamp(v + 3, 0, 6) / 6           (left to right, an IEEE division)
+ *       CB_PW_HARDSIGMOID  clamp(v + 3, 0, 6) / 6
+ *       CB_PW_SIGMOID      1 / (1 + expf(-v))
+ *       CB_PW_SILU         v / (1 + expf(-v))
+ *       CB_PW_TANH         tanhf(v)
+ *     The first seven are torch's CPU operators bit for bit; the last three call the device's expf / tanhf.  Every other
+ *     pixel of `out` keeps its bits; a pixel's bits depend neither on the other listed pixels nor on the operand's form.
+ *   hand-on: maskCopy receives the frame's mask every frame (all zeros for an empty frame: cbinfer_compact_bits makes
+ *     the ascending list from it on demand); `bits`, the working mask (cbinfer_mask_words(H, W) words, zero on first
+ *     use), is zero again when the launch ends.
+ * All arguments are checked before the first launch.  A null tensor or mask buffer, x == out, bits == maskCopy, the
+ * operand's mask == bits or maskCopy, both a mask and a list, a count without a list, capN < 0, an unknown kind or dtype,
+ * CB_PW_HARDTANH with p0 > p1, CB_PW_PRELU without slope, scale without shift or the reverse, C / H / W < 1, H W or 64 C
+ * beyond an int32 return CB_ERR_BADARG and launch nothing. */
+#define CB_PW_IDENTITY 0
+#define CB_PW_RELU 1
+#define CB_PW_HARDTANH 2
+#define CB_PW_LEAKY 3
+#define CB_PW_PRELU 4
+#define CB_PW_HARDSWISH 5
+#define CB_PW_HARDSIGMOID 6
+#define CB_PW_SIGMOID 7
+#define CB_PW_SILU 8
+#define CB_PW_TANH 9
+/* host, pure: 1 if `kind` is one of CB_PW_* and its parameters are usable (CB_PW_HARDTANH: p0 <= p1), else 0 */
+int cbinfer_pointwise_supported(int kind, float p0, float p1);
+/* The mask-driven launch.  mask: the operand's change mask, or NULL; all != 0: every pixel is listed.  The kernel ORs
+ * `bits` and mask word by word itself (or forms the full row word); without a mask the operand contributes what `bits`
+ * holds on entry.  No atomics. */
+int cbinfer_pointwise_changed(const void* x, void* out, const uint64_t* mask, int all, uint64_t* bits, uint64_t* maskCopy,
+                              int C, int H, int W, int kind, float p0, float p1, const float* scale, const float* shift,
+                              const float* slope, int dtype, cbStream_t stream);
+/* The whole frame enqueued without a host sync.  mask != NULL: mask form, ONE launch (cbinfer_pointwise_changed);
+ * list != NULL: list form (capN entries at most, countDev the device-side length or NULL: capN is the length; capN == 0
+ * launches nothing in front), one launch in front, which ORs the list's bits into `bits` (cbinfer_pool_footprint with a
+ * 1x1 / stride-1 window: one 64-bit atomicOr per entry); both NULL: no change information, every pixel is listed, one
+ * launch. */
+int cbinfer_cbpointwise_forward(const void* x, void* outputState, const uint64_t* mask, const int32_t* list, int capN,
+                                const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int kind,
+                                float p0, float p1, const float* scale, const float* shift, const float* slope, int dtype,
+                                cbStream_t stream);
 
 /* ---- change-based upsampling and channel concatenation for decoders (cb_decoder.hip) -------------------
  * No counterpart in the reference.  Both operators are exact for the reason the sum is: every producer leaves the pixels
