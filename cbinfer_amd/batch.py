@@ -31,6 +31,17 @@ from .dwconv import CBDepthwiseConv2d
 from .pointwise import CBPointwise2d
 
 
+# the change-based operators that have neither a batched kernel here nor a grouped launch in a BranchGroup: (types,
+# what the refusal calls them, the networks they stand in)
+CHAIN_OPERATORS = (
+    ((CBAdd2d,), 'a change-based sum', 'residual'),
+    ((CBUpsample2d, CBConcat2d), 'a change-based decoder operator', 'decoder'),
+    ((CBConvTranspose2d,), 'a change-based transposed convolution', 'decoder'),
+    ((CBDepthwiseConv2d,), 'a change-based depthwise convolution', 'separable'),
+    ((CBPointwise2d,), 'a change-based element-wise function', 'such'),
+)
+
+
 def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
 
@@ -49,21 +60,10 @@ class SequenceBatch(object):
             if type(m) in (CBPoolMax2d, CBPoolAvg2d) and m.__dict__.get('_general'):
                 raise CBinferError("SequenceBatch: layer %r is %r, a pool that is never folded into the next detection "
                                    "(only 2x2/stride 2 without padding is) and has no batched kernel" % (name, m))
-            if type(m) is CBAdd2d:
-                raise CBinferError("SequenceBatch: layer %r is %r, a change-based sum, which has no batched kernel: run "
-                                   "residual networks one sequence per stream" % (name, m))
-            if type(m) in (CBUpsample2d, CBConcat2d):
-                raise CBinferError("SequenceBatch: layer %r is %r, a change-based decoder operator, which has no batched "
-                                   "kernel: run decoder networks one sequence per stream" % (name, m))
-            if type(m) is CBConvTranspose2d:
-                raise CBinferError("SequenceBatch: layer %r is %r, a change-based transposed convolution, which has no "
-                                   "batched kernel: run decoder networks one sequence per stream" % (name, m))
-            if type(m) is CBDepthwiseConv2d:
-                raise CBinferError("SequenceBatch: layer %r is %r, a change-based depthwise convolution, which has no "
-                                   "batched kernel: run separable networks one sequence per stream" % (name, m))
-            if type(m) is CBPointwise2d:
-                raise CBinferError("SequenceBatch: layer %r is %r, a change-based element-wise function, which has no "
-                                   "batched kernel: run such networks one sequence per stream" % (name, m))
+            for types, noun, networks in CHAIN_OPERATORS:
+                if type(m) in types:
+                    raise CBinferError("SequenceBatch: layer %r is %r, %s, which has no batched kernel: run %s networks "
+                                       "one sequence per stream" % (name, m, noun, networks))
         self.net = net
         self.layers = None          # built on the first frame (needs the frame size)
         self._key = None

@@ -18,12 +18,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check
+from .batch import CHAIN_OPERATORS
 from .conv2d import CBConv2d
-from .residual import CBAdd2d
-from .decoder import CBConcat2d, CBUpsample2d
-from .tconv import CBConvTranspose2d
-from .dwconv import CBDepthwiseConv2d
-from .pointwise import CBPointwise2d
 
 
 def _kp(K):
@@ -43,21 +39,9 @@ class BranchGroup(nn.Module):
                                    "padding=%s dilation=%s%s), which has no grouped launch"
                                    % (name, tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation),
                                       '' if m.bias is not None else ', no bias'))
-            if type(m) is CBAdd2d:
-                raise CBinferError("BranchGroup: layer %r is %r, a change-based sum, which has no grouped launch"
-                                   % (name, m))
-            if type(m) in (CBUpsample2d, CBConcat2d):
-                raise CBinferError("BranchGroup: layer %r is %r, a change-based decoder operator, which has no grouped "
-                                   "launch" % (name, m))
-            if type(m) is CBConvTranspose2d:
-                raise CBinferError("BranchGroup: layer %r is %r, a change-based transposed convolution, which has no "
-                                   "grouped launch" % (name, m))
-            if type(m) is CBDepthwiseConv2d:
-                raise CBinferError("BranchGroup: layer %r is %r, a change-based depthwise convolution, which has no "
-                                   "grouped launch" % (name, m))
-            if type(m) is CBPointwise2d:
-                raise CBinferError("BranchGroup: layer %r is %r, a change-based element-wise function, which has no "
-                                   "grouped launch" % (name, m))
+            for types, noun, _ in CHAIN_OPERATORS:
+                if type(m) in types:
+                    raise CBinferError("BranchGroup: layer %r is %r, %s, which has no grouped launch" % (name, m, noun))
         self.__dict__['_pairs'] = {}
 
     def _pair_state(self, mods, geom):

@@ -1,0 +1,163 @@
+"""What the change-based operators behind a producer share on the host: how an operand and its change
+information are taken apart, the state module CBAdd2d, CBPointwise2d, CBUpsample2d and CBConcat2d derive from, the mask
+workspace and hand-back of every mask-driven module, and the ONE table of the modules that count as a producer.
+"""
+import functools
+
+import torch
+import torch.nn as nn
+
+from ._lib import C, CBinferError
+from .conv2d_cg import ChangeIndexes, MaskChangeIndexes
+
+
+# ---------------------------------------------------------------------------------------------------- operands
+def split_operand(name, x, which):
+    """(contiguous tensor, change indexes or None) of an operand: a tensor or ('changeIndexes', tensor, indexes)."""
+    if type(x) == tuple:
+        if len(x) != 3 or x[0] != 'changeIndexes':
+            raise CBinferError("%s: %s is a tuple, but not ('changeIndexes', tensor, indexes)" % (name, which))
+        x, indexes = x[1], x[2]
+    else:
+        indexes = None
+    if not torch.is_tensor(x):
+        raise CBinferError("%s: %s must be a tensor or the ('changeIndexes', tensor, indexes) tuple, got %s"
+                           % (name, which, type(x).__name__))
+    return x.detach().contiguous(), indexes
+
+
+# The three refusals of operand_changes -- indexes of another map, of another type, a buffer the kernels cannot read --
+# as the consumers word them; filled with name, which, the two map sizes and the type's name.
+OPERAND_WORDS = (
+    "%(name)s: the change indexes of %(which)s address a %(h)dx%(w)d map, the tensor is a %(H)dx%(W)d map",
+    "%(name)s: the change indexes of %(which)s must be an int32 tensor or a ChangeIndexes, got %(type)s",
+    "%(name)s: the change indexes of %(which)s must be a contiguous one-dimensional int32 tensor on the tensor's device")
+# ... and what CBDepthwiseConv2d (which: 'layer') and the general pools ('pool') ask of propagated indexes: their words
+# and their rule for a MaskChangeIndexes
+PROPAGATED = dict(
+    words=("%(name)s: the propagated change indexes address a %(h)dx%(w)d map, this %(which)s's input map is %(H)dx%(W)d",
+           "%(name)s: change indexes must be an int32 tensor or a ChangeIndexes",
+           "%(name)s: propagated change indexes must be a contiguous int32 tensor on the input's device"),
+    maskWhenMade=False, maskNeedsSize=True, contiguous=True)
+
+
+def operand_changes(name, which, indexes, H, W, dev, spare, words=OPERAND_WORDS, maskWhenMade=True, maskNeedsSize=False,
+                    contiguous=False):
+    """(mask, list, capacity, device count) of an operand's changes on its H x W map; all None / 0: every pixel is
+    listed.  `spare`: any int32 device buffer, which stands for the empty list (an empty tensor has no address).
+
+    When a MaskChangeIndexes is taken as its mask -- one launch less than its list, which is then not needed -- is each
+    consumer's own rule and decides what a FrameProgram records: maskWhenMade=False takes the list where the producer's
+    kernel already made it; maskNeedsSize additionally asks for a mask that names this very map.  contiguous: an int32
+    tensor is made contiguous instead of refused."""
+    if indexes is None:
+        return None, None, 0, None
+    said = dict(name=name, which=which, H=H, W=W, type=type(indexes).__name__)
+    if isinstance(indexes, ChangeIndexes):
+        if indexes.size is not None and tuple(indexes.size) != (H, W):
+            raise CBinferError(words[0] % dict(said, h=indexes.size[0], w=indexes.size[1]))
+        if (isinstance(indexes, MaskChangeIndexes) and indexes._mask is not None and
+                (maskWhenMade or not indexes._made) and (not maskNeedsSize or indexes.size == (H, W))):
+            return indexes._mask, None, 0, None
+        idx, count = indexes.buffer, indexes.count
+    elif torch.is_tensor(indexes):
+        idx, count = indexes.detach().contiguous() if contiguous else indexes.detach(), None
+    else:
+        raise CBinferError(words[1] % said)
+    if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != dev:
+        raise CBinferError(words[2] % said)
+    cap = idx.numel()
+    return None, (idx if cap else spare), cap, count
+
+
+# ---------------------------------------------------------------------------------------------------- state
+def mask_workspace(Ho, Wo, dev, nbits=1):
+    """The buffers of a mask-driven module on an Ho x Wo output map: nbits working masks `bits` (zero between frames),
+    the frame's mask `copy`, and index buffer and count for a consumer that wants the list."""
+    words = C.cbinfer_mask_words(Ho, Wo)
+    return dict(bits=torch.zeros(nbits * words, dtype=torch.int64, device=dev),
+                copy=torch.zeros(words, dtype=torch.int64, device=dev),
+                idx=torch.empty(Ho * Wo, dtype=torch.int32, device=dev),
+                count=torch.zeros(1, dtype=torch.int32, device=dev))
+
+
+def hand_back(module, state, copy, size, work):
+    """What a frame returns: a private copy of `state` -- or, with cloneOutput=False, the state itself, tagged, so that a
+    consumer that keeps a reference copies it then -- and with propChangeIndexes the frame's mask `copy` on the
+    size = (Ho, Wo) output map as a MaskChangeIndexes."""
+    if getattr(module, 'cloneOutput', True):
+        output = state.clone()
+    else:
+        output = state
+        output._cbinfer_inplace_state = True
+    if module.propChangeIndexes:
+        return 'changeIndexes', output, MaskChangeIndexes(copy, size, work['idx'], work['count'])
+    return output
+
+
+class CBStateModule(nn.Module):
+    """A module whose only state is `outputState`: the flags propChangeIndexes / cloneOutput, clearMemory,
+    getStateTensors, and transient work buffers that are neither state nor pickled."""
+    _WORK = '_work'        # the slot of the work buffers in the instance's __dict__ (tests and old pickles read it)
+    _TRANSIENT = ()        # further slots that are made again on demand (ctypes arguments)
+
+    def __init__(self):
+        super(CBStateModule, self).__init__()
+        self.propChangeIndexes = False
+        self.cloneOutput = True
+        self.register_buffer('outputState', torch.zeros(0))
+        self.clearMemory()
+
+    def clearMemory(self):
+        if 'outputState' not in self._buffers:
+            self.register_buffer('outputState', torch.zeros(0))
+        self.outputState = self.outputState.new_zeros(0)
+        self.__dict__[self._WORK] = None
+
+    def getStateTensors(self):
+        return [self.outputState]
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        for name in (self._WORK,) + self._TRANSIENT:
+            if name in d:
+                d[name] = None
+        return d
+
+    def _result(self, work, Ho, Wo):
+        return hand_back(self, self.outputState, work['copy'], (Ho, Wo), work)
+
+
+# ---------------------------------------------------------------------------------------------------- producers
+@functools.lru_cache(maxsize=None)
+def producer_types(forUpsampling=False):
+    """The module types (exactly, not a subclass) that leave every pixel outside their change list bit for bit as it
+    was and can hand that list on: what linkDepthwise, insertCBPointwise and insertCBTransposedConv accept in front of
+    their module.  CBConcat2d is none: its forward takes a list of operands and never stands in an nn.Sequential.
+    forUpsampling: insertCBUpsampling's set -- the same but for CBConvTranspose2d, which it has never accepted."""
+    from .conv2d import CBConv2d, CBPoolAvg2d, CBPoolMax2d
+    from .decoder import CBUpsample2d
+    from .dwconv import CBDepthwiseConv2d
+    from .pointwise import CBPointwise2d
+    from .residual import CBAdd2d, CBResidual
+    from .tconv import CBConvTranspose2d
+    types = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBConvTranspose2d,
+             CBDepthwiseConv2d, CBPointwise2d)
+    return tuple(t for t in types if not (forUpsampling and t is CBConvTranspose2d))
+
+
+def hand_on_changes(prod):
+    """Switch the change output of the producer `prod` on for the consumer behind it: propChangeIndexes (a CBResidual's
+    at its `.add`); a 2x2 CBPoolMax2d of the reference's kind also hands on the OUTPUT-resolution list."""
+    from .conv2d import CBPoolMax2d
+    from .residual import CBResidual
+    (prod.add if type(prod) is CBResidual else prod).propChangeIndexes = True
+    if type(prod) is CBPoolMax2d and not prod.__dict__.get('_general'):
+        prod.downsampleIndexes = True      # (the list of the pool's input addresses another map)
+
+
+def is_1x1(m):
+    """A 1x1 / stride-1 / padding-0 CBConv2d: the consumer that reads exactly the pixels it is handed."""
+    from .conv2d import CBConv2d
+    return (type(m) is CBConv2d and tuple(m.kernel_size) == (1, 1) and tuple(m.stride) == (1, 1) and
+            tuple(m.padding) == (0, 0))

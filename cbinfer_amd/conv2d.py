@@ -28,6 +28,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import C, check, dtype_code, ptr, raw_stream, require_device, stream_ptr
+from .chain import PROPAGATED, hand_back, mask_workspace, operand_changes
 from .conv2d_cg import (ChangeIndexes, MaskChangeIndexes, changeDetection, changeIndexesExtr, dilateChangeIndexes,
                         genXMatrix, matrixMult, maxPool2d, newConvWorkspace, poolChangeIndexes, prepWeights, updateOutput)
 from .conv2d_fg import cbconvFG, cbconvFG_deterministic
@@ -301,60 +302,29 @@ class CBPoolMax2d(nn.Module):
         work = self.__dict__.get('_poolWork')
         if work is None or work['key'] != key:
             Ho, Wo = self._out_hw(Hi, Wi)
-            words = C.cbinfer_mask_words(Ho, Wo)
-            work = self.__dict__['_poolWork'] = dict(
-                key=key, size=(Ho, Wo),
-                bits=torch.zeros(words, dtype=torch.int64, device=dev),
-                copy=torch.zeros(words, dtype=torch.int64, device=dev),
-                idx=torch.empty(Ho * Wo, dtype=torch.int32, device=dev),
-                count=torch.zeros(1, dtype=torch.int32, device=dev))
+            work = self.__dict__['_poolWork'] = dict(mask_workspace(Ho, Wo, dev), key=key, size=(Ho, Wo))
         return work
 
     def _forward_general(self, input, changeIndexes):
         """A frame on cb_pool2d.hip: cbinfer_cbpool2d_forward, two launches, no host sync.  The output pixels whose
         window holds a listed input pixel are pooled again; the list handed on lives on the OUTPUT map."""
-        Err = _lib.CBinferError
-        name = self.__class__.__name__
         nc, Hi, Wi = input.size(-3), input.size(-2), input.size(-1)
         assert input.dim() == 4 and input.size(0) == 1
         work = self._pool_workspace(Hi, Wi, input.device)
         Ho, Wo = work['size']
-        idx, count, mask, cap = None, None, None, 0
-        if isinstance(changeIndexes, ChangeIndexes):
-            if changeIndexes.size not in (None, (Hi, Wi)):
-                raise Err("%s: the propagated change indexes address a %dx%d map, this pool's input map is %dx%d"
-                          % ((name,) + tuple(changeIndexes.size) + (Hi, Wi)))
-            if (isinstance(changeIndexes, MaskChangeIndexes) and not changeIndexes._made and
-                    changeIndexes._mask is not None and changeIndexes.size == (Hi, Wi)):
-                mask = changeIndexes._mask      # (the producer's list is never made)
-            else:
-                idx, count = changeIndexes.buffer, changeIndexes.count
-        elif isinstance(changeIndexes, torch.Tensor):
-            idx = changeIndexes.detach().contiguous()
-            assert idx.dim() == 1
-        else:
-            raise Err("%s: change indexes must be an int32 tensor or a ChangeIndexes" % name)
-        if mask is None:
-            if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.device != input.device:
-                raise Err("%s: propagated change indexes must be a contiguous int32 tensor on the input's device" % name)
-            cap = idx.numel()
-            if cap == 0:
-                idx = work['idx']      # (an empty tensor has no address: any buffer stands for the empty list)
+        assert not isinstance(changeIndexes, torch.Tensor) or changeIndexes.dim() == 1
+        if changeIndexes is None:      # (a pool always stands behind a producer)
+            raise _lib.CBinferError(PROPAGATED['words'][1] % dict(name=self.__class__.__name__))
+        mask, idx, cap, count = operand_changes(self.__class__.__name__, 'pool', changeIndexes, Hi, Wi, input.device,
+                                                work['idx'], **PROPAGATED)
         if (not _same_shape(self.outputState, (1, nc, Ho, Wo)) or self.outputState.dtype != input.dtype or
                 self.outputState.device != input.device):
             self.outputState = torch.full((1, nc, Ho, Wo), float('inf'), dtype=input.dtype, device=input.device)
         check(C.cbinfer_cbpool2d_forward(ptr(input), ptr(self.outputState), ptr(idx), cap, ptr(count), ptr(mask),
                                          ptr(work['bits']), ptr(work['copy']), nc, Hi, Wi, self._pool_struct(),
                                          dtype_code(input), stream_ptr(input)))
-        if getattr(self, 'cloneOutput', True):
-            output = self.outputState.clone()
-        else:
-            output = self.outputState
-            output._cbinfer_inplace_state = True
-        if self.propChangeIndexes:
-            # (an input-resolution list means nothing behind such a pool: downsampleIndexes is ignored)
-            return 'changeIndexes', output, MaskChangeIndexes(work['copy'], (Ho, Wo), work['idx'], work['count'])
-        return output
+        # (an input-resolution list means nothing behind such a pool: downsampleIndexes is ignored)
+        return hand_back(self, self.outputState, work['copy'], (Ho, Wo), work)
 
     def forward(self, inp):
         assert type(inp) == tuple and inp[0] == 'changeIndexes'

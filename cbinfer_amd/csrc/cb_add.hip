@@ -3,18 +3,13 @@
 // pixels outside its change list bit for bit as they were, so the sum can differ from last frame's only at the UNION of
 // the two operands' changes: recomputing there gives the dense result exactly, without a threshold.  A frame is
 //   per operand in LIST form, one launch in front: the list's bits ORed into the zeroed working mask
-//              (cbinfer_pool_footprint of cb_pool2d.hip with a 1x1 / stride-1 window: one 64-bit atomicOr per entry);
-//   one launch, mask-driven in cbp2_pool_kernel's form: workgroups of four waves stride over the mask words, OR the
-//              operands' change masks (or the full row word of an operand without change information) into the working
-//              word themselves, and spread the (set bit, channel) items of a non-empty word over the 256 threads, set bit
-//              fastest.  The word's owner copies it to the frame's mask copy and zeroes the working word.
+//              (cb_list_to_bits of cb_maskwalk.h);
+//   one launch, the word walk of cb_maskwalk.h (cb_walk_words): the operands' change masks (or the full row word of
+//              an operand without change information) are ORed into the working word, one sum per (set bit, channel).
 // No host sync, memset, allocation, data atomics or inline assembly.
-#include "cb_common.h"
+#include "cb_maskwalk.h"
 
 namespace {
-
-__device__ __forceinline__ float cba_load(const float* p) { return *p; }
-__device__ __forceinline__ float cba_load(const cb_half* p) { return (float)*p; }
 
 // a, b, out [C, H, W].  maskA / maskB: the operand's change mask of this frame, or NULL; all: one of the operands lists
 // every pixel.  An operand without a mask has its bits in `bits` already (list form) -- or did not change.
@@ -25,34 +20,16 @@ __global__ __launch_bounds__(256) void cba_add_kernel(const T* __restrict__ a, c
                                                      unsigned long long* bits, unsigned long long* __restrict__ maskCopy,
                                                      long words, int C, int H, int W, int wpr) {
     const long HW = (long)H * W;
-    for (long w = blockIdx.x; w < words; w += gridDim.x) {
-        // (uniform over the workgroup: the working word is zeroed only behind the barrier below)
-        const unsigned long long own = bits[w];
-        const int y = (int)(w / wpr), tile = (int)(w - (long)y * wpr);
-        const unsigned long long valid = cb_valid_mask(W, tile);
-        unsigned long long word = own;
-        if (maskA) word |= maskA[w];
-        if (maskB) word |= maskB[w];
-        word = all ? valid : (word & valid);      // (the bits of the row padding are never set)
-        if (threadIdx.x == 0) maskCopy[w] = word;
-        if (word != 0) {
-            const int n = __popcll(word);
-            const long rowBase = (long)y * W + tile * 64;
-            const int total = n * C;
-            for (int e = threadIdx.x; e < total; e += 256) {
-                const int c = e / n, i = e - c * n;
-                const long o = (long)c * HW + rowBase + (n == 64 ? i : cb_select_bit(word, i));
-                // fp32: one IEEE addition; fp16: the sum in f32, rounded to f16 once (the correctly rounded f16 sum)
-                float v = cba_load(a + o) + cba_load(b + o);
-                if (RELU) v = v != v ? v : (v > 0.f ? v : 0.f);      // (a NaN stays a NaN, as torch.relu)
-                out[o] = (T)v;
-            }
-        }
-        if (own != 0) {
-            __syncthreads();      // every wave has read the word
-            if (threadIdx.x == 0) bits[w] = 0;
-        }
-    }
+    cb_walk_words(
+        bits, maskCopy, words, C, W, wpr, all,
+        [&](long w, int, int) { return (maskA ? maskA[w] : 0ull) | (maskB ? maskB[w] : 0ull); },
+        [&](int c, int y, int x) {
+            const long o = (long)c * HW + (y * W + x);      // (H W fits an int: cba_args_ok)
+            // fp32: one IEEE addition; fp16: the sum in f32, rounded to f16 once (the correctly rounded f16 sum)
+            float v = cb_load_f32(a + o) + cb_load_f32(b + o);
+            if (RELU) v = v != v ? v : (v > 0.f ? v : 0.f);      // (a NaN stays a NaN, as torch.relu)
+            out[o] = (T)v;
+        });
 }
 
 template <typename T>
@@ -60,10 +37,7 @@ void cba_launch(const void* a, const void* b, void* out, const uint64_t* maskA, 
                 uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int relu, hipStream_t s) {
     const int wpr = (W + 63) / 64;
     const long words = (long)H * wpr;
-    long blocks = words;
-    const long cap = (long)cb_num_cus() * 8;
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(cb_walk_grid(words)), block(256);
 #define CBA_GO(RELU)                                                                                                  \
     hipLaunchKernelGGL((cba_add_kernel<T, RELU>), grid, block, 0, s, (const T*)a, (const T*)b, (T*)out,              \
                        (const unsigned long long*)maskA, (const unsigned long long*)maskB, all,                      \
@@ -92,10 +66,9 @@ int cbinfer_add_changed(const void* a, const void* b, void* out, const uint64_t*
     CB_REQUIRE(cba_args_ok(a, b, out, bits, maskCopy, C, H, W, dtype));
     CB_REQUIRE(maskA != maskCopy && maskB != maskCopy && maskA != bits && maskB != bits);
     const int all = allA || allB;
-    if (dtype == CB_F32)
-        cba_launch<float>(a, b, out, maskA, maskB, all, bits, maskCopy, C, H, W, relu, (hipStream_t)stream);
-    else
-        cba_launch<cb_half>(a, b, out, maskA, maskB, all, bits, maskCopy, C, H, W, relu, (hipStream_t)stream);
+    cb_dispatch_dtype(dtype, [&](auto t) {
+        cba_launch<decltype(t)>(a, b, out, maskA, maskB, all, bits, maskCopy, C, H, W, relu, (hipStream_t)stream);
+    });
     return cb_launch_status();
 }
 
@@ -111,10 +84,9 @@ int cbinfer_cbadd_forward(const void* a, const void* b, void* outputState, const
     CB_REQUIRE(maskA != maskCopy && maskB != maskCopy && maskA != bits && maskB != bits);
     const int allA = !maskA && !listA, allB = !maskB && !listB;
     if (!allA && !allB) {      // (behind an operand that lists every pixel the other's list changes nothing)
-        const cbPool one = {1, 1, 1, 1, 0, 0, 0, CB_POOL_MAX};      // a 1x1 / stride-1 window reaches its own pixel only
         int st = CB_OK;
-        if (listA) st = cbinfer_pool_footprint(listA, capA, countA, nullptr, H, W, &one, bits, stream);
-        if (st == CB_OK && listB) st = cbinfer_pool_footprint(listB, capB, countB, nullptr, H, W, &one, bits, stream);
+        if (listA) st = cb_list_to_bits(listA, capA, countA, H, W, bits, stream);
+        if (st == CB_OK && listB) st = cb_list_to_bits(listB, capB, countB, H, W, bits, stream);
         if (st != CB_OK) return st;
     }
     return cbinfer_add_changed(a, b, outputState, maskA, allA, maskB, allB, bits, maskCopy, C, H, W, relu, dtype, stream);

@@ -6,24 +6,21 @@
 // exactly, without a threshold.  A frame is
 //   per operand in LIST form, one launch in front: the list's footprint ORed into a zeroed working mask of the OUTPUT
 //              map (upsample: the output pixels that read a listed input pixel, one thread per (entry, candidate output
-//              row), at most two 64-bit atomicOr per row; concat: cbinfer_pool_footprint of cb_pool2d.hip with a 1x1 /
-//              stride-1 window into the operand's own working mask);
-//   one launch, mask-driven in cba_add_kernel's form: workgroups of four waves stride over the output mask words.
-//              Upsample: lane j of every wave owns output column 64 w + j of the word, tests the input change bits of its
-//              source pixels, and one ballot makes the word (cbp2_footprint_mask_kernel's scheme in front of the
-//              recompute).  Concat: every operand has a word of its own -- its channels are copied at ITS pixels only --
-//              and the union is handed on.  The (set bit, channel) items of a word are spread over the 256 threads, set
-//              bit fastest.  The word's owner writes the frame's mask copy and zeroes the working words it used.
+//              row), at most two 64-bit atomicOr per row; concat: cb_list_to_bits of cb_maskwalk.h into the operand's
+//              own working mask);
+//   one launch, mask-driven: workgroups of four waves stride over the output mask words.  Upsample is the word walk of
+//              cb_maskwalk.h (cb_walk_words): lane j of every wave owns output column 64 w + j of the word, tests the
+//              input change bits of its source pixels, and one ballot makes the word (cbp2_footprint_mask_kernel's
+//              scheme in front of the recompute).  Concat keeps a loop of its own in the walk's order: every operand
+//              has a word of its own -- its channels are copied at ITS pixels only -- and the union is handed on; the
+//              word's owner writes the frame's mask copy and zeroes the working words it used.
 // No host sync, memset, allocation, data atomics or inline assembly.
-#include "cb_common.h"
+#include "cb_maskwalk.h"
 
 namespace {
 
 #define CBU_MAXS 8      // scale limit per axis
 #define CBC_MAXN 4      // operands of a concat
-
-__device__ __forceinline__ float cbd_load(const float* p) { return *p; }
-__device__ __forceinline__ float cbd_load(const cb_half* p) { return (float)*p; }
 
 // ---------------------------------------------------------------------------------------------------- upsample
 // MODE 0: nearest; 1: bilinear, align_corners=False; 2: bilinear, align_corners=True.
@@ -101,15 +98,12 @@ __global__ __launch_bounds__(256) void cbu_upsample_kernel(const T* __restrict__
                                                           int wprO) {
     const long HWi = (long)Hi * Wi, HWo = (long)Ho * Wo;
     const int lane = threadIdx.x & 63;
-    for (long w = blockIdx.x; w < words; w += gridDim.x) {
-        // (uniform over the workgroup: the working word is zeroed only behind the barrier below)
-        const unsigned long long own = bits[w];
-        const int oy = (int)(w / wprO), tile = (int)(w - (long)oy * wprO);
-        const unsigned long long valid = cb_valid_mask(Wo, tile);
-        int y0, y1, rhoY, denY;
-        cbu_source<MODE>(oy, Hi, sH, Ho, y0, y1, rhoY, denY);
-        unsigned long long word = own;
-        if (inMask) {
+    int y0, y1, rhoY, denY;      // the source rows of the word's output row: made by makeWord, read by the items
+    cb_walk_words(
+        bits, maskCopy, words, C, Wo, wprO, all,
+        [&](long, int oy, int tile) {
+            cbu_source<MODE>(oy, Hi, sH, Ho, y0, y1, rhoY, denY);
+            if (!inMask) return 0ull;
             // every wave makes the same word: lane j tests the change bits of the source pixels of column 64 tile + j
             const int ox = tile * 64 + lane;
             bool bit = false;
@@ -122,40 +116,25 @@ __global__ __launch_bounds__(256) void cbu_upsample_kernel(const T* __restrict__
                                              (r0[x1 >> 6] | r1[x1 >> 6]) >> (x1 & 63);
                 bit = (m & 1ull) != 0;
             }
-            word |= __ballot(bit);
-        }
-        word = all ? valid : (word & valid);      // (the bits of the row padding are never set)
-        if (threadIdx.x == 0) maskCopy[w] = word;
-        if (word != 0) {
-            const int n = __popcll(word);
-            const int total = n * C;
-            const float ly = __fdiv_rn((float)rhoY, (float)denY);
-            const long rowOut = (long)oy * Wo;
-            for (int e = threadIdx.x; e < total; e += 256) {
-                const int c = e / n, i = e - c * n;
-                const int ox = tile * 64 + (n == 64 ? i : cb_select_bit(word, i));
-                int x0, x1, rho, den;
-                cbu_source<MODE>(ox, Wi, sW, Wo, x0, x1, rho, den);
-                const T* src = in + (long)c * HWi;
-                T res;
-                if (MODE == 0) {
-                    res = src[(long)y0 * Wi + x0];      // (a copy: bit for bit)
-                } else {
-                    // lambda = rho / den, one IEEE division; the value in f32, rounded to T once
-                    const float lx = __fdiv_rn((float)rho, (float)den);
-                    const float a = cbd_load(src + (long)y0 * Wi + x0), b = cbd_load(src + (long)y0 * Wi + x1);
-                    const float cc = cbd_load(src + (long)y1 * Wi + x0), d = cbd_load(src + (long)y1 * Wi + x1);
-                    const float top = (1.f - lx) * a + lx * b, bot = (1.f - lx) * cc + lx * d;
-                    res = (T)((1.f - ly) * top + ly * bot);
-                }
-                out[(long)c * HWo + rowOut + ox] = res;
+            return (unsigned long long)__ballot(bit);
+        },
+        [&](int c, int oy, int ox) {
+            int x0, x1, rho, den;
+            cbu_source<MODE>(ox, Wi, sW, Wo, x0, x1, rho, den);
+            const T* src = in + (long)c * HWi;
+            T res;
+            if (MODE == 0) {
+                res = src[(long)y0 * Wi + x0];      // (a copy: bit for bit)
+            } else {
+                // lambda = rho / den, one IEEE division; the value in f32, rounded to T once
+                const float ly = __fdiv_rn((float)rhoY, (float)denY), lx = __fdiv_rn((float)rho, (float)den);
+                const float a = cb_load_f32(src + (long)y0 * Wi + x0), b = cb_load_f32(src + (long)y0 * Wi + x1);
+                const float cc = cb_load_f32(src + (long)y1 * Wi + x0), d = cb_load_f32(src + (long)y1 * Wi + x1);
+                const float top = (1.f - lx) * a + lx * b, bot = (1.f - lx) * cc + lx * d;
+                res = (T)((1.f - ly) * top + ly * bot);
             }
-        }
-        if (own != 0) {
-            __syncthreads();      // every wave has read the word
-            if (threadIdx.x == 0) bits[w] = 0;
-        }
-    }
+            out[(long)c * HWo + (long)oy * Wo + ox] = res;
+        });
 }
 
 inline int cbu_mode(const cbUpsample& u) {
@@ -168,10 +147,7 @@ void cbu_launch(const void* in, void* out, const uint64_t* inMask, int all, uint
     const int Ho = Hi * u.sH, Wo = Wi * u.sW;
     const int wprO = (Wo + 63) / 64, wprI = (Wi + 63) / 64;
     const long words = (long)Ho * wprO;
-    long blocks = words;
-    const long cap = (long)cb_num_cus() * 8;
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(cb_walk_grid(words)), block(256);
 #define CBU_GO(MODE)                                                                                                  \
     hipLaunchKernelGGL((cbu_upsample_kernel<T, MODE>), grid, block, 0, s, (const T*)in, (T*)out,                     \
                        (const unsigned long long*)inMask, all, (unsigned long long*)bits,                            \
@@ -270,10 +246,7 @@ template <typename T>
 void cbc_launch(const cbc_operands& ops, void* out, uint64_t* bits, uint64_t* maskCopy, int H, int W, hipStream_t s) {
     const int wpr = (W + 63) / 64;
     const long words = (long)H * wpr;
-    long blocks = words;
-    const long cap = (long)cb_num_cus() * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((cbc_concat_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, s, ops, (T*)out,
+    hipLaunchKernelGGL((cbc_concat_kernel<T>), dim3(cb_walk_grid(words)), dim3(256), 0, s, ops, (T*)out,
                        (unsigned long long*)bits, (unsigned long long*)maskCopy, words, H, W, wpr);
 }
 
@@ -303,10 +276,9 @@ int cbinfer_cbupsample_forward(const void* input, void* outputState, const uint6
         const int st = cb_launch_status();
         if (st != CB_OK) return st;
     }
-    if (dtype == CB_F32)
-        cbu_launch<float>(input, outputState, inputMask, all, bits, maskCopy, C, Hi, Wi, *up, (hipStream_t)stream);
-    else
-        cbu_launch<cb_half>(input, outputState, inputMask, all, bits, maskCopy, C, Hi, Wi, *up, (hipStream_t)stream);
+    cb_dispatch_dtype(dtype, [&](auto t) {
+        cbu_launch<decltype(t)>(input, outputState, inputMask, all, bits, maskCopy, C, Hi, Wi, *up, (hipStream_t)stream);
+    });
     return cb_launch_status();
 }
 
@@ -338,16 +310,14 @@ int cbinfer_cbconcat_forward(const void* const* sources, const int32_t* channels
         total += channels[k];
         CB_REQUIRE(total * 64 < (1l << 31));      // (the kernel numbers a word's items with an int)
     }
-    const cbPool one = {1, 1, 1, 1, 0, 0, 0, CB_POOL_MAX};      // a 1x1 / stride-1 window reaches its own pixel only
     for (int k = 0; k < n; ++k)
         if (lists && lists[k]) {
-            const int st = cbinfer_pool_footprint(lists[k], caps ? caps[k] : 0, counts ? counts[k] : nullptr, nullptr, H,
-                                                  W, &one, bits + k * words, stream);
+            const int st = cb_list_to_bits(lists[k], caps ? caps[k] : 0, counts ? counts[k] : nullptr, H, W,
+                                           bits + k * words, stream);
             if (st != CB_OK) return st;
         }
-    if (dtype == CB_F32)
-        cbc_launch<float>(ops, outputState, bits, maskCopy, H, W, (hipStream_t)stream);
-    else
-        cbc_launch<cb_half>(ops, outputState, bits, maskCopy, H, W, (hipStream_t)stream);
+    cb_dispatch_dtype(dtype, [&](auto t) {
+        cbc_launch<decltype(t)>(ops, outputState, bits, maskCopy, H, W, (hipStream_t)stream);
+    });
     return cb_launch_status();
 }

@@ -1,7 +1,8 @@
 // Change-based depthwise convolution (groups == in_channels, channel multiplier) on gfx950.  The
 // reference has no such operator; contracts of the entry points in include/cbinfer_hip.h.  A depthwise layer is not a
 // contraction: output channel k reads input channel k / mult only, kH kW taps each.  It is a VALU stencil driven by the
-// change mask of the OUTPUT map, in the form of cb_pool2d.hip and cb_add.hip:
+// change mask of the OUTPUT map.  Not the word walk of cb_maskwalk.h (its unit is word x channel block and it only reads
+// the mask copy); it takes the header's grid sizing, load pair and dtype dispatch:
 //   unit       one mask word (64 consecutive output pixels of a row) x a block of 16 output channels; a persistent
 //              grid strides over the units.  Lane = output column, unlisted lanes are predicated off, an empty word
 //              costs its one load.  A wave takes four channels side by side (four independent loads per tap); the
@@ -15,15 +16,12 @@
 //              stencil launch then only READS maskCopy -- with units that split a word's channels over workgroups no
 //              unit could zero the word while others still read it.
 // No LDS, no inline assembly, no atomics beyond the one arrival counter; all stores are plain vector stores.
-#include "cb_common.h"
+#include "cb_maskwalk.h"
 
 namespace {
 
 #define CBDW_CB 16      // output channels per unit
 #define CBDW_WC 4       // ... of which each of the four waves takes four, side by side
-
-__device__ __forceinline__ float cbdw_load(const float* p) { return *p; }
-__device__ __forceinline__ float cbdw_load(const cb_half* p) { return (float)*p; }
 
 // bits -> maskCopy, bits <- 0 (all != 0: every pixel of the map is listed instead; bits is zeroed all the same)
 __global__ __launch_bounds__(256) void cbdw_take_kernel(unsigned long long* __restrict__ bits,
@@ -83,7 +81,7 @@ __global__ __launch_bounds__(256) void cbdw_kernel(const T* __restrict__ in, con
             const int k = min(k0 + j, K - 1);      // (a channel behind the last one is computed twice and not stored)
             src[j] = in + (long)(k / mult) * HWi;
             wk[j] = wgt + (long)k * taps;
-            acc[j] = bias ? cbdw_load(bias + k) : 0.f;
+            acc[j] = bias ? cb_load_f32(bias + k) : 0.f;
         }
         bool hit = false;
         for (int ky = 0; ky < g.kH; ++ky) {
@@ -97,8 +95,8 @@ __global__ __launch_bounds__(256) void cbdw_kernel(const T* __restrict__ in, con
                 float v[CBDW_WC], wv[CBDW_WC];
 #pragma unroll
                 for (int j = 0; j < CBDW_WC; ++j) {
-                    v[j] = cbdw_load(src[j] + off);
-                    wv[j] = cbdw_load(wk[j] + ky * g.kW + kx);
+                    v[j] = cb_load_f32(src[j] + off);
+                    wv[j] = cb_load_f32(wk[j] + ky * g.kW + kx);
                 }
 #pragma unroll
                 for (int j = 0; j < CBDW_WC; ++j) acc[j] = ok ? __builtin_fmaf(wv[j], v[j], acc[j]) : acc[j];
@@ -131,10 +129,7 @@ void cbdw_launch(const void* in, const void* wgt, const void* bias, void* out, u
                  int K, int mult, int Hi, int Wi, int Ho, int Wo, const cbGeom& g, int act, hipStream_t s) {
     const int wpr = (Wo + 63) / 64;
     const long words = (long)Ho * wpr;
-    long blocks = words * ((K + CBDW_CB - 1) / CBDW_CB);
-    const long cap = (long)cb_num_cus() * 8;
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(cb_walk_grid(words * ((K + CBDW_CB - 1) / CBDW_CB))), block(256);
 #define CBDW_GO(ACT)                                                                                                  \
     hipLaunchKernelGGL((cbdw_kernel<T, ACT>), grid, block, 0, s, (const T*)in, (const T*)wgt, (const T*)bias, (T*)out, \
                        (unsigned long long*)frameMasks, (const unsigned long long*)mask, words, K, mult, Hi, Wi, Ho,  \
@@ -146,6 +141,22 @@ void cbdw_launch(const void* in, const void* wgt, const void* bias, void* out, u
     else
         CBDW_GO(CB_ACT_NONE);
 #undef CBDW_GO
+}
+
+// the launch in front of a bits / maskCopy frame (cbdw_take_kernel), then the stencil reading maskCopy
+int cbdw_take_and_launch(const void* in, const void* wgt, const void* bias, void* out, uint64_t* bits, uint64_t* maskCopy,
+                         int all, int K, int mult, int Hi, int Wi, int Ho, int Wo, const cbGeom& g, int act, int dtype,
+                         hipStream_t s) {
+    const int wpr = (Wo + 63) / 64;
+    const long words = (long)Ho * wpr;
+    hipLaunchKernelGGL(cbdw_take_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s,
+                       (unsigned long long*)bits, (unsigned long long*)maskCopy, words, Wo, wpr, all);
+    const int st = cb_launch_status();
+    if (st != CB_OK) return st;
+    cb_dispatch_dtype(dtype, [&](auto t) {
+        cbdw_launch<decltype(t)>(in, wgt, bias, out, nullptr, maskCopy, K, mult, Hi, Wi, Ho, Wo, g, act, s);
+    });
+    return cb_launch_status();
 }
 
 // CB_OK and the output map, or the status every entry point returns before its first launch
@@ -188,20 +199,13 @@ int cbinfer_dwconv_changed(const void* input, const void* weight, const void* bi
     int Ho, Wo;
     const int st = cbdw_shape(C, mult, Hi, Wi, geom, act, dtype, &Ho, &Wo);
     if (st != CB_OK) return st;
-    if (!frameMasks) {
-        const int wpr = (Wo + 63) / 64;
-        const long words = (long)Ho * wpr;
-        hipLaunchKernelGGL(cbdw_take_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           (unsigned long long*)bits, (unsigned long long*)maskCopy, words, Wo, wpr, 0);
-        const int e = cb_launch_status();
-        if (e != CB_OK) return e;
-    }
-    if (dtype == CB_F32)
-        cbdw_launch<float>(input, weight, bias, output, frameMasks, maskCopy, C * mult, mult, Hi, Wi, Ho, Wo, *geom, act,
-                           (hipStream_t)stream);
-    else
-        cbdw_launch<cb_half>(input, weight, bias, output, frameMasks, maskCopy, C * mult, mult, Hi, Wi, Ho, Wo, *geom,
-                             act, (hipStream_t)stream);
+    if (!frameMasks)
+        return cbdw_take_and_launch(input, weight, bias, output, bits, maskCopy, 0, C * mult, mult, Hi, Wi, Ho, Wo, *geom,
+                                    act, dtype, (hipStream_t)stream);
+    cb_dispatch_dtype(dtype, [&](auto t) {
+        cbdw_launch<decltype(t)>(input, weight, bias, output, frameMasks, nullptr, C * mult, mult, Hi, Wi, Ho, Wo, *geom,
+                                 act, (hipStream_t)stream);
+    });
     return cb_launch_status();
 }
 
@@ -239,21 +243,9 @@ int cbinfer_cbdwconv2d_forward_propagated(const void* input, void* outputState, 
     cbPool win;
     if (!cbdw_window(*geom, &win)) return CB_ERR_UNSUPPORTED;
     CB_REQUIRE((long)Hi * Wi < (1l << 31));
-    if (allPixels) {
-        const int wpr = (Wo + 63) / 64;
-        const long words = (long)Ho * wpr;
-        hipLaunchKernelGGL(cbdw_take_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           (unsigned long long*)bits, (unsigned long long*)maskCopy, words, Wo, wpr, 1);
-        st = cb_launch_status();
-        if (st != CB_OK) return st;
-        if (dtype == CB_F32)
-            cbdw_launch<float>(input, weight, bias, outputState, nullptr, maskCopy, C * mult, mult, Hi, Wi, Ho, Wo, *geom,
-                               act, (hipStream_t)stream);
-        else
-            cbdw_launch<cb_half>(input, weight, bias, outputState, nullptr, maskCopy, C * mult, mult, Hi, Wi, Ho, Wo,
-                                 *geom, act, (hipStream_t)stream);
-        return cb_launch_status();
-    }
+    if (allPixels)
+        return cbdw_take_and_launch(input, weight, bias, outputState, bits, maskCopy, 1, C * mult, mult, Hi, Wi, Ho, Wo,
+                                    *geom, act, dtype, (hipStream_t)stream);
     st = cbinfer_pool_footprint(changeIndexes, capN, countDev, inputMask, Hi, Wi, &win, bits, stream);
     if (st != CB_OK) return st;
     return cbinfer_dwconv_changed(input, weight, bias, outputState, nullptr, bits, maskCopy, C, mult, Hi, Wi, geom, act,

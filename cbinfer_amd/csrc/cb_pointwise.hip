@@ -3,15 +3,13 @@
 // leaves the pixels outside its change list bit for bit as they were, so f(x) can differ from last frame's only at the
 // operand's changed pixels: recomputing there gives the dense result exactly, without a threshold.  A frame is
 //   for an operand in LIST form, one launch in front: the list's bits ORed into the zeroed working mask
-//              (cbinfer_pool_footprint of cb_pool2d.hip with a 1x1 / stride-1 window: one 64-bit atomicOr per entry);
-//   one launch, mask-driven in cba_add_kernel's form: workgroups of four waves stride over the mask words, OR the
-//              operand's change mask (or the full row word of an operand without change information) into the working
-//              word themselves, and spread the (set bit, channel) items of a non-empty word over the 256 threads, set bit
-//              fastest.  The word's owner copies it to the frame's mask copy and zeroes the working word.
+//              (cb_list_to_bits of cb_maskwalk.h);
+//   one launch, the word walk of cb_maskwalk.h (cb_walk_words): the operand's change mask (or the full row word of an
+//              operand without change information) is ORed into the working word, one value per (set bit, channel).
 // The function is a template parameter (one kernel per kind and dtype); the affine and its per-channel operands are
 // decided by a pointer that is uniform over the launch.  No LDS, host sync, memset, allocation, data atomics or inline
 // assembly.
-#include "cb_common.h"
+#include "cb_maskwalk.h"
 
 // hipcc contracts a * b + c to an FMA by default -- also through __fmul_rn / __fadd_rn, which are plain operators compiled
 // under the header's own setting --, so the arithmetic below is written with operators under this file's pragma:
@@ -19,9 +17,6 @@
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ float cbw_load(const float* p) { return *p; }
-__device__ __forceinline__ float cbw_load(const cb_half* p) { return (float)*p; }
 
 // lo <= t <= hi by comparisons: a NaN stays a NaN (fminf / fmaxf would drop it)
 __device__ __forceinline__ float cbw_clamp(float t, float lo, float hi) { return t < lo ? lo : (t > hi ? hi : t); }
@@ -57,34 +52,16 @@ __global__ __launch_bounds__(256) void cbw_pointwise_kernel(const T* __restrict_
                                                            const float* __restrict__ slope, float p0, float p1,
                                                            long words, int C, int H, int W, int wpr) {
     const long HW = (long)H * W;
-    for (long w = blockIdx.x; w < words; w += gridDim.x) {
-        // (uniform over the workgroup: the working word is zeroed only behind the barrier below)
-        const unsigned long long own = bits[w];
-        const int y = (int)(w / wpr), tile = (int)(w - (long)y * wpr);
-        const unsigned long long valid = cb_valid_mask(W, tile);
-        unsigned long long word = own;
-        if (mask) word |= mask[w];
-        word = all ? valid : (word & valid);      // (the bits of the row padding are never set)
-        if (threadIdx.x == 0) maskCopy[w] = word;
-        if (word != 0) {
-            const int n = __popcll(word);
-            const long rowBase = (long)y * W + tile * 64;
-            const int total = n * C;
-            for (int e = threadIdx.x; e < total; e += 256) {
-                const int c = e / n, i = e - c * n;
-                const long o = (long)c * HW + rowBase + (n == 64 ? i : cb_select_bit(word, i));
-                float v = cbw_load(x + o);
-                // two roundings, never one FMA
-                if (scale) v = v * scale[c] + shift[c];
-                v = cbw_act<KIND>(v, p0, p1, KIND == CB_PW_PRELU ? slope[c] : 0.f);
-                out[o] = (T)v;      // fp16: rounded once
-            }
-        }
-        if (own != 0) {
-            __syncthreads();      // every wave has read the word
-            if (threadIdx.x == 0) bits[w] = 0;
-        }
-    }
+    cb_walk_words(
+        bits, maskCopy, words, C, W, wpr, all, [&](long w, int, int) { return mask ? mask[w] : 0ull; },
+        [&](int c, int y, int col) {
+            const long o = (long)c * HW + (y * W + col);      // (H W fits an int: cbw_args_ok)
+            float v = cb_load_f32(x + o);
+            // two roundings, never one FMA
+            if (scale) v = v * scale[c] + shift[c];
+            v = cbw_act<KIND>(v, p0, p1, KIND == CB_PW_PRELU ? slope[c] : 0.f);
+            out[o] = (T)v;      // fp16: rounded once
+        });
 }
 
 template <typename T>
@@ -93,10 +70,7 @@ void cbw_launch(const void* x, void* out, const uint64_t* mask, int all, uint64_
                 hipStream_t s) {
     const int wpr = (W + 63) / 64;
     const long words = (long)H * wpr;
-    long blocks = words;
-    const long cap = (long)cb_num_cus() * 8;
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(cb_walk_grid(words)), block(256);
 #define CBW_GO(KIND)                                                                                                  \
     case KIND:                                                                                                        \
         hipLaunchKernelGGL((cbw_pointwise_kernel<T, KIND>), grid, block, 0, s, (const T*)x, (T*)out,                  \
@@ -141,12 +115,10 @@ int cbinfer_pointwise_changed(const void* x, void* out, const uint64_t* mask, in
                               int C, int H, int W, int kind, float p0, float p1, const float* scale, const float* shift,
                               const float* slope, int dtype, cbStream_t stream) {
     CB_REQUIRE(cbw_args_ok(x, out, mask, bits, maskCopy, C, H, W, kind, p0, p1, scale, shift, slope, dtype));
-    if (dtype == CB_F32)
-        cbw_launch<float>(x, out, mask, all, bits, maskCopy, C, H, W, kind, p0, p1, scale, shift, slope,
-                          (hipStream_t)stream);
-    else
-        cbw_launch<cb_half>(x, out, mask, all, bits, maskCopy, C, H, W, kind, p0, p1, scale, shift, slope,
-                            (hipStream_t)stream);
+    cb_dispatch_dtype(dtype, [&](auto t) {
+        cbw_launch<decltype(t)>(x, out, mask, all, bits, maskCopy, C, H, W, kind, p0, p1, scale, shift, slope,
+                                (hipStream_t)stream);
+    });
     return cb_launch_status();
 }
 
@@ -158,8 +130,7 @@ int cbinfer_cbpointwise_forward(const void* x, void* outputState, const uint64_t
     CB_REQUIRE(cbw_args_ok(x, outputState, mask, bits, maskCopy, C, H, W, kind, p0, p1, scale, shift, slope, dtype));
     CB_REQUIRE(capN >= 0 && !(mask && list) && (list || !countDev));
     if (list) {
-        const cbPool one = {1, 1, 1, 1, 0, 0, 0, CB_POOL_MAX};      // a 1x1 / stride-1 window reaches its own pixel only
-        const int st = cbinfer_pool_footprint(list, capN, countDev, nullptr, H, W, &one, bits, stream);
+        const int st = cb_list_to_bits(list, capN, countDev, H, W, bits, stream);
         if (st != CB_OK) return st;
     }
     return cbinfer_pointwise_changed(x, outputState, mask, !mask && !list, bits, maskCopy, C, H, W, kind, p0, p1, scale,

@@ -6,12 +6,12 @@
 //              output row it reaches, at most two 64-bit atomicOr per row) or from its change MASK (one wave per output
 //              mask word, one ballot, no atomics);
 //   pooling    mask-driven: workgroups of four waves stride over the output mask words, the (set bit, channel) items of
-//              a non-empty word spread over the 256 threads, set bit fastest.  The word's owner copies it to the frame's
-//              mask copy and zeroes it in the working mask for the next frame.
+//              a non-empty word spread over the 256 threads (cb_walk_items of cb_maskwalk.h).  The word's owner copies
+//              it to the frame's mask copy and zeroes it in the working mask for the next frame.
 // No host sync, memset, allocation, data atomics or inline assembly.
 #include <math.h>
 
-#include "cb_common.h"
+#include "cb_maskwalk.h"
 
 namespace {
 
@@ -86,12 +86,10 @@ __global__ __launch_bounds__(256) void cbp2_footprint_mask_kernel(const unsigned
     if (lane == 0 && m) bits[word] |= m;
 }
 
-// torch's max rule (max_pool2d: a later value wins only if greater; a NaN wins always)
-__device__ __forceinline__ float cbp2_load(const float* p) { return *p; }
-__device__ __forceinline__ float cbp2_load(const cb_half* p) { return (float)*p; }
-
 // Pooling driven by the mask.  OP 0: max, 1: average, divisor counts the padding, 2: average over the in-map pixels.
 // The average is summed in f32 in row-major window order and divided once (IEEE division), then rounded to T once.
+// The outer loop is this kernel's own, not cb_walk_words: cbinfer_pool_changed copies every word of `bits` to maskCopy AS
+// IT IS, row-padding bits a caller set included (they are skipped per item), where the walk cuts the word to the row.
 template <typename T, int OP>
 __global__ __launch_bounds__(256) void cbp2_pool_kernel(const T* __restrict__ in, T* __restrict__ out,
                                                        unsigned long long* bits, unsigned long long* __restrict__ maskCopy,
@@ -103,37 +101,35 @@ __global__ __launch_bounds__(256) void cbp2_pool_kernel(const T* __restrict__ in
         const unsigned long long word = bits[w];
         if (threadIdx.x == 0) maskCopy[w] = word;
         if (word == 0) continue;
-        const int n = __popcll(word);
         const int oy = (int)(w / wprO), xBase = (int)(w - (long)oy * wprO) * 64;
         const int y0 = oy * g.sH - g.pH;
         const int yl = max(y0, 0), yh = min(y0 + g.kH, Hi);
-        const int total = n * C;
-        for (int e = threadIdx.x; e < total; e += 256) {
-            const int c = e / n, i = e - c * n;
-            const int ox = xBase + cb_select_bit(word, i);
-            if (ox >= Wo) continue;      // (a bit of the row padding: never set by the footprint launches)
+        cb_walk_items(word, C, [&](int c, int bit) {
+            const int ox = xBase + bit;
+            if (ox >= Wo) return;      // (a bit of the row padding: never set by the footprint launches)
             const int x0 = ox * g.sW - g.pW;
             const int xl = max(x0, 0), xh = min(x0 + g.kW, Wi);
             const T* src = in + (long)c * HWi;
             T res;
             if (OP == 0) {
+                // torch's max rule (max_pool2d: a later value wins only if greater; a NaN wins always)
                 float v = -INFINITY;
                 for (int y = yl; y < yh; ++y)
                     for (int x = xl; x < xh; ++x) {
-                        const float t = cbp2_load(src + (long)y * Wi + x);
+                        const float t = cb_load_f32(src + (long)y * Wi + x);
                         if (t > v || t != t) v = t;
                     }
                 res = (T)v;      // (exact: v is one of the inputs, or -inf for an empty window)
             } else {
                 float sum = 0.f;
                 for (int y = yl; y < yh; ++y)
-                    for (int x = xl; x < xh; ++x) sum += cbp2_load(src + (long)y * Wi + x);
+                    for (int x = xl; x < xh; ++x) sum += cb_load_f32(src + (long)y * Wi + x);
                 const int div = OP == 1 ? (min(y0 + g.kH, Hi + g.pH) - y0) * (min(x0 + g.kW, Wi + g.pW) - x0)
                                         : (yh - yl) * (xh - xl);
                 res = (T)__fdiv_rn(sum, (float)div);
             }
             out[(long)c * HWo + (long)oy * Wo + ox] = res;
-        }
+        });
         __syncthreads();      // every wave has read the word
         if (threadIdx.x == 0) bits[w] = 0;
     }
@@ -150,10 +146,7 @@ int cbp2_axis_out(int n, int k, int s, int p, int ceilMode) {
 template <typename T>
 void cbp2_launch_pool(const void* input, void* output, uint64_t* bits, uint64_t* maskCopy, long words, int C, int Hi,
                       int Wi, int Ho, int Wo, const cbPool& g, hipStream_t s) {
-    long blocks = words;
-    const long cap = (long)cb_num_cus() * 8;
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(cb_walk_grid(words)), block(256);
     const int wprO = (Wo + 63) / 64;
 #define CBP2_GO(OP)                                                                                                   \
     hipLaunchKernelGGL((cbp2_pool_kernel<T, OP>), grid, block, 0, s, (const T*)input, (T*)output,                    \
@@ -222,10 +215,9 @@ int cbinfer_pool_changed(const void* input, void* output, uint64_t* bits, uint64
     // (the kernel numbers a word's items with an int)
     CB_REQUIRE((long)C * 64 < (1l << 31));
     const long words = (long)Ho * ((Wo + 63) / 64);
-    if (dtype == CB_F32)
-        cbp2_launch_pool<float>(input, output, bits, maskCopy, words, C, Hi, Wi, Ho, Wo, *pool, (hipStream_t)stream);
-    else
-        cbp2_launch_pool<cb_half>(input, output, bits, maskCopy, words, C, Hi, Wi, Ho, Wo, *pool, (hipStream_t)stream);
+    cb_dispatch_dtype(dtype, [&](auto t) {
+        cbp2_launch_pool<decltype(t)>(input, output, bits, maskCopy, words, C, Hi, Wi, Ho, Wo, *pool, (hipStream_t)stream);
+    });
     return cb_launch_status();
 }
 

@@ -18,49 +18,10 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .conv2d import CBConv2d, CBPoolAvg2d, CBPoolMax2d, _same_shape
-from .conv2d_cg import ChangeIndexes, MaskChangeIndexes
-from .residual import CBAdd2d, CBResidual
+from .chain import CBStateModule, hand_on_changes, mask_workspace, operand_changes, producer_types, split_operand
+from .conv2d import CBConv2d, _same_shape
 
 MAX_SCALE = 8
-
-
-def _split(name, x, which):
-    """(contiguous tensor, change indexes or None) of an operand: a tensor or ('changeIndexes', tensor, indexes)."""
-    if type(x) == tuple:
-        if len(x) != 3 or x[0] != 'changeIndexes':
-            raise CBinferError("%s: %s is a tuple, but not ('changeIndexes', tensor, indexes)" % (name, which))
-        x, indexes = x[1], x[2]
-    else:
-        indexes = None
-    if not torch.is_tensor(x):
-        raise CBinferError("%s: %s must be a tensor or the ('changeIndexes', tensor, indexes) tuple, got %s"
-                           % (name, which, type(x).__name__))
-    return x.detach().contiguous(), indexes
-
-
-def _form(name, which, indexes, H, W, dev, spare):
-    """(mask, list, capacity, device count) of an operand's changes on its H x W map; all None / 0: every pixel is
-    listed.  `spare`: any int32 device buffer, which stands for the empty list (an empty tensor has no address)."""
-    if indexes is None:
-        return None, None, 0, None
-    if isinstance(indexes, ChangeIndexes):
-        if indexes.size is not None and tuple(indexes.size) != (H, W):
-            raise CBinferError("%s: the change indexes of %s address a %dx%d map, the tensor is a %dx%d map"
-                               % ((name, which) + tuple(indexes.size) + (H, W)))
-        if isinstance(indexes, MaskChangeIndexes) and indexes._mask is not None:
-            return indexes._mask, None, 0, None      # (the producer's list is not needed)
-        idx, count = indexes.buffer, indexes.count
-    elif torch.is_tensor(indexes):
-        idx, count = indexes.detach(), None
-    else:
-        raise CBinferError("%s: the change indexes of %s must be an int32 tensor or a ChangeIndexes, got %s"
-                           % (name, which, type(indexes).__name__))
-    if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != dev:
-        raise CBinferError("%s: the change indexes of %s must be a contiguous one-dimensional int32 tensor on the "
-                           "tensor's device" % (name, which))
-    cap = idx.numel()
-    return None, (idx if cap else spare), cap, count
 
 
 def _integer_scale(v):
@@ -103,44 +64,7 @@ def _check_upsample(m):
     return pair[0], pair[1], m.mode, bool(m.align_corners)
 
 
-class _CBDecoderModule(nn.Module):
-    """What the two modules share: the state buffer, the flags of CBAdd2d, transient work buffers."""
-
-    def __init__(self):
-        super(_CBDecoderModule, self).__init__()
-        self.propChangeIndexes = False
-        self.cloneOutput = True
-        self.register_buffer('outputState', torch.zeros(0))
-        self.clearMemory()
-
-    def clearMemory(self):
-        if 'outputState' not in self._buffers:
-            self.register_buffer('outputState', torch.zeros(0))
-        self.outputState = self.outputState.new_zeros(0)
-        self.__dict__['_work'] = None      # (device work buffers and ctypes arguments, not part of the state)
-
-    def getStateTensors(self):
-        return [self.outputState]
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        for name in ('_work', '_upC'):      # (transient: device work buffers, ctypes arguments)
-            if name in d:
-                d[name] = None
-        return d
-
-    def _result(self, work, H, W):
-        if self.cloneOutput:
-            output = self.outputState.clone()
-        else:
-            output = self.outputState
-            output._cbinfer_inplace_state = True
-        if self.propChangeIndexes:
-            return 'changeIndexes', output, MaskChangeIndexes(work['copy'], (H, W), work['idx'], work['count'])
-        return output
-
-
-class CBUpsample2d(_CBDecoderModule):
+class CBUpsample2d(CBStateModule):
     """nn.Upsample with an integer scale_factor (1..8 per axis), mode 'nearest' or 'bilinear' (align_corners False or
     True), recomputed at the output pixels that read a changed input pixel.
 
@@ -149,6 +73,8 @@ class CBUpsample2d(_CBDecoderModule):
     mask (one launch, the list is not needed); any other ChangeIndexes, or an exact int32 tensor, as a list (one launch
     in front).  The flags are CBAdd2d's: propChangeIndexes hands on the frame's footprint as a MaskChangeIndexes on the
     OUTPUT map; cloneOutput=False hands out the state itself, tagged, and the frame is then free of torch operators."""
+
+    _TRANSIENT = ('_upC',)
 
     def __init__(self, m):
         super(CBUpsample2d, self).__init__()
@@ -170,17 +96,11 @@ class CBUpsample2d(_CBDecoderModule):
         work = self.__dict__.get('_work')
         if work is None or work['key'] != key:
             Ho, Wo = Hi * self.scale_factor[0], Wi * self.scale_factor[1]
-            words = C.cbinfer_mask_words(Ho, Wo)
-            work = self.__dict__['_work'] = dict(
-                key=key, size=(Ho, Wo),
-                bits=torch.zeros(words, dtype=torch.int64, device=dev),
-                copy=torch.zeros(words, dtype=torch.int64, device=dev),
-                idx=torch.empty(Ho * Wo, dtype=torch.int32, device=dev),
-                count=torch.zeros(1, dtype=torch.int32, device=dev))
+            work = self.__dict__['_work'] = dict(mask_workspace(Ho, Wo, dev), key=key, size=(Ho, Wo))
         return work
 
     def forward(self, inp):
-        x, indexes = _split('CBUpsample2d', inp, 'the input')
+        x, indexes = split_operand('CBUpsample2d', inp, 'the input')
         if x.dim() != 4 or x.size(0) != 1:
             raise CBinferError("CBUpsample2d: the input must be a [1, C, H, W] tensor, got %s" % (tuple(x.shape),))
         if x.dtype not in (torch.float32, torch.float16):
@@ -189,7 +109,7 @@ class CBUpsample2d(_CBDecoderModule):
         nc, Hi, Wi = x.size(1), x.size(2), x.size(3)
         work = self._workspace(Hi, Wi, x.device)
         Ho, Wo = work['size']
-        form = _form('CBUpsample2d', 'the input', indexes, Hi, Wi, x.device, work['idx'])
+        form = operand_changes('CBUpsample2d', 'the input', indexes, Hi, Wi, x.device, work['idx'])
         if (not _same_shape(self.outputState, (1, nc, Ho, Wo)) or self.outputState.dtype != x.dtype or
                 self.outputState.device != x.device):
             # a new state is written completely: the change information is not used
@@ -205,7 +125,7 @@ class CBUpsample2d(_CBDecoderModule):
                 % (self.scale_factor, self.mode, self.align_corners, self.propChangeIndexes))
 
 
-class CBConcat2d(_CBDecoderModule):
+class CBConcat2d(CBStateModule):
     """torch.cat(operands, dim=1) of 2..4 [1, Ck, H, W] maps: operand k's channels are copied at operand k's changed
     pixels only -- a skip connection that did not change is not touched -- and the union of the operands' changes is
     handed on.
@@ -228,13 +148,8 @@ class CBConcat2d(_CBDecoderModule):
         key = (n, H, W, dev)
         work = self.__dict__.get('_work')
         if work is None or work['key'] != key:
-            words = C.cbinfer_mask_words(H, W)
             work = self.__dict__['_work'] = dict(
-                key=key,
-                bits=torch.zeros(n * words, dtype=torch.int64, device=dev),
-                copy=torch.zeros(words, dtype=torch.int64, device=dev),
-                idx=torch.empty(H * W, dtype=torch.int32, device=dev),
-                count=torch.zeros(1, dtype=torch.int32, device=dev),
+                mask_workspace(H, W, dev, nbits=n), key=key,
                 srcs=(ctypes.c_void_p * n)(), chans=(ctypes.c_int32 * n)(), masks=(ctypes.c_void_p * n)(),
                 lists=(ctypes.c_void_p * n)(), caps=(ctypes.c_int32 * n)(), counts=(ctypes.c_void_p * n)())
         return work
@@ -246,7 +161,7 @@ class CBConcat2d(_CBDecoderModule):
         n = len(operands)
         if not 2 <= n <= 4:
             raise CBinferError("CBConcat2d: 2..4 operands, got %d" % n)
-        split = [_split('CBConcat2d', x, 'operand %d' % k) for k, x in enumerate(operands)]
+        split = [split_operand('CBConcat2d', x, 'operand %d' % k) for k, x in enumerate(operands)]
         t0 = split[0][0]
         for k, (t, _) in enumerate(split):
             if t.dim() != 4 or t.size(0) != 1:
@@ -261,7 +176,7 @@ class CBConcat2d(_CBDecoderModule):
         H, W = t0.size(2), t0.size(3)
         chans = tuple(t.size(1) for t, _ in split)
         work = self._workspace(n, H, W, t0.device)
-        forms = [_form('CBConcat2d', 'operand %d' % k, ix, H, W, t0.device, work['idx'])
+        forms = [operand_changes('CBConcat2d', 'operand %d' % k, ix, H, W, t0.device, work['idx'])
                  for k, (_, ix) in enumerate(split)]
         if (not _same_shape(self.outputState, (1, sum(chans), H, W)) or self.outputState.dtype != t0.dtype or
                 self.outputState.device != t0.device or self.__dict__.get('_channels') != chans):
@@ -282,7 +197,6 @@ class CBConcat2d(_CBDecoderModule):
 
 
 _UPSAMPLERS = (nn.Upsample, nn.UpsamplingNearest2d, nn.UpsamplingBilinear2d)
-_PRODUCERS = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d)
 
 
 def insertCBUpsampling(rootModule, cloneOutput=True):
@@ -297,15 +211,13 @@ def insertCBUpsampling(rootModule, cloneOutput=True):
         names = list(seq._modules.keys())
         for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
             prod, up = seq._modules[a], seq._modules[b]
-            if type(prod) not in _PRODUCERS or type(up) not in _UPSAMPLERS:
+            if type(prod) not in producer_types(forUpsampling=True) or type(up) not in _UPSAMPLERS:
                 continue
             try:
                 cb = CBUpsample2d(up)
             except CBinferError:
                 continue      # (beyond the limits: stays dense)
-            (prod.add if type(prod) is CBResidual else prod).propChangeIndexes = True
-            if type(prod) is CBPoolMax2d and not prod.__dict__.get('_general'):
-                prod.downsampleIndexes = True      # (the list of the pool's input addresses another map)
+            hand_on_changes(prod)
             cb.cloneOutput = cloneOutput
             seq._modules[b] = cb
             if pos + 2 < len(names):

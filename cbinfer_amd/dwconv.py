@@ -15,11 +15,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from . import decoder, tconv
-from .conv2d import CBConv2d, CBPoolMax2d, _padding_pair, _same_shape
-from .conv2d_cg import ChangeIndexes, MaskChangeIndexes
-from .residual import CBResidual
-from .tconv import CBConvTranspose2d
+from .chain import PROPAGATED, hand_back, hand_on_changes, is_1x1, mask_workspace, operand_changes, producer_types
+from .conv2d import _padding_pair, _same_shape
 
 MAX_K, MAX_S, MAX_D, MAX_P = 7, 4, 8, 64
 
@@ -172,41 +169,14 @@ class CBDepthwiseConv2d(nn.Module):
         work = self.__dict__.get('_work')
         if work is None or work['key'] != key:
             Ho, Wo = self._out_hw(Hi, Wi)
-            words = C.cbinfer_mask_words(Ho, Wo)
             frame = torch.zeros(C.cbinfer_frame_mask_bytes(Ho, Wo) // 8, dtype=torch.int64, device=dev)
             off = C.cbinfer_frame_mask_copy_offset(Ho, Wo) // 8
             work = self.__dict__['_work'] = dict(
-                key=key, size=(Ho, Wo), frame=frame, frameCopy=frame[off:off + words],
-                bits=torch.zeros(words, dtype=torch.int64, device=dev),
-                copy=torch.zeros(words, dtype=torch.int64, device=dev),
-                idx=torch.empty(Ho * Wo, dtype=torch.int32, device=dev),
-                count=torch.zeros(1, dtype=torch.int32, device=dev))
+                mask_workspace(Ho, Wo, dev), key=key, size=(Ho, Wo), frame=frame,
+                frameCopy=frame[off:off + C.cbinfer_mask_words(Ho, Wo)])
         return work
 
     # ---------------------------------------------------------------- frame
-    def _producer_changes(self, indexes, Hi, Wi, x, work):
-        """(list, capacity, device count, mask) of a producer's changes for cbinfer_cbdwconv2d_forward_propagated."""
-        Err = CBinferError
-        if isinstance(indexes, ChangeIndexes):
-            if indexes.size not in (None, (Hi, Wi)):
-                raise Err("CBDepthwiseConv2d: the propagated change indexes address a %dx%d map, this layer's input map "
-                          "is %dx%d" % (tuple(indexes.size) + (Hi, Wi)))
-            if (isinstance(indexes, MaskChangeIndexes) and not indexes._made and indexes._mask is not None and
-                    indexes.size == (Hi, Wi)):
-                return None, 0, None, indexes._mask      # (the producer's list is never made)
-            idx, count = indexes.buffer, indexes.count
-        elif isinstance(indexes, torch.Tensor):
-            idx, count = indexes.detach().contiguous(), None
-        else:
-            raise Err("CBDepthwiseConv2d: change indexes must be an int32 tensor or a ChangeIndexes")
-        if idx.dim() != 1 or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.device != x.device:
-            raise Err("CBDepthwiseConv2d: propagated change indexes must be a contiguous int32 tensor on the input's "
-                      "device")
-        cap = idx.numel()
-        if cap == 0:
-            idx = work['idx']      # (an empty tensor has no address: any buffer stands for the empty list)
-        return idx, cap, count, None
-
     def forward(self, inp):
         indexes = None
         if type(inp) == tuple:
@@ -237,12 +207,12 @@ class CBDepthwiseConv2d(nn.Module):
                                    "per axis (kernel_size=%s padding=%s dilation=%s): the layer must detect for itself"
                                    % (self.kernel_size, self.padding, self.dilation))
             fresh = self._state_for(x, Ho, Wo, keepInput=False)
-            idx, cap, count, mask = None, 0, None, None
+            # (checked on every frame, read on all but the first)
+            mask, idx, cap, count = operand_changes('CBDepthwiseConv2d', 'layer', indexes, Hi, Wi, x.device, work['idx'],
+                                                    **PROPAGATED)
             every = fresh or indexes is None
-            if indexes is not None:      # (checked on every frame, read on all but the first)
-                idx, cap, count, mask = self._producer_changes(indexes, Hi, Wi, x, work)
             if every:
-                idx, cap, count, mask = None, 0, None, None
+                mask, idx, cap, count = None, None, 0, None
             check(C.cbinfer_cbdwconv2d_forward_propagated(
                 ptr(x), ptr(self.prevOutput), ptr(idx), cap, ptr(count), ptr(mask), int(every), ptr(work['bits']),
                 ptr(work['copy']), ptr(weight), ptr(bias), Cin, mult, Hi, Wi, self._struct(), act, dt, stream_ptr(x)))
@@ -258,26 +228,13 @@ class CBDepthwiseConv2d(nn.Module):
             if not self.feedbackLoop and not self.copyInput:
                 self.prevInput = x.clone() if live else x
             copy = work['frameCopy']
-        if self.cloneOutput:
-            output = self.prevOutput.clone()
-        else:
-            output = self.prevOutput
-            output._cbinfer_inplace_state = True
-        if self.propChangeIndexes:
-            return 'changeIndexes', output, MaskChangeIndexes(copy, (Ho, Wo), work['idx'], work['count'])
-        return output
+        return hand_back(self, self.prevOutput, copy, (Ho, Wo), work)
 
     def __repr__(self):
         return ('CBDepthwiseConv2d (%d, %d, k=%s, s=%s, p=%s, d=%s, th=%s, withReLU=%s, reluCap=%s, propChgIdxs=%s, '
                 'propagated=%s)' % (self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding,
                                     self.dilation, self.threshold, self.withReLU, self.reluCap, self.propChangeIndexes,
                                     self.propagatedChanges))
-
-
-_DW_PRODUCERS = tconv._TCONV_PRODUCERS + (CBDepthwiseConv2d,)
-# the layer hands on its changes like every producer: insertCBUpsampling and insertCBTransposedConv take it as one
-decoder._PRODUCERS = decoder._PRODUCERS + (CBDepthwiseConv2d,)
-tconv._TCONV_PRODUCERS = tconv._TCONV_PRODUCERS + (CBDepthwiseConv2d,)
 
 
 def linkDepthwise(rootModule):
@@ -289,13 +246,10 @@ def linkDepthwise(rootModule):
     for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
         kids = list(seq.children())
         for prod, cons in zip(kids[:-1], kids[1:]):
-            if (type(cons) is CBDepthwiseConv2d and type(prod) in _DW_PRODUCERS and
+            if (type(cons) is CBDepthwiseConv2d and type(prod) in producer_types() and
                     _propagated_ok(cons.kernel_size, cons.padding, cons.dilation)):
                 cons.propagatedChanges = True
-                (prod.add if type(prod) is CBResidual else prod).propChangeIndexes = True
-                if type(prod) is CBPoolMax2d and not prod.__dict__.get('_general'):
-                    prod.downsampleIndexes = True      # (the list of the pool's input addresses another map)
-            if (type(prod) is CBDepthwiseConv2d and type(cons) is CBConv2d and tuple(cons.kernel_size) == (1, 1) and
-                    tuple(cons.stride) == (1, 1) and tuple(cons.padding) == (0, 0)):
+                hand_on_changes(prod)
+            if type(prod) is CBDepthwiseConv2d and is_1x1(cons):
                 prod.propChangeIndexes = True
     return rootModule

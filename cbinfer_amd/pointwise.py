@@ -12,11 +12,9 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from . import decoder, dwconv, tconv
-from .conv2d import CBConv2d, CBPoolMax2d, _same_shape
-from .conv2d_cg import MaskChangeIndexes
-from .decoder import _form, _split
-from .residual import CBResidual
+from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, producer_types,
+                    split_operand)
+from .conv2d import _same_shape
 
 # nn type (exactly, not a subclass) -> (CB_PW_* kind, p0, p1 of the instance)
 _ACTIVATIONS = {
@@ -54,7 +52,7 @@ def _bn_affine(norm):
         return scale.float(), shift.float()
 
 
-class CBPointwise2d(nn.Module):
+class CBPointwise2d(CBStateModule):
     """out = act(norm(x)), recomputed at the operand's changed pixels (no counterpart in the reference).
 
     act: None or an instance of exactly one of nn.ReLU, nn.ReLU6, nn.Hardtanh, nn.LeakyReLU, nn.PReLU (1 or C
@@ -70,6 +68,8 @@ class CBPointwise2d(nn.Module):
     is taken as its mask, as CBUpsample2d and CBConcat2d take it (its list is never made); any other ChangeIndexes, or an
     exact int32 tensor, as a list.  The flags are CBAdd2d's: propChangeIndexes hands on the frame's mask as a MaskChangeIndexes;
     cloneOutput=False hands out the state itself, tagged, and the frame is then free of torch operators."""
+
+    _WORK = '_pwWork'
 
     def __init__(self, act=None, norm=None):
         super(CBPointwise2d, self).__init__()
@@ -97,10 +97,8 @@ class CBPointwise2d(nn.Module):
                 slope = slope.to(scale.device)
         for name, t in zip(_PER_CHANNEL, (scale, shift, slope)):
             self.register_buffer(name, t)
-        self.propChangeIndexes = False
-        self.cloneOutput = True
-        self.register_buffer('outputState', torch.zeros(0))
-        self.clearMemory()
+        # (the state behind the per-channel operands, as state_dict() has always listed them)
+        self._buffers['outputState'] = self._buffers.pop('outputState')
 
     def _apply(self, fn, *args, **kwargs):
         # (.half() / .double() convert every floating-point buffer: the per-channel operands stay float32, the kernel's)
@@ -111,40 +109,20 @@ class CBPointwise2d(nn.Module):
                 self._buffers[n] = t.to(self._buffers[n].device)
         return self
 
-    def clearMemory(self):
-        if 'outputState' not in self._buffers:
-            self.register_buffer('outputState', torch.zeros(0))
-        self.outputState = self.outputState.new_zeros(0)
-        self.__dict__['_pwWork'] = None      # (device work buffers, not part of the state)
-
-    def getStateTensors(self):
-        return [self.outputState]
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d.update(_pwWork=None)      # (transient)
-        return d
-
     def _workspace(self, nc, H, W, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer and count, the slope of a
         one-parameter PReLU broadcast over the channels: once per map size."""
         key = (nc, H, W, dev)
         work = self.__dict__.get('_pwWork')
         if work is None or work['key'] != key:
-            words = C.cbinfer_mask_words(H, W)
             slope = self.slope
             if slope is not None and slope.numel() == 1 and nc != 1:
                 slope = slope.expand(nc).contiguous()
-            work = self.__dict__['_pwWork'] = dict(
-                key=key, slope=slope,
-                bits=torch.zeros(words, dtype=torch.int64, device=dev),
-                copy=torch.zeros(words, dtype=torch.int64, device=dev),
-                idx=torch.empty(H * W, dtype=torch.int32, device=dev),
-                count=torch.zeros(1, dtype=torch.int32, device=dev))
+            work = self.__dict__['_pwWork'] = dict(mask_workspace(H, W, dev), key=key, slope=slope)
         return work
 
     def forward(self, inp):
-        x, indexes = _split('CBPointwise2d', inp, 'the input')
+        x, indexes = split_operand('CBPointwise2d', inp, 'the input')
         if x.dim() != 4 or x.size(0) != 1:
             raise CBinferError("CBPointwise2d: the input must be a [1, C, H, W] tensor, got %s" % (tuple(x.shape),))
         if x.dtype not in (torch.float32, torch.float16):
@@ -162,7 +140,7 @@ class CBPointwise2d(nn.Module):
                 raise CBinferError("CBPointwise2d: the input is on %s, %s on %s (move the module with .to())"
                                    % (x.device, name, t.device))
         work = self._workspace(nc, H, W, x.device)
-        mask, lst, cap, count = _form('CBPointwise2d', 'the input', indexes, H, W, x.device, work['idx'])
+        mask, lst, cap, count = operand_changes('CBPointwise2d', 'the input', indexes, H, W, x.device, work['idx'])
         if (not _same_shape(self.outputState, x.shape) or self.outputState.dtype != x.dtype or
                 self.outputState.device != x.device):
             # a new state is written completely: the operand's change information is not used
@@ -172,31 +150,11 @@ class CBPointwise2d(nn.Module):
                                             ptr(work['bits']), ptr(work['copy']), nc, H, W, self.kind, self.p0, self.p1,
                                             ptr(self.scale), ptr(self.shift), ptr(work['slope']), dtype_code(x),
                                             stream_ptr(x)))
-        if self.cloneOutput:
-            output = self.outputState.clone()
-        else:
-            output = self.outputState
-            output._cbinfer_inplace_state = True
-        if self.propChangeIndexes:
-            return 'changeIndexes', output, MaskChangeIndexes(work['copy'], (H, W), work['idx'], work['count'])
-        return output
+        return self._result(work, H, W)
 
     def __repr__(self):
         return 'CBPointwise2d (act=%s, p0=%s, p1=%s, norm=%s, propChgIdxs=%s)' % (
             self.actName, self.p0, self.p1, self.scale is not None, self.propChangeIndexes)
-
-
-_PW_PRODUCERS = dwconv._DW_PRODUCERS + (CBPointwise2d,)
-# the module hands on its changes like every producer: linkDepthwise, insertCBUpsampling and insertCBTransposedConv take
-# it as one (and insertCBPooling(generalGeometry=True), whose pools take a mask: cbinfer_amd/__init__.py)
-dwconv._DW_PRODUCERS = dwconv._DW_PRODUCERS + (CBPointwise2d,)
-decoder._PRODUCERS = decoder._PRODUCERS + (CBPointwise2d,)
-tconv._TCONV_PRODUCERS = tconv._TCONV_PRODUCERS + (CBPointwise2d,)
-
-
-def _is_1x1(m):
-    return (type(m) is CBConv2d and tuple(m.kernel_size) == (1, 1) and tuple(m.stride) == (1, 1) and
-            tuple(m.padding) == (0, 0))
 
 
 def insertCBPointwise(rootModule):
@@ -217,7 +175,7 @@ def insertCBPointwise(rootModule):
             names = list(seq._modules.keys())
             prod, first = seq._modules[names[pos - 1]], seq._modules[names[pos]]
             pos += 1
-            if type(prod) not in _PW_PRODUCERS:
+            if type(prod) not in producer_types():
                 continue
             norm = first if type(first) is nn.BatchNorm2d else None
             after = seq._modules[names[pos]] if norm is not None and pos < len(names) else first
@@ -225,14 +183,12 @@ def insertCBPointwise(rootModule):
             if norm is None and act is None:
                 continue
             cb = CBPointwise2d(act=act, norm=norm)
-            (prod.add if type(prod) is CBResidual else prod).propChangeIndexes = True
-            if type(prod) is CBPoolMax2d and not prod.__dict__.get('_general'):
-                prod.downsampleIndexes = True      # (the list of the pool's input addresses another map)
+            hand_on_changes(prod)
             seq._modules[names[pos - 1]] = cb
             if norm is not None and act is not None:
                 del seq._modules[names[pos]]
             # (pos now names the module behind the run)
             names = list(seq._modules.keys())
-            if pos < len(names) and _is_1x1(seq._modules[names[pos]]):
+            if pos < len(names) and is_1x1(seq._modules[names[pos]]):
                 cb.propChangeIndexes = True
     return rootModule

@@ -11,11 +11,18 @@ import torch
 import torch.nn as nn
 
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
+from .chain import OPERAND_WORDS, CBStateModule, mask_workspace, operand_changes, split_operand
 from .conv2d import CBConv2d, _same_shape
-from .conv2d_cg import ChangeIndexes, MaskChangeIndexes
 
 
-class CBAdd2d(nn.Module):
+# operand_changes' refusals in this module's words (which: 'operand a' / 'operand b')
+_ADD_WORDS = (
+    "%(name)s: the change indexes of %(which)s address a %(h)dx%(w)d map, the operands are %(H)dx%(W)d maps",
+    OPERAND_WORDS[1],
+    "%(name)s: the change indexes of %(which)s must be a contiguous one-dimensional int32 tensor on the operands' device")
+
+
+class CBAdd2d(CBStateModule):
     """out = a + b, with relu=True relu(a + b), recomputed at the union of the operands' changed pixels.
 
     forward(a, b): each argument a [1, C, H, W] tensor or the ('changeIndexes', tensor, indexes) tuple of a producer with
@@ -23,83 +30,23 @@ class CBAdd2d(nn.Module):
     whose list is not made is taken as its mask (the list is never made); any other ChangeIndexes, or an exact int32
     tensor, as a list.  The flags are CBPoolMax2d's: propChangeIndexes hands on the union as a MaskChangeIndexes;
     cloneOutput=False hands out the state itself, tagged, and the frame is then free of torch operators."""
+    _WORK = '_addWork'
 
     def __init__(self, relu=False):
         super(CBAdd2d, self).__init__()
         self.relu = bool(relu)
-        self.propChangeIndexes = False
-        self.cloneOutput = True
-        self.register_buffer('outputState', torch.zeros(0))
-        self.clearMemory()
-
-    def clearMemory(self):
-        if 'outputState' not in self._buffers:
-            self.register_buffer('outputState', torch.zeros(0))
-        self.outputState = self.outputState.new_zeros(0)
-        self.__dict__['_addWork'] = None      # (device work buffers, not part of the state)
-
-    def getStateTensors(self):
-        return [self.outputState]
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d.update(_addWork=None)      # (transient)
-        return d
 
     def _workspace(self, H, W, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer and count: once per map size."""
         key = (H, W, dev)
         work = self.__dict__.get('_addWork')
         if work is None or work['key'] != key:
-            words = C.cbinfer_mask_words(H, W)
-            work = self.__dict__['_addWork'] = dict(
-                key=key,
-                bits=torch.zeros(words, dtype=torch.int64, device=dev),
-                copy=torch.zeros(words, dtype=torch.int64, device=dev),
-                idx=torch.empty(H * W, dtype=torch.int32, device=dev),
-                count=torch.zeros(1, dtype=torch.int32, device=dev))
+            work = self.__dict__['_addWork'] = dict(mask_workspace(H, W, dev), key=key)
         return work
 
-    @staticmethod
-    def _split(x, which):
-        if type(x) == tuple:
-            if len(x) != 3 or x[0] != 'changeIndexes':
-                raise CBinferError("CBAdd2d: operand %s is a tuple, but not ('changeIndexes', tensor, indexes)" % which)
-            x, indexes = x[1], x[2]
-        else:
-            indexes = None
-        if not torch.is_tensor(x):
-            raise CBinferError("CBAdd2d: operand %s must be a tensor or the ('changeIndexes', tensor, indexes) tuple, "
-                               "got %s" % (which, type(x).__name__))
-        return x.detach().contiguous(), indexes
-
-    @staticmethod
-    def _form(indexes, H, W, dev, work, which):
-        """(mask, list, capacity, device count) of an operand's changes; all None / 0: every pixel is listed."""
-        if indexes is None:
-            return None, None, 0, None
-        if isinstance(indexes, ChangeIndexes):
-            if indexes.size is not None and tuple(indexes.size) != (H, W):
-                raise CBinferError("CBAdd2d: the change indexes of operand %s address a %dx%d map, the operands are "
-                                   "%dx%d maps" % ((which,) + tuple(indexes.size) + (H, W)))
-            if isinstance(indexes, MaskChangeIndexes) and not indexes._made and indexes._mask is not None:
-                return indexes._mask, None, 0, None      # (the producer's list is never made)
-            idx, count = indexes.buffer, indexes.count
-        elif torch.is_tensor(indexes):
-            idx, count = indexes.detach(), None
-        else:
-            raise CBinferError("CBAdd2d: the change indexes of operand %s must be an int32 tensor or a ChangeIndexes, "
-                               "got %s" % (which, type(indexes).__name__))
-        if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != dev:
-            raise CBinferError("CBAdd2d: the change indexes of operand %s must be a contiguous one-dimensional int32 "
-                               "tensor on the operands' device" % which)
-        cap = idx.numel()
-        # (an empty tensor has no address: any buffer stands for the empty list)
-        return None, (idx if cap else work['idx']), cap, count
-
     def forward(self, a, b):
-        a, ia = self._split(a, 'a')
-        b, ib = self._split(b, 'b')
+        a, ia = split_operand('CBAdd2d', a, 'operand a')
+        b, ib = split_operand('CBAdd2d', b, 'operand b')
         if a.dim() != 4 or a.size(0) != 1:
             raise CBinferError("CBAdd2d: operands must be [1, C, H, W] tensors, a is %s" % (tuple(a.shape),))
         if a.shape != b.shape or a.dtype != b.dtype or a.device != b.device:
@@ -108,8 +55,9 @@ class CBAdd2d(nn.Module):
         require_device(a, b)
         nc, H, W = a.size(1), a.size(2), a.size(3)
         work = self._workspace(H, W, a.device)
-        fa = self._form(ia, H, W, a.device, work, 'a')
-        fb = self._form(ib, H, W, a.device, work, 'b')
+        # (a list the producer's kernel already made is taken before its mask)
+        fa, fb = (operand_changes('CBAdd2d', 'operand ' + which, ix, H, W, a.device, work['idx'], words=_ADD_WORDS,
+                                  maskWhenMade=False) for which, ix in (('a', ia), ('b', ib)))
         if (not _same_shape(self.outputState, a.shape) or self.outputState.dtype != a.dtype or
                 self.outputState.device != a.device):
             # a new state is written completely: neither operand's change information is used
@@ -118,14 +66,7 @@ class CBAdd2d(nn.Module):
         check(C.cbinfer_cbadd_forward(ptr(a), ptr(b), ptr(self.outputState), ptr(fa[0]), ptr(fa[1]), fa[2], ptr(fa[3]),
                                       ptr(fb[0]), ptr(fb[1]), fb[2], ptr(fb[3]), ptr(work['bits']), ptr(work['copy']),
                                       nc, H, W, int(self.relu), dtype_code(a), stream_ptr(a)))
-        if self.cloneOutput:
-            output = self.outputState.clone()
-        else:
-            output = self.outputState
-            output._cbinfer_inplace_state = True
-        if self.propChangeIndexes:
-            return 'changeIndexes', output, MaskChangeIndexes(work['copy'], (H, W), work['idx'], work['count'])
-        return output
+        return self._result(work, H, W)
 
     def __repr__(self):
         return 'CBAdd2d (relu=%s, propChgIdxs=%s)' % (self.relu, self.propChangeIndexes)

@@ -14,9 +14,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
+from .chain import hand_back, producer_types
 from .conv2d import CBConv2d, _same_shape, _switch
-from .conv2d_cg import MaskChangeIndexes
-from .decoder import _PRODUCERS
 
 MAX_K, MAX_S, MAX_D = 8, 4, 4
 
@@ -208,22 +207,12 @@ class CBConvTranspose2d(nn.Module):
             int(bool(self.copyInput)), int(bool(self.withReLU)), ptr(work['conv']), arith, stream_ptr(x)))
         if not self.feedbackLoop and not self.copyInput:
             self.prevInput = x.clone() if live else x
-        if self.cloneOutput:
-            output = self.prevOutput.clone()
-        else:
-            output = self.prevOutput
-            output._cbinfer_inplace_state = True
-        if self.propChangeIndexes:
-            return 'changeIndexes', output, MaskChangeIndexes(work['copy'], (Ho, Wo), work['idx'], work['count'])
-        return output
+        return hand_back(self, self.prevOutput, work['copy'], (Ho, Wo), work)
 
     def __repr__(self):
         return ('CBConvTranspose2d (%d, %d, k=%s, s=%s, p=%s, d=%s, op=%s, th=%s, withReLU=%s, propChgIdxs=%s)'
                 % (self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding, self.dilation,
                    self.output_padding, self.threshold, self.withReLU, self.propChangeIndexes))
-
-
-_TCONV_PRODUCERS = _PRODUCERS + (CBConvTranspose2d,)      # (insertCBUpsampling's list, CBUpsample2d included)
 
 
 def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
@@ -240,7 +229,7 @@ def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
             prod, tc = seq._modules[names[pos - 1]], seq._modules[names[pos]]
             if names[pos - 1] in gone and pos >= 2:
                 prod = seq._modules[names[pos - 2]]
-            if type(prod) not in _TCONV_PRODUCERS or type(tc) != nn.ConvTranspose2d:
+            if type(prod) not in producer_types() or type(tc) != nn.ConvTranspose2d:
                 continue
             try:
                 cb = CBConvTranspose2d(tc, threshold)

@@ -17,7 +17,8 @@ import torch.nn as nn
 pytestmark = pytest.mark.gpu
 
 TH = 0.05
-SHAPES = [(1, 3, 64), (5, 5, 70), (67, 9, 130), (3, 2, 1)]
+SHAPES = [(1, 3, 64), (5, 5, 70), (67, 9, 130), (3, 2, 1), (1, 2100, 9)]
+STRIDED = (1, 2100, 9)      # more mask words than workgroups: the grid-stride leg of the word walk
 FORMS = ["mask", "list", "all"]
 
 
@@ -121,6 +122,8 @@ def test_every_operand_form_through_the_c_abi(lib, shape, dtype):
     Cn, H, W = shape
     words = C.cbinfer_mask_words(H, W)
     assert words == H * ((W + 63) // 64)
+    if shape == STRIDED:
+        assert words > 8 * torch.cuda.get_device_properties(0).multi_processor_count
     rng = np.random.default_rng(11)
     sawUnlisted = 0
     for relu in (0, 1):

@@ -22,7 +22,9 @@ pytestmark = pytest.mark.gpu
 TH = 0.05
 MODES = [("nearest", False), ("bilinear", False), ("bilinear", True)]
 #            C, Hi, Wi, sH, sW
-UP_SHAPES = [(1, 1, 1, 8, 8), (5, 3, 32, 1, 2), (5, 4, 13, 2, 5), (3, 5, 23, 3, 3), (2, 3, 70, 2, 1), (5, 2, 9, 7, 8)]
+UP_SHAPES = [(1, 1, 1, 8, 8), (5, 3, 32, 1, 2), (5, 4, 13, 2, 5), (3, 5, 23, 3, 3), (2, 3, 70, 2, 1), (5, 2, 9, 7, 8),
+             (1, 1050, 9, 2, 1)]
+UP_STRIDED = (1, 1050, 9, 2, 1)      # more output mask words than workgroups: the grid-stride leg of the word walk
 SENTINEL = 0x5BCD
 
 
@@ -120,6 +122,8 @@ def test_upsample_every_form_through_the_c_abi(lib, shape, mode, dtype):
     Ho, Wo = Hi * sH, Wi * sW
     up = up_struct(lib, sH, sW, *mode)
     words = C.cbinfer_mask_words(Ho, Wo)
+    if shape == UP_STRIDED:
+        assert words > 8 * torch.cuda.get_device_properties(0).multi_processor_count
     rng = np.random.default_rng(7)
     x = torch.from_numpy(rng.standard_normal((1, Cn, Hi, Wi)) * 10).to(dtype).cuda()
     dt = lib.dtype_code(x)
@@ -237,6 +241,9 @@ def cat_frames(rng, n, H, W):
             ("half", [rng.random((H, W)) < 0.5 for _ in range(n)])]
 
 
+CAT_STRIDED = (2100, 9)      # more mask words than workgroups: the grid-stride leg of the kernel's loop over the words
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16], ids=["f32", "f16"])
 @pytest.mark.parametrize("size", CAT_MAPS, ids=lambda s: "%dx%d" % s)
 @pytest.mark.parametrize("chans", CAT_CHANNELS, ids=lambda c: "+".join(map(str, c)))
@@ -244,6 +251,18 @@ def test_concat_every_form_through_the_c_abi(lib, chans, size, dtype):
     """cbinfer_cbconcat_forward on two states: one whose unlisted values are overwritten with a sentinel before every
     frame -- operand k's channels are written at operand k's pixels only -- and one left alone, which equals torch.cat
     bit for bit after every frame.  The mask handed on is the union; the working masks are zero."""
+    concat_every_form(lib, chans, size, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16], ids=["f32", "f16"])
+def test_concat_every_form_on_more_words_than_workgroups(lib, dtype):
+    """The same on a 2100 x 9 map with the smallest channel split: every workgroup takes several words."""
+    words = lib.C.cbinfer_mask_words(*CAT_STRIDED)
+    assert words > 8 * torch.cuda.get_device_properties(0).multi_processor_count
+    concat_every_form(lib, CAT_CHANNELS[0], CAT_STRIDED, dtype)
+
+
+def concat_every_form(lib, chans, size, dtype):
     C, ptr, check = lib.C, lib.ptr, lib.check
     H, W = size
     n, total = len(chans), sum(chans)

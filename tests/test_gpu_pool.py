@@ -33,7 +33,9 @@ WINDOWS = {
     "5x5s1p2": ((5, 5), (1, 1), (2, 2), False),
     "4x4s2p1": ((4, 4), (2, 2), (1, 1), False),
     "aniso": ((3, 2), (2, 1), (1, 0), False),
+    "2x2s2p0": ((2, 2), (2, 2), (0, 0), False),
 }
+STRIDED = ("2x2s2p0", (4200, 9))      # 2100 output mask words, more than workgroups: the grid-stride leg of the kernel
 NAMES = list(WINDOWS)
 OPS = ["max", "avg_pad", "avg_nopad"]
 
@@ -223,8 +225,12 @@ def test_values_through_the_c_abi(lib, name, op):
         maps = [(11, 9) if name == "2x2s2p1ceil" else (13, 17)]      # (a 9-wide axis: the drop rule of ceil mode)
         if Cn == 5:      # more than one mask word per row, more than one workgroup
             maps.append((in_size_for(3, kH, sH, pH, ceil), in_size_for(66, kW, sW, pW, ceil)))
+        if Cn == 1 and name == STRIDED[0]:
+            maps.append(STRIDED[1])
         for Hi, Wi in maps:
             Ho, Wo = out_hw(win, Hi, Wi)
+            if (Hi, Wi) == STRIDED[1]:
+                assert C.cbinfer_mask_words(Ho, Wo) > 8 * torch.cuda.get_device_properties(0).multi_processor_count
             x = rng.standard_normal((1, Cn, Hi, Wi))
             if Cn == 5 and npdtype == np.float32:
                 x = -np.abs(x) - 0.25      # negative values only: the zero padding must not win

@@ -304,11 +304,18 @@ def test_insert_on_a_pre_activation_type_block(pkg, lib):
 
 
 def test_the_class_is_in_the_producer_lists(pkg):
-    from cbinfer_amd import decoder, dwconv, pointwise, tconv
+    from cbinfer_amd import chain
     P = pkg.CBPointwise2d
-    assert P in decoder._PRODUCERS and P in tconv._TCONV_PRODUCERS and P in dwconv._DW_PRODUCERS
-    assert P in pointwise._PW_PRODUCERS and pkg.CBDepthwiseConv2d in pointwise._PW_PRODUCERS
-    assert pkg.CBResidual in pointwise._PW_PRODUCERS and pkg.CBConcat2d not in pointwise._PW_PRODUCERS
+    every = (pkg.CBConv2d, pkg.CBPoolMax2d, pkg.CBPoolAvg2d, pkg.CBAdd2d, pkg.CBResidual, pkg.CBUpsample2d,
+             pkg.CBConvTranspose2d, pkg.CBDepthwiseConv2d, P)
+    # ONE table for linkDepthwise, insertCBPointwise and insertCBTransposedConv; insertCBUpsampling's is the same but
+    # for the transposed convolution; a CBConcat2d is in neither
+    assert set(chain.producer_types()) == set(every) and len(chain.producer_types()) == len(every)
+    assert set(chain.producer_types(forUpsampling=True)) == set(every) - {pkg.CBConvTranspose2d}
+    assert pkg.CBConcat2d not in chain.producer_types() + chain.producer_types(forUpsampling=True)
+    # ... and no module keeps a list of its own that another could extend on import
+    for mod in ('decoder', 'tconv', 'dwconv', 'pointwise'):
+        assert not [n for n in vars(getattr(__import__('cbinfer_amd.' + mod), mod)) if n.endswith('PRODUCERS')]
     # the passes take it as a producer
     pw = lambda: pkg.CBPointwise2d(nn.SiLU())      # noqa: E731
     seq = pkg.insertCBUpsampling(nn.Sequential(pw(), nn.Upsample(scale_factor=2, mode='nearest')))
