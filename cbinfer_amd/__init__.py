@@ -24,6 +24,7 @@ from .decoder import CBUpsample2d, CBConcat2d, insertCBUpsampling
 from .tconv import CBConvTranspose2d, insertCBTransposedConv
 from .dwconv import CBDepthwiseConv2d, linkDepthwise
 from .pointwise import CBPointwise2d, insertCBPointwise
+from .groupconv import CBGroupedConv2d, linkGrouped
 
 __version__ = "0.1.0"
 
@@ -50,24 +51,29 @@ def _rebuild(container, rule):
     return out
 
 
-def subsitute(node, threshold=1e-1, finegrained=False, generalGeometry=False, depthwise=False):
+def subsitute(node, threshold=1e-1, finegrained=False, generalGeometry=False, depthwise=False, grouped=False):
     """(module, replaced?): exactly torch.nn.Conv2d -- not a subclass -- becomes a CBConv2d sharing its
     parameters (reference: __init__.py:10-17; the spelling of the name is the reference's).  generalGeometry=True
     also takes strided, dilated, freely padded and bias-free convolutions (CBConv2d(..., generalGeometry=True)).
-    depthwise=True: a depthwise convolution (groups == in_channels > 1) becomes a CBDepthwiseConv2d; with the default it
-    is refused as every grouped convolution is."""
+    depthwise=True: a depthwise convolution (groups == in_channels > 1) becomes a CBDepthwiseConv2d.  grouped=True: a
+    convolution with groups > 1 becomes a CBGroupedConv2d (a depthwise one only where depthwise=True does not take it).
+    With the defaults every grouped convolution is refused."""
     if type(node) is not nn.Conv2d:
         return node, False
     if depthwise and node.groups == node.in_channels > 1:
         _log('replacing depthwise conv2d')
         return CBDepthwiseConv2d(node, threshold), True
+    if grouped and node.groups > 1:
+        _log('replacing grouped conv2d')
+        return CBGroupedConv2d(node, threshold), True
     _log('replacing conv2d')
     cb = CBConv2d(node, threshold, generalGeometry=True) if generalGeometry else CBConv2d(node, threshold)
     cb.finegrained = finegrained
     return cb, True
 
 
-def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False, generalGeometry=False, depthwise=False):
+def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False, generalGeometry=False, depthwise=False,
+                 grouped=False):
     """(converted nn.Sequential, anything changed?) for the children of `m` (reference: __init__.py:20-45):
     names preserved; nn.Dropout and the types of ignoreList dropped; nested nn.Sequential containers
     converted recursively -- as in the reference (:28) WITHOUT handing `finegrained` down; every other
@@ -80,13 +86,13 @@ def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False, generalGeo
     def rule(child, before, after):
         if type(child) is nn.Sequential:
             child, hit = convertRecur(child, ignoreList, threshold, generalGeometry=generalGeometry,
-                                      depthwise=depthwise)
+                                      depthwise=depthwise, grouped=grouped)
         elif type(child) in dropped:
             _log('removing node %s' % (type(child),))
             child, hit = None, True
         else:
             child, hit = subsitute(child, threshold=threshold, finegrained=finegrained, generalGeometry=generalGeometry,
-                                   depthwise=depthwise)
+                                   depthwise=depthwise, grouped=grouped)
         outcomes.append(hit)
         return child
 
@@ -100,11 +106,12 @@ def convertRecur(m, ignoreList=[], threshold=1e-1, finegrained=False, generalGeo
 def mergeReLURecur(m):
     """An nn.ReLU right behind a CBConv2d is absorbed into it (withReLU=True) and leaves the container,
     nested nn.Sequential containers included (reference: __init__.py:47-66).  A CBDepthwiseConv2d absorbs an nn.ReLU
-    and an nn.ReLU6 (reluCap = 6.0); an nn.ReLU6 behind a CBConv2d stays the dense module it is."""
+    and an nn.ReLU6 (reluCap = 6.0); a CBGroupedConv2d absorbs an nn.ReLU; an nn.ReLU6 behind a CBConv2d or a
+    CBGroupedConv2d stays the dense module it is."""
     def rule(child, before, after):
         if type(child) is nn.Sequential:
             return mergeReLURecur(child)
-        if type(child) is CBConv2d and type(after) is nn.ReLU:
+        if type(child) in (CBConv2d, CBGroupedConv2d) and type(after) is nn.ReLU:
             child.withReLU = True
         if type(child) is CBDepthwiseConv2d and type(after) in (nn.ReLU, nn.ReLU6):
             child.withReLU = True
@@ -112,7 +119,7 @@ def mergeReLURecur(m):
         if type(child) in (nn.ReLU, nn.ReLU6) and type(before) is CBDepthwiseConv2d:
             _log('merging ReLU layer')
             return None
-        if type(child) is nn.ReLU and type(before) is CBConv2d:
+        if type(child) is nn.ReLU and type(before) in (CBConv2d, CBGroupedConv2d):
             _log('merging ReLU layer')
             return None
         return child
@@ -266,7 +273,7 @@ def linkConsumers(producer, consumers):
 
 
 _STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d,
-             CBDepthwiseConv2d, CBPointwise2d)
+             CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d)
 
 
 def _stateful(net):
@@ -284,14 +291,16 @@ def getStateTensors(net):
     return [t for m in _stateful(net) for t in m.getStateTensors()]
 
 
-def convert(m, ignoreList=[], threshold=1e-1, generalGeometry=False, depthwise=False):
+def convert(m, ignoreList=[], threshold=1e-1, generalGeometry=False, depthwise=False, grouped=False):
     """nn.Sequential in -> nn.Sequential out with every Conv2d replaced by a CBConv2d sharing its
     weights, ReLUs merged, Dropout removed (reference: __init__.py:91-94).  generalGeometry=True: strided, dilated,
     freely padded and bias-free convolutions are converted too (the default stops at them with an AssertionError, as
     the reference does).  depthwise=True: depthwise convolutions (groups == in_channels > 1) become CBDepthwiseConv2d
-    modules, an nn.ReLU or nn.ReLU6 behind one is absorbed; other grouped convolutions are refused as before."""
+    modules, an nn.ReLU or nn.ReLU6 behind one is absorbed.  grouped=True: convolutions with groups > 1 (depthwise ones
+    only where depthwise=True does not take them) become CBGroupedConv2d modules, an nn.ReLU behind one is absorbed.  With
+    the defaults grouped convolutions are refused as before."""
     converted, _ = convertRecur(m, ignoreList=ignoreList, threshold=threshold, generalGeometry=generalGeometry,
-                                depthwise=depthwise)
+                                depthwise=depthwise, grouped=grouped)
     return mergeReLURecur(converted)
 
 
@@ -385,7 +394,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

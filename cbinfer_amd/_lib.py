@@ -294,6 +294,13 @@ _SIGNATURES = {
     "cbinfer_pointwise_changed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i, _vp]),
     "cbinfer_cbpointwise_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i,
                                          _vp]),
+    "cbinfer_groupconv_supported": (_i, [_i, _i, _i, _gp]),
+    "cbinfer_groupconv_prepared_weights_bytes": (_l, [_i, _i, _i, _gp, _i]),
+    "cbinfer_groupconv_prep_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _gp, _i, _vp]),
+    "cbinfer_conv_changed_grouped": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _gp, _i,
+                                          _i, _vp]),
+    "cbinfer_cbgroupconv2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _gp, _f, _i, _i,
+                                           _i, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

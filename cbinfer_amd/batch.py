@@ -29,6 +29,7 @@ from .decoder import CBConcat2d, CBUpsample2d
 from .tconv import CBConvTranspose2d
 from .dwconv import CBDepthwiseConv2d
 from .pointwise import CBPointwise2d
+from .groupconv import CBGroupedConv2d
 
 
 # the change-based operators that have neither a batched kernel here nor a grouped launch in a BranchGroup: (types,
@@ -39,6 +40,7 @@ CHAIN_OPERATORS = (
     ((CBConvTranspose2d,), 'a change-based transposed convolution', 'decoder'),
     ((CBDepthwiseConv2d,), 'a change-based depthwise convolution', 'separable'),
     ((CBPointwise2d,), 'a change-based element-wise function', 'such'),
+    ((CBGroupedConv2d,), 'a change-based grouped convolution', 'ResNeXt-type'),
 )
 
 

@@ -81,17 +81,18 @@ def mask_workspace(Ho, Wo, dev, nbits=1):
                 count=torch.zeros(1, dtype=torch.int32, device=dev))
 
 
-def hand_back(module, state, copy, size, work):
+def hand_back(module, state, copy, size, work, made=False):
     """What a frame returns: a private copy of `state` -- or, with cloneOutput=False, the state itself, tagged, so that a
     consumer that keeps a reference copies it then -- and with propChangeIndexes the frame's mask `copy` on the
-    size = (Ho, Wo) output map as a MaskChangeIndexes."""
+    size = (Ho, Wo) output map as a MaskChangeIndexes.  made: the frame's kernel already left the list and its count in
+    work['idx'] / work['count'] (CBGroupedConv2d), so a consumer that wants the list launches nothing for it."""
     if getattr(module, 'cloneOutput', True):
         output = state.clone()
     else:
         output = state
         output._cbinfer_inplace_state = True
     if module.propChangeIndexes:
-        return 'changeIndexes', output, MaskChangeIndexes(copy, size, work['idx'], work['count'])
+        return 'changeIndexes', output, MaskChangeIndexes(copy, size, work['idx'], work['count'], made=made)
     return output
 
 

@@ -1,5 +1,6 @@
-// LDS stage images and the MFMA stage of the 64 x 64 x 32 gather contractions (cb_geomconv.hip, cb_tconv.hip): written
-// once, included by both translation units.
+// LDS stage images and the MFMA stage of the 64 x 64 x 32 gather contractions (cb_geomconv.hip, cb_tconv.hip), and the
+// mask -> list prologue and list lookup of cb_geomconv.hip and cb_groupconv.hip: written once, included by the
+// translation units that use them.
 #pragma once
 #include "cb_common.h"
 
@@ -47,6 +48,98 @@ struct CbgStage<CB_F32> {
         for (int i = 0; i < 8; ++i) v[row][k0 + i] = x[i];
     }
 };
+
+// ---------------------------------------------------------------------------------------------
+// The change list of a mask-mode launch (cbg_conv_kernel, cbgr_conv_kernel; 256 threads): every workgroup counts the
+// bits of the mask the parity selects -- thread t the words [t chunk, (t + 1) chunk), chunk = ceil(words / 256) -- and
+// scans the 256 counts into sPre[257]; for its share of the words (w % gridDim.x == blockIdx.x) it writes the ascending
+// list entries, the mask copy and the zeros of the OTHER mask (the next frame's); the last workgroup to arrive flips the
+// parity.  Returns the number of listed pixels, `cur` the frame's mask.  sWave: four ints of LDS.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int cbg_list_from_mask(unsigned long long* frameMasks, long words, int chunk, int wpr, int Wo,
+                                                  int32_t* listOut, int32_t* countOut, int* sPre, int* sWave,
+                                                  const unsigned long long*& cur) {
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int G = gridDim.x;
+    int* ctl = (int*)(frameMasks + 2 * words);
+    const int par = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    cur = frameMasks + (par ? words : 0);
+    unsigned long long* other = frameMasks + (par ? 0 : words);
+    unsigned long long* copy = frameMasks + 2 * words + 2;
+    const long w0 = (long)t * chunk, w1 = min(words, w0 + chunk);
+    int cnt = 0;
+    for (long w = w0; w < w1; ++w) cnt += __popcll(cur[w]);
+    // inclusive scan of the 256 chunk counts: within each wave by lane shifts, then the four wave totals
+    int inc = cnt;
+#pragma unroll
+    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+        const int up = __shfl_up(inc, dlt, 64);
+        if (lane >= dlt) inc += up;
+    }
+    if (lane == 63) sWave[wave] = inc;
+    __syncthreads();
+    for (int i = 0; i < wave; ++i) inc += sWave[i];
+    sPre[t + 1] = inc;
+    if (t == 0) sPre[0] = 0;
+    __syncthreads();
+    const int N = sPre[256];
+    // every workgroup writes the list entries, the mask copy and the zeros of the OTHER mask (the next frame's) for
+    // its share of the words
+    int run = sPre[t];
+    for (long w = w0; w < w1; ++w) {
+        const unsigned long long mw = cur[w];
+        if ((int)(w % G) == (int)blockIdx.x) {
+            const int yy = (int)(w / wpr), xx = (int)(w % wpr) * 64;
+            unsigned long long r = mw;
+            int at = run;
+            while (r) {
+                listOut[at++] = yy * Wo + xx + __builtin_ctzll(r);
+                r &= r - 1;
+            }
+            copy[w] = mw;
+            other[w] = 0ull;
+        }
+        run += __popcll(mw);
+    }
+    if (blockIdx.x == 0 && t == 0) countOut[0] = N;
+    // every workgroup has read the parity and the mask by now: the last one to arrive flips the parity
+    __syncthreads();
+    if (t == 0 && __hip_atomic_fetch_add(ctl + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) {
+        __hip_atomic_store(ctl + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ctl, par ^ 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return N;
+}
+
+// Entry q of the list (q < N checked by the caller's tile): from the mask `cur` through the scan sPre -- the last thread
+// chunk whose prefix is <= q, then the words of that chunk -- or from a caller's list; -1 for an entry outside the map
+// (a foreign list is not trusted with addresses).
+__device__ __forceinline__ int cbg_list_entry(int q, const unsigned long long* cur, const int* sPre, long words, int chunk,
+                                              int wpr, int Wo, const int32_t* list, int HWo) {
+    int pix = -1;
+    if (cur) {
+        int lo = 0, hi = 255;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (sPre[mid] <= q) lo = mid; else hi = mid - 1;
+        }
+        int r = q - sPre[lo];
+        long w = (long)lo * chunk;
+        const long wEnd = min(words, w + chunk);
+        unsigned long long mw = 0ull;
+        for (; w < wEnd; ++w) {
+            mw = cur[w];
+            const int c = __popcll(mw);
+            if (r < c) break;
+            r -= c;
+        }
+        if (w < wEnd) pix = (int)(w / wpr) * Wo + (int)(w % wpr) * 64 + cb_select_bit(mw, r);
+    } else {
+        pix = list[q];
+    }
+    if (pix < 0 || pix >= HWo) pix = -1;
+    return pix;
+}
 
 template <int ARITH>
 __device__ __forceinline__ floatx16 cbg_mfma_stage(const CbgStage<ARITH>& A, const CbgStage<ARITH>& B, int ra, int rb,

@@ -205,54 +205,7 @@ __global__ __launch_bounds__(256) void cbg_conv_kernel(GeomConvParams p) {
     const long words = p.maskWords;
     const int chunk = (int)((words + 255) / 256);
     if (p.frameMasks) {
-        int* ctl = (int*)(p.frameMasks + 2 * words);
-        const int par = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cur = p.frameMasks + (par ? words : 0);
-        unsigned long long* other = p.frameMasks + (par ? 0 : words);
-        unsigned long long* copy = p.frameMasks + 2 * words + 2;
-        const long w0 = (long)t * chunk, w1 = min(words, w0 + chunk);
-        int cnt = 0;
-        for (long w = w0; w < w1; ++w) cnt += __popcll(cur[w]);
-        // inclusive scan of the 256 chunk counts: within each wave by lane shifts, then the four wave totals
-        int inc = cnt;
-#pragma unroll
-        for (int dlt = 1; dlt < 64; dlt <<= 1) {
-            const int up = __shfl_up(inc, dlt, 64);
-            if (lane >= dlt) inc += up;
-        }
-        if (lane == 63) sWave[wave] = inc;
-        __syncthreads();
-        for (int i = 0; i < wave; ++i) inc += sWave[i];
-        sPre[t + 1] = inc;
-        if (t == 0) sPre[0] = 0;
-        __syncthreads();
-        N = sPre[256];
-        // every workgroup writes the list entries, the mask copy and the zeros of the OTHER mask (the next frame's) for
-        // its share of the words
-        int run = sPre[t];
-        for (long w = w0; w < w1; ++w) {
-            const unsigned long long mw = cur[w];
-            if ((int)(w % G) == (int)blockIdx.x) {
-                const int yy = (int)(w / p.wpr), xx = (int)(w % p.wpr) * 64;
-                unsigned long long r = mw;
-                int at = run;
-                while (r) {
-                    p.listOut[at++] = yy * p.Wo + xx + __builtin_ctzll(r);
-                    r &= r - 1;
-                }
-                copy[w] = mw;
-                other[w] = 0ull;
-            }
-            run += __popcll(mw);
-        }
-        if (blockIdx.x == 0 && t == 0) p.countOut[0] = N;
-        // every workgroup has read the parity and the mask by now: the last one to arrive flips the parity
-        __syncthreads();
-        if (t == 0 &&
-            __hip_atomic_fetch_add(ctl + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) {
-            __hip_atomic_store(ctl + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(ctl, par ^ 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        N = cbg_list_from_mask(p.frameMasks, words, chunk, p.wpr, p.Wo, p.listOut, p.countOut, sPre, sWave, cur);
     } else {
         N = p.countDev ? min(*p.countDev, p.nHost) : p.nHost;
         N = max(0, min(N, HWo));
@@ -277,31 +230,7 @@ __global__ __launch_bounds__(256) void cbg_conv_kernel(GeomConvParams p) {
         __syncthreads();
         if (t < CBG_BN) {
             const int q = tn * CBG_BN + t;
-            int pix = -1;
-            if (q < N) {
-                if (cur) {
-                    int lo = 0, hi = 255;      // last thread chunk whose prefix is <= q
-                    while (lo < hi) {
-                        const int mid = (lo + hi + 1) >> 1;
-                        if (sPre[mid] <= q) lo = mid; else hi = mid - 1;
-                    }
-                    int r = q - sPre[lo];
-                    long w = (long)lo * chunk;
-                    const long wEnd = min(words, w + chunk);
-                    unsigned long long mw = 0ull;
-                    for (; w < wEnd; ++w) {
-                        mw = cur[w];
-                        const int c = __popcll(mw);
-                        if (r < c) break;
-                        r -= c;
-                    }
-                    if (w < wEnd) pix = (int)(w / p.wpr) * p.Wo + (int)(w % p.wpr) * 64 + cb_select_bit(mw, r);
-                } else {
-                    pix = p.list[q];
-                }
-                if (pix < 0 || pix >= HWo) pix = -1;      // (a foreign list is not trusted with addresses)
-            }
-            sList[t] = pix;
+            sList[t] = q < N ? cbg_list_entry(q, cur, sPre, words, chunk, p.wpr, p.Wo, p.list, HWo) : -1;
         }
         __syncthreads();
 

@@ -66,8 +66,9 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_cbadd_forward) and the decoder operators (cbUpsample, cbinfer_upsample_supported,
  * cbinfer_cbupsample_forward, cbinfer_cbconcat_forward) and the transposed convolution (cbTGeom, cbinfer_tconv_*,
  * cbinfer_*_tconv, cbinfer_cbconvtranspose2d_forward), the depthwise convolution (cbinfer_dwconv_*,
- * cbinfer_cbdwconv2d_forward*) and the element-wise functions (CB_PW_*, cbinfer_pointwise_supported,
- * cbinfer_pointwise_changed, cbinfer_cbpointwise_forward). */
+ * cbinfer_cbdwconv2d_forward*), the element-wise functions (CB_PW_*, cbinfer_pointwise_supported,
+ * cbinfer_pointwise_changed, cbinfer_cbpointwise_forward) and the grouped convolution (cbinfer_groupconv_*,
+ * cbinfer_conv_changed_grouped, cbinfer_cbgroupconv2d_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1105,6 +1106,49 @@ int cbinfer_cbdwconv2d_forward_propagated(const void* input, void* outputState, 
                                           uint64_t* bits, uint64_t* maskCopy, const void* weight, const void* bias, int C,
                                           int mult, int Hi, int Wi, const cbGeom* geom, int act, int dtype,
                                           cbStream_t stream);
+
+/* ---- grouped convolution (cb_groupconv.hip) -----------------------------------------------------------
+ * The reference has no counterpart: its CBConv2d asserts groups == 1 (conv2d.py:92-104).  G = groups >= 2 with
+ * C % G == 0 and K % G == 0: input [C, Hi, Wi], weight [K, Cg, kH, kW] (torch's layout), Cg = C / G, Kg = K / G, a cbGeom
+ * within the general-geometry limits, output [K, Ho, Wo] by cbinfer_geom_out_size; output channel m reads the input
+ * channels (m / Kg) Cg ... + Cg - 1 only.  groups == C (depthwise) is accepted and correct, but cbinfer_dwconv_* is the
+ * fast path for it.  Status as in the general geometry: a null pointer, a non-positive C, K, groups, Hi or Wi or geometry
+ * entry, an unknown dtype, a filter that does not fit the padded map, or Ho Wo >= 2^31: CB_ERR_BADARG; a geometry beyond
+ * the limits, groups == 1, C or K no multiple of groups, Cg Hi Wi elemSize >= 2^31 (the tap table holds group-relative
+ * byte offsets in an int) or Hi Wi >= 2^30: CB_ERR_UNSUPPORTED.  Nothing is launched in either case.  Output pixels no
+ * tap reaches (see the general geometry) are never written by the frame entry point: the caller initialises them to
+ * act(bias). */
+/* host, pure: 1 if groups >= 2 divides C and K and the geometry is within the limits, else 0.  No counterpart in the
+ * reference (groups == 1 asserted). */
+int cbinfer_groupconv_supported(int C, int K, int groups, const cbGeom* geom);
+/* Prepared weights (no counterpart in the reference): W[G][KgP][CkkgP] in the tensors' element type, k contiguous, zero
+ * padded -- KgP = Kg rounded up to ROWS (16 if Kg <= 16, 32 if Kg <= 32, else 64), CkkgP = Cg kH kW rounded up to 32;
+ * CB_F32S shares CB_F32's layout -- followed by the group-relative k -> tap table of 2 CkkgP ints for an Hi x Wi input
+ * map (format of cbinfer_geom_prep_weights, c counted within the group; the same for every group).
+ * G KgP CkkgP elemSize + 8 CkkgP bytes; 0 for a rejected shape. */
+long cbinfer_groupconv_prepared_weights_bytes(int K, int C, int groups, const cbGeom* geom, int dtype);
+int cbinfer_groupconv_prep_weights(const void* weight, void* prepared, int K, int C, int groups, int Hi, int Wi,
+                                   const cbGeom* geom, int dtype, cbStream_t stream);
+/* Contraction, one launch, no workspace (no counterpart in the reference): gather -> MFMA -> bias / ReLU -> scatter at
+ * the listed OUTPUT pixels, nothing else of output [K, Ho, Wo] is written.  bias may be NULL.  dtype selects the
+ * arithmetic as in cbinfer_conv_changed_geom (CB_F16; CB_F32S; CB_F32).  The list comes from frameMasks (idxOut /
+ * countOut written, mask copied, other mask zeroed, parity flipped -- also for an empty mask) or from changeList /
+ * numChanges / countDev, exactly as there; entries outside the map are ignored and never used for an address.  A listed
+ * pixel's bits depend only on the input, the weights and the arithmetic: not on the other listed pixels, its place in
+ * the list, or the list's source. */
+int cbinfer_conv_changed_grouped(const void* input, const int32_t* changeList, int numChanges, const int32_t* countDev,
+                                 uint64_t* frameMasks, int32_t* idxOut, int32_t* countOut, const void* prepared,
+                                 const void* bias, void* output, int C, int Hi, int Wi, int K, int groups,
+                                 const cbGeom* geom, int relu, int dtype, cbStream_t stream);
+/* The whole frame enqueued without a host sync (no counterpart in the reference): cbinfer_change_detection_geom
+ * (unchanged, called as it is: change over all C channels) + cbinfer_conv_changed_grouped from the frame mask.
+ * feedbackLoop / copyInput contract and the updateInputState mapping exactly as cbinfer_cbconv2d_forward_geom, without
+ * haveIndexes; prevInput [C,Hi,Wi], prevOutput [K,Ho,Wo]; idx (capacity Ho Wo) / countDev receive the frame's list.  All
+ * arguments are checked before the first launch. */
+int cbinfer_cbgroupconv2d_forward(const void* input, void* prevInput, void* prevOutput, uint64_t* frameMasks,
+                                  int32_t* idx, int32_t* countDev, const void* prepared, const void* bias, int C, int Hi,
+                                  int Wi, int K, int groups, const cbGeom* geom, float threshold, int feedbackLoop,
+                                  int copyInput, int relu, int dtype, cbStream_t stream);
 
 /* replaces conv2d_fg_cpu, cbconv2d_fg_backend.cu:81-112: HOST pointers, host code, race-free. */
 void cbinfer_conv2d_fg_cpu(const float* input, const float* prevInput, float* output,
