@@ -133,6 +133,17 @@ class TGeom(ctypes.Structure):
 
 _tgp = ctypes.POINTER(TGeom)
 
+REARRANGE_SHUFFLE, REARRANGE_UNSHUFFLE, REARRANGE_CHANNELS = 0, 1, 2      # CB_REARRANGE_*
+
+
+class Rearrange(ctypes.Structure):
+    """cbRearrange of include/cbinfer_hip.h: the kind of a change-based rearrangement and its factor (r of a pixel
+    shuffle / unshuffle, the group count of a channel shuffle)."""
+    _fields_ = [("kind", _i), ("factor", _i)]
+
+
+_rp = ctypes.POINTER(Rearrange)
+
 _SIGNATURES = {
     # name: (restype, [argtypes])
     "cbinfer_abi_version": (_i, []),
@@ -301,6 +312,9 @@ _SIGNATURES = {
                                           _i, _vp]),
     "cbinfer_cbgroupconv2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _gp, _f, _i, _i,
                                            _i, _i, _vp]),
+    "cbinfer_rearrange_supported": (_i, [_rp]),
+    "cbinfer_rearrange_out_shape": (_i, [_rp, _i, _i, _i, _ip, _ip, _ip]),
+    "cbinfer_cbrearrange_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _rp, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

@@ -30,6 +30,7 @@ from .tconv import CBConvTranspose2d
 from .dwconv import CBDepthwiseConv2d
 from .pointwise import CBPointwise2d
 from .groupconv import CBGroupedConv2d
+from .rearrange import CBChannelShuffle2d, CBPixelShuffle2d
 
 
 # the change-based operators that have neither a batched kernel here nor a grouped launch in a BranchGroup: (types,
@@ -41,6 +42,7 @@ CHAIN_OPERATORS = (
     ((CBDepthwiseConv2d,), 'a change-based depthwise convolution', 'separable'),
     ((CBPointwise2d,), 'a change-based element-wise function', 'such'),
     ((CBGroupedConv2d,), 'a change-based grouped convolution', 'ResNeXt-type'),
+    ((CBPixelShuffle2d, CBChannelShuffle2d), 'a change-based rearrangement', 'super-resolution and ShuffleNet-type'),
 )
 
 

@@ -1,6 +1,7 @@
 """What the change-based operators behind a producer share on the host: how an operand and its change
-information are taken apart, the state module CBAdd2d, CBPointwise2d, CBUpsample2d and CBConcat2d derive from, the mask
-workspace and hand-back of every mask-driven module, and the ONE table of the modules that count as a producer.
+information are taken apart, the state module CBAdd2d, CBPointwise2d, CBUpsample2d, CBConcat2d, CBPixelShuffle2d and CBChannelShuffle2d derive from, the mask
+workspace and hand-back of every mask-driven module, and the ONE table of the modules that count as a producer (with
+its later additions in a second one, later_producer_types).
 """
 import functools
 
@@ -145,6 +146,15 @@ def producer_types(forUpsampling=False):
     types = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBConvTranspose2d,
              CBDepthwiseConv2d, CBPointwise2d)
     return tuple(t for t in types if not (forUpsampling and t is CBConvTranspose2d))
+
+
+@functools.lru_cache(maxsize=None)
+def later_producer_types():
+    """The producers that joined after producer_types() was pinned -- CBPixelShuffle2d and CBChannelShuffle2d, which keep
+    that rule as well --: linkDepthwise, insertCBPointwise, insertCBUpsampling and insertCBTransposedConv accept
+    producer_types(...) + later_producer_types() in front of their module."""
+    from .rearrange import CBChannelShuffle2d, CBPixelShuffle2d
+    return (CBPixelShuffle2d, CBChannelShuffle2d)
 
 
 def hand_on_changes(prod):

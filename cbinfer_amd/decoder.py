@@ -18,7 +18,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import CBStateModule, hand_on_changes, mask_workspace, operand_changes, producer_types, split_operand
+from .chain import (CBStateModule, hand_on_changes, later_producer_types, mask_workspace, operand_changes,
+                    producer_types, split_operand)
 from .conv2d import CBConv2d, _same_shape
 
 MAX_SCALE = 8
@@ -201,8 +202,9 @@ _UPSAMPLERS = (nn.Upsample, nn.UpsamplingNearest2d, nn.UpsamplingBilinear2d)
 
 def insertCBUpsampling(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.Upsample / nn.UpsamplingNearest2d / nn.UpsamplingBilinear2d within
-    the library's limits that directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual or another
-    CBUpsample2d becomes a CBUpsample2d fed by that producer's changes: propChangeIndexes is switched on at the producer
+    the library's limits that directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBPixelShuffle2d,
+    CBChannelShuffle2d or another CBUpsample2d becomes a CBUpsample2d fed by that producer's changes: propChangeIndexes
+    is switched on at the producer
     (a CBResidual's `.add`; a 2x2 CBPoolMax2d of the reference's kind also hands on the OUTPUT-resolution list,
     downsampleIndexes).  A CBConv2d consuming the upsampled map then needs its own input copy (copyInput) unless it runs
     in feedback mode, as behind a pool of insertCBPooling.  An upsampling beyond the limits stays the dense torch
@@ -211,7 +213,8 @@ def insertCBUpsampling(rootModule, cloneOutput=True):
         names = list(seq._modules.keys())
         for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
             prod, up = seq._modules[a], seq._modules[b]
-            if type(prod) not in producer_types(forUpsampling=True) or type(up) not in _UPSAMPLERS:
+            if (type(prod) not in producer_types(forUpsampling=True) + later_producer_types() or
+                    type(up) not in _UPSAMPLERS):
                 continue
             try:
                 cb = CBUpsample2d(up)

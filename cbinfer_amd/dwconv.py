@@ -15,7 +15,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import PROPAGATED, hand_back, hand_on_changes, is_1x1, mask_workspace, operand_changes, producer_types
+from .chain import (PROPAGATED, hand_back, hand_on_changes, is_1x1, later_producer_types, mask_workspace,
+                    operand_changes, producer_types)
 from .conv2d import _padding_pair, _same_shape
 
 MAX_K, MAX_S, MAX_D, MAX_P = 7, 4, 8, 64
@@ -239,14 +240,15 @@ class CBDepthwiseConv2d(nn.Module):
 
 def linkDepthwise(rootModule):
     """Inside every nn.Sequential of rootModule: a CBDepthwiseConv2d with dilation 1 and padding <= kernel_size / 2 that
-    directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBConvTranspose2d or another
-    CBDepthwiseConv2d takes that producer's changes (propagatedChanges on the layer, propChangeIndexes on the producer)
+    directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBConvTranspose2d,
+    CBPixelShuffle2d, CBChannelShuffle2d or another CBDepthwiseConv2d takes that producer's changes (propagatedChanges
+    on the layer, propChangeIndexes on the producer)
     and runs no detection; a CBDepthwiseConv2d directly in front of a 1x1 / stride-1 / padding-0 CBConv2d hands its
     changes on (propChangeIndexes).  Returns rootModule."""
     for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
         kids = list(seq.children())
         for prod, cons in zip(kids[:-1], kids[1:]):
-            if (type(cons) is CBDepthwiseConv2d and type(prod) in producer_types() and
+            if (type(cons) is CBDepthwiseConv2d and type(prod) in producer_types() + later_producer_types() and
                     _propagated_ok(cons.kernel_size, cons.padding, cons.dilation)):
                 cons.propagatedChanges = True
                 hand_on_changes(prod)

@@ -12,8 +12,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, producer_types,
-                    split_operand)
+from .chain import (CBStateModule, hand_on_changes, is_1x1, later_producer_types, mask_workspace, operand_changes,
+                    producer_types, split_operand)
 from .conv2d import _same_shape
 
 # nn type (exactly, not a subclass) -> (CB_PW_* kind, p0, p1 of the instance)
@@ -160,7 +160,8 @@ class CBPointwise2d(CBStateModule):
 def insertCBPointwise(rootModule):
     """Inside every nn.Sequential of rootModule, a run  [nn.BatchNorm2d] [activation]  (at least one of the two; the
     activations of CBPointwise2d) that directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual,
-    CBUpsample2d, CBConvTranspose2d, CBDepthwiseConv2d or another CBPointwise2d becomes ONE CBPointwise2d under the run's
+    CBUpsample2d, CBConvTranspose2d, CBDepthwiseConv2d, CBPixelShuffle2d, CBChannelShuffle2d or another CBPointwise2d
+    becomes ONE CBPointwise2d under the run's
     first name, fed by that producer's changes: propChangeIndexes is switched on at the producer (a CBResidual's `.add`;
     a 2x2 CBPoolMax2d of the reference's kind also hands on the OUTPUT-resolution list, downsampleIndexes).  The new
     module hands its own changes on (propChangeIndexes) only where it stands directly in front of a 1x1 / stride-1 /
@@ -175,7 +176,7 @@ def insertCBPointwise(rootModule):
             names = list(seq._modules.keys())
             prod, first = seq._modules[names[pos - 1]], seq._modules[names[pos]]
             pos += 1
-            if type(prod) not in producer_types():
+            if type(prod) not in producer_types() + later_producer_types():
                 continue
             norm = first if type(first) is nn.BatchNorm2d else None
             after = seq._modules[names[pos]] if norm is not None and pos < len(names) else first

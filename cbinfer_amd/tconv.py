@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import hand_back, producer_types
+from .chain import hand_back, later_producer_types, producer_types
 from .conv2d import CBConv2d, _same_shape, _switch
 
 MAX_K, MAX_S, MAX_D = 8, 4, 4
@@ -217,7 +217,8 @@ class CBConvTranspose2d(nn.Module):
 
 def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.ConvTranspose2d within the library's limits that directly follows
-    a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d or another CBConvTranspose2d becomes a
+    a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBPixelShuffle2d, CBChannelShuffle2d or
+    another CBConvTranspose2d becomes a
     CBConvTranspose2d with `threshold` (it runs its own change detection: nothing is switched on at the producer).  An
     nn.ReLU right behind it is absorbed (withReLU).  A CBConv2d consuming the output then needs its own input copy
     (copyInput) unless it runs in feedback mode.  A module beyond the limits stays the dense torch operator.  Returns
@@ -229,7 +230,7 @@ def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
             prod, tc = seq._modules[names[pos - 1]], seq._modules[names[pos]]
             if names[pos - 1] in gone and pos >= 2:
                 prod = seq._modules[names[pos - 2]]
-            if type(prod) not in producer_types() or type(tc) != nn.ConvTranspose2d:
+            if type(prod) not in producer_types() + later_producer_types() or type(tc) != nn.ConvTranspose2d:
                 continue
             try:
                 cb = CBConvTranspose2d(tc, threshold)

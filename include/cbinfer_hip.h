@@ -68,7 +68,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_*_tconv, cbinfer_cbconvtranspose2d_forward), the depthwise convolution (cbinfer_dwconv_*,
  * cbinfer_cbdwconv2d_forward*), the element-wise functions (CB_PW_*, cbinfer_pointwise_supported,
  * cbinfer_pointwise_changed, cbinfer_cbpointwise_forward) and the grouped convolution (cbinfer_groupconv_*,
- * cbinfer_conv_changed_grouped, cbinfer_cbgroupconv2d_forward). */
+ * cbinfer_conv_changed_grouped, cbinfer_cbgroupconv2d_forward) and the rearrangements (cbRearrange, CB_REARRANGE_*,
+ * cbinfer_rearrange_supported, cbinfer_rearrange_out_shape, cbinfer_cbrearrange_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -992,6 +993,46 @@ int cbinfer_cbconcat_forward(const void* const* sources, const int32_t* channels
                              const uint64_t* const* masks, const int32_t* const* lists, const int32_t* caps,
                              const int32_t* const* counts, uint64_t* bits, uint64_t* maskCopy, int H, int W, int dtype,
                              cbStream_t stream);
+
+/* ---- change-based pixel shuffle, pixel unshuffle and channel shuffle (cb_rearrange.hip) -----------------
+ * No counterpart in the reference.  The three operators compute nothing: values are copied bit for bit, never converted,
+ * and -- every producer leaves the pixels outside its change list bit for bit as they were -- the output can differ from
+ * last frame's only at the footprint of the input's changes on the OUTPUT map.  Tensors are contiguous, CB_F32 or
+ * CB_F16, batch 1; masks are row-padded (cbinfer_mask_words); an int32 list holds flat indexes y W + x of the INPUT map,
+ * entries outside it are dropped; bits of the row padding are never set.  `factor` is r for the two pixel shuffles and
+ * the group count g for the channel shuffle.
+ *   CB_REARRANGE_SHUFFLE, 1 <= r <= 8:    input [Co r r, H, W] -> out [Co, H r, W r],
+ *       out[c, y r + i, x r + j] = in[c r r + i r + j, y, x];  (oy, ox) is listed iff input pixel (oy / r, ox / r) is.
+ *   CB_REARRANGE_UNSHUFFLE, 1 <= r <= 8:  input [C, Ho r, Wo r] -> out [C r r, Ho, Wo],
+ *       out[c r r + i r + j, y, x] = in[c, y r + i, x r + j];  (y, x) is listed iff any of the r x r input pixels of its
+ *       block is.
+ *   CB_REARRANGE_CHANNELS, 1 <= g <= C, g divides C:  the same shape,
+ *       out[k g + q] = in[q (C / g) + k] for q < g, k < C / g;  the same pixel is listed.
+ *   the input's changes: inputMask (over the INPUT map; one launch, the footprint gathered inside it), list (capN
+ *     entries at most, countDev the device-side length or NULL: capN is the length; one launch in front, which ORs the
+ *     footprint into `bits` -- shuffle: the r x r block of every entry, at most two 64-bit atomicOr per row; unshuffle:
+ *     cbinfer_pool_footprint with an r x r / stride-r window; channels: with a 1x1 window; capN == 0 launches nothing
+ *     in front), or neither: every output pixel is listed.
+ *   hand-on: maskCopy (cbinfer_mask_words(Ho, Wo) words) receives the frame's mask every frame; `bits`, the working
+ *     mask of the OUTPUT map (zero on first use), is zero again when the frame ends.  Unlisted pixels keep their bits.
+ * Bad arguments (a null tensor or mask buffer, input == outputState, C / H / W < 1, an unknown dtype or kind, a factor
+ * outside the limits, a channel count that r r (shuffle) or g does not divide, a height or width that r (unshuffle) does
+ * not divide, capN < 0, both a mask and a list, a count without a list, inputMask == bits or maskCopy, bits == maskCopy,
+ * H W, Ho Wo or 64 Co beyond an int32) return CB_ERR_BADARG and launch nothing. */
+enum { CB_REARRANGE_SHUFFLE, CB_REARRANGE_UNSHUFFLE, CB_REARRANGE_CHANNELS };
+typedef struct cbRearrange {
+    int kind;   /* CB_REARRANGE_* */
+    int factor; /* r, or g for CB_REARRANGE_CHANNELS */
+} cbRearrange;
+/* host, pure: 1 if kind and factor are within the limits above (g <= C is the shape's matter), else 0 */
+int cbinfer_rearrange_supported(const cbRearrange* r);
+/* host, pure: the output shape of a [C, H, W] input (CB_OK; CB_ERR_UNSUPPORTED beyond the limits; CB_ERR_BADARG for a
+ * null pointer, a size < 1 or a size the factor does not divide; Co / Ho / Wo untouched on failure) */
+int cbinfer_rearrange_out_shape(const cbRearrange* r, int C, int H, int W, int* Co, int* Ho, int* Wo);
+/* The whole frame of a change-based rearrangement enqueued without a host sync; C, H, W are the INPUT's. */
+int cbinfer_cbrearrange_forward(const void* input, void* outputState, const uint64_t* inputMask, const int32_t* list,
+                                int capN, const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W,
+                                const cbRearrange* r, int dtype, cbStream_t stream);
 
 /* ---- transposed convolution (cb_tconv.hip) ------------------------------------------------------------
  * The reference has no counterpart: its CBConv2d asserts transposed == False (conv2d.py:92-104).  Input map Hi x Wi,
