@@ -1,7 +1,8 @@
 """What the change-based operators behind a producer share on the host: how an operand and its change
-information are taken apart, the state module CBAdd2d, CBPointwise2d, CBUpsample2d, CBConcat2d, CBPixelShuffle2d and CBChannelShuffle2d derive from, the mask
-workspace and hand-back of every mask-driven module, and the ONE table of the modules that count as a producer (with
-its later additions in a second one, later_producer_types).
+information are taken apart, the state module CBAdd2d, CBPointwise2d, CBUpsample2d, CBConcat2d, CBPixelShuffle2d and
+CBChannelShuffle2d derive from, the ONE test for a state that no longer fits its frame (state_fits: these modules and
+the layers of layer.py), the mask workspace and hand-back of every mask-driven module, and the ONE table of
+the modules that count as a producer (with its later additions in a second one, later_producer_types).
 """
 import functools
 
@@ -72,6 +73,12 @@ def operand_changes(name, which, indexes, H, W, dev, spare, words=OPERAND_WORDS,
 
 
 # ---------------------------------------------------------------------------------------------------- state
+def state_fits(state, shape, like):
+    """Whether the state tensor `state` still serves a frame: it has `shape`, and the dtype and device of `like`."""
+    return (state is not None and tuple(state.size()) == tuple(shape) and state.dtype == like.dtype and
+            state.device == like.device)
+
+
 def mask_workspace(Ho, Wo, dev, nbits=1):
     """The buffers of a mask-driven module on an Ho x Wo output map: nbits working masks `bits` (zero between frames),
     the frame's mask `copy`, and index buffer and count for a consumer that wants the list."""

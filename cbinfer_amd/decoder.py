@@ -19,8 +19,8 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (CBStateModule, hand_on_changes, later_producer_types, mask_workspace, operand_changes,
-                    producer_types, split_operand)
-from .conv2d import CBConv2d, _same_shape
+                    producer_types, split_operand, state_fits)
+from .conv2d import CBConv2d
 
 MAX_SCALE = 8
 
@@ -111,8 +111,7 @@ class CBUpsample2d(CBStateModule):
         work = self._workspace(Hi, Wi, x.device)
         Ho, Wo = work['size']
         form = operand_changes('CBUpsample2d', 'the input', indexes, Hi, Wi, x.device, work['idx'])
-        if (not _same_shape(self.outputState, (1, nc, Ho, Wo)) or self.outputState.dtype != x.dtype or
-                self.outputState.device != x.device):
+        if not state_fits(self.outputState, (1, nc, Ho, Wo), x):
             # a new state is written completely: the change information is not used
             self.outputState = torch.empty((1, nc, Ho, Wo), dtype=x.dtype, device=x.device)
             form = (None, None, 0, None)
@@ -179,8 +178,7 @@ class CBConcat2d(CBStateModule):
         work = self._workspace(n, H, W, t0.device)
         forms = [operand_changes('CBConcat2d', 'operand %d' % k, ix, H, W, t0.device, work['idx'])
                  for k, (_, ix) in enumerate(split)]
-        if (not _same_shape(self.outputState, (1, sum(chans), H, W)) or self.outputState.dtype != t0.dtype or
-                self.outputState.device != t0.device or self.__dict__.get('_channels') != chans):
+        if not state_fits(self.outputState, (1, sum(chans), H, W), t0) or self.__dict__.get('_channels') != chans:
             # a new state is written completely: no operand's change information is used
             self.outputState = torch.empty((1, sum(chans), H, W), dtype=t0.dtype, device=t0.device)
             self.__dict__['_channels'] = chans

@@ -10,14 +10,14 @@ and leaves every other output pixel bit for bit as it was.
 """
 import ctypes
 
-import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
+from ._lib import C, CBinferError, check, dtype_code, ptr, stream_ptr
 from .chain import (PROPAGATED, hand_back, hand_on_changes, is_1x1, later_producer_types, mask_workspace,
                     operand_changes, producer_types)
-from .conv2d import _padding_pair, _same_shape
+from .conv2d import _padding_pair
+from .layer import CBDetectingLayer, check_limits, frame_masks
 
 MAX_K, MAX_S, MAX_D, MAX_P = 7, 4, 8, 64
 
@@ -38,15 +38,8 @@ def _check_depthwise(m):
         raise Err("CBDepthwiseConv2d: padding_mode=%r is not supported, only 'zeros'" % (m.padding_mode,))
     p = _padding_pair(m, 'CBDepthwiseConv2d')
     k, s, d = (tuple(int(v) for v in t) for t in (m.kernel_size, m.stride, m.dilation))
-    for i in (0, 1):
-        if k[i] > MAX_K:
-            raise Err("CBDepthwiseConv2d: kernel_size=%s is beyond what the library takes (<= %d per axis)" % (k, MAX_K))
-        if s[i] > MAX_S:
-            raise Err("CBDepthwiseConv2d: stride=%s is beyond what the library takes (<= %d per axis)" % (s, MAX_S))
-        if d[i] > MAX_D:
-            raise Err("CBDepthwiseConv2d: dilation=%s is beyond what the library takes (<= %d per axis)" % (d, MAX_D))
-        if p[i] > MAX_P:
-            raise Err("CBDepthwiseConv2d: padding=%s is beyond what the library takes (<= %d per axis)" % (p, MAX_P))
+    check_limits('CBDepthwiseConv2d', [('kernel_size', k, MAX_K), ('stride', s, MAX_S), ('dilation', d, MAX_D),
+                                       ('padding', p, MAX_P)])
     g = _lib.Geom(k[0], k[1], s[0], s[1], p[0], p[1], d[0], d[1])
     if not C.cbinfer_dwconv_supported(m.in_channels, m.out_channels // m.in_channels, ctypes.byref(g)):
         raise Err("CBDepthwiseConv2d: kernel_size=%s stride=%s padding=%s dilation=%s is beyond what the library takes"
@@ -59,7 +52,7 @@ def _propagated_ok(k, p, d):
     return all(d[i] == 1 and 2 * p[i] <= k[i] for i in (0, 1))
 
 
-class CBDepthwiseConv2d(nn.Module):
+class CBDepthwiseConv2d(CBDetectingLayer):
     """Change-based depthwise nn.Conv2d (no counterpart in the reference): groups == in_channels, out_channels a
     multiple of it; per axis kernel_size <= 7, stride <= 4, dilation <= 8, padding <= 64 (ints, 'valid' or a symmetric
     'same'); with or without bias, batch 1, fp32 or fp16.  The parameters are shared with the source module.
@@ -76,55 +69,9 @@ class CBDepthwiseConv2d(nn.Module):
     written."""
 
     def __init__(self, m, threshold):
-        super(CBDepthwiseConv2d, self).__init__()
-        self.kernel_size, self.stride, self.padding, self.dilation = _check_depthwise(m)
-        self.groups = m.groups
-        self.transposed = False
-        self.in_channels = m.in_channels
-        self.out_channels = m.out_channels
-        self.weight = m.weight      # shared with the source module
-        self.bias = m.bias
-        self.threshold = threshold
-        self.withReLU = False
+        super(CBDepthwiseConv2d, self).__init__(m, threshold, _check_depthwise(m))
         self.reluCap = None
-        self.propChangeIndexes = False
         self.propagatedChanges = False
-        self.copyInput = True
-        self.feedbackLoop = False
-        self.cloneOutput = True
-        self.clearMemory()
-
-    # ---------------------------------------------------------------- state
-    def clearMemory(self):
-        for name in ('prevInput', 'prevOutput'):
-            if name not in self._buffers:
-                self.register_buffer(name, self.weight.detach().new_zeros(0))
-        self.prevInput = self.weight.detach().new_zeros(0)
-        self.prevOutput = self.weight.detach().new_zeros(0)
-        for name in ('_work', '_geomC'):      # (transient: device work buffers, ctypes arguments)
-            self.__dict__[name] = None
-
-    def getStateTensors(self):
-        return [self.prevInput, self.prevOutput]
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d.update(_work=None, _geomC=None)
-        return d
-
-    def _struct(self):
-        """(pointer to) the layer's cbGeom; transient, made again after unpickling."""
-        if self.__dict__.get('_geomC') is None:
-            k, s, p, d = self.kernel_size, self.stride, self.padding, self.dilation
-            self.__dict__['_geomC'] = ctypes.pointer(_lib.Geom(k[0], k[1], s[0], s[1], p[0], p[1], d[0], d[1]))
-        return self.__dict__['_geomC']
-
-    def _out_hw(self, Hi, Wi):
-        Ho, Wo = ctypes.c_int(), ctypes.c_int()
-        if C.cbinfer_geom_out_size(Hi, Wi, self._struct(), ctypes.byref(Ho), ctypes.byref(Wo)) != 0:
-            raise CBinferError("CBDepthwiseConv2d: a %dx%d map is smaller than the filter's reach (kernel_size=%s, "
-                               "dilation=%s, padding=%s)" % (Hi, Wi, self.kernel_size, self.dilation, self.padding))
-        return Ho.value, Wo.value
 
     def _act(self):
         if not self.withReLU:
@@ -135,67 +82,15 @@ class CBDepthwiseConv2d(nn.Module):
             raise CBinferError("CBDepthwiseConv2d: reluCap=%r is not supported, only None or 6.0" % (self.reluCap,))
         return _lib.ACT_RELU6
 
-    def _bias_map(self, size, like):
-        """The dense value of an output pixel no tap reaches, broadcast over the map: the bias (0 without one), after
-        the activation.  The first frame overwrites every reachable pixel."""
-        fill = torch.zeros(size, dtype=like.dtype, device=like.device)
-        if self.bias is not None:
-            b = self.bias.detach().to(device=like.device, dtype=like.dtype)
-            act = self._act()
-            if act != _lib.ACT_NONE:
-                b = torch.relu(b) if act == _lib.ACT_RELU else torch.clamp(b, 0.0, 6.0)
-            fill += b.view(1, -1, 1, 1)
-        return fill
-
-    def _state_for(self, input, Ho, Wo, keepInput):
-        """(Re)allocate the state on a new resolution, dtype or device: prevInput +inf -- the first frame of a sequence
-        is dense through the same kernel, every input pixel changed.  True if prevOutput was (re)allocated."""
-        if not keepInput:
-            if self.prevInput.numel():
-                self.prevInput = input.new_zeros(0)
-        elif (not _same_shape(self.prevInput, input.size()) or self.prevInput.dtype != input.dtype or
-                self.prevInput.device != input.device):
-            self.prevInput = torch.full(input.size(), float('inf'), dtype=input.dtype, device=input.device)
-        size = (1, self.out_channels, Ho, Wo)
-        if (not _same_shape(self.prevOutput, size) or self.prevOutput.dtype != input.dtype or
-                self.prevOutput.device != input.device):
-            self.prevOutput = self._bias_map(size, input)
-            return True
-        return False
-
-    def _workspace(self, Hi, Wi, dev):
+    def _buffers_for(self, Ho, Wo, dev):
         """Frame masks (zero once) and their mask-copy view for the layer's own detection, working mask and mask copy
-        for propagated changes, index buffer and count for a consumer that wants the list: once per map size."""
-        key = (Hi, Wi, dev)
-        work = self.__dict__.get('_work')
-        if work is None or work['key'] != key:
-            Ho, Wo = self._out_hw(Hi, Wi)
-            frame = torch.zeros(C.cbinfer_frame_mask_bytes(Ho, Wo) // 8, dtype=torch.int64, device=dev)
-            off = C.cbinfer_frame_mask_copy_offset(Ho, Wo) // 8
-            work = self.__dict__['_work'] = dict(
-                mask_workspace(Ho, Wo, dev), key=key, size=(Ho, Wo), frame=frame,
-                frameCopy=frame[off:off + C.cbinfer_mask_words(Ho, Wo)])
-        return work
+        for propagated changes, index buffer and count for a consumer that wants the list."""
+        frame, frameCopy = frame_masks(Ho, Wo, dev)
+        return dict(mask_workspace(Ho, Wo, dev), frame=frame, frameCopy=frameCopy)
 
     # ---------------------------------------------------------------- frame
     def forward(self, inp):
-        indexes = None
-        if type(inp) == tuple:
-            if len(inp) != 3 or inp[0] != 'changeIndexes':
-                raise CBinferError("CBDepthwiseConv2d: the input is a tuple, but not ('changeIndexes', tensor, indexes)")
-            inp, indexes = inp[1], inp[2]
-        if not torch.is_tensor(inp):
-            raise CBinferError("CBDepthwiseConv2d: the input must be a tensor or the ('changeIndexes', tensor, indexes) "
-                               "tuple, got %s" % type(inp).__name__)
-        live = bool(getattr(inp, '_cbinfer_inplace_state', False))
-        x = inp.detach().contiguous()
-        if x.dim() != 4 or x.size(0) != 1 or x.size(1) != self.in_channels:
-            raise CBinferError("CBDepthwiseConv2d: the input must be a [1, %d, H, W] tensor, got %s"
-                               % (self.in_channels, tuple(x.shape)))
-        require_device(x)
-        if x.dtype != self.weight.dtype or x.device != self.weight.device:
-            raise CBinferError("CBDepthwiseConv2d: input (%s on %s) and weights (%s on %s) differ in dtype or device"
-                               % (x.dtype, x.device, self.weight.dtype, self.weight.device))
+        x, indexes, live = self._operand(inp)
         Cin, mult, Hi, Wi = self.in_channels, self.out_channels // self.in_channels, x.size(2), x.size(3)
         act, dt = self._act(), dtype_code(x)
         work = self._workspace(Hi, Wi, x.device)
@@ -219,15 +114,12 @@ class CBDepthwiseConv2d(nn.Module):
                 ptr(work['copy']), ptr(weight), ptr(bias), Cin, mult, Hi, Wi, self._struct(), act, dt, stream_ptr(x)))
             copy = work['copy']
         else:
-            self._state_for(x, Ho, Wo, keepInput=True)
-            if not self.prevInput.is_contiguous():
-                self.prevInput = self.prevInput.contiguous()
+            self._state_for(x, Ho, Wo)
             check(C.cbinfer_cbdwconv2d_forward(
                 ptr(x), ptr(self.prevInput), ptr(self.prevOutput), ptr(work['frame']), ptr(weight), ptr(bias), Cin, mult,
                 Hi, Wi, self._struct(), float(self.threshold), int(bool(self.feedbackLoop)), int(bool(self.copyInput)),
                 act, dt, stream_ptr(x)))
-            if not self.feedbackLoop and not self.copyInput:
-                self.prevInput = x.clone() if live else x
+            self._keep_input(x, live)
             copy = work['frameCopy']
         return hand_back(self, self.prevOutput, copy, (Ho, Wo), work)
 

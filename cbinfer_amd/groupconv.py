@@ -13,9 +13,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
+from ._lib import C, CBinferError, check, ptr, stream_ptr
 from .chain import hand_back, is_1x1
-from .conv2d import CBConv2d, _padding_pair, _same_shape, _switch
+from .conv2d import CBConv2d, _padding_pair
+from .layer import CBContractingLayer, check_limits
 
 MAX_K, MAX_S, MAX_D, MAX_P = 7, 4, 8, 64
 
@@ -32,15 +33,8 @@ def _check_grouped(m):
         raise Err("CBGroupedConv2d: padding_mode=%r is not supported, only 'zeros'" % (m.padding_mode,))
     p = _padding_pair(m, 'CBGroupedConv2d')
     k, s, d = (tuple(int(v) for v in t) for t in (m.kernel_size, m.stride, m.dilation))
-    for i in (0, 1):
-        if k[i] > MAX_K:
-            raise Err("CBGroupedConv2d: kernel_size=%s is beyond what the library takes (<= %d per axis)" % (k, MAX_K))
-        if s[i] > MAX_S:
-            raise Err("CBGroupedConv2d: stride=%s is beyond what the library takes (<= %d per axis)" % (s, MAX_S))
-        if d[i] > MAX_D:
-            raise Err("CBGroupedConv2d: dilation=%s is beyond what the library takes (<= %d per axis)" % (d, MAX_D))
-        if p[i] > MAX_P:
-            raise Err("CBGroupedConv2d: padding=%s is beyond what the library takes (<= %d per axis)" % (p, MAX_P))
+    check_limits('CBGroupedConv2d', [('kernel_size', k, MAX_K), ('stride', s, MAX_S), ('dilation', d, MAX_D),
+                                     ('padding', p, MAX_P)])
     g = _lib.Geom(k[0], k[1], s[0], s[1], p[0], p[1], d[0], d[1])
     if not C.cbinfer_groupconv_supported(m.in_channels, m.out_channels, m.groups, ctypes.byref(g)):
         raise Err("CBGroupedConv2d: groups=%d in_channels=%d out_channels=%d kernel_size=%s stride=%s padding=%s "
@@ -48,7 +42,7 @@ def _check_grouped(m):
     return k, s, p, d
 
 
-class CBGroupedConv2d(nn.Module):
+class CBGroupedConv2d(CBContractingLayer):
     """Change-based grouped nn.Conv2d (no counterpart in the reference): groups >= 2 dividing in_channels and
     out_channels; per axis kernel_size <= 7, stride <= 4, dilation <= 8, padding <= 64 (ints, 'valid' or a symmetric
     'same'); with or without bias, batch 1, fp32 or fp16.  groups == in_channels is taken and correct, but
@@ -62,146 +56,30 @@ class CBGroupedConv2d(nn.Module):
     the state is allocated and are never written."""
 
     def __init__(self, m, threshold):
-        super(CBGroupedConv2d, self).__init__()
-        self.kernel_size, self.stride, self.padding, self.dilation = _check_grouped(m)
-        self.groups = m.groups
-        self.transposed = False
-        self.in_channels = m.in_channels
-        self.out_channels = m.out_channels
-        self.weight = m.weight      # shared with the source module
-        self.bias = m.bias
-        self.threshold = threshold
-        self.withReLU = False
-        self.propChangeIndexes = False
-        self.copyInput = True
-        self.feedbackLoop = False
-        self.exactF32 = False
-        self.cloneOutput = True
-        self.clearMemory()
+        super(CBGroupedConv2d, self).__init__(m, threshold, _check_grouped(m))
 
-    # ---------------------------------------------------------------- state
-    def clearMemory(self):
-        for name in ('prevInput', 'prevOutput'):
-            if name not in self._buffers:
-                self.register_buffer(name, self.weight.detach().new_zeros(0))
-        self.prevInput = self.weight.detach().new_zeros(0)
-        self.prevOutput = self.weight.detach().new_zeros(0)
-        for name in ('_work', '_wprep', '_geomC'):      # (transient: device work buffers, ctypes arguments)
-            self.__dict__[name] = None
-
-    def getStateTensors(self):
-        return [self.prevInput, self.prevOutput]
-
-    def invalidateWeights(self):
-        """Forget the cached prepared weights -- after a write through `weight.data`, which bumps neither the Parameter
-        object nor its version counter."""
-        self.__dict__['_wprep'] = None
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d.update(_work=None, _wprep=None, _geomC=None)
-        return d
-
-    def _struct(self):
-        """(pointer to) the layer's cbGeom; transient, made again after unpickling."""
-        if self.__dict__.get('_geomC') is None:
-            k, s, p, d = self.kernel_size, self.stride, self.padding, self.dilation
-            self.__dict__['_geomC'] = ctypes.pointer(_lib.Geom(k[0], k[1], s[0], s[1], p[0], p[1], d[0], d[1]))
-        return self.__dict__['_geomC']
-
-    def _out_hw(self, Hi, Wi):
-        Ho, Wo = ctypes.c_int(), ctypes.c_int()
-        if C.cbinfer_geom_out_size(Hi, Wi, self._struct(), ctypes.byref(Ho), ctypes.byref(Wo)) != 0:
-            raise CBinferError("CBGroupedConv2d: a %dx%d map is smaller than the filter's reach (kernel_size=%s, "
-                               "dilation=%s, padding=%s)" % (Hi, Wi, self.kernel_size, self.dilation, self.padding))
-        return Ho.value, Wo.value
-
-    def _bias_map(self, size, like):
-        """The dense value of an output pixel no tap reaches, broadcast over the map: the bias (0 without one), after
-        the ReLU when withReLU.  The first frame overwrites every reachable pixel."""
-        fill = torch.zeros(size, dtype=like.dtype, device=like.device)
-        if self.bias is not None:
-            b = self.bias.detach().to(device=like.device, dtype=like.dtype)
-            fill += (torch.relu(b) if self.withReLU else b).view(1, -1, 1, 1)
-        return fill
-
-    def _state_for(self, input, Ho, Wo):
-        """(Re)allocate the state on a new resolution, dtype or device: prevInput +inf -- the first frame of a sequence
-        is dense through the same kernels, every input pixel changed."""
-        if (not _same_shape(self.prevInput, input.size()) or self.prevInput.dtype != input.dtype or
-                self.prevInput.device != input.device):
-            self.prevInput = torch.full(input.size(), float('inf'), dtype=input.dtype, device=input.device)
-        size = (1, self.out_channels, Ho, Wo)
-        if (not _same_shape(self.prevOutput, size) or self.prevOutput.dtype != input.dtype or
-                self.prevOutput.device != input.device):
-            self.prevOutput = self._bias_map(size, input)
-
-    def _workspace(self, Hi, Wi, dev):
-        """Frame masks (zero once), their mask-copy view, index buffer and count of the frame's list: once per map
-        size."""
-        key = (Hi, Wi, dev)
-        work = self.__dict__.get('_work')
-        if work is None or work['key'] != key:
-            Ho, Wo = self._out_hw(Hi, Wi)
-            bits = torch.zeros(C.cbinfer_frame_mask_bytes(Ho, Wo) // 8, dtype=torch.int64, device=dev)
-            off = C.cbinfer_frame_mask_copy_offset(Ho, Wo) // 8
-            work = self.__dict__['_work'] = dict(
-                key=key, size=(Ho, Wo), bits=bits, copy=bits[off:off + C.cbinfer_mask_words(Ho, Wo)],
-                idx=torch.empty(Ho * Wo, dtype=torch.int32, device=dev),
-                count=torch.zeros(1, dtype=torch.int32, device=dev))
-        return work
-
-    def _arith(self, t):
-        if dtype_code(t) == _lib.CB_F16:
-            return _lib.CB_F16
-        return _lib.CB_F32 if (self.exactF32 or _switch('CBINFER_EXACT_F32')) else _lib.CB_F32S
-
-    def _weights(self, Hi, Wi, arith):
-        w = self.weight
-        key = (w.data_ptr(), w._version, w.dtype, w.device, Hi, Wi, arith)
-        wprep = self.__dict__.get('_wprep')
-        if wprep is None or wprep[0] != key:
-            K, Cin, G, g = self.out_channels, self.in_channels, self.groups, self._struct()
-            wp = torch.empty(C.cbinfer_groupconv_prepared_weights_bytes(K, Cin, G, g, arith), dtype=torch.uint8,
-                             device=w.device)
-            check(C.cbinfer_groupconv_prep_weights(ptr(w.detach().contiguous()), ptr(wp), K, Cin, G, Hi, Wi, g, arith,
-                                                   stream_ptr(w)))
-            wprep = self.__dict__['_wprep'] = (key, wp)
-        return wprep[1]
+    def _prepare(self, w, Hi, Wi, arith):
+        K, Cin, G, g = self.out_channels, self.in_channels, self.groups, self._struct()
+        wp = torch.empty(C.cbinfer_groupconv_prepared_weights_bytes(K, Cin, G, g, arith), dtype=torch.uint8,
+                         device=w.device)
+        check(C.cbinfer_groupconv_prep_weights(ptr(w), ptr(wp), K, Cin, G, Hi, Wi, g, arith, stream_ptr(w)))
+        return wp
 
     # ---------------------------------------------------------------- frame
     def forward(self, inp):
-        if type(inp) == tuple:
-            if len(inp) != 3 or inp[0] != 'changeIndexes':
-                raise CBinferError("CBGroupedConv2d: the input is a tuple, but not ('changeIndexes', tensor, indexes)")
-            inp = inp[1]      # (the layer runs its own detection)
-        if not torch.is_tensor(inp):
-            raise CBinferError("CBGroupedConv2d: the input must be a tensor or the ('changeIndexes', tensor, indexes) "
-                               "tuple, got %s" % type(inp).__name__)
-        live = bool(getattr(inp, '_cbinfer_inplace_state', False))
-        x = inp.detach().contiguous()
-        if x.dim() != 4 or x.size(0) != 1 or x.size(1) != self.in_channels:
-            raise CBinferError("CBGroupedConv2d: the input must be a [1, %d, H, W] tensor, got %s"
-                               % (self.in_channels, tuple(x.shape)))
-        require_device(x)
-        if x.dtype != self.weight.dtype or x.device != self.weight.device:
-            raise CBinferError("CBGroupedConv2d: input (%s on %s) and weights (%s on %s) differ in dtype or device"
-                               % (x.dtype, x.device, self.weight.dtype, self.weight.device))
+        x, _, live = self._operand(inp)      # (the indexes are ignored: the layer runs its own detection)
         arith = self._arith(x)
         Cin, K, Hi, Wi = self.in_channels, self.out_channels, x.size(2), x.size(3)
         work = self._workspace(Hi, Wi, x.device)
         Ho, Wo = work['size']
         self._state_for(x, Ho, Wo)
-        if not self.prevInput.is_contiguous():
-            self.prevInput = self.prevInput.contiguous()
         bias = self.bias.detach() if self.bias is not None else None
         check(C.cbinfer_cbgroupconv2d_forward(
             ptr(x), ptr(self.prevInput), ptr(self.prevOutput), ptr(work['bits']), ptr(work['idx']), ptr(work['count']),
             ptr(self._weights(Hi, Wi, arith)), ptr(bias), Cin, Hi, Wi, K, self.groups, self._struct(),
             float(self.threshold), int(bool(self.feedbackLoop)), int(bool(self.copyInput)), int(bool(self.withReLU)),
             arith, stream_ptr(x)))
-        if not self.feedbackLoop and not self.copyInput:
-            self.prevInput = x.clone() if live else x
+        self._keep_input(x, live)
         # (the contraction left the frame's list and count in work['idx'] / work['count']: made)
         return hand_back(self, self.prevOutput, work['copy'], (Ho, Wo), work, made=True)
 

@@ -13,8 +13,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (CBStateModule, hand_on_changes, is_1x1, later_producer_types, mask_workspace, operand_changes,
-                    producer_types, split_operand)
-from .conv2d import _same_shape
+                    producer_types, split_operand, state_fits)
 
 # nn type (exactly, not a subclass) -> (CB_PW_* kind, p0, p1 of the instance)
 _ACTIVATIONS = {
@@ -141,8 +140,7 @@ class CBPointwise2d(CBStateModule):
                                    % (x.device, name, t.device))
         work = self._workspace(nc, H, W, x.device)
         mask, lst, cap, count = operand_changes('CBPointwise2d', 'the input', indexes, H, W, x.device, work['idx'])
-        if (not _same_shape(self.outputState, x.shape) or self.outputState.dtype != x.dtype or
-                self.outputState.device != x.device):
+        if not state_fits(self.outputState, x.shape, x):
             # a new state is written completely: the operand's change information is not used
             self.outputState = torch.empty_like(x)
             mask, lst, cap, count = None, None, 0, None

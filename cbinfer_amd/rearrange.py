@@ -16,8 +16,8 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (CBStateModule, hand_on_changes, is_1x1, later_producer_types, mask_workspace, operand_changes,
-                    producer_types, split_operand)
-from .conv2d import CBConv2d, _same_shape
+                    producer_types, split_operand, state_fits)
+from .conv2d import CBConv2d
 from .groupconv import CBGroupedConv2d
 
 MAX_FACTOR = 8      # of the two pixel shuffles: CBUpsample2d's scale limit
@@ -87,8 +87,7 @@ class _CBRearrange2d(CBStateModule):
         work = self._workspace(nc, Hi, Wi, x.device)
         Co, Ho, Wo = work['shape']
         form = operand_changes(self.NAME, 'the input', indexes, Hi, Wi, x.device, work['idx'])
-        if (not _same_shape(self.outputState, (1, Co, Ho, Wo)) or self.outputState.dtype != x.dtype or
-                self.outputState.device != x.device):
+        if not state_fits(self.outputState, (1, Co, Ho, Wo), x):
             # a new state is written completely: the change information is not used
             self.outputState = torch.empty((1, Co, Ho, Wo), dtype=x.dtype, device=x.device)
             form = (None, None, 0, None)

@@ -11,8 +11,8 @@ import torch
 import torch.nn as nn
 
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import OPERAND_WORDS, CBStateModule, mask_workspace, operand_changes, split_operand
-from .conv2d import CBConv2d, _same_shape
+from .chain import OPERAND_WORDS, CBStateModule, mask_workspace, operand_changes, split_operand, state_fits
+from .conv2d import CBConv2d
 
 
 # operand_changes' refusals in this module's words (which: 'operand a' / 'operand b')
@@ -58,8 +58,7 @@ class CBAdd2d(CBStateModule):
         # (a list the producer's kernel already made is taken before its mask)
         fa, fb = (operand_changes('CBAdd2d', 'operand ' + which, ix, H, W, a.device, work['idx'], words=_ADD_WORDS,
                                   maskWhenMade=False) for which, ix in (('a', ia), ('b', ib)))
-        if (not _same_shape(self.outputState, a.shape) or self.outputState.dtype != a.dtype or
-                self.outputState.device != a.device):
+        if not state_fits(self.outputState, a.shape, a):
             # a new state is written completely: neither operand's change information is used
             self.outputState = torch.empty_like(a)
             fa = fb = (None, None, 0, None)
