@@ -26,6 +26,7 @@ from .dwconv import CBDepthwiseConv2d, linkDepthwise
 from .pointwise import CBPointwise2d, insertCBPointwise
 from .groupconv import CBGroupedConv2d, linkGrouped
 from .rearrange import CBPixelShuffle2d, CBChannelShuffle2d, insertCBRearrange
+from .chanreduce import CBChannelReduce2d, insertCBChannelOps
 
 __version__ = "0.1.0"
 
@@ -274,7 +275,7 @@ def linkConsumers(producer, consumers):
 
 
 _STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d,
-             CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d)
+             CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d, CBChannelReduce2d)
 
 
 def _stateful(net):
@@ -395,7 +396,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'insertCBRearrange', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'insertCBRearrange', 'CBChannelReduce2d', 'insertCBChannelOps', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

@@ -114,6 +114,7 @@ ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2      # CB_ACT_*
 # CB_PW_*
 (PW_IDENTITY, PW_RELU, PW_HARDTANH, PW_LEAKY, PW_PRELU, PW_HARDSWISH, PW_HARDSIGMOID, PW_SIGMOID, PW_SILU,
  PW_TANH) = range(10)
+CH_LAYERNORM, CH_L2NORM, CH_SOFTMAX, CH_LOGSOFTMAX = range(4)      # CB_CH_*
 
 
 class Upsample(ctypes.Structure):
@@ -305,6 +306,9 @@ _SIGNATURES = {
     "cbinfer_pointwise_changed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i, _vp]),
     "cbinfer_cbpointwise_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i,
                                          _vp]),
+    "cbinfer_chanreduce_supported": (_i, [_i, _i, _f]),
+    "cbinfer_chanreduce_changed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    "cbinfer_cbchanreduce_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     "cbinfer_groupconv_supported": (_i, [_i, _i, _i, _gp]),
     "cbinfer_groupconv_prepared_weights_bytes": (_l, [_i, _i, _i, _gp, _i]),
     "cbinfer_groupconv_prep_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _gp, _i, _vp]),

@@ -1,0 +1,188 @@
+"""Change-based reductions over the channels of one pixel: CBChannelReduce2d and insertCBChannelOps (cb_chanreduce.hip,
+DESIGN 5.21).
+
+The reference has no such operator: the channels-first LayerNorm of a ConvNeXt-type block, the nn.Softmax2d /
+nn.Softmax(dim=1) / nn.LogSoftmax(dim=1) of a segmentation head and the F.normalize(x, dim=1) of a descriptor head stay
+dense torch operators -- they recompute the whole map, drop the producer's change information and cannot be recorded by a
+FrameProgram.  None of them is element-wise, but all are PIXEL-wise: the output at a pixel depends on the C values at
+that pixel alone.  Every producer of this package leaves the pixels outside its change list bit for bit as they were, so
+CBChannelReduce2d recomputes at the producer's changed pixels and is the dense result exactly, without a threshold.
+Norms that also reduce over H x W (GroupNorm, InstanceNorm) do not have this property and are not taken.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
+from .chain import (CBStateModule, hand_on_changes, is_1x1, later_producer_types, mask_workspace, operand_changes,
+                    producer_types, split_operand, state_fits)
+
+_AFFINE = ('gamma', 'beta')
+_SOFTMAX = {nn.Softmax2d: _lib.CH_SOFTMAX, nn.Softmax: _lib.CH_SOFTMAX, nn.LogSoftmax: _lib.CH_LOGSOFTMAX}
+KIND_NAMES = ('layernorm', 'l2norm', 'softmax', 'logsoftmax')
+
+
+def _f32_vector(t, name):
+    """A detached float32 copy [C] of a parameter (an fp16 parameter converts exactly), or None."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.dim() != 1:
+        raise CBinferError("CBChannelReduce2d: op.%s must be a one-dimensional tensor or None" % name)
+    return t.detach().float().clone()
+
+
+def _layer_norm(op, eps):
+    """(gamma, beta, eps) of a layer norm over the channel axis: an nn.LayerNorm over (C,), or a channels-first class of
+    the user's with .weight, .bias (or None) and .eps."""
+    if type(op) is nn.LayerNorm and len(op.normalized_shape) != 1:
+        raise CBinferError("CBChannelReduce2d: op=%r normalises over normalized_shape=%s: only a LayerNorm over (C,), "
+                           "read as a normalisation over the channel axis, is a per-pixel operator"
+                           % (op, tuple(op.normalized_shape)))
+    gamma, beta = _f32_vector(getattr(op, 'weight', None), 'weight'), _f32_vector(getattr(op, 'bias', None), 'bias')
+    if gamma is None and beta is not None:
+        raise CBinferError("CBChannelReduce2d: op=%r has a bias but no weight" % (op,))
+    if gamma is not None and beta is None:
+        beta = torch.zeros_like(gamma)      # (nn.LayerNorm(bias=False): adding +0 changes no value but a -0)
+    if gamma is not None and gamma.numel() != beta.numel():
+        raise CBinferError("CBChannelReduce2d: op.weight has %d values, op.bias %d" % (gamma.numel(), beta.numel()))
+    return gamma, beta.to(gamma.device) if gamma is not None else None, (op.eps if eps is None else eps)
+
+
+class CBChannelReduce2d(CBStateModule):
+    """A reduction over the channel axis at every pixel, recomputed at the operand's changed pixels (no counterpart in the
+    reference).
+
+    op: an nn.Softmax2d; an nn.Softmax or nn.LogSoftmax with dim 1 or -3; an nn.LayerNorm whose normalized_shape is (C,),
+    read as a normalisation over the channel axis of the [1, C, H, W] map (it supplies weight, bias and eps;
+    elementwise_affine=False: no gamma / beta); or the string 'l2norm' (F.normalize(x, p=2, dim=1, eps), eps 1e-12 by
+    default).  The types are taken exactly, not by subclass; layerNormTypes names further -- channels-first --
+    layer-norm classes of the user's, exact types with .weight, .bias (or None) and .eps.  eps overrides the operator's.
+    gamma / beta are copied HERE and kept as float32 buffers (pickled, moved by .to(), kept float32 by .half()): later
+    edits of the source module are not followed.  LayerNorm and the L2 norm are the float32 specification of DESIGN 5.21
+    bit for bit; the softmax kinds call the device's expf / logf (the bound is there).
+
+    forward(x), propChangeIndexes and cloneOutput are CBPointwise2d's: a bare tensor carries no change information, a
+    MaskChangeIndexes is taken as its mask, any other ChangeIndexes or an int32 tensor as a list; the first frame or a new
+    shape recomputes every pixel."""
+
+    _WORK = '_chWork'
+
+    def __init__(self, op, eps=None, layerNormTypes=()):
+        super(CBChannelReduce2d, self).__init__()
+        gamma = beta = None
+        self.opName = op if isinstance(op, str) else type(op).__name__
+        if isinstance(op, str):
+            if op != 'l2norm':
+                raise CBinferError("CBChannelReduce2d: op=%r is not supported, of the strings only 'l2norm'" % (op,))
+            self.kind, eps = _lib.CH_L2NORM, (1e-12 if eps is None else eps)
+        elif type(op) in _SOFTMAX:
+            dim = 1 if type(op) is nn.Softmax2d else op.dim
+            if dim not in (1, -3):
+                raise CBinferError("CBChannelReduce2d: op=%r reduces over dim=%r: only dim=1 (or -3), the channel axis "
+                                   "of a [1, C, H, W] map, is a per-pixel operator" % (op, dim))
+            if eps is not None:
+                raise CBinferError("CBChannelReduce2d: eps=%r given for op=%s, which has none" % (eps, self.opName))
+            self.kind, eps = _SOFTMAX[type(op)], 0.0
+        elif type(op) is nn.LayerNorm or type(op) in tuple(layerNormTypes):
+            self.kind = _lib.CH_LAYERNORM
+            gamma, beta, eps = _layer_norm(op, eps)
+        else:
+            raise CBinferError("CBChannelReduce2d: op=%s is not supported, only an instance of exactly nn.Softmax2d, "
+                               "nn.Softmax, nn.LogSoftmax, nn.LayerNorm (or one of layerNormTypes), or 'l2norm'"
+                               % self.opName)
+        try:
+            self.eps = float(np.float32(eps))      # (the kernel's value: rounded to f32 once)
+        except (TypeError, ValueError):
+            raise CBinferError("CBChannelReduce2d: eps=%r is not a number" % (eps,))
+        if not C.cbinfer_chanreduce_supported(self.kind, 1, self.eps):
+            raise CBinferError("CBChannelReduce2d: eps=%r must be a number >= 0" % (eps,))
+        for name, t in zip(_AFFINE, (gamma, beta)):
+            self.register_buffer(name, t)
+        # (the state behind the per-channel operands, as CBPointwise2d lists them)
+        self._buffers['outputState'] = self._buffers.pop('outputState')
+
+    def _apply(self, fn, *args, **kwargs):
+        # (.half() / .double() convert every floating-point buffer: gamma / beta stay float32, the kernel's)
+        keep = {n: self._buffers[n] for n in _AFFINE if self._buffers.get(n) is not None}
+        super(CBChannelReduce2d, self)._apply(fn, *args, **kwargs)
+        for n, t in keep.items():
+            if self._buffers[n].dtype != torch.float32:
+                self._buffers[n] = t.to(self._buffers[n].device)
+        return self
+
+    def _workspace(self, nc, H, W, dev):
+        """Working mask (zero between frames), the frame's mask copy, index buffer and count: once per map size."""
+        key = (nc, H, W, dev)
+        work = self.__dict__.get('_chWork')
+        if work is None or work['key'] != key:
+            work = self.__dict__['_chWork'] = dict(mask_workspace(H, W, dev), key=key)
+        return work
+
+    def forward(self, inp):
+        x, indexes = split_operand('CBChannelReduce2d', inp, 'the input')
+        if x.dim() != 4 or x.size(0) != 1:
+            raise CBinferError("CBChannelReduce2d: the input must be a [1, C, H, W] tensor, got %s" % (tuple(x.shape),))
+        if x.dtype not in (torch.float32, torch.float16):
+            raise CBinferError("CBChannelReduce2d: float32 and float16 tensors only, got %s" % x.dtype)
+        nc, H, W = x.size(1), x.size(2), x.size(3)
+        if self.gamma is not None and self.gamma.numel() != nc:
+            raise CBinferError("CBChannelReduce2d: the input has %d channels, gamma was made for %d"
+                               % (nc, self.gamma.numel()))
+        require_device(x)
+        if self.gamma is not None and self.gamma.device != x.device:
+            raise CBinferError("CBChannelReduce2d: the input is on %s, gamma on %s (move the module with .to())"
+                               % (x.device, self.gamma.device))
+        work = self._workspace(nc, H, W, x.device)
+        mask, lst, cap, count = operand_changes('CBChannelReduce2d', 'the input', indexes, H, W, x.device, work['idx'])
+        if not state_fits(self.outputState, x.shape, x):
+            # a new state is written completely: the operand's change information is not used
+            self.outputState = torch.empty_like(x)
+            mask, lst, cap, count = None, None, 0, None
+        check(C.cbinfer_cbchanreduce_forward(ptr(x), ptr(self.outputState), ptr(mask), ptr(lst), cap, ptr(count),
+                                             ptr(work['bits']), ptr(work['copy']), nc, H, W, self.kind, self.eps,
+                                             ptr(self.gamma), ptr(self.beta), dtype_code(x), stream_ptr(x)))
+        return self._result(work, H, W)
+
+    def __repr__(self):
+        return 'CBChannelReduce2d (op=%s, kind=%s, eps=%s, affine=%s, propChgIdxs=%s)' % (
+            self.opName, KIND_NAMES[self.kind], self.eps, self.gamma is not None, self.propChangeIndexes)
+
+
+def insertCBChannelOps(rootModule, layerNormTypes=()):
+    """Inside every nn.Sequential of rootModule, an nn.Softmax2d, an nn.Softmax / nn.LogSoftmax over dim 1 (or -3), or an
+    instance of one of layerNormTypes -- the user's channels-first layer-norm classes, exact types with .weight, .bias (or
+    None) and .eps, as ConvNeXt's LayerNorm2d; torch has no such class of its own -- that directly follows a producer
+    (chain.producer_types() + later_producer_types(), a CBGroupedConv2d or another CBChannelReduce2d) becomes a
+    CBChannelReduce2d under the same name, fed by that producer's changes: propChangeIndexes is switched on at the
+    producer (chain.hand_on_changes).  The new module hands its own changes on where it stands directly in front of a
+    1x1 / stride-1 / padding-0 CBConv2d; any other CBConv2d directly behind it needs its own input copy (copyInput)
+    unless it runs in feedback mode, as insertCBRearrange has it.  Anything else -- a softmax over another axis, a module
+    behind a dense operator -- stays dense.  The producer tables are pinned, so linkDepthwise, insertCBPointwise,
+    insertCBUpsampling, insertCBTransposedConv and the general pools do not yet take the new module as a producer.
+    Returns rootModule."""
+    from .conv2d import CBConv2d
+    from .groupconv import CBGroupedConv2d
+    layerNormTypes = tuple(layerNormTypes)
+    producers = producer_types() + later_producer_types() + (CBGroupedConv2d, CBChannelReduce2d)
+    for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
+        names = list(seq._modules.keys())
+        for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
+            prod, op = seq._modules[a], seq._modules[b]
+            if type(prod) not in producers:
+                continue
+            if type(op) in _SOFTMAX:
+                if type(op) is not nn.Softmax2d and op.dim not in (1, -3):
+                    continue
+            elif type(op) not in layerNormTypes:
+                continue
+            cb = CBChannelReduce2d(op, layerNormTypes=layerNormTypes)
+            hand_on_changes(prod)
+            seq._modules[b] = cb
+            if pos + 2 < len(names):
+                consumer = seq._modules[names[pos + 2]]
+                if is_1x1(consumer):
+                    cb.propChangeIndexes = True
+                elif type(consumer) is CBConv2d and not consumer.feedbackLoop:
+                    consumer.copyInput = True
+    return rootModule

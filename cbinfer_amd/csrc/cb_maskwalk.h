@@ -47,6 +47,28 @@ __device__ __forceinline__ void cb_walk_words(unsigned long long* bits, unsigned
     }
 }
 
+// The same walk for an operator whose unit of work is the whole word (cb_chanreduce.hip: a reduction over the channels
+// of each listed pixel, which the (set bit, channel) items of cb_walk_items cannot express): the same OR of working
+// word and makeWord, the same cut, maskCopy store and zeroing; unit(word, y, tile) runs on all 256 threads for every
+// non-empty word, which is uniform over the workgroup -- unit may hold barriers.
+template <typename MakeWord, typename Unit>
+__device__ __forceinline__ void cb_walk_word_units(unsigned long long* bits, unsigned long long* __restrict__ maskCopy,
+                                                   long words, int W, int wpr, int all, MakeWord makeWord, Unit unit) {
+    for (long w = blockIdx.x; w < words; w += gridDim.x) {
+        const unsigned long long own = bits[w];
+        const int y = (int)(w / wpr), tile = (int)(w - (long)y * wpr);
+        const unsigned long long valid = cb_valid_mask(W, tile);
+        unsigned long long word = own | makeWord(w, y, tile);
+        word = all ? valid : (word & valid);      // (the bits of the row padding are never set)
+        if (threadIdx.x == 0) maskCopy[w] = word;
+        if (word != 0) unit(word, y, tile);
+        if (own != 0) {
+            __syncthreads();      // every wave has read the word
+            if (threadIdx.x == 0) bits[w] = 0;
+        }
+    }
+}
+
 // workgroups of a persistent grid over `units` units of work: all of them, at most eight per CU
 inline unsigned cb_walk_grid(long units) {
     const long cap = (long)cb_num_cus() * 8;

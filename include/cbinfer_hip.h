@@ -69,7 +69,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_cbdwconv2d_forward*), the element-wise functions (CB_PW_*, cbinfer_pointwise_supported,
  * cbinfer_pointwise_changed, cbinfer_cbpointwise_forward) and the grouped convolution (cbinfer_groupconv_*,
  * cbinfer_conv_changed_grouped, cbinfer_cbgroupconv2d_forward) and the rearrangements (cbRearrange, CB_REARRANGE_*,
- * cbinfer_rearrange_supported, cbinfer_rearrange_out_shape, cbinfer_cbrearrange_forward). */
+ * cbinfer_rearrange_supported, cbinfer_rearrange_out_shape, cbinfer_cbrearrange_forward) and the per-pixel channel
+ * reductions (CB_CH_*, cbinfer_chanreduce_supported, cbinfer_chanreduce_changed, cbinfer_cbchanreduce_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -940,6 +941,59 @@ int cbinfer_cbpointwise_forward(const void* x, void* outputState, const uint64_t
                                 const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int kind,
                                 float p0, float p1, const float* scale, const float* shift, const float* slope, int dtype,
                                 cbStream_t stream);
+
+/* ---- change-based reductions over the channels of one pixel (cb_chanreduce.hip) -------------------------
+ * No counterpart in the reference.  Channels-first LayerNorm, L2 normalisation, softmax and log-softmax: the output at a
+ * pixel depends on the C values at that pixel and on nothing else.  x and the state `out` are [C, H, W], contiguous, one
+ * dtype (CB_F32 or CB_F16), two different tensors.  Every producer of this library leaves the pixels outside its change
+ * list bit for bit as they were, so the output can differ from last frame's only at the operand's changed pixels;
+ * recomputing there is the dense result.
+ *   listed pixels: the operand's changes, as its row-padded change MASK (cbinfer_mask_words(H, W) words), as an int32
+ *     LIST (flat indexes y W + x; entries outside the map are dropped), or not at all: every pixel is listed then.  Bits
+ *     of the row padding are never set.
+ *   values: at listed pixels, all in f32, every operation correctly rounded in the order written and never contracted
+ *     to an FMA; the result is rounded to f16 once at the end for CB_F16.
+ *       sum16(v) of v_0 .. v_{C-1}: 16 slices, slice s holds the channels c = s mod 16; a slice's partial starts at +0
+ *         and adds its channels in ascending c; the 16 partials are combined in the fixed tree p[2i] + p[2i+1], four
+ *         levels (an empty slice contributes +0).
+ *       max16(v): the same slices and tree with op(a, b) = b > a ? b : a, a slice starting at -inf (a NaN is never taken).
+ *       CB_CH_LAYERNORM    mean = sum16(x) / C;  d_c = x_c - mean;  var = sum16(d_c d_c) / C;  r = 1 / sqrtf(var + eps);
+ *                          y_c = d_c r;  with gamma, beta (f32 [C], both or neither): y_c = y_c gamma_c, then
+ *                          y_c = y_c + beta_c                      (F.layer_norm over the channel axis, biased variance)
+ *       CB_CH_L2NORM       s = sum16(x_c x_c);  t = sqrtf(s);  y_c = x_c / (t < eps ? eps : t)
+ *                                                                                       (F.normalize(x, p=2, dim=1, eps))
+ *       CB_CH_SOFTMAX      m = max16(x);  a_c = x_c - m;  e_c = expf(a_c);  s = sum16(e);  y_c = e_c / s
+ *       CB_CH_LOGSOFTMAX   the same m, a, s;  y_c = a_c - logf(s)
+ *     Division and sqrtf are the IEEE correctly rounded ones; expf / logf are the device's.  Every other pixel of `out`
+ *     keeps its bits; a pixel's bits depend neither on the other listed pixels nor on the operand's form -- how slices
+ *     and pixels are dealt to lanes depends on a word's popcount, the arithmetic does not.
+ *   hand-on: maskCopy receives the frame's mask every frame (all zeros for an empty frame: cbinfer_compact_bits makes
+ *     the ascending list from it on demand); `bits`, the working mask (cbinfer_mask_words(H, W) words, zero on first
+ *     use), is zero again when the launch ends.
+ * All arguments are checked before the first launch.  A null tensor or mask buffer, x == out, bits == maskCopy, the
+ * operand's mask == bits or maskCopy, both a mask and a list, a count without a list, capN < 0, an unknown kind or dtype,
+ * eps < 0 or a NaN, gamma without beta or the reverse, gamma with a kind other than CB_CH_LAYERNORM, C / H / W < 1, H W or
+ * 64 C beyond an int32 return CB_ERR_BADARG and launch nothing.  There is no other limit on C. */
+#define CB_CH_LAYERNORM 0
+#define CB_CH_L2NORM 1
+#define CB_CH_SOFTMAX 2
+#define CB_CH_LOGSOFTMAX 3
+/* host, pure: 1 if `kind` is one of CB_CH_*, C >= 1 and eps >= 0 (not a NaN), else 0 */
+int cbinfer_chanreduce_supported(int kind, int C, float eps);
+/* The mask-driven launch.  mask: the operand's change mask, or NULL; all != 0: every pixel is listed.  The kernel ORs
+ * `bits` and mask word by word itself (or forms the full row word); without a mask the operand contributes what `bits`
+ * holds on entry.  gamma / beta: plain pointers, NULL = absent.  No atomics. */
+int cbinfer_chanreduce_changed(const void* x, void* out, const uint64_t* mask, int all, uint64_t* bits, uint64_t* maskCopy,
+                               int C, int H, int W, int kind, float eps, const float* gamma, const float* beta, int dtype,
+                               cbStream_t stream);
+/* The whole frame enqueued without a host sync.  mask != NULL: mask form, ONE launch (cbinfer_chanreduce_changed);
+ * list != NULL: list form (capN entries at most, countDev the device-side length or NULL: capN is the length; capN == 0
+ * launches nothing in front), one launch in front, which ORs the list's bits into `bits` (cbinfer_pool_footprint with a
+ * 1x1 / stride-1 window: one 64-bit atomicOr per entry); both NULL: no change information, every pixel is listed, one
+ * launch. */
+int cbinfer_cbchanreduce_forward(const void* x, void* outputState, const uint64_t* mask, const int32_t* list, int capN,
+                                 const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int kind,
+                                 float eps, const float* gamma, const float* beta, int dtype, cbStream_t stream);
 
 /* ---- change-based upsampling and channel concatenation for decoders (cb_decoder.hip) -------------------
  * No counterpart in the reference.  Both operators are exact for the reason the sum is: every producer leaves the pixels
