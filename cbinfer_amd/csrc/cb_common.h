@@ -165,6 +165,17 @@ __device__ __forceinline__ T cb_pooled_load(const T* q, int px1, int py1) {
     return cb_max(cb_max(q[0], q[px1]), cb_max(q[py1], q[py1 + px1]));
 }
 
+// Frame-mask protocol, end of a launch that consumed the frame's mask: ctl = {parity, arrivals} behind the two masks.
+// Called by every one of the launch's `groups` workgroups once it has read the parity `par` and its words of the mask;
+// the last one to arrive flips the parity and leaves the arrival counter at zero.
+__device__ __forceinline__ void cb_flip_parity_last(int* ctl, int par, int groups) {
+    __syncthreads();
+    if (threadIdx.x == 0 && __hip_atomic_fetch_add(ctl + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1) {
+        __hip_atomic_store(ctl + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ctl, par ^ 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // x = hi + mid + lo with three bf16 terms (24 significant bits): hi = bf16(x), mid = bf16(x - hi),
 // lo = bf16(x - hi - mid); both differences are exact in f32.  Returned as the raw 16-bit patterns.
 // (cbs_split3 in cb_split_common.h is NOT a copy: it carries non-finite inputs and truncates near FLT_MAX.)

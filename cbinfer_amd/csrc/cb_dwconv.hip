@@ -112,16 +112,8 @@ __global__ __launch_bounds__(256) void cbdw_kernel(const T* __restrict__ in, con
             if (hit && k0 + j < K) out[(long)(k0 + j) * HWo + (long)oy * Wo + ox] = (T)r;
         }
     }
-    if (frameMasks) {
-        // this workgroup has read the parity and its words: the last one to arrive flips the parity
-        int* ctl = (int*)(frameMasks + 2 * words);
-        __syncthreads();
-        if (threadIdx.x == 0 &&
-            __hip_atomic_fetch_add(ctl + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
-            __hip_atomic_store(ctl + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(ctl, par ^ 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    // this workgroup has read the parity and its words
+    if (frameMasks) cb_flip_parity_last((int*)(frameMasks + 2 * words), par, (int)gridDim.x);
 }
 
 template <typename T>

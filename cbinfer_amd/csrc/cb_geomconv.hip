@@ -23,12 +23,6 @@ namespace {
 #define CBG_MAX_S 4      // stride per axis
 #define CBG_MAX_D 8      // dilation per axis
 #define CBG_MAX_P 64     // padding per axis
-#define CBG_BM 64        // output channels per tile
-#define CBG_BN 64        // listed pixels per tile
-#define CBG_BK 32        // k-depth per LDS stage
-#define CBG_GRID 512     // persistent grid of the contraction (2 workgroups per CU of an MI355X)
-#define CBG_SKMAX 8      // most k-slices per tile
-#define CBG_SLAB (CBG_BM * CBG_BN)
 
 int cbg_geom_status(const cbGeom* g) {
     if (!g) return CB_ERR_BADARG;
@@ -51,33 +45,19 @@ int cbg_out_size(int Hi, int Wi, const cbGeom* g, int* Ho, int* Wo) {
     return CB_OK;
 }
 
-int cbg_kpad(int K) { return (K + CBG_BM - 1) / CBG_BM * CBG_BM; }
-int cbg_ckkpad(int Ckk) { return (Ckk + CBG_BK - 1) / CBG_BK * CBG_BK; }
-
 // ---------------------------------------------------------------------------------------------
-// weight preparation: W[KP][CkkP] in the tensors' element type (k contiguous, zero padded), then the k -> tap table:
-//   off[k]  = byte offset of tap (c, ky, kx) relative to the BASE pixel (oy sH, ox sW) of the input map
-//   dydx[k] = (dx << 16) | (dy & 0xffff) with dy = ky dH - pH, dx = kx dW - pW (the border test against Hi, Wi)
-// The padded tail k >= Ckk gets dy = dx = -32768: outside every map (either one alone is not -- a base pixel at row
-// 32768 or beyond brings the tap back inside a map that tall; both at once would need 2^30 pixels, which
-// cbinfer_geom_prep_weights refuses).
+// weight preparation: W[KP][CkkP] in the tensors' element type (k contiguous, zero padded), then the k -> tap table
+// (cbg_tab_entry): tap (c, ky, kx) lies at dy = ky dH - pH, dx = kx dW - pW from the BASE pixel (oy sH, ox sW) of the
+// input map.  The padded tail's marker needs a map of fewer than 2^30 pixels, which cbinfer_geom_prep_weights checks.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void cbg_prep_kernel(const T* __restrict__ w, T* __restrict__ wp, int K, int Ckk,
                                                       int KP, int CkkP, int Hi, int Wi, cbGeom g) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < CkkP) {
-        int* tab = (int*)(wp + (long)KP * CkkP);
-        const int k = (int)e;
-        if (k >= Ckk) {
-            tab[k] = 0;
-            tab[CkkP + k] = (int)0x80008000u;
-        } else {
-            const int c = k / (g.kH * g.kW), r = k % (g.kH * g.kW);
-            const int dy = (r / g.kW) * g.dH - g.pH, dx = (r % g.kW) * g.dW - g.pW;
-            tab[k] = (c * Hi * Wi + dy * Wi + dx) * (int)sizeof(T);
-            tab[CkkP + k] = (dx << 16) | (dy & 0xffff);
-        }
+        const int k = (int)e, c = k / (g.kH * g.kW), r = k % (g.kH * g.kW);
+        cbg_tab_entry<T>((int*)(wp + (long)KP * CkkP), CkkP, k, k >= Ckk, c, (r / g.kW) * g.dH - g.pH,
+                         (r % g.kW) * g.dW - g.pW, Hi, Wi);
     }
     if (e >= (long)KP * CkkP) return;
     const int k = (int)(e % CkkP), m = (int)(e / CkkP);
@@ -86,8 +66,7 @@ __global__ __launch_bounds__(256) void cbg_prep_kernel(const T* __restrict__ w, 
 
 // ---------------------------------------------------------------------------------------------
 // detection: one workgroup = one 64-pixel row segment of the INPUT map x all channels (1 to 16 waves by the channel
-// count; wave g scans channels g, g+G, ...; one coalesced row segment per wave load), ballots OR-reduced through LDS as in cb_detect_kernel.
-//   update 1: in[:, p] -> state[:, p] at the changed pixels only (feedback);  2: wherever the values differ at all.
+// count; one coalesced row segment per wave load); the scan and the state refresh are cbg_detect_scan (cb_geom_stage.h).
 // The footprint is built by wave 0 with word arithmetic: for every output word the segment can reach, lane j owns
 // output column ox = 64 w + j and tests the kW input bits its taps fall on; a ballot makes the word, which is ORed into
 // the kH output rows the input row feeds (at most one per ky: oy = (y + pH - ky dH) / sH where that divides).  With a
@@ -101,43 +80,11 @@ __global__ __launch_bounds__(1024) void cbg_detect_kernel(const T* __restrict__ 
                                                         int update) {
     unsigned long long* bits = masks;
     if (*(const int*)(masks + 2 * maskWords)) bits += maskWords;      // the mask the parity selects
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, G = blockDim.x >> 6;
-    const int tx = blockIdx.x, y = blockIdx.y;
+    const int lane = threadIdx.x & 63, tx = blockIdx.x, y = blockIdx.y;
     const int x = tx * 64 + lane;
-    const bool valid = x < Wi;
-    const long HW = (long)Hi * Wi, p = (long)y * Wi + x;
-    const T th = cb_threshold(thf, (T*)nullptr);
-
-    bool chg = false;
-    if (valid) {
-        int c = wv;
-#pragma unroll 1
-        for (; c + G < C; c += 2 * G) {
-            const T s0 = state[(long)c * HW + p], x0 = in[(long)c * HW + p];
-            const T s1 = state[(long)(c + G) * HW + p], x1 = in[(long)(c + G) * HW + p];
-            chg |= cb_changed(s0, x0, th) | cb_changed(s1, x1, th);
-            if (update == 2) {
-                if (cb_differs(s0, x0)) state[(long)c * HW + p] = x0;
-                if (cb_differs(s1, x1)) state[(long)(c + G) * HW + p] = x1;
-            }
-        }
-        if (c < C) {
-            const T s0 = state[(long)c * HW + p], x0 = in[(long)c * HW + p];
-            chg |= cb_changed(s0, x0, th);
-            if (update == 2 && cb_differs(s0, x0)) state[(long)c * HW + p] = x0;
-        }
-    }
-    __shared__ unsigned long long sm[16];
-    const unsigned long long b = __ballot(chg);
-    if (lane == 0) sm[wv] = b;
-    __syncthreads();
-    unsigned long long m = 0;
-    for (int i = 0; i < G; ++i) m |= sm[i];
+    const unsigned long long m = cbg_detect_scan(in, state, C, (long)Hi * Wi, (long)y * Wi + x, x < Wi, thf, update);
     if (m == 0) return;      // uniform over the workgroup
-
-    if (update == 1 && ((m >> lane) & 1ull))
-        for (int c = wv; c < C; c += G) state[(long)c * HW + p] = in[(long)c * HW + p];
-    if (wv != 0) return;
+    if (threadIdx.x >> 6 != 0) return;      // (the footprint: wave 0)
 
     const int x0 = tx * 64;
     const int lo = x0 + g.pW - (g.kW - 1) * g.dW;
@@ -170,25 +117,16 @@ struct GeomConvParams {
     const void* src;     // the map the gather reads [C, Hi, Wi]
     const void* bias;    // [K] or null
     void* out;           // [K, Ho, Wo]
-    const int32_t* list;               // list mode: ascending flat output pixels ...
-    const int32_t* countDev;           // ... and their number on the device (null: nHost)
-    int nHost;
-    unsigned long long* frameMasks;    // mask mode: [2][maskWords] masks, {parity, done}, mask copy
-    long maskWords;
-    int wpr;
-    int32_t* listOut;                  // mask mode: the list and its length as a by-product
+    CbgListArgs L;
+    int32_t* listOut;    // mask mode: the list and its length as a by-product
     int32_t* countOut;
-    float* slabs;                      // split-k workspace (null: no split) ...
-    int* tickets;                      // ... and arrival counters, zero between launches
+    CbgWorkspace ws;
     int K, KP, CkkP, Hi, Wi, Ho, Wo, sH, sW, relu;
 };
 
-// T: element type of the tensors; ARITH: CB_F16 (T = half), CB_F32S or CB_F32 (T = float).
-// 256 threads = 2 x 2 waves, one 32 x 32 MFMA tile each (output channel in the accumulator registers, listed pixel on
-// the lane: a store instruction of the epilogue writes 32 pixels of one output plane).  Per stage of 32 k every thread
-// loads 8 consecutive k of one weight row (16 / 32 bytes) and gathers 8 consecutive k of one pixel -- a wave's k are
-// uniform, so its taps come from the table by scalar loads --; the loads of stage s+1 are in flight while the MFMAs of
-// stage s run (two LDS buffers, one barrier per stage).
+// The tile, its stages, the split along k and the epilogue: cb_geom_stage.h (CBG_TILE_STAGES, CBG_SPLITK_HANDOFF,
+// CBG_TILE_STORE).  This kernel's own: the items (pixel tile, channel tile, k-slice) over ONE list, and the base input
+// pixel (oy sH, ox sW) of an output pixel.
 template <typename T, int ARITH>
 __global__ __launch_bounds__(256) void cbg_conv_kernel(GeomConvParams p) {
     __shared__ CbgStage<ARITH> sA[2], sB[2];
@@ -202,25 +140,22 @@ __global__ __launch_bounds__(256) void cbg_conv_kernel(GeomConvParams p) {
     // ---- the change list: from the frame mask (ascending by construction) or as given
     int N;
     const unsigned long long* cur = nullptr;
-    const long words = p.maskWords;
+    const long words = p.L.maskWords;
     const int chunk = (int)((words + 255) / 256);
-    if (p.frameMasks) {
-        N = cbg_list_from_mask(p.frameMasks, words, chunk, p.wpr, p.Wo, p.listOut, p.countOut, sPre, sWave, cur);
-    } else {
-        N = p.countDev ? min(*p.countDev, p.nHost) : p.nHost;
-        N = max(0, min(N, HWo));
-    }
+    if (p.L.frameMasks)
+        N = cbg_list_from_mask(p.L.frameMasks, words, chunk, p.L.wpr, p.Wo, p.listOut, p.countOut, sPre, sWave, cur);
+    else
+        N = CBG_LIST_COUNT(p.L, HWo);
     if (N == 0) return;
 
     // ---- work items: (pixel tile, channel tile, k-slice)
     const int tilesN = (N + CBG_BN - 1) / CBG_BN, tilesM = p.KP / CBG_BM, stages = p.CkkP / CBG_BK;
     const int base = tilesN * tilesM;
     int SK = 1;
-    if (p.slabs && base < G) SK = max(1, min(min(G / base, CBG_SKMAX), stages));
+    if (p.ws.slabs && base < G) SK = max(1, min(min(G / base, CBG_SKMAX), stages));
     const int items = base * SK;      // (SK > 1: items <= G, one item and one slab per workgroup)
-
-    const int gn = t & 63, gk = wave * 8;      // gather: pixel row, first k of the stage
-    const int am = t >> 2, ak = (t & 3) * 8;   // weights: channel row, first k of the stage
+    const int gn = t & 63, gk = wave * 8;      // the thread's place in the tile (cb_geom_stage.h)
+    const int am = t >> 2, ak = (t & 3) * 8;
     const int wm = wave & 1, wn = wave >> 1;
     const T* src = (const T*)p.src;
 
@@ -230,7 +165,7 @@ __global__ __launch_bounds__(256) void cbg_conv_kernel(GeomConvParams p) {
         __syncthreads();
         if (t < CBG_BN) {
             const int q = tn * CBG_BN + t;
-            sList[t] = q < N ? cbg_list_entry(q, cur, sPre, words, chunk, p.wpr, p.Wo, p.list, HWo) : -1;
+            sList[t] = q < N ? cbg_list_entry(q, cur, sPre, words, chunk, p.L.wpr, p.Wo, p.L.list, HWo) : -1;
         }
         __syncthreads();
 
@@ -239,120 +174,10 @@ __global__ __launch_bounds__(256) void cbg_conv_kernel(GeomConvParams p) {
         const int iy0 = oy * p.sH, ix0 = ox * p.sW;
         const char* pbase = (const char*)(src + (long)iy0 * p.Wi + ix0);
         const T* wrow = (const T*)p.W + ((long)tm * CBG_BM + am) * p.CkkP + ak;
-
-        T ra[8], rb[8];
-        auto load = [&](int s) {
-            const T* wsrc = wrow + (long)s * CBG_BK;
-            if constexpr (sizeof(T) == 2) {
-                const uint4 v = *(const uint4*)wsrc;
-                __builtin_memcpy(ra, &v, 16);
-            } else {
-                const float4 v0 = *(const float4*)wsrc, v1 = *(const float4*)(wsrc + 4);
-                __builtin_memcpy(ra, &v0, 16);
-                __builtin_memcpy(ra + 4, &v1, 16);
-            }
-            const int* tab = p.tab + s * CBG_BK + gk;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int off = tab[i], dd = tab[p.CkkP + i];
-                const int dy = (short)(dd & 0xffff), dx = dd >> 16;
-                const bool inb = pix >= 0 && (unsigned)(iy0 + dy) < (unsigned)p.Hi && (unsigned)(ix0 + dx) < (unsigned)p.Wi;
-                rb[i] = inb ? *(const T*)(pbase + off) : T(0);
-            }
-        };
-
-        floatx16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        // two LDS buffers, one barrier per stage: the loads of stage s+1 fly during the MFMAs of stage s and land in
-        // the other buffer behind them (whose last readers passed the previous barrier)
-        if (s0 < s1) {
-            load(s0);
-            sA[0].put(am, ak, ra);
-            sB[0].put(gn, gk, rb);
-        }
-        __syncthreads();
-        for (int s = s0; s < s1; ++s) {
-            const int cb = (s - s0) & 1;
-            if (s + 1 < s1) load(s + 1);
-            acc = cbg_mfma_stage<ARITH>(sA[cb], sB[cb], wm * 32 + (lane & 31), wn * 32 + (lane & 31), lane, acc);
-            if (s + 1 < s1) {
-                sA[cb ^ 1].put(am, ak, ra);
-                sB[cb ^ 1].put(gn, gk, rb);
-            }
-            __syncthreads();
-        }
-
-        // ---- split-k: partial tiles to the workspace, summed in slice order by the last workgroup to arrive.  The
-        // hand-off needs no agent-scope release (an L2 write-back per workgroup, which serialises the launch): every
-        // slab store is write-through (sc1: an agent-scope relaxed atomic store) and drained before the workgroup's
-        // ticket, every slab load is an sc1 load behind the reducer's acquire (MI355X_MICROARCH.md, "Inter-workgroup
-        // visibility").
-        if (SK > 1) {
-            // (slab = [4 waves][4 register quads][64 lanes] float4: 16 bytes per lane, 1 KB per wave instruction)
-            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
-            const __amdgpu_buffer_rsrc_t srsrc =
-                __builtin_amdgcn_make_buffer_rsrc((void*)p.slabs, 0, CBG_GRID * CBG_SLAB * 4, 0x00020000);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 f = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f), srsrc,
-                                                       (item * (CBG_SLAB / 4) + (wave * 4 + q) * 64 + lane) * 16, 0,
-                                                       16 /* sc1 */);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            int* ticket = p.tickets + (tn * tilesM + tm);
-            if (t == 0) {
-                const int old = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (old == SK - 1) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                sLast = old == SK - 1;
-            }
-            __syncthreads();
-            if (!sLast) continue;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-            for (int sl = 0; sl < SK; ++sl)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 f = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                        srsrc, ((item - slice + sl) * (CBG_SLAB / 4) + (wave * 4 + q) * 64 + lane) * 16, 0, 16 /* sc1 */));
-                    acc[4 * q] += f.x, acc[4 * q + 1] += f.y, acc[4 * q + 2] += f.z, acc[4 * q + 3] += f.w;
-                }
-        }
-
-        // ---- bias, ReLU, scatter
-        const int opix = sList[wn * 32 + (lane & 31)];
-        if (opix >= 0) {
-            T* out = (T*)p.out;
-            const T* bias = (const T*)p.bias;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int m = tm * CBG_BM + wm * 32 + (j >> 2) * 8 + (lane >> 5) * 4 + (j & 3);
-                if (m < p.K) {
-                    float v = acc[j] + (bias ? (float)bias[m] : 0.f);
-                    if (p.relu) v = v <= 0.f ? 0.f : v;
-                    out[(long)m * HWo + opix] = (T)v;
-                }
-            }
-        }
+        CBG_TILE_STAGES(acc, wrow, p.tab, p.CkkP, pbase, pix, iy0, ix0, p.Hi, p.Wi, s0, s1)
+        if (SK > 1) CBG_SPLITK_HANDOFF(acc, p.ws.slabs, p.ws.tickets + (tn * tilesM + tm), item, slice, SK, sLast, continue)
+        CBG_TILE_STORE(acc, sList, tm, p.bias, p.out, p.K, HWo, p.relu)
     }
-}
-
-int cbg_launch_conv(const GeomConvParams& p, int dtype, hipStream_t s) {
-    dim3 grid(CBG_GRID), block(256);
-    if (dtype == CB_F16)
-        hipLaunchKernelGGL((cbg_conv_kernel<cb_half, CB_F16>), grid, block, 0, s, p);
-    else if (dtype == CB_F32S)
-        hipLaunchKernelGGL((cbg_conv_kernel<float, CB_F32S>), grid, block, 0, s, p);
-    else
-        hipLaunchKernelGGL((cbg_conv_kernel<float, CB_F32>), grid, block, 0, s, p);
-    return cb_launch_status();
 }
 
 }  // namespace
@@ -370,7 +195,7 @@ long cbinfer_geom_prepared_weights_bytes(int K, int C, const cbGeom* geom, int d
     return KP * CkkP * (dtype == CB_F16 ? 2 : 4) + CkkP * 8;
 }
 
-long cbinfer_geom_workspace_bytes(void) { return (long)CBG_GRID * CBG_SLAB * 4 + (long)CBG_GRID * 4; }
+long cbinfer_geom_workspace_bytes(void) { return cbg_workspace_bytes(); }
 
 int cbinfer_geom_prep_weights(const void* weight, void* prepared, int K, int C, int Hi, int Wi, const cbGeom* geom,
                               int dtype, cbStream_t stream) {
@@ -401,18 +226,8 @@ int cbinfer_change_detection_geom(const void* input, void* state, uint64_t* fram
     const int st = cbg_out_size(Hi, Wi, geom, &Ho, &Wo);
     if (st != CB_OK) return st;
     if (Hi > 65535) return CB_ERR_UNSUPPORTED;
-    const int wprO = cbinfer_mask_words_per_row(Wo);
-    const long words = cbinfer_mask_words(Ho, Wo);
-    dim3 grid(cb_div_up(Wi, 64), Hi), block(64 * (C >= 32 ? 16 : C >= 8 ? 8 : C >= 4 ? 4 : C));      // (waves over the channels)
-    if (dtype == CB_F16)
-        hipLaunchKernelGGL(cbg_detect_kernel<cb_half>, grid, block, 0, (hipStream_t)stream, (const cb_half*)input,
-                           (cb_half*)state, (unsigned long long*)frameMasks, words, C, Hi, Wi, Ho, Wo, wprO, *geom,
-                           threshold, updateInputState);
-    else
-        hipLaunchKernelGGL(cbg_detect_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)input,
-                           (float*)state, (unsigned long long*)frameMasks, words, C, Hi, Wi, Ho, Wo, wprO, *geom,
-                           threshold, updateInputState);
-    return cb_launch_status();
+    return cbg_launch_detect(cbg_detect_kernel<float>, cbg_detect_kernel<cb_half>, input, state, frameMasks, C, Hi, Wi,
+                             Ho, Wo, *geom, threshold, updateInputState, dtype, (hipStream_t)stream);
 }
 
 int cbinfer_conv_changed_geom(const void* input, const int32_t* changeList, int numChanges, const int32_t* countDev,
@@ -426,28 +241,21 @@ int cbinfer_conv_changed_geom(const void* input, const int32_t* changeList, int 
     if (st != CB_OK) return st;
     if ((long)Ho * Wo >= (1l << 31) / K || (long)C * Hi * Wi * 4 >= (1l << 30)) return CB_ERR_UNSUPPORTED;
     GeomConvParams p = {};
-    if (frameMasks) {
-        CB_REQUIRE(idxOut && countOut && !changeList);
-        p.frameMasks = (unsigned long long*)frameMasks;
-        p.maskWords = cbinfer_mask_words(Ho, Wo);
-        p.wpr = cbinfer_mask_words_per_row(Wo);
-        p.listOut = idxOut, p.countOut = countOut;
-    } else {
-        CB_REQUIRE(changeList && numChanges >= 0 && numChanges <= Ho * Wo);
-        if (numChanges == 0) return CB_OK;
-        p.list = changeList, p.countDev = countDev, p.nHost = numChanges;
-    }
+    const int ls = cbg_list_args(p.L, changeList, numChanges, countDev, frameMasks, idxOut && countOut, Ho, Wo);
+    if (ls != CB_OK || cbg_nothing_listed(p.L)) return ls;
+    p.listOut = idxOut, p.countOut = countOut;
     const int Ckk = C * geom->kH * geom->kW;
     p.KP = cbg_kpad(K), p.CkkP = cbg_ckkpad(Ckk);
     p.W = prepared;
     p.tab = (const int*)((const char*)prepared + (long)p.KP * p.CkkP * (dtype == CB_F16 ? 2 : 4));
     p.src = input, p.bias = bias, p.out = output;
-    if (workspace) {
-        p.slabs = (float*)workspace;
-        p.tickets = (int*)((char*)workspace + (long)CBG_GRID * CBG_SLAB * 4);
-    }
+    p.ws = cbg_workspace(workspace);
     p.K = K, p.Hi = Hi, p.Wi = Wi, p.Ho = Ho, p.Wo = Wo, p.sH = geom->sH, p.sW = geom->sW, p.relu = relu;
-    return cbg_launch_conv(p, dtype, (hipStream_t)stream);
+    cbg_dispatch_arith(dtype, [&](auto a) {
+        hipLaunchKernelGGL((cbg_conv_kernel<typename decltype(a)::T, decltype(a)::ARITH>), dim3(CBG_GRID), dim3(256), 0,
+                           (hipStream_t)stream, p);
+    });
+    return cb_launch_status();
 }
 
 int cbinfer_cbconv2d_forward_geom(const void* input, void* prevInput, void* prevOutput, uint64_t* frameMasks,
@@ -459,27 +267,24 @@ int cbinfer_cbconv2d_forward_geom(const void* input, void* prevInput, void* prev
     int Ho, Wo;
     int st = cbg_out_size(Hi, Wi, geom, &Ho, &Wo);
     if (st != CB_OK) return st;
-    const int edt = dtype == CB_F32S ? CB_F32 : dtype;
-    const void* src = (feedbackLoop || copyInput) ? prevInput : input;
+    const CbgFrameMode fm = cbg_frame_mode(input, prevInput, feedbackLoop, copyInput, dtype);
     if (haveIndexes) {
         // propagated indexes address the input map: only where it is the output map do they mean what they mean for a
         // unit-geometry layer (no detection ran: the state copy is a copy)
         if (Ho != Hi || Wo != Wi) return CB_ERR_UNSUPPORTED;
         CB_REQUIRE(!feedbackLoop && capN >= 0 && capN <= Ho * Wo);
-        if (copyInput && prevInput != input) {
-            const hipError_t e = hipMemcpyAsync(prevInput, input, (size_t)C * Hi * Wi * (edt == CB_F16 ? 2 : 4),
+        if (fm.copyAll) {
+            const hipError_t e = hipMemcpyAsync(prevInput, input, (size_t)C * Hi * Wi * (fm.edt == CB_F16 ? 2 : 4),
                                                 hipMemcpyDeviceToDevice, (hipStream_t)stream);
             if (e != hipSuccess) return (int)e;
         }
-        return cbinfer_conv_changed_geom(src, idx, capN, countDev, nullptr, nullptr, nullptr, prepared, bias,
+        return cbinfer_conv_changed_geom(fm.src, idx, capN, countDev, nullptr, nullptr, nullptr, prepared, bias,
                                          prevOutput, C, Hi, Wi, K, geom, relu, workspace, dtype, stream);
     }
     CB_REQUIRE(frameMasks != nullptr);
-    const bool copyAll = !feedbackLoop && copyInput && prevInput != input;
-    st = cbinfer_change_detection_geom(input, prevInput, frameMasks, C, Hi, Wi, geom, threshold,
-                                       feedbackLoop ? 1 : (copyAll ? 2 : 0), edt, stream);
+    st = cbinfer_change_detection_geom(input, prevInput, frameMasks, C, Hi, Wi, geom, threshold, fm.update, fm.edt, stream);
     if (st != CB_OK) return st;
-    return cbinfer_conv_changed_geom(src, nullptr, 0, nullptr, frameMasks, idx, countDev, prepared, bias, prevOutput, C,
+    return cbinfer_conv_changed_geom(fm.src, nullptr, 0, nullptr, frameMasks, idx, countDev, prepared, bias, prevOutput, C,
                                      Hi, Wi, K, geom, relu, workspace, dtype, stream);
 }
 

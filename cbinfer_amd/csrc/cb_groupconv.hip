@@ -9,20 +9,16 @@
 //                      (16x16 tiles: f16; f32 as bf16 triples, six products; or the exact f32 MFMA), adds the bias,
 //                      applies the ReLU and scatters into the group's output planes.  No workspace and no split along k:
 //                      the groups supply the parallelism.  No MFMA instruction holds rows of two groups.
-// The mask -> list prologue and the tile's pixel lookup are cbg_conv_kernel's, written once in cb_geom_stage.h.
+// The mask -> list prologue and the tile's pixel lookup are cbg_conv_kernel's; they, the weight-row load and the 8-tap
+// gather are written once in cb_geom_stage.h (DESIGN 5.22 on why the stage loop is not).
 // Entry-point contracts: include/cbinfer_hip.h, "grouped convolution".
 #include "cb_common.h"
 #include "cb_geom_stage.h"
 
 namespace {
 
-#define CBGR_BN 64        // listed pixels per tile
-#define CBGR_BK 32        // k-depth per LDS stage
-#define CBGR_GRID 512     // persistent grid (2 workgroups per CU of an MI355X)
-
 int cbgr_rows(int Kg) { return Kg <= 16 ? 16 : Kg <= 32 ? 32 : 64; }
 int cbgr_kgpad(int Kg) { const int r = cbgr_rows(Kg); return (Kg + r - 1) / r * r; }
-int cbgr_ckkpad(int Ckkg) { return (Ckkg + CBGR_BK - 1) / CBGR_BK * CBGR_BK; }
 
 // CB_OK if the channel counts divide into 2 or more groups and the geometry is within cbGeom's limits
 int cbgr_shape_status(int C, int K, int groups, const cbGeom* geom) {
@@ -57,18 +53,10 @@ __global__ __launch_bounds__(256) void cbgr_prep_kernel(const T* __restrict__ w,
                                                        int Ckkg, int KgP, int CkkgP, int Hi, int Wi, cbGeom g) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x, total = (long)G * KgP * CkkgP;
     if (e < CkkgP) {
-        int* tab = (int*)(wp + total);
-        const int k = (int)e;
-        if (k >= Ckkg) {
-            tab[k] = 0;
-            tab[CkkgP + k] = (int)0x80008000u;
-        } else {
-            const int c = k / (g.kH * g.kW), r = k % (g.kH * g.kW);
-            const int dy = (r / g.kW) * g.dH - g.pH, dx = (r % g.kW) * g.dW - g.pW;
-            // (a tap inside the map is within the group's Cg Hi Wi elements; the others are never used for an address)
-            tab[k] = (int)(((long)c * Hi * Wi + (long)dy * Wi + dx) * (long)sizeof(T));
-            tab[CkkgP + k] = (dx << 16) | (dy & 0xffff);
-        }
+        // (a tap inside the map is within the group's Cg Hi Wi elements)
+        const int k = (int)e, c = k / (g.kH * g.kW), r = k % (g.kH * g.kW);
+        cbg_tab_entry<T>((int*)(wp + total), CkkgP, k, k >= Ckkg, c, (r / g.kW) * g.dH - g.pH, (r % g.kW) * g.dW - g.pW,
+                         Hi, Wi);
     }
     if (e >= total) return;
     const int k = (int)(e % CkkgP), m = (int)(e / CkkgP % KgP), grp = (int)(e / ((long)CkkgP * KgP));
@@ -84,13 +72,8 @@ struct GroupConvParams {
     const void* src;     // the map the gather reads [C, Hi, Wi]
     const void* bias;    // [K] or null
     void* out;           // [K, Ho, Wo]
-    const int32_t* list;               // list mode: flat output pixels ...
-    const int32_t* countDev;           // ... and their number on the device (null: nHost)
-    int nHost;
-    unsigned long long* frameMasks;    // mask mode: [2][maskWords] masks, {parity, done}, mask copy
-    long maskWords;
-    int wpr;
-    int32_t* listOut;                  // mask mode: the list and its length as a by-product
+    CbgListArgs L;
+    int32_t* listOut;    // mask mode: the list and its length as a by-product
     int32_t* countOut;
     int G, Cg, Kg, KgP, CkkgP, Hi, Wi, Ho, Wo, sH, sW, relu;
 };
@@ -149,7 +132,7 @@ __global__ __launch_bounds__(256) void cbgr_conv_kernel(GroupConvParams p) {
     constexpr int NACC = ROWS / 16;
     __shared__ CbgStage<ARITH> sA[2], sB[2];
     __shared__ int sPre[257];
-    __shared__ int sList[CBGR_BN];
+    __shared__ int sList[CBG_BN];
     __shared__ int sWave[4];
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int NB = gridDim.x, HWo = p.Ho * p.Wo;
@@ -157,18 +140,16 @@ __global__ __launch_bounds__(256) void cbgr_conv_kernel(GroupConvParams p) {
     // ---- the change list: from the frame mask (ascending by construction) or as given
     int N;
     const unsigned long long* cur = nullptr;
-    const long words = p.maskWords;
+    const long words = p.L.maskWords;
     const int chunk = (int)((words + 255) / 256);
-    if (p.frameMasks) {
-        N = cbg_list_from_mask(p.frameMasks, words, chunk, p.wpr, p.Wo, p.listOut, p.countOut, sPre, sWave, cur);
-    } else {
-        N = p.countDev ? min(*p.countDev, p.nHost) : p.nHost;
-        N = max(0, min(N, HWo));
-    }
+    if (p.L.frameMasks)
+        N = cbg_list_from_mask(p.L.frameMasks, words, chunk, p.L.wpr, p.Wo, p.listOut, p.countOut, sPre, sWave, cur);
+    else
+        N = CBG_LIST_COUNT(p.L, HWo);
     if (N == 0) return;
 
     // ---- work items: (pixel tile, group, row tile), the row tile fastest
-    const int tilesN = (N + CBGR_BN - 1) / CBGR_BN, rowTiles = p.KgP / ROWS, stages = p.CkkgP / CBGR_BK;
+    const int tilesN = (N + CBG_BN - 1) / CBG_BN, rowTiles = p.KgP / ROWS, stages = p.CkkgP / CBG_BK;
     const long items = (long)tilesN * p.G * rowTiles;
 
     const int gn = t & 63, gk = wave * 8;      // gather: pixel row, first k of the stage
@@ -179,9 +160,9 @@ __global__ __launch_bounds__(256) void cbgr_conv_kernel(GroupConvParams p) {
     for (long item = blockIdx.x; item < items; item += NB) {
         const int rt = (int)(item % rowTiles), grp = (int)(item / rowTiles % p.G), tn = (int)(item / ((long)rowTiles * p.G));
         __syncthreads();
-        if (t < CBGR_BN) {
-            const int q = tn * CBGR_BN + t;
-            sList[t] = q < N ? cbg_list_entry(q, cur, sPre, words, chunk, p.wpr, p.Wo, p.list, HWo) : -1;
+        if (t < CBG_BN) {
+            const int q = tn * CBG_BN + t;
+            sList[t] = q < N ? cbg_list_entry(q, cur, sPre, words, chunk, p.L.wpr, p.Wo, p.L.list, HWo) : -1;
         }
         __syncthreads();
 
@@ -194,25 +175,9 @@ __global__ __launch_bounds__(256) void cbgr_conv_kernel(GroupConvParams p) {
 
         T ra[8], rb[8];
         auto load = [&](int s) {
-            if (am < ROWS) {
-                const T* wsrc = wrow + (long)s * CBGR_BK;
-                if constexpr (sizeof(T) == 2) {
-                    const uint4 v = *(const uint4*)wsrc;
-                    __builtin_memcpy(ra, &v, 16);
-                } else {
-                    const float4 v0 = *(const float4*)wsrc, v1 = *(const float4*)(wsrc + 4);
-                    __builtin_memcpy(ra, &v0, 16);
-                    __builtin_memcpy(ra + 4, &v1, 16);
-                }
-            }
-            const int* tab = p.tab + s * CBGR_BK + gk;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int off = tab[i], dd = tab[p.CkkgP + i];
-                const int dy = (short)(dd & 0xffff), dx = dd >> 16;
-                const bool inb = pix >= 0 && (unsigned)(iy0 + dy) < (unsigned)p.Hi && (unsigned)(ix0 + dx) < (unsigned)p.Wi;
-                rb[i] = inb ? *(const T*)(pbase + off) : T(0);
-            }
+            if (am < ROWS) cbg_load_wrow(ra, wrow + (long)s * CBG_BK);
+            const int* tab = p.tab + s * CBG_BK + gk;
+            CBG_GATHER8(T, rb, tab, p.CkkgP, pbase, pix, iy0, ix0, p.Hi, p.Wi);
         };
         auto put = [&](int b) {
             if (am < ROWS) sA[b].put(am, ak, ra);
@@ -258,7 +223,7 @@ __global__ __launch_bounds__(256) void cbgr_conv_kernel(GroupConvParams p) {
 
 template <typename T, int ARITH>
 void cbgr_launch_rows(const GroupConvParams& p, int rows, hipStream_t s) {
-    dim3 grid(CBGR_GRID), block(256);
+    dim3 grid(CBG_GRID), block(256);
     if (rows == 16)
         hipLaunchKernelGGL((cbgr_conv_kernel<T, ARITH, 16>), grid, block, 0, s, p);
     else if (rows == 32)
@@ -269,12 +234,7 @@ void cbgr_launch_rows(const GroupConvParams& p, int rows, hipStream_t s) {
 
 int cbgr_launch_conv(const GroupConvParams& p, int dtype, hipStream_t s) {
     const int rows = cbgr_rows(p.Kg);
-    if (dtype == CB_F16)
-        cbgr_launch_rows<cb_half, CB_F16>(p, rows, s);
-    else if (dtype == CB_F32S)
-        cbgr_launch_rows<float, CB_F32S>(p, rows, s);
-    else
-        cbgr_launch_rows<float, CB_F32>(p, rows, s);
+    cbg_dispatch_arith(dtype, [&](auto a) { cbgr_launch_rows<typename decltype(a)::T, decltype(a)::ARITH>(p, rows, s); });
     return cb_launch_status();
 }
 
@@ -288,7 +248,7 @@ int cbinfer_groupconv_supported(int C, int K, int groups, const cbGeom* geom) {
 
 long cbinfer_groupconv_prepared_weights_bytes(int K, int C, int groups, const cbGeom* geom, int dtype) {
     if (cbgr_shape_status(C, K, groups, geom) != CB_OK) return 0;
-    const long KgP = cbgr_kgpad(K / groups), CkkgP = cbgr_ckkpad(C / groups * geom->kH * geom->kW);
+    const long KgP = cbgr_kgpad(K / groups), CkkgP = cbg_ckkpad(C / groups * geom->kH * geom->kW);
     return groups * KgP * CkkgP * (dtype == CB_F16 ? 2 : 4) + CkkgP * 8;
 }
 
@@ -299,7 +259,7 @@ int cbinfer_groupconv_prep_weights(const void* weight, void* prepared, int K, in
     int Ho, Wo;
     const int st = cbgr_map_status(C, K, groups, Hi, Wi, geom, dtype, &Ho, &Wo);
     if (st != CB_OK) return st;
-    const int Kg = K / groups, Ckkg = C / groups * geom->kH * geom->kW, KgP = cbgr_kgpad(Kg), CkkgP = cbgr_ckkpad(Ckkg);
+    const int Kg = K / groups, Ckkg = C / groups * geom->kH * geom->kW, KgP = cbgr_kgpad(Kg), CkkgP = cbg_ckkpad(Ckkg);
     dim3 grid(cb_div_up((long)groups * KgP * CkkgP, 256)), block(256);
     if (dtype == CB_F16)
         hipLaunchKernelGGL(cbgr_prep_kernel<cb_half>, grid, block, 0, (hipStream_t)stream, (const cb_half*)weight,
@@ -320,19 +280,11 @@ int cbinfer_conv_changed_grouped(const void* input, const int32_t* changeList, i
     const int st = cbgr_map_status(C, K, groups, Hi, Wi, geom, dtype, &Ho, &Wo);
     if (st != CB_OK) return st;
     GroupConvParams p = {};
-    if (frameMasks) {
-        CB_REQUIRE(idxOut && countOut && !changeList);
-        p.frameMasks = (unsigned long long*)frameMasks;
-        p.maskWords = cbinfer_mask_words(Ho, Wo);
-        p.wpr = cbinfer_mask_words_per_row(Wo);
-        p.listOut = idxOut, p.countOut = countOut;
-    } else {
-        CB_REQUIRE(changeList && numChanges >= 0 && numChanges <= Ho * Wo);
-        if (numChanges == 0) return CB_OK;
-        p.list = changeList, p.countDev = countDev, p.nHost = numChanges;
-    }
+    const int ls = cbg_list_args(p.L, changeList, numChanges, countDev, frameMasks, idxOut && countOut, Ho, Wo);
+    if (ls != CB_OK || cbg_nothing_listed(p.L)) return ls;
+    p.listOut = idxOut, p.countOut = countOut;
     p.G = groups, p.Cg = C / groups, p.Kg = K / groups;
-    p.KgP = cbgr_kgpad(p.Kg), p.CkkgP = cbgr_ckkpad(p.Cg * geom->kH * geom->kW);
+    p.KgP = cbgr_kgpad(p.Kg), p.CkkgP = cbg_ckkpad(p.Cg * geom->kH * geom->kW);
     p.W = prepared;
     p.tab = (const int*)((const char*)prepared + (long)groups * p.KgP * p.CkkgP * (dtype == CB_F16 ? 2 : 4));
     p.src = input, p.bias = bias, p.out = output;
@@ -351,13 +303,10 @@ int cbinfer_cbgroupconv2d_forward(const void* input, void* prevInput, void* prev
     int st = cbgr_map_status(C, K, groups, Hi, Wi, geom, dtype, &Ho, &Wo);
     if (st != CB_OK) return st;
     if (Hi > 65535) return CB_ERR_UNSUPPORTED;      // (cbinfer_change_detection_geom's limit, before any launch)
-    const int edt = dtype == CB_F32S ? CB_F32 : dtype;
-    const void* src = (feedbackLoop || copyInput) ? prevInput : input;
-    const bool copyAll = !feedbackLoop && copyInput && prevInput != input;
-    st = cbinfer_change_detection_geom(input, prevInput, frameMasks, C, Hi, Wi, geom, threshold,
-                                       feedbackLoop ? 1 : (copyAll ? 2 : 0), edt, stream);
+    const CbgFrameMode fm = cbg_frame_mode(input, prevInput, feedbackLoop, copyInput, dtype);
+    st = cbinfer_change_detection_geom(input, prevInput, frameMasks, C, Hi, Wi, geom, threshold, fm.update, fm.edt, stream);
     if (st != CB_OK) return st;
-    return cbinfer_conv_changed_grouped(src, nullptr, 0, nullptr, frameMasks, idx, countDev, prepared, bias, prevOutput, C,
+    return cbinfer_conv_changed_grouped(fm.src, nullptr, 0, nullptr, frameMasks, idx, countDev, prepared, bias, prevOutput, C,
                                         Hi, Wi, K, groups, geom, relu, dtype, stream);
 }
 

@@ -14,7 +14,8 @@
 //   cbt_conv_kernel    counts the listed pixels per phase from that mask (or from a caller's list) by itself, gathers
 //                      the taps of 64 listed pixels of ONE phase per tile through that phase's k -> tap table and
 //                      contracts them with that phase's weight matrix: the stages, the MFMA forms, the split along k
-//                      and the epilogue are cbg_conv_kernel's (cb_geomconv.hip; stage images shared, cb_geom_stage.h).
+//                      and the epilogue are the shared 64 x 64 x 32 tile's (cb_geom_stage.h: CBG_TILE_STAGES,
+//                      CBG_SPLITK_HANDOFF, CBG_TILE_STORE), as in cbg_conv_kernel.
 // Entry-point contracts: include/cbinfer_hip.h, "transposed convolution".
 #include "cb_common.h"
 #include "cb_geom_stage.h"
@@ -25,12 +26,6 @@ namespace {
 #define CBT_MAX_S 4      // stride per axis
 #define CBT_MAX_D 4      // dilation per axis
 #define CBT_MAX_PH 16    // phases
-#define CBT_BM 64        // output channels per tile
-#define CBT_BN 64        // listed pixels per tile
-#define CBT_BK 32        // k-depth per LDS stage
-#define CBT_GRID 512     // persistent grid of the contraction (2 workgroups per CU of an MI355X)
-#define CBT_SKMAX 8      // most k-slices per tile
-#define CBT_SLAB (CBT_BM * CBT_BN)
 
 int cbt_geom_status(const cbTGeom* g) {
     if (!g) return CB_ERR_BADARG;
@@ -76,12 +71,12 @@ struct TConvLayout {
 
 TConvLayout cbt_layout(int K, int C, const cbTGeom* g, int dtype) {
     TConvLayout L = {};
-    const long KP = (K + CBT_BM - 1) / CBT_BM * CBT_BM, es = dtype == CB_F16 ? 2 : 4;
+    const long KP = cbg_kpad(K), es = dtype == CB_F16 ? 2 : 4;
     for (int ry = 0; ry < g->sH; ++ry)
         for (int rx = 0; rx < g->sW; ++rx) {
             const int ph = ry * g->sW + rx;
             const long ckk = (long)C * cbt_ntaps(g->kH, g->dH, g->sH, ry) * cbt_ntaps(g->kW, g->dW, g->sW, rx);
-            const long ckkP = (ckk + CBT_BK - 1) / CBT_BK * CBT_BK;
+            const long ckkP = (ckk + CBG_BK - 1) / CBG_BK * CBG_BK;
             L.ckkP[ph] = (int)ckkP;
             L.wOff[ph] = L.total;
             L.total += KP * ckkP * es + ckkP * 8;
@@ -106,10 +101,8 @@ int cbt_shape(int C, int K, int Hi, int Wi, const cbTGeom* g, int* Ho, int* Wo) 
 // weight preparation, blockIdx.y = phase: W_ph[KP][ckkP] in the tensors' element type (k = c taps + tap, contiguous,
 // zero padded) from torch's [C, K, kH, kW], then the phase's k -> tap table.  An output pixel (oy, ox) of phase
 // (ry, rx) has oy + pH = sH iy0 + ry: (iy0, ix0) is its BASE input pixel, and tap (ky, kx) reads (iy0 + dy, ix0 + dx),
-// dy = (ry - ky dH) / sH, dx = (rx - kx dW) / sW (exact divisions):
-//   off[k]  = byte offset (c Hi Wi + dy Wi + dx) elemSize relative to the base pixel
-//   dydx[k] = (dx << 16) | (dy & 0xffff), for the border test against Hi, Wi
-// The padded tail gets dy = dx = -32768, outside every map cbt_shape admits (cbg_prep_kernel, cb_geomconv.hip).
+// dy = (ry - ky dH) / sH, dx = (rx - kx dW) / sW (exact divisions); the table entry is cbg_tab_entry's
+// (cb_geom_stage.h), whose marker for the padded tail is outside every map cbt_shape admits.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void cbt_prep_kernel(const T* __restrict__ w, char* __restrict__ prepared, int K, int C,
@@ -120,7 +113,6 @@ __global__ __launch_bounds__(256) void cbt_prep_kernel(const T* __restrict__ w, 
     const int ry = ph / g.sW, rx = ph % g.sW;
     const int ntW = cbt_ntaps(g.kW, g.dW, g.sW, rx), nt = cbt_ntaps(g.kH, g.dH, g.sH, ry) * ntW, Ckk = C * nt;
     T* wp = (T*)(prepared + L.wOff[ph]);
-    int* tab = (int*)(wp + (long)KP * CkkP);
     const int k = (int)(e % CkkP), m = (int)(e / CkkP);
     int c = 0, ky = 0, kx = 0;
     if (k < Ckk) {
@@ -128,16 +120,9 @@ __global__ __launch_bounds__(256) void cbt_prep_kernel(const T* __restrict__ w, 
         ky = cbt_nth_tap(g.kH, g.dH, g.sH, ry, (k % nt) / ntW);
         kx = cbt_nth_tap(g.kW, g.dW, g.sW, rx, (k % nt) % ntW);
     }
-    if (m == 0) {
-        if (k >= Ckk) {
-            tab[k] = 0;
-            tab[CkkP + k] = (int)0x80008000u;
-        } else {
-            const int dy = (ry - ky * g.dH) / g.sH, dx = (rx - kx * g.dW) / g.sW;
-            tab[k] = (c * Hi * Wi + dy * Wi + dx) * (int)sizeof(T);
-            tab[CkkP + k] = (int)(((unsigned)dx << 16) | ((unsigned)dy & 0xffffu));
-        }
-    }
+    if (m == 0)
+        cbg_tab_entry<T>((int*)(wp + (long)KP * CkkP), CkkP, k, k >= Ckk, c, (ry - ky * g.dH) / g.sH,
+                         (rx - kx * g.dW) / g.sW, Hi, Wi);
     wp[e] = (m < K && k < Ckk) ? w[(((long)c * K + m) * g.kH + ky) * g.kW + kx] : T(0);
 }
 
@@ -148,8 +133,7 @@ __device__ __forceinline__ int cbt_div_s(int x, int s) { return s == 1 ? x : s =
 
 // ---------------------------------------------------------------------------------------------
 // detection: cbg_detect_kernel's form -- one workgroup = one 64-pixel row segment of the INPUT map x all channels (1 to
-// 16 waves; wave g scans channels g, g+G, ...), ballots OR-reduced through LDS.
-//   update 1: in[:, p] -> state[:, p] at the changed pixels only (feedback);  2: wherever the values differ at all.
+// 16 waves); the scan and the state refresh are cbg_detect_scan (cb_geom_stage.h).
 // The footprint in gather form on wave 0: for every output word the segment can reach (columns x0 sW - pW ..
 // (x0 + 63) sW - pW + (kW-1) dW: up to six words with s = 4, k = 8, d = 4), lane j owns output column ox = 64 w + j and
 // tests the input bits of its column-valid taps (nx = ox + pW - kx dW >= 0, divisible by sW, nx / sW in the segment);
@@ -163,43 +147,11 @@ __global__ __launch_bounds__(1024) void cbt_detect_kernel(const T* __restrict__ 
                                                         int update) {
     unsigned long long* bits = masks;
     if (*(const int*)(masks + 2 * maskWords)) bits += maskWords;      // the mask the parity selects
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, G = blockDim.x >> 6;
-    const int tx = blockIdx.x, y = blockIdx.y;
+    const int lane = threadIdx.x & 63, tx = blockIdx.x, y = blockIdx.y;
     const int x = tx * 64 + lane;
-    const bool valid = x < Wi;
-    const long HW = (long)Hi * Wi, p = (long)y * Wi + x;
-    const T th = cb_threshold(thf, (T*)nullptr);
-
-    bool chg = false;
-    if (valid) {
-        int c = wv;
-#pragma unroll 1
-        for (; c + G < C; c += 2 * G) {
-            const T s0 = state[(long)c * HW + p], x0 = in[(long)c * HW + p];
-            const T s1 = state[(long)(c + G) * HW + p], x1 = in[(long)(c + G) * HW + p];
-            chg |= cb_changed(s0, x0, th) | cb_changed(s1, x1, th);
-            if (update == 2) {
-                if (cb_differs(s0, x0)) state[(long)c * HW + p] = x0;
-                if (cb_differs(s1, x1)) state[(long)(c + G) * HW + p] = x1;
-            }
-        }
-        if (c < C) {
-            const T s0 = state[(long)c * HW + p], x0 = in[(long)c * HW + p];
-            chg |= cb_changed(s0, x0, th);
-            if (update == 2 && cb_differs(s0, x0)) state[(long)c * HW + p] = x0;
-        }
-    }
-    __shared__ unsigned long long sm[16];
-    const unsigned long long b = __ballot(chg);
-    if (lane == 0) sm[wv] = b;
-    __syncthreads();
-    unsigned long long m = 0;
-    for (int i = 0; i < G; ++i) m |= sm[i];
+    const unsigned long long m = cbg_detect_scan(in, state, C, (long)Hi * Wi, (long)y * Wi + x, x < Wi, thf, update);
     if (m == 0) return;      // uniform over the workgroup
-
-    if (update == 1 && ((m >> lane) & 1ull))
-        for (int c = wv; c < C; c += G) state[(long)c * HW + p] = in[(long)c * HW + p];
-    if (wv != 0) return;
+    if (threadIdx.x >> 6 != 0) return;      // (the footprint: wave 0)
 
     const int x0 = tx * 64;
     const int oxLo = max(0, x0 * g.sW - g.pW);
@@ -230,14 +182,8 @@ struct TConvParams {
     const void* src;         // the map the gather reads [C, Hi, Wi]
     const void* bias;        // [K] or null
     void* out;               // [K, Ho, Wo]
-    const int32_t* list;               // list mode: ascending flat output pixels ...
-    const int32_t* countDev;           // ... and their number on the device (null: nHost)
-    int nHost;
-    unsigned long long* frameMasks;    // mask mode: [2][maskWords] masks, {parity, done}, mask copy
-    long maskWords;
-    int wpr;
-    float* slabs;                      // split-k workspace (null: no split) ...
-    int* tickets;                      // ... and arrival counters, zero between launches
+    CbgListArgs L;
+    CbgWorkspace ws;
     int K, KP, Hi, Wi, Ho, Wo, sH, sW, pH, pW, relu;
     double rWo;                        // 1 / Wo
     int ckkP[CBT_MAX_PH];
@@ -271,10 +217,11 @@ __device__ __forceinline__ int cbt_phase_of(const TConvParams& p, int pix) {
     return cbt_mod_s(oy + p.pH, p.sH) * p.sW + cbt_mod_s(ox + p.pW, p.sW);
 }
 
-// T, ARITH, the 2 x 2 waves, the stage pipeline, the split along k and the epilogue: see cbg_conv_kernel.  What differs:
-// work items are (phase, pixel tile of that phase, channel tile, k-slice).  The listed pixels of a phase are found
-// through ONE prefix table over 256 chunks (of mask words, or of list entries), built for the phase of the item at
-// hand: every thread keeps its chunk's count per phase in registers (one pass at launch start, which also gives the
+// T, ARITH, the 2 x 2 waves, the stage pipeline, the split along k and the epilogue: the shared tile of cb_geom_stage.h
+// (CBG_TILE_STAGES, CBG_SPLITK_HANDOFF, CBG_TILE_STORE).  This kernel's own: work items are (phase, pixel tile of that
+// phase, channel tile, k-slice), and the base input pixel is ((oy + pH) / sH, (ox + pW) / sW).  The listed pixels of a
+// phase are found through ONE prefix table over 256 chunks (of mask words, or of list entries), built for the phase of
+// the item at hand: every thread keeps its chunk's count per phase in registers (one pass at launch start, which also gives the
 // totals per phase, sTot), and the table is a scan of those -- built for the first item and again only when a
 // workgroup's next item has another phase, never while base <= grid, where a workgroup has one item.  LDS: the F32S
 // stage buffers leave 2.7 KB under the 64 KB static limit, which per-phase tables (16 x 257 ints) would exceed.
@@ -282,29 +229,28 @@ template <typename T, int ARITH>
 __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
     __shared__ CbgStage<ARITH> sA[2], sB[2];
     __shared__ int sPre[257];
-    __shared__ int sList[CBT_BN];
+    __shared__ int sList[CBG_BN];
     __shared__ int sTot[CBT_MAX_PH];
     __shared__ int sLast;
     __shared__ int sWave[4];
     __shared__ int sWaveTot[4][CBT_MAX_PH];
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int G = CBT_GRID, HWo = p.Ho * p.Wo, P = p.sH * p.sW;      // (the launcher's grid)
+    const int G = CBG_GRID, HWo = p.Ho * p.Wo, P = p.sH * p.sW;      // (the launcher's grid)
 
     const unsigned long long* cur = nullptr;
-    const int words = (int)p.maskWords;      // (Ho Wo < 2^31)
+    const int words = (int)p.L.maskWords;      // (Ho Wo < 2^31)
     int par = 0, nList = 0;
-    if (p.frameMasks) {
-        par = __hip_atomic_load((int*)(p.frameMasks + 2 * words), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cur = p.frameMasks + (par ? words : 0);
+    if (p.L.frameMasks) {
+        par = __hip_atomic_load((int*)(p.L.frameMasks + 2 * words), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cur = p.L.frameMasks + (par ? words : 0);
     } else {
-        nList = p.countDev ? min(*p.countDev, p.nHost) : p.nHost;
-        nList = max(0, min(nList, HWo));
+        nList = CBG_LIST_COUNT(p.L, HWo);
     }
     // thread t's chunk: of the mask's words, or of the list's entries
     const int total = cur ? words : nList;
     const int chunk = (total + 255) / 256;
     const int c0 = (int)min((long)total, (long)t * chunk), c1 = min(total, c0 + chunk);
-    const int y0 = cur ? c0 / p.wpr : 0, col0 = cur ? c0 - y0 * p.wpr : 0;      // (the chunk's first word)
+    const int y0 = cur ? c0 / p.L.wpr : 0, col0 = cur ? c0 - y0 * p.L.wpr : 0;      // (the chunk's first word)
 
     // ONE pass over the chunk, four loads in flight (a dependent load per element and phase was most of a short
     // launch): per phase this thread's number of listed pixels.  The phase loops are unrolled, so the array is never
@@ -315,8 +261,8 @@ __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
 #pragma unroll
     for (int i = 0; i < CBT_MAX_PH; ++i) cnt[i] = 0;
     if (cur) {
-        unsigned long long* other = p.frameMasks + (par ? 0 : words);
-        unsigned long long* copy = p.frameMasks + 2 * words + 2;
+        unsigned long long* other = p.L.frameMasks + (par ? 0 : words);
+        unsigned long long* copy = p.L.frameMasks + 2 * words + 2;
         const unsigned long long every = p.sW == 1   ? ~0ull
                                          : p.sW == 2 ? 0x5555555555555555ull
                                          : p.sW == 3 ? 0x9249249249249249ull
@@ -328,7 +274,7 @@ __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (w + j >= c1) continue;
-                if ((w + j) % CBT_GRID == (int)blockIdx.x) {      // (the grid is CBT_GRID workgroups)
+                if ((w + j) % CBG_GRID == (int)blockIdx.x) {      // (the grid is CBG_GRID workgroups)
                     copy[w + j] = mw[j];
                     other[w + j] = 0ull;
                 }
@@ -343,14 +289,14 @@ __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
                     const int r = cbt_div_s(ph, p.sW), rx = ph - r * p.sW;
                     cnt[ph] += r == ry ? (rx == 0 ? c[0] : rx == 1 ? c[1] : rx == 2 ? c[2] : c[3]) : 0;
                 }
-                if (++col == p.wpr) col = 0, ++yy;
+                if (++col == p.L.wpr) col = 0, ++yy;
             }
         }
     } else {
         for (int i = c0; i < c1; i += 4) {
             int e[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) e[j] = i + j < c1 ? p.list[i + j] : -1;
+            for (int j = 0; j < 4; ++j) e[j] = i + j < c1 ? p.L.list[i + j] : -1;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int phE = cbt_phase_of(p, e[j]);
@@ -372,18 +318,10 @@ __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
     }
     __syncthreads();
     if (t < CBT_MAX_PH) sTot[t] = t < P ? sWaveTot[0][t] + sWaveTot[1][t] + sWaveTot[2][t] + sWaveTot[3][t] : 0;
-    if (cur) {
-        // every workgroup has read the parity and the mask by now: the last one to arrive flips the parity
-        int* ctl = (int*)(p.frameMasks + 2 * words);
+    if (cur)      // every workgroup has read the parity and the mask by now
+        cb_flip_parity_last((int*)(p.L.frameMasks + 2 * words), par, G);
+    else
         __syncthreads();
-        if (t == 0 &&
-            __hip_atomic_fetch_add(ctl + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) {
-            __hip_atomic_store(ctl + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(ctl, par ^ 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    } else {
-        __syncthreads();
-    }
 
     // inclusive prefix over the 256 chunks of their numbers of listed pixels of phase ph -> sPre
     auto prefix = [&](int ph) {
@@ -406,20 +344,20 @@ __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
     int curPh = -1;
 
     // ---- work items: per phase (pixel tile, channel tile, k-slice); the k-split of a phase is capped by its stages
-    const int tilesM = p.KP / CBT_BM;
+    const int tilesM = p.KP / CBG_BM;
     int base = 0;
-    for (int ph = 0; ph < P; ++ph) base += (__builtin_amdgcn_readfirstlane(sTot[ph]) + CBT_BN - 1) / CBT_BN * tilesM;
+    for (int ph = 0; ph < P; ++ph) base += (__builtin_amdgcn_readfirstlane(sTot[ph]) + CBG_BN - 1) / CBG_BN * tilesM;
     if (base == 0) return;
     int SKmax = 1;
-    if (p.slabs && base < G) SKmax = min(G / base, CBT_SKMAX);
+    if (p.ws.slabs && base < G) SKmax = min(G / base, CBG_SKMAX);
     int items = 0;
     for (int ph = 0; ph < P; ++ph)
-        items += (__builtin_amdgcn_readfirstlane(sTot[ph]) + CBT_BN - 1) / CBT_BN * tilesM *
-                 max(1, min(SKmax, p.ckkP[ph] / CBT_BK));
+        items += (__builtin_amdgcn_readfirstlane(sTot[ph]) + CBG_BN - 1) / CBG_BN * tilesM *
+                 max(1, min(SKmax, p.ckkP[ph] / CBG_BK));
     // (SKmax > 1: items <= base SKmax <= G, one item and one slab per workgroup)
 
-    const int gn = t & 63, gk = wave * 8;      // gather: pixel row, first k of the stage
-    const int am = t >> 2, ak = (t & 3) * 8;   // weights: channel row, first k of the stage
+    const int gn = t & 63, gk = wave * 8;      // the thread's place in the tile (cb_geom_stage.h)
+    const int am = t >> 2, ak = (t & 3) * 8;
     const int wm = wave & 1, wn = wave >> 1;
     const T* src = (const T*)p.src;
 
@@ -427,8 +365,8 @@ __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
         int ph = 0, rem = item, SK = 1, stages = 0, tileBase = 0, nPh = 0;
         for (; ph < P; ++ph) {
             nPh = __builtin_amdgcn_readfirstlane(sTot[ph]);
-            const int tiles = (nPh + CBT_BN - 1) / CBT_BN * tilesM;
-            stages = p.ckkP[ph] / CBT_BK;
+            const int tiles = (nPh + CBG_BN - 1) / CBG_BN * tilesM;
+            stages = p.ckkP[ph] / CBG_BK;
             SK = max(1, min(SKmax, stages));
             if (rem < tiles * SK) break;
             rem -= tiles * SK;
@@ -439,8 +377,8 @@ __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
         const int CkkP = p.ckkP[ph];
         if (ph != curPh) prefix(ph), curPh = ph;
         __syncthreads();
-        if (t < CBT_BN) {
-            const int q = tn * CBT_BN + t;
+        if (t < CBG_BN) {
+            const int q = tn * CBG_BN + t;
             int pix = -1;
             if (q < nPh) {
                 int lo = 0, hi = 255;      // last thread chunk whose prefix is <= q
@@ -453,21 +391,21 @@ __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
                 const int wEnd = min(total, w + chunk);
                 if (cur) {
                     const int ry = cbt_div_s(ph, p.sW), rx = ph - ry * p.sW;
-                    int yy = w / p.wpr, col = w - yy * p.wpr;
+                    int yy = w / p.L.wpr, col = w - yy * p.L.wpr;
                     unsigned long long mw = 0ull;
                     for (; w < wEnd; ++w) {
                         mw = cur[w] & cbt_phase_bits(p, ry, rx, yy, col);
                         const int c = __popcll(mw);
                         if (r < c) break;
                         r -= c;
-                        if (++col == p.wpr) col = 0, ++yy;
+                        if (++col == p.L.wpr) col = 0, ++yy;
                     }
                     if (w < wEnd) pix = yy * p.Wo + col * 64 + cb_select_bit(mw, r);
                 } else {
                     for (; w < wEnd && pix < 0; w += 4) {      // (four loads in flight)
                         int e[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) e[j] = w + j < wEnd ? p.list[w + j] : -1;
+                        for (int j = 0; j < 4; ++j) e[j] = w + j < wEnd ? p.L.list[w + j] : -1;
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
                             if (pix < 0 && cbt_phase_of(p, e[j]) == ph && r-- == 0) pix = e[j];
@@ -486,118 +424,12 @@ __global__ __launch_bounds__(256) void cbt_conv_kernel(TConvParams p) {
         const char* pbase = (const char*)(src + (long)iy0 * p.Wi + ix0);
         const T* wph = (const T*)(p.prepared + p.wOff[ph]);
         const int* tabPh = (const int*)(wph + (long)p.KP * CkkP);
-        const T* wrow = wph + ((long)tm * CBT_BM + am) * CkkP + ak;
-
-        T ra[8], rb[8];
-        auto load = [&](int s) {
-            const T* wsrc = wrow + (long)s * CBT_BK;
-            if constexpr (sizeof(T) == 2) {
-                const uint4 v = *(const uint4*)wsrc;
-                __builtin_memcpy(ra, &v, 16);
-            } else {
-                const float4 v0 = *(const float4*)wsrc, v1 = *(const float4*)(wsrc + 4);
-                __builtin_memcpy(ra, &v0, 16);
-                __builtin_memcpy(ra + 4, &v1, 16);
-            }
-            const int* tab = tabPh + s * CBT_BK + gk;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int off = tab[i], dd = tab[CkkP + i];
-                const int dy = (short)(dd & 0xffff), dx = dd >> 16;
-                const bool inb = pix >= 0 && (unsigned)(iy0 + dy) < (unsigned)p.Hi && (unsigned)(ix0 + dx) < (unsigned)p.Wi;
-                rb[i] = inb ? *(const T*)(pbase + off) : T(0);
-            }
-        };
-
-        floatx16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        // two LDS buffers, one barrier per stage: the loads of stage s+1 fly during the MFMAs of stage s and land in
-        // the other buffer behind them (whose last readers passed the previous barrier)
-        if (s0 < s1) {
-            load(s0);
-            sA[0].put(am, ak, ra);
-            sB[0].put(gn, gk, rb);
-        }
-        __syncthreads();
-        for (int s = s0; s < s1; ++s) {
-            const int cb = (s - s0) & 1;
-            if (s + 1 < s1) load(s + 1);
-            acc = cbg_mfma_stage<ARITH>(sA[cb], sB[cb], wm * 32 + (lane & 31), wn * 32 + (lane & 31), lane, acc);
-            if (s + 1 < s1) {
-                sA[cb ^ 1].put(am, ak, ra);
-                sB[cb ^ 1].put(gn, gk, rb);
-            }
-            __syncthreads();
-        }
-
-        // ---- split-k: partial tiles to the workspace, summed in slice order by the last workgroup to arrive; the
-        // hand-off is cbg_conv_kernel's: write-through (sc1) slab stores drained before the workgroup's ticket, sc1
-        // loads behind the reducer's acquire (MI355X_MICROARCH.md, "Inter-workgroup visibility")
-        if (SK > 1) {
-            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
-            const __amdgpu_buffer_rsrc_t srsrc =
-                __builtin_amdgcn_make_buffer_rsrc((void*)p.slabs, 0, CBT_GRID * CBT_SLAB * 4, 0x00020000);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 f = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f), srsrc,
-                                                       (item * (CBT_SLAB / 4) + (wave * 4 + q) * 64 + lane) * 16, 0,
-                                                       16 /* sc1 */);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            int* ticket = p.tickets + (tileBase + tn * tilesM + tm);
-            if (t == 0) {
-                const int old = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (old == SK - 1) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                sLast = old == SK - 1;
-            }
-            __syncthreads();
-            if (!sLast) continue;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-            for (int sl = 0; sl < SK; ++sl)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 f = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                        srsrc, ((item - slice + sl) * (CBT_SLAB / 4) + (wave * 4 + q) * 64 + lane) * 16, 0, 16 /* sc1 */));
-                    acc[4 * q] += f.x, acc[4 * q + 1] += f.y, acc[4 * q + 2] += f.z, acc[4 * q + 3] += f.w;
-                }
-        }
-
-        // ---- bias, ReLU, scatter
-        const int opix = sList[wn * 32 + (lane & 31)];
-        if (opix >= 0) {
-            T* out = (T*)p.out;
-            const T* bias = (const T*)p.bias;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int m = tm * CBT_BM + wm * 32 + (j >> 2) * 8 + (lane >> 5) * 4 + (j & 3);
-                if (m < p.K) {
-                    float v = acc[j] + (bias ? (float)bias[m] : 0.f);
-                    if (p.relu) v = v <= 0.f ? 0.f : v;
-                    out[(long)m * HWo + opix] = (T)v;
-                }
-            }
-        }
+        const T* wrow = wph + ((long)tm * CBG_BM + am) * CkkP + ak;
+        CBG_TILE_STAGES(acc, wrow, tabPh, CkkP, pbase, pix, iy0, ix0, p.Hi, p.Wi, s0, s1)
+        if (SK > 1)
+            CBG_SPLITK_HANDOFF(acc, p.ws.slabs, p.ws.tickets + (tileBase + tn * tilesM + tm), item, slice, SK, sLast, continue)
+        CBG_TILE_STORE(acc, sList, tm, p.bias, p.out, p.K, HWo, p.relu)
     }
-}
-
-int cbt_launch_conv(const TConvParams& p, int dtype, hipStream_t s) {
-    dim3 grid(CBT_GRID), block(256);
-    if (dtype == CB_F16)
-        hipLaunchKernelGGL((cbt_conv_kernel<cb_half, CB_F16>), grid, block, 0, s, p);
-    else if (dtype == CB_F32S)
-        hipLaunchKernelGGL((cbt_conv_kernel<float, CB_F32S>), grid, block, 0, s, p);
-    else
-        hipLaunchKernelGGL((cbt_conv_kernel<float, CB_F32>), grid, block, 0, s, p);
-    return cb_launch_status();
 }
 
 bool cbt_arith_ok(int dtype) { return dtype == CB_F32 || dtype == CB_F16 || dtype == CB_F32S; }
@@ -621,7 +453,7 @@ long cbinfer_tconv_prepared_weights_bytes(int K, int C, const cbTGeom* geom, int
     return cbt_layout(K, C, geom, dtype).total;
 }
 
-long cbinfer_tconv_workspace_bytes(void) { return (long)CBT_GRID * CBT_SLAB * 4 + (long)CBT_GRID * 4; }
+long cbinfer_tconv_workspace_bytes(void) { return cbg_workspace_bytes(); }
 
 int cbinfer_tconv_prep_weights(const void* weight, void* prepared, int K, int C, int Hi, int Wi, const cbTGeom* geom,
                                int dtype, cbStream_t stream) {
@@ -633,7 +465,7 @@ int cbinfer_tconv_prep_weights(const void* weight, void* prepared, int K, int C,
     int most = 0;
     for (int ph = 0; ph < geom->sH * geom->sW; ++ph) most = most > L.ckkP[ph] ? most : L.ckkP[ph];
     if (most == 0) return CB_OK;
-    const int KP = (K + CBT_BM - 1) / CBT_BM * CBT_BM;
+    const int KP = cbg_kpad(K);
     dim3 grid(cb_div_up((long)KP * most, 256), geom->sH * geom->sW), block(256);
     if (dtype == CB_F16)
         hipLaunchKernelGGL(cbt_prep_kernel<cb_half>, grid, block, 0, (hipStream_t)stream, (const cb_half*)weight,
@@ -654,18 +486,8 @@ int cbinfer_change_detection_tconv(const void* input, void* state, uint64_t* fra
     const int st = cbt_shape(C, 1, Hi, Wi, geom, &Ho, &Wo);
     if (st != CB_OK) return st;
     if (Hi > 65535) return CB_ERR_UNSUPPORTED;      // (one grid row per input row)
-    const int wprO = cbinfer_mask_words_per_row(Wo);
-    const long words = cbinfer_mask_words(Ho, Wo);
-    dim3 grid(cb_div_up(Wi, 64), Hi), block(64 * (C >= 32 ? 16 : C >= 8 ? 8 : C >= 4 ? 4 : C));      // (waves over the channels)
-    if (dtype == CB_F16)
-        hipLaunchKernelGGL(cbt_detect_kernel<cb_half>, grid, block, 0, (hipStream_t)stream, (const cb_half*)input,
-                           (cb_half*)state, (unsigned long long*)frameMasks, words, C, Hi, Wi, Ho, Wo, wprO, *geom,
-                           threshold, updateInputState);
-    else
-        hipLaunchKernelGGL(cbt_detect_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)input,
-                           (float*)state, (unsigned long long*)frameMasks, words, C, Hi, Wi, Ho, Wo, wprO, *geom,
-                           threshold, updateInputState);
-    return cb_launch_status();
+    return cbg_launch_detect(cbt_detect_kernel<float>, cbt_detect_kernel<cb_half>, input, state, frameMasks, C, Hi, Wi,
+                             Ho, Wo, *geom, threshold, updateInputState, dtype, (hipStream_t)stream);
 }
 
 int cbinfer_conv_changed_tconv(const void* input, const int32_t* changeList, int numChanges, const int32_t* countDev,
@@ -677,29 +499,22 @@ int cbinfer_conv_changed_tconv(const void* input, const int32_t* changeList, int
     const int st = cbt_shape(C, K, Hi, Wi, geom, &Ho, &Wo);
     if (st != CB_OK) return st;
     TConvParams p = {};
-    if (frameMasks) {
-        CB_REQUIRE(!changeList && !countDev);
-        p.frameMasks = (unsigned long long*)frameMasks;
-        p.maskWords = cbinfer_mask_words(Ho, Wo);
-        p.wpr = cbinfer_mask_words_per_row(Wo);
-    } else {
-        CB_REQUIRE(changeList && numChanges >= 0 && numChanges <= Ho * Wo);
-        if (numChanges == 0) return CB_OK;
-        p.list = changeList, p.countDev = countDev, p.nHost = numChanges;
-    }
+    const int ls = cbg_list_args(p.L, changeList, numChanges, countDev, frameMasks, !countDev, Ho, Wo);
+    if (ls != CB_OK || cbg_nothing_listed(p.L)) return ls;
     const TConvLayout L = cbt_layout(K, C, geom, dtype);
     for (int ph = 0; ph < CBT_MAX_PH; ++ph) p.ckkP[ph] = L.ckkP[ph], p.wOff[ph] = L.wOff[ph];
     p.prepared = (const char*)prepared;
-    p.KP = (K + CBT_BM - 1) / CBT_BM * CBT_BM;
+    p.KP = cbg_kpad(K);
     p.src = input, p.bias = bias, p.out = output;
-    if (workspace) {
-        p.slabs = (float*)workspace;
-        p.tickets = (int*)((char*)workspace + (long)CBT_GRID * CBT_SLAB * 4);
-    }
+    p.ws = cbg_workspace(workspace);
     p.K = K, p.Hi = Hi, p.Wi = Wi, p.Ho = Ho, p.Wo = Wo, p.relu = relu;
     p.sH = geom->sH, p.sW = geom->sW, p.pH = geom->pH, p.pW = geom->pW;
     p.rWo = 1.0 / Wo;
-    return cbt_launch_conv(p, dtype, (hipStream_t)stream);
+    cbg_dispatch_arith(dtype, [&](auto a) {
+        hipLaunchKernelGGL((cbt_conv_kernel<typename decltype(a)::T, decltype(a)::ARITH>), dim3(CBG_GRID), dim3(256), 0,
+                           (hipStream_t)stream, p);
+    });
+    return cb_launch_status();
 }
 
 int cbinfer_cbconvtranspose2d_forward(const void* input, void* prevInput, void* prevOutput, uint64_t* frameMasks,
@@ -710,13 +525,10 @@ int cbinfer_cbconvtranspose2d_forward(const void* input, void* prevInput, void* 
     int Ho, Wo;
     int st = cbt_shape(C, K, Hi, Wi, geom, &Ho, &Wo);
     if (st != CB_OK) return st;
-    const int edt = dtype == CB_F32S ? CB_F32 : dtype;
-    const void* src = (feedbackLoop || copyInput) ? prevInput : input;
-    const bool copyAll = !feedbackLoop && copyInput && prevInput != input;
-    st = cbinfer_change_detection_tconv(input, prevInput, frameMasks, C, Hi, Wi, geom, threshold,
-                                        feedbackLoop ? 1 : (copyAll ? 2 : 0), edt, stream);
+    const CbgFrameMode fm = cbg_frame_mode(input, prevInput, feedbackLoop, copyInput, dtype);
+    st = cbinfer_change_detection_tconv(input, prevInput, frameMasks, C, Hi, Wi, geom, threshold, fm.update, fm.edt, stream);
     if (st != CB_OK) return st;
-    return cbinfer_conv_changed_tconv(src, nullptr, 0, nullptr, frameMasks, prepared, bias, prevOutput, C, Hi, Wi, K,
+    return cbinfer_conv_changed_tconv(fm.src, nullptr, 0, nullptr, frameMasks, prepared, bias, prevOutput, C, Hi, Wi, K,
                                       geom, relu, workspace, dtype, stream);
 }
 
