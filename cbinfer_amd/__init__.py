@@ -27,6 +27,7 @@ from .pointwise import CBPointwise2d, insertCBPointwise
 from .groupconv import CBGroupedConv2d, linkGrouped
 from .rearrange import CBPixelShuffle2d, CBChannelShuffle2d, insertCBRearrange
 from .chanreduce import CBChannelReduce2d, insertCBChannelOps
+from .resize import CBResize2d, insertCBResize
 
 __version__ = "0.1.0"
 
@@ -275,7 +276,8 @@ def linkConsumers(producer, consumers):
 
 
 _STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d,
-             CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d, CBChannelReduce2d)
+             CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d, CBChannelReduce2d,
+             CBResize2d)
 
 
 def _stateful(net):
@@ -396,7 +398,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'insertCBRearrange', 'CBChannelReduce2d', 'insertCBChannelOps', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'insertCBRearrange', 'CBChannelReduce2d', 'insertCBChannelOps', 'CBResize2d', 'insertCBResize', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

@@ -145,6 +145,18 @@ class Rearrange(ctypes.Structure):
 
 _rp = ctypes.POINTER(Rearrange)
 
+RESIZE_NEAREST, RESIZE_NEAREST_EXACT, RESIZE_BILINEAR, RESIZE_BICUBIC = range(4)      # CB_RESIZE_*
+
+
+class Resize(ctypes.Structure):
+    """cbResize of include/cbinfer_hip.h: output size, the step a / b (input pixels per output pixel) of either axis, mode
+    and align_corners of a change-based resize."""
+    _fields_ = [("Ho", _i), ("Wo", _i), ("aH", _i), ("bH", _i), ("aW", _i), ("bW", _i), ("mode", _i),
+                ("alignCorners", _i)]
+
+
+_rsp = ctypes.POINTER(Resize)
+
 _SIGNATURES = {
     # name: (restype, [argtypes])
     "cbinfer_abi_version": (_i, []),
@@ -319,6 +331,8 @@ _SIGNATURES = {
     "cbinfer_rearrange_supported": (_i, [_rp]),
     "cbinfer_rearrange_out_shape": (_i, [_rp, _i, _i, _i, _ip, _ip, _ip]),
     "cbinfer_cbrearrange_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _rp, _i, _vp]),
+    "cbinfer_resize_supported": (_i, [_rsp, _i, _i]),
+    "cbinfer_cbresize_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _rsp, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

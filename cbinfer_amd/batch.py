@@ -32,6 +32,7 @@ from .pointwise import CBPointwise2d
 from .groupconv import CBGroupedConv2d
 from .rearrange import CBChannelShuffle2d, CBPixelShuffle2d
 from .chanreduce import CBChannelReduce2d
+from .resize import CBResize2d
 
 
 # the change-based operators that have neither a batched kernel here nor a grouped launch in a BranchGroup: (types,
@@ -45,6 +46,7 @@ CHAIN_OPERATORS = (
     ((CBGroupedConv2d,), 'a change-based grouped convolution', 'ResNeXt-type'),
     ((CBPixelShuffle2d, CBChannelShuffle2d), 'a change-based rearrangement', 'super-resolution and ShuffleNet-type'),
     ((CBChannelReduce2d,), 'a change-based per-pixel channel reduction', 'ConvNeXt-type and segmentation'),
+    ((CBResize2d,), 'a change-based resize', 'dense-prediction'),
 )
 
 

@@ -2,7 +2,8 @@
 information are taken apart, the state module CBAdd2d, CBPointwise2d, CBUpsample2d, CBConcat2d, CBPixelShuffle2d and
 CBChannelShuffle2d derive from, the ONE test for a state that no longer fits its frame (state_fits: these modules and
 the layers of layer.py), the mask workspace and hand-back of every mask-driven module, and the ONE table of
-the modules that count as a producer (with its later additions in a second one, later_producer_types).
+the modules that count as a producer (with its later additions in a second one, later_producer_types, and what the
+passes accept on top of both, chain_producers).
 """
 import functools
 
@@ -162,6 +163,15 @@ def later_producer_types():
     producer_types(...) + later_producer_types() in front of their module."""
     from .rearrange import CBChannelShuffle2d, CBPixelShuffle2d
     return (CBPixelShuffle2d, CBChannelShuffle2d)
+
+
+def chain_producers(forUpsampling=False):
+    """What the passes that build their producer set from the two pinned tables accept in front of their module --
+    linkDepthwise, insertCBPointwise, insertCBTransposedConv, insertCBUpsampling (forUpsampling), insertCBRearrange and
+    insertCBChannelOps, each with its own further types --: the tables, which stay as they are pinned, and CBResize2d,
+    which keeps their rule as well."""
+    from .resize import CBResize2d
+    return producer_types(forUpsampling=forUpsampling) + later_producer_types() + (CBResize2d,)
 
 
 def hand_on_changes(prod):

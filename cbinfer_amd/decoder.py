@@ -18,8 +18,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, later_producer_types, mask_workspace, operand_changes,
-                    producer_types, split_operand, state_fits)
+from .chain import (CBStateModule, chain_producers, hand_on_changes, mask_workspace, operand_changes,
+                    split_operand, state_fits)
 from .conv2d import CBConv2d
 
 MAX_SCALE = 8
@@ -201,7 +201,8 @@ _UPSAMPLERS = (nn.Upsample, nn.UpsamplingNearest2d, nn.UpsamplingBilinear2d)
 def insertCBUpsampling(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.Upsample / nn.UpsamplingNearest2d / nn.UpsamplingBilinear2d within
     the library's limits that directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBPixelShuffle2d,
-    CBChannelShuffle2d or another CBUpsample2d becomes a CBUpsample2d fed by that producer's changes: propChangeIndexes
+    CBChannelShuffle2d, CBResize2d or another CBUpsample2d (chain.chain_producers) becomes a CBUpsample2d fed by that
+    producer's changes: propChangeIndexes
     is switched on at the producer
     (a CBResidual's `.add`; a 2x2 CBPoolMax2d of the reference's kind also hands on the OUTPUT-resolution list,
     downsampleIndexes).  A CBConv2d consuming the upsampled map then needs its own input copy (copyInput) unless it runs
@@ -211,7 +212,7 @@ def insertCBUpsampling(rootModule, cloneOutput=True):
         names = list(seq._modules.keys())
         for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
             prod, up = seq._modules[a], seq._modules[b]
-            if (type(prod) not in producer_types(forUpsampling=True) + later_producer_types() or
+            if (type(prod) not in chain_producers(forUpsampling=True) or
                     type(up) not in _UPSAMPLERS):
                 continue
             try:

@@ -70,7 +70,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_pointwise_changed, cbinfer_cbpointwise_forward) and the grouped convolution (cbinfer_groupconv_*,
  * cbinfer_conv_changed_grouped, cbinfer_cbgroupconv2d_forward) and the rearrangements (cbRearrange, CB_REARRANGE_*,
  * cbinfer_rearrange_supported, cbinfer_rearrange_out_shape, cbinfer_cbrearrange_forward) and the per-pixel channel
- * reductions (CB_CH_*, cbinfer_chanreduce_supported, cbinfer_chanreduce_changed, cbinfer_cbchanreduce_forward). */
+ * reductions (CB_CH_*, cbinfer_chanreduce_supported, cbinfer_chanreduce_changed, cbinfer_cbchanreduce_forward) and the
+ * resize to any size (cbResize, CB_RESIZE_*, cbinfer_resize_supported, cbinfer_cbresize_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1047,6 +1048,67 @@ int cbinfer_cbconcat_forward(const void* const* sources, const int32_t* channels
                              const uint64_t* const* masks, const int32_t* const* lists, const int32_t* caps,
                              const int32_t* const* counts, uint64_t* bits, uint64_t* maskCopy, int H, int W, int dtype,
                              cbStream_t stream);
+
+/* ---- change-based resize to any size (cb_resize.hip) -----------------------------------------------------
+ * No counterpart in the reference.  F.interpolate to a size or by any scale, up or down: an output pixel reads 1, 2x2 or
+ * 4x4 input pixels at coordinates that are a rational function of its own, so -- every producer leaves the pixels outside
+ * its change list bit for bit as they were -- the output can differ from last frame's only at the footprint of the
+ * input's changes.  Tensors, masks, lists and the frame (inputMask / list / neither, maskCopy, bits) are
+ * cbinfer_cbupsample_forward's: input [C, Hi, Wi], the state `out` [C, Ho, Wo], CB_F32 or CB_F16; the mask form is one
+ * launch, the list form one more in front, which ORs the footprint into `bits` (one thread per entry and candidate
+ * output row, every candidate tested with the source rule, at most two 64-bit atomicOr per row).
+ *
+ * THIS SECTION IS THE SPECIFICATION; tests/resize_cases.py is its numpy twin and equals the kernel bit for bit.
+ *   source coordinates per axis, ALL IN INTEGERS (exact; within the limits below an int32 holds every intermediate):
+ *   n the input extent, N the output extent, o the output coordinate, a / b the step in input pixels per output pixel
+ *   (aH / bH, aW / bW), handed in by the host:
+ *     CB_RESIZE_NEAREST:        one tap i = min(o a / b, n - 1).
+ *     CB_RESIZE_NEAREST_EXACT:  one tap i = min((2 o + 1) a / (2 b), n - 1).
+ *     CB_RESIZE_BILINEAR, CB_RESIZE_BICUBIC:
+ *       alignCorners == 0: num = (2 o + 1) a - b, den = 2 b;
+ *       alignCorners == 1: num = o (n - 1), den = N - 1 (N == 1: num = 0, den = 1), whatever a / b is.
+ *       BILINEAR: num = max(num, 0), i0 = num / den, rho = num - i0 den, the taps i0 and i0 + 1, both clamped to n - 1
+ *         (within the limits below i0 <= n - 1 by itself).
+ *       BICUBIC: num is not clamped, i0 = floor(num / den) (floor division for a negative num), rho = num - i0 den, the
+ *         taps i0 - 1 .. i0 + 2, each clamped to [0, n - 1].
+ *       t = (float)rho / (float)den, ONE correctly rounded division of two exactly represented integers.
+ *   values: the nearest kinds copy bit for bit.  Otherwise everything is f32, every operation written below is rounded on
+ *   its own (round to nearest even, never an FMA), in exactly this order, and the result is rounded to the dtype once:
+ *     weights of an axis  BILINEAR: w0 = 1 - t, w1 = t.
+ *                         BICUBIC, A = -0.75:  far(s) = ((A s - 5 A) s + 8 A) s - 4 A   evaluated as
+ *                           m = A * s; m = m - (-3.75); m = m * s; m = m + (-6); m = m * s; m - (-3);
+ *                         near(u) = ((A + 2) u - (A + 3)) u u + 1   evaluated as
+ *                           m = 1.25 * u; m = m - 2.25; m = m * u; m = m * u; m + 1;
+ *                         w0 = far(t + 1), w1 = near(t), w2 = near(1 - t), w3 = far(2 - t).
+ *     a row  r_k = ((wx0 p(k,0) + wx1 p(k,1)) + wx2 p(k,2)) + wx3 p(k,3)  with p(k,j) the input at (tap row k, tap
+ *            column j): the products in ascending j, summed left to right (BILINEAR: the first two terms);
+ *     out    = ((wy0 r_0 + wy1 r_1) + wy2 r_2) + wy3 r_3, likewise.
+ *   A pixel's bits therefore depend neither on the other listed pixels nor on the operand's form.  torch derives the
+ *   source coordinate from a float scale, so bilinear and bicubic follow F.interpolate to about 1e-5 and are not
+ *   bit-compared with it; the nearest kinds are bit-identical to torch.
+ *   footprint: (oy, ox) is listed iff any of its 1 / 2x2 / 4x4 clamped taps is listed -- a zero weight does not
+ *   matter, the mask handed on is a function of the input's mask alone.  An input pixel that no output reads
+ *   (downscaling) lists nothing.
+ * Limits (cbinfer_resize_supported): per axis 1 <= a, b <= 4096, 1/8 <= a / b <= 8, n / 8 <= N <= 8 n, n and N below
+ * 2^15, and with alignCorners == 0 N a <= n b -- the output map does not reach beyond the input, as with torch's
+ * a / b = n / N (size) or 1 / scale_factor with N = floor(n scale_factor); mode one of the four, alignCorners 0 or 1 and
+ * 0 for the nearest kinds.
+ * Bad arguments (a null tensor or mask, C / Hi / Wi < 1, an unknown dtype, a cbResize beyond the limits, capN < 0, both a
+ * mask and a list, a count without a list, inputMask == bits or maskCopy, bits == maskCopy, Ho Wo or 64 C beyond an
+ * int32) return CB_ERR_BADARG and launch nothing. */
+#define CB_RESIZE_NEAREST 0
+#define CB_RESIZE_NEAREST_EXACT 1
+#define CB_RESIZE_BILINEAR 2
+#define CB_RESIZE_BICUBIC 3
+typedef struct cbResize {
+    int Ho, Wo, aH, bH, aW, bW, mode, alignCorners;
+} cbResize;
+/* host, pure: 1 if the resize of an Hi x Wi map is within the limits above, else 0 */
+int cbinfer_resize_supported(const cbResize* rs, int Hi, int Wi);
+/* The whole frame of a change-based resize enqueued without a host sync. */
+int cbinfer_cbresize_forward(const void* input, void* outputState, const uint64_t* inputMask, const int32_t* list,
+                             int capN, const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int Hi, int Wi,
+                             const cbResize* rs, int dtype, cbStream_t stream);
 
 /* ---- change-based pixel shuffle, pixel unshuffle and channel shuffle (cb_rearrange.hip) -----------------
  * No counterpart in the reference.  The three operators compute nothing: values are copied bit for bit, never converted,
