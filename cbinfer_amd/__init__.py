@@ -28,6 +28,7 @@ from .groupconv import CBGroupedConv2d, linkGrouped
 from .rearrange import CBPixelShuffle2d, CBChannelShuffle2d, insertCBRearrange
 from .chanreduce import CBChannelReduce2d, insertCBChannelOps
 from .resize import CBResize2d, insertCBResize
+from .pad import CBPad2d, insertCBPadding, splitConvPadding
 
 __version__ = "0.1.0"
 
@@ -160,8 +161,8 @@ def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
     conv), so only the windows holding a changed pixel are pooled again.  A CBConv2d consuming the pool
     then needs its own input copy (copyInput) unless it runs in feedback mode.  generalGeometry=True: every
     nn.MaxPool2d and nn.AvgPool2d within the library's limits (CBPoolMax2d(m, generalGeometry=True), CBPoolAvg2d) is
-    converted, also directly behind a CBPointwise2d (the general pools take its mask); a pool beyond them stays the dense
-    torch operator.  Returns rootModule."""
+    converted, also directly behind a CBPointwise2d or a CBPad2d (the general pools take their mask); a pool beyond them
+    stays the dense torch operator.  Returns rootModule."""
     def _pair(v):
         return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
@@ -186,7 +187,7 @@ def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
         for a, b in zip(names[:-1], names[1:]):
             conv, pool = seq._modules[a], seq._modules[b]
             cb = _converted(pool) if (type(conv) == CBConv2d or
-                                      (generalGeometry and type(conv) is CBPointwise2d)) else None
+                                      (generalGeometry and type(conv) in (CBPointwise2d, CBPad2d))) else None
             if cb is not None:
                 _log('change-based pooling after %s' % a)
                 conv.propChangeIndexes = True
@@ -277,7 +278,7 @@ def linkConsumers(producer, consumers):
 
 _STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d,
              CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d, CBChannelReduce2d,
-             CBResize2d)
+             CBResize2d, CBPad2d)
 
 
 def _stateful(net):
@@ -398,7 +399,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'insertCBRearrange', 'CBChannelReduce2d', 'insertCBChannelOps', 'CBResize2d', 'insertCBResize', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'insertCBRearrange', 'CBChannelReduce2d', 'insertCBChannelOps', 'CBResize2d', 'insertCBResize', 'CBPad2d', 'insertCBPadding', 'splitConvPadding', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

@@ -157,6 +157,17 @@ class Resize(ctypes.Structure):
 
 _rsp = ctypes.POINTER(Resize)
 
+PAD_CONSTANT, PAD_REFLECT, PAD_REPLICATE, PAD_CIRCULAR = range(4)      # CB_PAD_*
+
+
+class Pad(ctypes.Structure):
+    """cbPad of include/cbinfer_hip.h: mode, the four pads in torch's (left, right, top, bottom) order and the value of
+    constant mode of a change-based padding."""
+    _fields_ = [("mode", _i), ("left", _i), ("right", _i), ("top", _i), ("bottom", _i), ("value", _f)]
+
+
+_pdp = ctypes.POINTER(Pad)
+
 _SIGNATURES = {
     # name: (restype, [argtypes])
     "cbinfer_abi_version": (_i, []),
@@ -333,6 +344,9 @@ _SIGNATURES = {
     "cbinfer_cbrearrange_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _rp, _i, _vp]),
     "cbinfer_resize_supported": (_i, [_rsp, _i, _i]),
     "cbinfer_cbresize_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _rsp, _i, _vp]),
+    "cbinfer_pad_supported": (_i, [_pdp, _i, _i]),
+    "cbinfer_pad_out_size": (_i, [_pdp, _i, _i, _ip, _ip]),
+    "cbinfer_cbpad_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _pdp, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

@@ -33,6 +33,7 @@ from .groupconv import CBGroupedConv2d
 from .rearrange import CBChannelShuffle2d, CBPixelShuffle2d
 from .chanreduce import CBChannelReduce2d
 from .resize import CBResize2d
+from .pad import CBPad2d
 
 
 # the change-based operators that have neither a batched kernel here nor a grouped launch in a BranchGroup: (types,
@@ -47,6 +48,7 @@ CHAIN_OPERATORS = (
     ((CBPixelShuffle2d, CBChannelShuffle2d), 'a change-based rearrangement', 'super-resolution and ShuffleNet-type'),
     ((CBChannelReduce2d,), 'a change-based per-pixel channel reduction', 'ConvNeXt-type and segmentation'),
     ((CBResize2d,), 'a change-based resize', 'dense-prediction'),
+    ((CBPad2d,), 'a change-based padding', 'reflection-padded and restoration'),
 )
 
 

@@ -3,7 +3,7 @@ information are taken apart, the state module CBAdd2d, CBPointwise2d, CBUpsample
 CBChannelShuffle2d derive from, the ONE test for a state that no longer fits its frame (state_fits: these modules and
 the layers of layer.py), the mask workspace and hand-back of every mask-driven module, and the ONE table of
 the modules that count as a producer (with its later additions in a second one, later_producer_types, and what the
-passes accept on top of both, chain_producers).
+passes accept on top of both, chain_producers and pass_producers).
 """
 import functools
 
@@ -172,6 +172,15 @@ def chain_producers(forUpsampling=False):
     which keeps their rule as well."""
     from .resize import CBResize2d
     return producer_types(forUpsampling=forUpsampling) + later_producer_types() + (CBResize2d,)
+
+
+def pass_producers(forUpsampling=False):
+    """chain_producers(...), which stays as it is pinned, and CBPad2d, which keeps the producers' rule as well: what
+    linkDepthwise, insertCBPointwise, insertCBTransposedConv, insertCBUpsampling (forUpsampling), insertCBRearrange,
+    insertCBChannelOps, insertCBResize and insertCBPadding accept in front of their module, each with its own further
+    types."""
+    from .pad import CBPad2d
+    return chain_producers(forUpsampling=forUpsampling) + (CBPad2d,)
 
 
 def hand_on_changes(prod):

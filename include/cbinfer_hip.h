@@ -71,7 +71,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_conv_changed_grouped, cbinfer_cbgroupconv2d_forward) and the rearrangements (cbRearrange, CB_REARRANGE_*,
  * cbinfer_rearrange_supported, cbinfer_rearrange_out_shape, cbinfer_cbrearrange_forward) and the per-pixel channel
  * reductions (CB_CH_*, cbinfer_chanreduce_supported, cbinfer_chanreduce_changed, cbinfer_cbchanreduce_forward) and the
- * resize to any size (cbResize, CB_RESIZE_*, cbinfer_resize_supported, cbinfer_cbresize_forward). */
+ * resize to any size (cbResize, CB_RESIZE_*, cbinfer_resize_supported, cbinfer_cbresize_forward) and the padding (cbPad,
+ * CB_PAD_*, cbinfer_pad_supported, cbinfer_pad_out_size, cbinfer_cbpad_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1149,6 +1150,58 @@ int cbinfer_rearrange_out_shape(const cbRearrange* r, int C, int H, int W, int* 
 int cbinfer_cbrearrange_forward(const void* input, void* outputState, const uint64_t* inputMask, const int32_t* list,
                                 int capN, const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W,
                                 const cbRearrange* r, int dtype, cbStream_t stream);
+
+/* ---- change-based padding (cb_pad.hip) -----------------------------------------------------------------
+ * No counterpart in the reference.  F.pad of a [C, H, W] map by (left, right, top, bottom) -- torch's order -- in the
+ * modes constant (with a value), reflect, replicate and circular: nn.ReflectionPad2d, nn.ReplicationPad2d, nn.ZeroPad2d,
+ * nn.ConstantPad2d, nn.CircularPad2d, and what torch runs in front of the contraction of an nn.Conv2d whose padding_mode
+ * is not 'zeros'.  A pad computes nothing: values are copied bit for bit, never converted, and -- every producer leaves
+ * the pixels outside its change list bit for bit as they were -- the output can differ from last frame's only at the
+ * footprint of the input's changes on the OUTPUT map.  Tensors are contiguous, CB_F32 or CB_F16, batch 1; masks are
+ * row-padded (cbinfer_mask_words); an int32 list holds flat indexes y W + x of the INPUT map, entries outside it are
+ * dropped; bits of the row padding are never set.
+ *
+ * THIS SECTION IS THE SPECIFICATION; tests/pad_cases.py is its numpy twin and equals torch's F.pad bit for bit.
+ *   output size: Ho = H + top + bottom, Wo = W + left + right.
+ *   source coordinate per axis, with n the input extent, p the LEADING pad (top / left) and o the output coordinate:
+ *   i = o - p, then
+ *     CB_PAD_CONSTANT:   i if 0 <= i < n; otherwise the pixel takes `value` and reads no input;
+ *     CB_PAD_REFLECT:    i <- |i|, then i <- 2 (n - 1) - i if i >= n;
+ *     CB_PAD_REPLICATE:  clamp(i, 0, n - 1);
+ *     CB_PAD_CIRCULAR:   i mod n (non-negative).
+ *   out[c, oy, ox] = in[c, source(oy), source(ox)].  `value` is converted once to the tensor's dtype ((T)value, round
+ *   to nearest even), which is what torch does.
+ *   footprint: (oy, ox) is listed iff the input pixel it reads is listed.  A constant-mode border pixel reads nothing:
+ *   it is written only by an every-pixel frame.  With a crop a listed input pixel may list nothing.
+ *   the input's changes: inputMask (over the INPUT map; one launch, the footprint gathered inside it: lane j of a wave
+ *     tests the input bit that output column 64 tile + j reads), list (capN entries at most, countDev the device-side
+ *     length or NULL: capN is the length; one launch in front, which ORs the footprint into `bits`: per axis an input
+ *     coordinate is read by at most three intervals of output coordinates -- its own image and up to two reflections /
+ *     wraps; a replicated border run of up to 65 coordinates is contiguous with the image --, one 64-bit atomicOr per
+ *     mask word an interval touches; capN == 0 launches nothing in front), or neither: every output pixel is listed.
+ *   hand-on: maskCopy (cbinfer_mask_words(Ho, Wo) words) receives the frame's mask every frame; `bits`, the working
+ *     mask of the OUTPUT map (zero on first use), is zero again when the frame ends.  Unlisted pixels keep their bits.
+ * Limits (cbinfer_pad_supported): every |pad| <= 64 (cbGeom's padding bound); negative pads (cropping) in constant mode
+ * only; Ho, Wo >= 1; reflect: every pad below the extent of its axis, circular: not above it (torch's own rules).
+ * Bad arguments (a null tensor or mask buffer, input == outputState, C / H / W < 1, an unknown dtype or mode, a pad beyond
+ * the limits, a negative pad outside constant mode, capN < 0, both a mask and a list, a count without a list,
+ * inputMask == bits or maskCopy, bits == maskCopy, H W, Ho Wo or 64 C beyond an int32) return CB_ERR_BADARG and launch
+ * nothing. */
+enum { CB_PAD_CONSTANT, CB_PAD_REFLECT, CB_PAD_REPLICATE, CB_PAD_CIRCULAR };
+typedef struct cbPad {
+    int mode;                     /* CB_PAD_* */
+    int left, right, top, bottom; /* torch's (l, r, t, b) order */
+    float value;                  /* CB_PAD_CONSTANT only */
+} cbPad;
+/* host, pure: 1 if the padding of an H x W map is within the limits above, else 0 */
+int cbinfer_pad_supported(const cbPad* p, int H, int W);
+/* host, pure: the output size of an H x W map (CB_OK; CB_ERR_UNSUPPORTED beyond the limits; CB_ERR_BADARG for a null
+ * pointer or a size < 1; Ho / Wo untouched on failure) */
+int cbinfer_pad_out_size(const cbPad* p, int H, int W, int* Ho, int* Wo);
+/* The whole frame of a change-based padding enqueued without a host sync; C, H, W are the INPUT's. */
+int cbinfer_cbpad_forward(const void* input, void* outputState, const uint64_t* inputMask, const int32_t* list, int capN,
+                          const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, const cbPad* p,
+                          int dtype, cbStream_t stream);
 
 /* ---- transposed convolution (cb_tconv.hip) ------------------------------------------------------------
  * The reference has no counterpart: its CBConv2d asserts transposed == False (conv2d.py:92-104).  Input map Hi x Wi,

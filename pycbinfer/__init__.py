@@ -8,7 +8,7 @@ import sys
 
 import cbinfer_amd
 from cbinfer_amd import *            # noqa: F401,F403
-from cbinfer_amd import chanreduce, conv2d, conv2d_cg, conv2d_fg, decoder, dwconv, groupconv, pointwise, rearrange, residual, resize, tconv
+from cbinfer_amd import chanreduce, conv2d, conv2d_cg, conv2d_fg, decoder, dwconv, groupconv, pad, pointwise, rearrange, residual, resize, tconv
 
 sys.modules[__name__ + '.conv2d'] = conv2d
 sys.modules[__name__ + '.conv2d_cg'] = conv2d_cg
@@ -22,5 +22,6 @@ sys.modules[__name__ + '.groupconv'] = groupconv
 sys.modules[__name__ + '.rearrange'] = rearrange
 sys.modules[__name__ + '.chanreduce'] = chanreduce
 sys.modules[__name__ + '.resize'] = resize
+sys.modules[__name__ + '.pad'] = pad
 
 __all__ = cbinfer_amd.__all__
