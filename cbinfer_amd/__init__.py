@@ -29,6 +29,7 @@ from .rearrange import CBPixelShuffle2d, CBChannelShuffle2d, insertCBRearrange
 from .chanreduce import CBChannelReduce2d, insertCBChannelOps
 from .resize import CBResize2d, insertCBResize
 from .pad import CBPad2d, insertCBPadding, splitConvPadding
+from .binary import CBBinary2d, CBGLU2d, CBGated, insertCBGating
 
 __version__ = "0.1.0"
 
@@ -278,7 +279,7 @@ def linkConsumers(producer, consumers):
 
 _STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d,
              CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d, CBChannelReduce2d,
-             CBResize2d, CBPad2d)
+             CBResize2d, CBPad2d, CBBinary2d, CBGLU2d)
 
 
 def _stateful(net):
@@ -399,7 +400,7 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'insertCBRearrange', 'CBChannelReduce2d', 'insertCBChannelOps', 'CBResize2d', 'insertCBResize', 'CBPad2d', 'insertCBPadding', 'splitConvPadding', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
+__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'insertCBRearrange', 'CBChannelReduce2d', 'insertCBChannelOps', 'CBResize2d', 'insertCBResize', 'CBPad2d', 'insertCBPadding', 'splitConvPadding', 'CBBinary2d', 'CBGLU2d', 'CBGated', 'insertCBGating', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',

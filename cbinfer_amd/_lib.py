@@ -168,6 +168,11 @@ class Pad(ctypes.Structure):
 
 _pdp = ctypes.POINTER(Pad)
 
+BIN_ADD, BIN_SUB, BIN_MUL, BIN_MAXIMUM, BIN_MINIMUM = range(5)      # CB_BIN_* ops
+BIN_GATE_NONE, BIN_GATE_SIGMOID, BIN_GATE_HARDSIGMOID = range(3)      # CB_BIN_GATE_*
+BIN_MAP, BIN_PIXEL, BIN_CHANNEL, BIN_SCALAR, BIN_HALVES = range(5)      # CB_BIN_* operand forms
+BIN_B_NONE, BIN_B_OWN = range(2)      # CB_BIN_B_*
+
 _SIGNATURES = {
     # name: (restype, [argtypes])
     "cbinfer_abi_version": (_i, []),
@@ -347,6 +352,10 @@ _SIGNATURES = {
     "cbinfer_pad_supported": (_i, [_pdp, _i, _i]),
     "cbinfer_pad_out_size": (_i, [_pdp, _i, _i, _ip, _ip]),
     "cbinfer_cbpad_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _pdp, _i, _vp]),
+    "cbinfer_binary_supported": (_i, [_i, _i, _i]),
+    "cbinfer_binary_changed": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cbinfer_cbbinary_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i,
+                                      _i, _i, _i, _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

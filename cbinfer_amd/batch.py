@@ -34,6 +34,7 @@ from .rearrange import CBChannelShuffle2d, CBPixelShuffle2d
 from .chanreduce import CBChannelReduce2d
 from .resize import CBResize2d
 from .pad import CBPad2d
+from .binary import CBBinary2d, CBGLU2d
 
 
 # the change-based operators that have neither a batched kernel here nor a grouped launch in a BranchGroup: (types,
@@ -49,6 +50,7 @@ CHAIN_OPERATORS = (
     ((CBChannelReduce2d,), 'a change-based per-pixel channel reduction', 'ConvNeXt-type and segmentation'),
     ((CBResize2d,), 'a change-based resize', 'dense-prediction'),
     ((CBPad2d,), 'a change-based padding', 'reflection-padded and restoration'),
+    ((CBBinary2d, CBGLU2d), 'a change-based element-wise operator of two maps', 'gated and attention'),
 )
 
 

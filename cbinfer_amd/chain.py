@@ -3,7 +3,7 @@ information are taken apart, the state module CBAdd2d, CBPointwise2d, CBUpsample
 CBChannelShuffle2d derive from, the ONE test for a state that no longer fits its frame (state_fits: these modules and
 the layers of layer.py), the mask workspace and hand-back of every mask-driven module, and the ONE table of
 the modules that count as a producer (with its later additions in a second one, later_producer_types, and what the
-passes accept on top of both, chain_producers and pass_producers).
+passes accept on top of both, chain_producers, pass_producers and operator_producers).
 """
 import functools
 
@@ -183,12 +183,23 @@ def pass_producers(forUpsampling=False):
     return chain_producers(forUpsampling=forUpsampling) + (CBPad2d,)
 
 
+def operator_producers(forUpsampling=False):
+    """pass_producers(...), which stays as it is pinned, and CBBinary2d, CBGLU2d and CBGated, which keep the producers'
+    rule as well: what linkDepthwise, insertCBPointwise, insertCBTransposedConv, insertCBUpsampling (forUpsampling),
+    insertCBRearrange, insertCBChannelOps, insertCBResize, insertCBPadding and insertCBGating accept in front of their
+    module, each with its own further types."""
+    from .binary import CBBinary2d, CBGated, CBGLU2d
+    return pass_producers(forUpsampling=forUpsampling) + (CBBinary2d, CBGLU2d, CBGated)
+
+
 def hand_on_changes(prod):
     """Switch the change output of the producer `prod` on for the consumer behind it: propChangeIndexes (a CBResidual's
-    at its `.add`); a 2x2 CBPoolMax2d of the reference's kind also hands on the OUTPUT-resolution list."""
+    at its `.add`, a CBGated's at its `.mul`); a 2x2 CBPoolMax2d of the reference's kind also hands on the
+    OUTPUT-resolution list."""
+    from .binary import CBGated
     from .conv2d import CBPoolMax2d
     from .residual import CBResidual
-    (prod.add if type(prod) is CBResidual else prod).propChangeIndexes = True
+    (prod.add if type(prod) is CBResidual else prod.mul if type(prod) is CBGated else prod).propChangeIndexes = True
     if type(prod) is CBPoolMax2d and not prod.__dict__.get('_general'):
         prod.downsampleIndexes = True      # (the list of the pool's input addresses another map)
 

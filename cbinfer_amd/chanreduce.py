@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, pass_producers,
+from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
                     split_operand, state_fits)
 
 _AFFINE = ('gamma', 'beta')
@@ -153,7 +153,7 @@ def insertCBChannelOps(rootModule, layerNormTypes=()):
     """Inside every nn.Sequential of rootModule, an nn.Softmax2d, an nn.Softmax / nn.LogSoftmax over dim 1 (or -3), or an
     instance of one of layerNormTypes -- the user's channels-first layer-norm classes, exact types with .weight, .bias (or
     None) and .eps, as ConvNeXt's LayerNorm2d; torch has no such class of its own -- that directly follows a producer
-    (chain.pass_producers(), a CBGroupedConv2d or another CBChannelReduce2d) becomes a
+    (chain.operator_producers(), a CBGroupedConv2d or another CBChannelReduce2d) becomes a
     CBChannelReduce2d under the same name, fed by that producer's changes: propChangeIndexes is switched on at the
     producer (chain.hand_on_changes).  The new module hands its own changes on where it stands directly in front of a
     1x1 / stride-1 / padding-0 CBConv2d; any other CBConv2d directly behind it needs its own input copy (copyInput)
@@ -164,7 +164,7 @@ def insertCBChannelOps(rootModule, layerNormTypes=()):
     from .conv2d import CBConv2d
     from .groupconv import CBGroupedConv2d
     layerNormTypes = tuple(layerNormTypes)
-    producers = pass_producers() + (CBGroupedConv2d, CBChannelReduce2d)
+    producers = operator_producers() + (CBGroupedConv2d, CBChannelReduce2d)
     for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
         names = list(seq._modules.keys())
         for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):

@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, mask_workspace, operand_changes, pass_producers,
+from .chain import (CBStateModule, hand_on_changes, mask_workspace, operand_changes, operator_producers,
                     split_operand, state_fits)
 from .conv2d import CBConv2d
 
@@ -201,7 +201,7 @@ _UPSAMPLERS = (nn.Upsample, nn.UpsamplingNearest2d, nn.UpsamplingBilinear2d)
 def insertCBUpsampling(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.Upsample / nn.UpsamplingNearest2d / nn.UpsamplingBilinear2d within
     the library's limits that directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBPixelShuffle2d,
-    CBChannelShuffle2d, CBResize2d, CBPad2d or another CBUpsample2d (chain.pass_producers) becomes a CBUpsample2d fed by that
+    CBChannelShuffle2d, CBResize2d, CBPad2d or another CBUpsample2d (chain.operator_producers) becomes a CBUpsample2d fed by that
     producer's changes: propChangeIndexes
     is switched on at the producer
     (a CBResidual's `.add`; a 2x2 CBPoolMax2d of the reference's kind also hands on the OUTPUT-resolution list,
@@ -212,7 +212,7 @@ def insertCBUpsampling(rootModule, cloneOutput=True):
         names = list(seq._modules.keys())
         for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
             prod, up = seq._modules[a], seq._modules[b]
-            if (type(prod) not in pass_producers(forUpsampling=True) or
+            if (type(prod) not in operator_producers(forUpsampling=True) or
                     type(up) not in _UPSAMPLERS):
                 continue
             try:

@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, stream_ptr
 from .chain import (PROPAGATED, hand_back, hand_on_changes, is_1x1, mask_workspace, operand_changes,
-                    pass_producers)
+                    operator_producers)
 from .conv2d import _padding_pair
 from .layer import CBDetectingLayer, check_limits, frame_masks
 
@@ -140,7 +140,7 @@ def linkDepthwise(rootModule):
     for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
         kids = list(seq.children())
         for prod, cons in zip(kids[:-1], kids[1:]):
-            if (type(cons) is CBDepthwiseConv2d and type(prod) in pass_producers() and
+            if (type(cons) is CBDepthwiseConv2d and type(prod) in operator_producers() and
                     _propagated_ok(cons.kernel_size, cons.padding, cons.dilation)):
                 cons.propagatedChanges = True
                 hand_on_changes(prod)

@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, pass_producers,
+from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
                     split_operand, state_fits)
 
 MAX_PAD = 64      # per side, either sign: cbGeom's padding bound
@@ -216,7 +216,7 @@ def _converted(m):
 def insertCBPadding(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.ReflectionPad2d, nn.ReplicationPad2d, nn.ZeroPad2d,
     nn.ConstantPad2d or nn.CircularPad2d within the library's limits that directly follows a producer --
-    chain.pass_producers() (another CBPad2d among them), a CBGroupedConv2d or a CBChannelReduce2d -- becomes a CBPad2d
+    chain.operator_producers() (another CBPad2d among them), a CBGroupedConv2d or a CBChannelReduce2d -- becomes a CBPad2d
     fed by that producer's changes: propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new
     module hands its own changes on where it stands directly in front of a 1x1 / stride-1 / padding-0 CBConv2d; any other
     CBConv2d directly behind it needs its own input copy (copyInput) unless it runs in feedback mode.  A module beyond the
@@ -225,7 +225,7 @@ def insertCBPadding(rootModule, cloneOutput=True):
     from .chanreduce import CBChannelReduce2d
     from .conv2d import CBConv2d
     from .groupconv import CBGroupedConv2d
-    producers = pass_producers() + (CBGroupedConv2d, CBChannelReduce2d)
+    producers = operator_producers() + (CBGroupedConv2d, CBChannelReduce2d)
     for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
         names = list(seq._modules.keys())
         for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):

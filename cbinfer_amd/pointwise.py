@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, pass_producers,
+from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
                     split_operand, state_fits)
 
 # nn type (exactly, not a subclass) -> (CB_PW_* kind, p0, p1 of the instance)
@@ -174,7 +174,7 @@ def insertCBPointwise(rootModule):
             names = list(seq._modules.keys())
             prod, first = seq._modules[names[pos - 1]], seq._modules[names[pos]]
             pos += 1
-            if type(prod) not in pass_producers():
+            if type(prod) not in operator_producers():
                 continue
             norm = first if type(first) is nn.BatchNorm2d else None
             after = seq._modules[names[pos]] if norm is not None and pos < len(names) else first

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, pass_producers,
+from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
                     split_operand, state_fits)
 from .conv2d import CBConv2d
 from .groupconv import CBGroupedConv2d
@@ -167,14 +167,14 @@ def _converted(m):
 
 def insertCBRearrange(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.PixelShuffle, nn.PixelUnshuffle or nn.ChannelShuffle within the
-    library's limits that directly follows a producer -- chain.pass_producers(), a CBGroupedConv2d, or another
+    library's limits that directly follows a producer -- chain.operator_producers(), a CBGroupedConv2d, or another
     CBPixelShuffle2d / CBChannelShuffle2d -- becomes the change-based module fed by that producer's changes:
     propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new module hands its own changes on
     where it stands directly in front of a 1x1 / stride-1 / padding-0 CBConv2d; any other CBConv2d consuming its output
     needs its own input copy (copyInput) unless it runs in feedback mode.  linkDepthwise, insertCBPointwise,
     insertCBUpsampling and insertCBTransposedConv, called afterwards, take the new modules as producers.  A module beyond
     the limits, or behind anything else, stays the dense torch operator.  Returns rootModule."""
-    producers = pass_producers() + (CBGroupedConv2d,)
+    producers = operator_producers() + (CBGroupedConv2d,)
     for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
         names = list(seq._modules.keys())
         for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):

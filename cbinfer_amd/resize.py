@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, pass_producers,
+from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
                     split_operand, state_fits)
 
 MAX_RATIO = 8          # per axis, either way
@@ -190,7 +190,7 @@ def insertCBResize(rootModule, cloneOutput=True):
     from .chanreduce import CBChannelReduce2d
     from .conv2d import CBConv2d
     from .groupconv import CBGroupedConv2d
-    producers = pass_producers(forUpsampling=True) + (CBGroupedConv2d, CBChannelReduce2d)
+    producers = operator_producers(forUpsampling=True) + (CBGroupedConv2d, CBChannelReduce2d)
     for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
         names = list(seq._modules.keys())
         for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):

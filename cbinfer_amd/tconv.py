@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, stream_ptr
-from .chain import hand_back, pass_producers
+from .chain import hand_back, operator_producers
 from .conv2d import CBConv2d
 from .layer import CBContractingLayer, check_limits
 
@@ -109,7 +109,7 @@ class CBConvTranspose2d(CBContractingLayer):
 def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.ConvTranspose2d within the library's limits that directly follows
     a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBPixelShuffle2d, CBChannelShuffle2d,
-    CBResize2d, CBPad2d or another CBConvTranspose2d (chain.pass_producers) becomes a
+    CBResize2d, CBPad2d or another CBConvTranspose2d (chain.operator_producers) becomes a
     CBConvTranspose2d with `threshold` (it runs its own change detection: nothing is switched on at the producer).  An
     nn.ReLU right behind it is absorbed (withReLU).  A CBConv2d consuming the output then needs its own input copy
     (copyInput) unless it runs in feedback mode.  A module beyond the limits stays the dense torch operator.  Returns
@@ -121,7 +121,7 @@ def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
             prod, tc = seq._modules[names[pos - 1]], seq._modules[names[pos]]
             if names[pos - 1] in gone and pos >= 2:
                 prod = seq._modules[names[pos - 2]]
-            if type(prod) not in pass_producers() or type(tc) != nn.ConvTranspose2d:
+            if type(prod) not in operator_producers() or type(tc) != nn.ConvTranspose2d:
                 continue
             try:
                 cb = CBConvTranspose2d(tc, threshold)

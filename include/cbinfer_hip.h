@@ -72,7 +72,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_rearrange_supported, cbinfer_rearrange_out_shape, cbinfer_cbrearrange_forward) and the per-pixel channel
  * reductions (CB_CH_*, cbinfer_chanreduce_supported, cbinfer_chanreduce_changed, cbinfer_cbchanreduce_forward) and the
  * resize to any size (cbResize, CB_RESIZE_*, cbinfer_resize_supported, cbinfer_cbresize_forward) and the padding (cbPad,
- * CB_PAD_*, cbinfer_pad_supported, cbinfer_pad_out_size, cbinfer_cbpad_forward). */
+ * CB_PAD_*, cbinfer_pad_supported, cbinfer_pad_out_size, cbinfer_cbpad_forward) and the element-wise operators of two
+ * maps (CB_BIN_*, cbinfer_binary_supported, cbinfer_binary_changed, cbinfer_cbbinary_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1202,6 +1203,78 @@ int cbinfer_pad_out_size(const cbPad* p, int H, int W, int* Ho, int* Wo);
 int cbinfer_cbpad_forward(const void* input, void* outputState, const uint64_t* inputMask, const int32_t* list, int capN,
                           const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, const cbPad* p,
                           int dtype, cbStream_t stream);
+
+/* ---- change-based element-wise operators of two maps (cb_binary.hip) -------------------------------------
+ * No counterpart in the reference.  out = op(a, b) with op a sum, a difference, a product -- plain or gated,
+ * a * sigmoid(b), a * hardsigmoid(b) --, a maximum or a minimum.  a and the state `out` are [C, H, W], contiguous, one
+ * dtype (CB_F32 or CB_F16), two different tensors; b has the same dtype.  Every producer of this library leaves the
+ * pixels outside its change list bit for bit as they were, so op(a, b) can differ from last frame's only at the union of
+ * the operands' changes, and a constant operand never changes; recomputing there is the dense result, exactly.
+ *
+ * THIS SECTION IS THE SPECIFICATION; tests/binary_cases.py is its numpy twin.
+ *   the second operand is addressed as b[c sc + p sp], p = y W + x, with the strides its form `bForm` gives:
+ *     CB_BIN_MAP      [C, H, W]   sc = H W, sp = 1;
+ *     CB_BIN_PIXEL    [1, H, W]   sc = 0,   sp = 1: one value per pixel, used for every channel;
+ *     CB_BIN_CHANNEL  [C]         sc = 1,   sp = 0;
+ *     CB_BIN_SCALAR   [1]         sc = 0,   sp = 0;
+ *     CB_BIN_HALVES   `a` is really [2C, H, W] and b its upper half, a + C H W elements (nn.GLU over the channels): the
+ *                     entry points derive that address from `a` themselves -- a caller that patches a new frame's address
+ *                     into `a` also moves b --, and b must be NULL.
+ *   values: at listed pixels, every channel c.  Both operands go to f32 (exact), then ONE correctly rounded f32 operation
+ *   -- there is never a multiply-add, so no FMA can be formed --, rounded to f16 once for CB_F16 (the correctly rounded
+ *   f16 result):
+ *     CB_BIN_ADD      a + b
+ *     CB_BIN_SUB      a - b;  reverse != 0: b - a (reverse is accepted with CB_BIN_SUB only)
+ *     CB_BIN_MUL      a * g(b), g by `gate` (a gate is accepted with CB_BIN_MUL only):
+ *                       CB_BIN_GATE_NONE         g(v) = v
+ *                       CB_BIN_GATE_SIGMOID      1 / (1 + expf(-v))          (the device's expf: DESIGN 5.25 has the bound)
+ *                       CB_BIN_GATE_HARDSIGMOID  clamp(v + 3, 0, 6) / 6,  clamp(t, lo, hi) = t < lo ? lo : (t > hi ? hi : t)
+ *                     the pointwise formulas, evaluated in f32 and ROUNDED TO THE OPERAND DTYPE FIRST, as the separate
+ *                     torch operator would round its result; then the product.
+ *     CB_BIN_MAXIMUM  a != a ? a : (b != b ? b : (b > a ? b : a))
+ *     CB_BIN_MINIMUM  a != a ? a : (b != b ? b : (b < a ? b : a))
+ *                     comparisons, not fmaxf / fminf: a NaN if either operand is one; `a` on a tie, +0 against -0
+ *                     included.
+ *   Except for the sigmoid gate this is torch's CPU operator bit for bit in fp32 and fp16 (torch.add / sub / mul /
+ *   maximum / minimum, a * F.hardsigmoid(b)); a NaN result is a NaN, its payload is not specified.  A pixel's bits depend
+ *   neither on the other listed pixels nor on the forms the operands' changes arrive in.  Every other pixel of `out`
+ *   keeps its bits.
+ *   listed pixels: the union of the operands' changes.  `a` arrives as its row-padded change MASK
+ *     (cbinfer_mask_words(H, W) words), as an int32 LIST (flat indexes y W + x; entries outside the map are dropped), or
+ *     not at all: every pixel is listed then.  b in MAP or PIXEL form with bChanges == CB_BIN_B_OWN arrives the same way.
+ *     With bChanges == CB_BIN_B_NONE -- a constant operand; always in HALVES form, whose changes are a's -- b contributes
+ *     no pixel and takes neither mask nor list.  CHANNEL or SCALAR with CB_BIN_B_OWN lists every pixel: a per-frame
+ *     channel vector changes the whole map.  Bits of the row padding are never set.
+ *   hand-on: maskCopy receives the frame's union mask every frame (all zeros for an empty frame); `bits`, the working
+ *     mask (cbinfer_mask_words(H, W) words, zero on first use), is zero again when the launch ends.
+ * Bad arguments -- a null tensor or mask buffer, C / H / W < 1, an unknown dtype, bForm, op, gate or bChanges, a gate
+ * without CB_BIN_MUL, reverse without CB_BIN_SUB, b != NULL in HALVES form or b == NULL in any other, `out` aliasing an
+ * operand, a mask or list for b where b cannot have one (CHANNEL, SCALAR, HALVES; CB_BIN_B_NONE; CB_BIN_B_OWN in HALVES
+ * form), both a mask and a list for one operand, a count without a list, a negative list capacity, bits == maskCopy, an
+ * operand's mask == bits or maskCopy, H W or 64 C beyond an int32 -- return CB_ERR_BADARG and launch nothing. */
+enum { CB_BIN_ADD, CB_BIN_SUB, CB_BIN_MUL, CB_BIN_MAXIMUM, CB_BIN_MINIMUM };
+enum { CB_BIN_GATE_NONE, CB_BIN_GATE_SIGMOID, CB_BIN_GATE_HARDSIGMOID };
+enum { CB_BIN_MAP, CB_BIN_PIXEL, CB_BIN_CHANNEL, CB_BIN_SCALAR, CB_BIN_HALVES };
+enum { CB_BIN_B_NONE, CB_BIN_B_OWN };
+/* host, pure: 1 if (op, gate, reverse) is a combination above, else 0 */
+int cbinfer_binary_supported(int op, int gate, int reverse);
+/* The mask-driven launch.  maskA / maskB: the operand's change mask, or NULL (maskB only in MAP or PIXEL form); allA /
+ * allB != 0: the operand lists every pixel.  The kernel ORs `bits`, maskA and maskB word by word itself (or forms the
+ * full row word); an operand with neither contributes what `bits` holds on entry.  In PIXEL form g(b[p]) is evaluated
+ * once per listed pixel and shared over the channels through LDS.  No atomics. */
+int cbinfer_binary_changed(const void* a, const void* b, void* out, const uint64_t* maskA, int allA, const uint64_t* maskB,
+                           int allB, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int bForm, int op, int gate,
+                           int reverse, int dtype, cbStream_t stream);
+/* The whole frame enqueued without a host sync.  Per operand X: maskX != NULL: mask form; listX != NULL: list form (capX
+ * entries at most, countX the device-side length or NULL: capX is the length; capX == 0 launches nothing); both NULL: no
+ * change information -- for `a`, and for b with CB_BIN_B_OWN, every pixel is listed; for b with CB_BIN_B_NONE, none.
+ * With both operands in mask or all form the frame is ONE launch (cbinfer_binary_changed); an operand in list form costs
+ * one launch in front, which ORs its bits into `bits` -- skipped when the other operand lists every pixel anyway.  All
+ * arguments are checked before the first launch. */
+int cbinfer_cbbinary_forward(const void* a, const void* b, void* outputState, const uint64_t* maskA, const int32_t* listA,
+                             int capA, const int32_t* countA, const uint64_t* maskB, const int32_t* listB, int capB,
+                             const int32_t* countB, int bForm, int bChanges, uint64_t* bits, uint64_t* maskCopy, int C,
+                             int H, int W, int op, int gate, int reverse, int dtype, cbStream_t stream);
 
 /* ---- transposed convolution (cb_tconv.hip) ------------------------------------------------------------
  * The reference has no counterpart: its CBConv2d asserts transposed == False (conv2d.py:92-104).  Input map Hi x Wi,

@@ -8,7 +8,7 @@ import sys
 
 import cbinfer_amd
 from cbinfer_amd import *            # noqa: F401,F403
-from cbinfer_amd import chanreduce, conv2d, conv2d_cg, conv2d_fg, decoder, dwconv, groupconv, pad, pointwise, rearrange, residual, resize, tconv
+from cbinfer_amd import binary, chanreduce, conv2d, conv2d_cg, conv2d_fg, decoder, dwconv, groupconv, pad, pointwise, rearrange, residual, resize, tconv
 
 sys.modules[__name__ + '.conv2d'] = conv2d
 sys.modules[__name__ + '.conv2d_cg'] = conv2d_cg
@@ -23,5 +23,6 @@ sys.modules[__name__ + '.rearrange'] = rearrange
 sys.modules[__name__ + '.chanreduce'] = chanreduce
 sys.modules[__name__ + '.resize'] = resize
 sys.modules[__name__ + '.pad'] = pad
+sys.modules[__name__ + '.binary'] = binary
 
 __all__ = cbinfer_amd.__all__
