@@ -15,8 +15,10 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, require_device, stream_ptr
-from .chain import (OPERAND_WORDS, CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes,
-                    operator_producers, split_operand, state_fits)
+from .chain import (EVERY_PIXEL, OPERAND_WORDS, CBStateModule, check_map, form_args, insert_behind_producers,
+                    mask_workspace, operand_changes, operator_producers, split_operand)
+from .chanreduce import CBChannelReduce2d
+from .groupconv import CBGroupedConv2d
 from .residual import _sequential
 
 _OPS = {'add': _lib.BIN_ADD, 'sub': _lib.BIN_SUB, 'mul': _lib.BIN_MUL, 'maximum': _lib.BIN_MAXIMUM,
@@ -48,11 +50,7 @@ class _CBBinaryBase(CBStateModule):
 
     def _workspace(self, H, W, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer and count: once per map size."""
-        key = (H, W, dev)
-        work = self.__dict__.get(self._WORK)
-        if work is None or work['key'] != key:
-            work = self.__dict__[self._WORK] = dict(mask_workspace(H, W, dev), key=key)
-        return work
+        return self._cached_work((H, W, dev), lambda: mask_workspace(H, W, dev))
 
     def _frame(self, name, a, ia, b, ib, form, bChanges, nc, H, W):
         """One frame: a [1, nc (2 nc in halves form), H, W], b in `form` (None in halves form), ia / ib the operands'
@@ -60,26 +58,15 @@ class _CBBinaryBase(CBStateModule):
         work = self._workspace(H, W, a.device)
         # (a list the producer's kernel already made is taken before its mask: CBAdd2d's rule)
         fa = operand_changes(name, 'operand a', ia, H, W, a.device, work['idx'], words=_WORDS, maskWhenMade=False)
-        fb = (None, None, 0, None)
+        fb = EVERY_PIXEL
         if bChanges == _lib.BIN_B_OWN and form in (_lib.BIN_MAP, _lib.BIN_PIXEL):
             fb = operand_changes(name, 'operand b', ib, H, W, a.device, work['idx'], words=_WORDS, maskWhenMade=False)
-        shape = (1, nc, H, W)
-        if not state_fits(self.outputState, shape, a):
-            # a new state is written completely: neither operand's change information is used
-            self.outputState = a.new_empty(shape)
-            fa = fb = (None, None, 0, None)
-        check(C.cbinfer_cbbinary_forward(ptr(a), ptr(b), ptr(self.outputState), ptr(fa[0]), ptr(fa[1]), fa[2], ptr(fa[3]),
-                                         ptr(fb[0]), ptr(fb[1]), fb[2], ptr(fb[3]), form, bChanges, ptr(work['bits']),
-                                         ptr(work['copy']), nc, H, W, _OPS[self.op], _GATES[self.gate], int(self.reverse),
-                                         _lib.dtype_code(a), stream_ptr(a)))
+        if self._fresh_state((1, nc, H, W), a):      # (written completely: neither operand's change information is used)
+            fa = fb = EVERY_PIXEL
+        check(C.cbinfer_cbbinary_forward(ptr(a), ptr(b), ptr(self.outputState), *form_args(fa), *form_args(fb), form,
+                                         bChanges, ptr(work['bits']), ptr(work['copy']), nc, H, W, _OPS[self.op],
+                                         _GATES[self.gate], int(self.reverse), _lib.dtype_code(a), stream_ptr(a)))
         return self._result(work, H, W)
-
-
-def _checked_map(name, a, which='a'):
-    if a.dim() != 4 or a.size(0) != 1:
-        raise CBinferError("%s: operand %s must be a [1, C, H, W] tensor, got %s" % (name, which, tuple(a.shape)))
-    if a.dtype not in (torch.float32, torch.float16):
-        raise CBinferError("%s: float32 and float16 tensors only, got %s" % (name, a.dtype))
 
 
 class CBBinary2d(_CBBinaryBase):
@@ -161,7 +148,7 @@ class CBBinary2d(_CBBinaryBase):
         if not self.hasOther and b is None:
             raise CBinferError("CBBinary2d: forward(a, b) takes two operands (or give the module a constant `other`)")
         a, ia = split_operand('CBBinary2d', a, 'operand a')
-        _checked_map('CBBinary2d', a)
+        check_map('CBBinary2d', a, 'operand a')
         nc, H, W = a.size(1), a.size(2), a.size(3)
         if self.hasOther:
             t, form = self._constant(a, nc, H, W)
@@ -212,7 +199,7 @@ class CBGLU2d(_CBBinaryBase):
 
     def forward(self, inp):
         x, ix = split_operand('CBGLU2d', inp, 'the input')
-        _checked_map('CBGLU2d', x, 'x')
+        check_map('CBGLU2d', x, 'operand x')
         if x.size(1) % 2:
             raise CBinferError("CBGLU2d: the input %s has an odd number of channels: nn.GLU halves them"
                                % (tuple(x.shape),))
@@ -262,24 +249,10 @@ def insertCBGating(rootModule, cloneOutput=True):
     stride-1 / padding-0 CBConv2d; any other CBConv2d directly behind it needs its own input copy (copyInput) unless it
     runs in feedback mode.  A GLU over another dim, or behind anything else, stays the dense torch operator.  Returns
     rootModule."""
-    from .chanreduce import CBChannelReduce2d
-    from .conv2d import CBConv2d
-    from .groupconv import CBGroupedConv2d
-    producers = operator_producers() + (CBGroupedConv2d, CBChannelReduce2d)
-    for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
-        names = list(seq._modules.keys())
-        for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
-            prod, glu = seq._modules[a], seq._modules[b]
-            if type(prod) not in producers or type(glu) is not nn.GLU or glu.dim not in (1, -3):
-                continue
-            cb = CBGLU2d(glu)
-            hand_on_changes(prod)
-            cb.cloneOutput = cloneOutput
-            seq._modules[b] = cb
-            if pos + 2 < len(names):
-                consumer = seq._modules[names[pos + 2]]
-                if is_1x1(consumer):
-                    cb.propChangeIndexes = True
-                elif type(consumer) is CBConv2d and not consumer.feedbackLoop:
-                    consumer.copyInput = True
-    return rootModule
+    def convert(glu):
+        try:
+            return CBGLU2d(glu) if type(glu) is nn.GLU else None
+        except CBinferError:
+            return None      # (over another dim: stays dense)
+    return insert_behind_producers(rootModule, operator_producers() + (CBGroupedConv2d, CBChannelReduce2d), convert,
+                                   cloneOutput=cloneOutput)

@@ -1,16 +1,23 @@
-"""What the change-based operators behind a producer share on the host: how an operand and its change
-information are taken apart, the state module CBAdd2d, CBPointwise2d, CBUpsample2d, CBConcat2d, CBPixelShuffle2d and
-CBChannelShuffle2d derive from, the ONE test for a state that no longer fits its frame (state_fits: these modules and
-the layers of layer.py), the mask workspace and hand-back of every mask-driven module, and the ONE table of
-the modules that count as a producer (with its later additions in a second one, later_producer_types, and what the
-passes accept on top of both, chain_producers, pass_producers and operator_producers).
+"""What the change-based operators behind a producer share on the host.
+
+The frame: how an operand and its change information are taken apart (split_operand, check_map, operand_changes), the
+form that lists every pixel (EVERY_PIXEL) and how a form is handed to the library (form_args), the ONE test for a state
+that no longer fits its frame (state_fits: these modules and the layers of layer.py), the mask workspace and
+hand-back of every mask-driven module, and CBStateModule, which CBAdd2d, CBPointwise2d, CBUpsample2d, CBConcat2d, the
+shuffles, CBChannelReduce2d, CBResize2d, CBPad2d, CBBinary2d and CBGLU2d derive from: the flags, the keyed workspace
+cache (_cached_work) and the state step (_fresh_state).
+
+The passes: the ONE table of the modules that count as a producer (with its later additions in a second one,
+later_producer_types, and what the passes accept on top of both, chain_producers, pass_producers and
+operator_producers), what is switched on at a producer (hand_on_changes) and at the module behind a new one
+(link_consumer), and the ONE walk that puts an operator behind its producers (insert_behind_producers).
 """
 import functools
 
 import torch
 import torch.nn as nn
 
-from ._lib import C, CBinferError
+from ._lib import C, CBinferError, ptr
 from .conv2d_cg import ChangeIndexes, MaskChangeIndexes
 
 
@@ -28,6 +35,19 @@ def split_operand(name, x, which):
                            % (name, which, type(x).__name__))
     return x.detach().contiguous(), indexes
 
+
+def check_map(name, x, which='the input', note=''):
+    """CBinferError in the module's words unless `x` is a [1, C, H, W] map of float32 or float16.  which: how the module
+    calls the operand; note: what it adds behind "tensor" (CBResize2d and CBPad2d: ' (batch 1)')."""
+    if x.dim() != 4 or x.size(0) != 1:
+        raise CBinferError("%s: %s must be a [1, C, H, W] tensor%s, got %s" % (name, which, note, tuple(x.shape)))
+    if x.dtype not in (torch.float32, torch.float16):
+        raise CBinferError("%s: float32 and float16 tensors only, got %s" % (name, x.dtype))
+
+
+# The form (mask, list, capacity, device count) of an operand that lists every pixel: what a bare tensor carries, and what
+# every operand counts as in a frame that writes a new state
+EVERY_PIXEL = (None, None, 0, None)
 
 # The three refusals of operand_changes -- indexes of another map, of another type, a buffer the kernels cannot read --
 # as the consumers word them; filled with name, which, the two map sizes and the type's name.
@@ -54,7 +74,7 @@ def operand_changes(name, which, indexes, H, W, dev, spare, words=OPERAND_WORDS,
     kernel already made it; maskNeedsSize additionally asks for a mask that names this very map.  contiguous: an int32
     tensor is made contiguous instead of refused."""
     if indexes is None:
-        return None, None, 0, None
+        return EVERY_PIXEL
     said = dict(name=name, which=which, H=H, W=W, type=type(indexes).__name__)
     if isinstance(indexes, ChangeIndexes):
         if indexes.size is not None and tuple(indexes.size) != (H, W):
@@ -71,6 +91,11 @@ def operand_changes(name, which, indexes, H, W, dev, spare, words=OPERAND_WORDS,
         raise CBinferError(words[2] % said)
     cap = idx.numel()
     return None, (idx if cap else spare), cap, count
+
+
+def form_args(form):
+    """The four arguments a library call takes for an operand's form: mask, list, capacity, device count."""
+    return ptr(form[0]), ptr(form[1]), form[2], ptr(form[3])
 
 
 # ---------------------------------------------------------------------------------------------------- state
@@ -107,7 +132,8 @@ def hand_back(module, state, copy, size, work, made=False):
 
 class CBStateModule(nn.Module):
     """A module whose only state is `outputState`: the flags propChangeIndexes / cloneOutput, clearMemory,
-    getStateTensors, and transient work buffers that are neither state nor pickled."""
+    getStateTensors, transient work buffers that are neither state nor pickled and are kept per key (_cached_work), the
+    step that keeps or replaces the state at the start of a frame (_fresh_state), and the hand-back (_result)."""
     _WORK = '_work'        # the slot of the work buffers in the instance's __dict__ (tests and old pickles read it)
     _TRANSIENT = ()        # further slots that are made again on demand (ctypes arguments)
 
@@ -133,6 +159,23 @@ class CBStateModule(nn.Module):
             if name in d:
                 d[name] = None
         return d
+
+    def _cached_work(self, key, make):
+        """The work buffers for `key`: those of the last frame if it had the same key, else dict(make(), key=key), which
+        replaces them.  A make() that raises leaves the old ones in place."""
+        work = self.__dict__.get(self._WORK)
+        if work is None or work['key'] != key:
+            work = self.__dict__[self._WORK] = dict(make(), key=key)
+        return work
+
+    def _fresh_state(self, shape, like):
+        """Keep outputState if it still serves a frame of `shape` with the dtype and device of `like`; else allocate it
+        and return True: a new state is written completely, so the caller uses no operand's change information
+        (EVERY_PIXEL)."""
+        if state_fits(self.outputState, shape, like):
+            return False
+        self.outputState = torch.empty(tuple(shape), dtype=like.dtype, device=like.device)
+        return True
 
     def _result(self, work, Ho, Wo):
         return hand_back(self, self.outputState, work['copy'], (Ho, Wo), work)
@@ -209,3 +252,40 @@ def is_1x1(m):
     from .conv2d import CBConv2d
     return (type(m) is CBConv2d and tuple(m.kernel_size) == (1, 1) and tuple(m.stride) == (1, 1) and
             tuple(m.padding) == (0, 0))
+
+
+def link_consumer(front, consumer, handOn=True):
+    """The consumer rule, for the module `consumer` directly behind `front`: a 1x1 / stride-1 / padding-0 CBConv2d takes
+    the changes of `front` (propChangeIndexes there); any other CBConv2d (exactly) reads a map that is the state of
+    `front` or may be, so it needs its own input copy (copyInput) unless it runs in feedback mode -- a k x k CBConv2d
+    that is handed indexes would skip its own detection, which would be wrong.  handOn=False: `front` never hands on,
+    a 1x1 layer is a CBConv2d like any other (insertCBUpsampling, insertCBTransposedConv)."""
+    from .conv2d import CBConv2d
+    if handOn and is_1x1(consumer):
+        front.propChangeIndexes = True
+    elif type(consumer) is CBConv2d and not consumer.feedbackLoop:
+        consumer.copyInput = True
+
+
+def insert_behind_producers(rootModule, producers, convert, cloneOutput=None, handOn=True):
+    """The walk of the passes that put ONE change-based operator behind a producer.  Inside every nn.Sequential (exactly)
+    of rootModule, for every module that directly follows one whose exact type is in `producers`: convert(module)
+    returns the change-based module to put in its place under its name, or None -- not the pass's operator, or beyond
+    the library's limits -- to leave it the dense torch operator.  The producer's change output is switched on
+    (hand_on_changes), the new module gets `cloneOutput` unless that is None, and the module behind it the consumer
+    rule (link_consumer with handOn).  A new module counts as a producer for the next one where its type is in
+    `producers`.  Returns rootModule."""
+    for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
+        names = list(seq._modules.keys())
+        for pos in range(1, len(names)):
+            prod = seq._modules[names[pos - 1]]
+            cb = convert(seq._modules[names[pos]]) if type(prod) in producers else None
+            if cb is None:
+                continue
+            hand_on_changes(prod)
+            if cloneOutput is not None:
+                cb.cloneOutput = cloneOutput
+            seq._modules[names[pos]] = cb
+            if pos + 1 < len(names):
+                link_consumer(cb, seq._modules[names[pos + 1]], handOn)
+    return rootModule

@@ -15,8 +15,9 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
-                    split_operand, state_fits)
+from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
+                    operand_changes, operator_producers, split_operand)
+from .groupconv import CBGroupedConv2d
 
 _AFFINE = ('gamma', 'beta')
 _SOFTMAX = {nn.Softmax2d: _lib.CH_SOFTMAX, nn.Softmax: _lib.CH_SOFTMAX, nn.LogSoftmax: _lib.CH_LOGSOFTMAX}
@@ -113,18 +114,11 @@ class CBChannelReduce2d(CBStateModule):
 
     def _workspace(self, nc, H, W, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer and count: once per map size."""
-        key = (nc, H, W, dev)
-        work = self.__dict__.get('_chWork')
-        if work is None or work['key'] != key:
-            work = self.__dict__['_chWork'] = dict(mask_workspace(H, W, dev), key=key)
-        return work
+        return self._cached_work((nc, H, W, dev), lambda: mask_workspace(H, W, dev))
 
     def forward(self, inp):
         x, indexes = split_operand('CBChannelReduce2d', inp, 'the input')
-        if x.dim() != 4 or x.size(0) != 1:
-            raise CBinferError("CBChannelReduce2d: the input must be a [1, C, H, W] tensor, got %s" % (tuple(x.shape),))
-        if x.dtype not in (torch.float32, torch.float16):
-            raise CBinferError("CBChannelReduce2d: float32 and float16 tensors only, got %s" % x.dtype)
+        check_map('CBChannelReduce2d', x)
         nc, H, W = x.size(1), x.size(2), x.size(3)
         if self.gamma is not None and self.gamma.numel() != nc:
             raise CBinferError("CBChannelReduce2d: the input has %d channels, gamma was made for %d"
@@ -134,14 +128,12 @@ class CBChannelReduce2d(CBStateModule):
             raise CBinferError("CBChannelReduce2d: the input is on %s, gamma on %s (move the module with .to())"
                                % (x.device, self.gamma.device))
         work = self._workspace(nc, H, W, x.device)
-        mask, lst, cap, count = operand_changes('CBChannelReduce2d', 'the input', indexes, H, W, x.device, work['idx'])
-        if not state_fits(self.outputState, x.shape, x):
-            # a new state is written completely: the operand's change information is not used
-            self.outputState = torch.empty_like(x)
-            mask, lst, cap, count = None, None, 0, None
-        check(C.cbinfer_cbchanreduce_forward(ptr(x), ptr(self.outputState), ptr(mask), ptr(lst), cap, ptr(count),
-                                             ptr(work['bits']), ptr(work['copy']), nc, H, W, self.kind, self.eps,
-                                             ptr(self.gamma), ptr(self.beta), dtype_code(x), stream_ptr(x)))
+        form = operand_changes('CBChannelReduce2d', 'the input', indexes, H, W, x.device, work['idx'])
+        if self._fresh_state(x.shape, x):      # (written completely: the operand's change information is not used)
+            form = EVERY_PIXEL
+        check(C.cbinfer_cbchanreduce_forward(ptr(x), ptr(self.outputState), *form_args(form), ptr(work['bits']),
+                                             ptr(work['copy']), nc, H, W, self.kind, self.eps, ptr(self.gamma),
+                                             ptr(self.beta), dtype_code(x), stream_ptr(x)))
         return self._result(work, H, W)
 
     def __repr__(self):
@@ -161,28 +153,13 @@ def insertCBChannelOps(rootModule, layerNormTypes=()):
     behind a dense operator -- stays dense.  The producer tables are pinned, so linkDepthwise, insertCBPointwise,
     insertCBUpsampling, insertCBTransposedConv and the general pools do not yet take the new module as a producer.
     Returns rootModule."""
-    from .conv2d import CBConv2d
-    from .groupconv import CBGroupedConv2d
     layerNormTypes = tuple(layerNormTypes)
-    producers = operator_producers() + (CBGroupedConv2d, CBChannelReduce2d)
-    for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
-        names = list(seq._modules.keys())
-        for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
-            prod, op = seq._modules[a], seq._modules[b]
-            if type(prod) not in producers:
-                continue
-            if type(op) in _SOFTMAX:
-                if type(op) is not nn.Softmax2d and op.dim not in (1, -3):
-                    continue
-            elif type(op) not in layerNormTypes:
-                continue
-            cb = CBChannelReduce2d(op, layerNormTypes=layerNormTypes)
-            hand_on_changes(prod)
-            seq._modules[b] = cb
-            if pos + 2 < len(names):
-                consumer = seq._modules[names[pos + 2]]
-                if is_1x1(consumer):
-                    cb.propChangeIndexes = True
-                elif type(consumer) is CBConv2d and not consumer.feedbackLoop:
-                    consumer.copyInput = True
-    return rootModule
+
+    def convert(op):
+        if type(op) in _SOFTMAX:
+            if type(op) is not nn.Softmax2d and op.dim not in (1, -3):
+                return None
+        elif type(op) not in layerNormTypes:
+            return None
+        return CBChannelReduce2d(op, layerNormTypes=layerNormTypes)      # (what it refuses of a layer norm is raised)
+    return insert_behind_producers(rootModule, operator_producers() + (CBGroupedConv2d, CBChannelReduce2d), convert)

@@ -18,9 +18,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, mask_workspace, operand_changes, operator_producers,
-                    split_operand, state_fits)
-from .conv2d import CBConv2d
+from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
+                    operand_changes, operator_producers, split_operand, state_fits)
 
 MAX_SCALE = 8
 
@@ -93,31 +92,21 @@ class CBUpsample2d(CBStateModule):
 
     def _workspace(self, Hi, Wi, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer and count: once per map size."""
-        key = (Hi, Wi, dev)
-        work = self.__dict__.get('_work')
-        if work is None or work['key'] != key:
-            Ho, Wo = Hi * self.scale_factor[0], Wi * self.scale_factor[1]
-            work = self.__dict__['_work'] = dict(mask_workspace(Ho, Wo, dev), key=key, size=(Ho, Wo))
-        return work
+        Ho, Wo = Hi * self.scale_factor[0], Wi * self.scale_factor[1]
+        return self._cached_work((Hi, Wi, dev), lambda: dict(mask_workspace(Ho, Wo, dev), size=(Ho, Wo)))
 
     def forward(self, inp):
         x, indexes = split_operand('CBUpsample2d', inp, 'the input')
-        if x.dim() != 4 or x.size(0) != 1:
-            raise CBinferError("CBUpsample2d: the input must be a [1, C, H, W] tensor, got %s" % (tuple(x.shape),))
-        if x.dtype not in (torch.float32, torch.float16):
-            raise CBinferError("CBUpsample2d: float32 and float16 tensors only, got %s" % x.dtype)
+        check_map('CBUpsample2d', x)
         require_device(x)
         nc, Hi, Wi = x.size(1), x.size(2), x.size(3)
         work = self._workspace(Hi, Wi, x.device)
         Ho, Wo = work['size']
         form = operand_changes('CBUpsample2d', 'the input', indexes, Hi, Wi, x.device, work['idx'])
-        if not state_fits(self.outputState, (1, nc, Ho, Wo), x):
-            # a new state is written completely: the change information is not used
-            self.outputState = torch.empty((1, nc, Ho, Wo), dtype=x.dtype, device=x.device)
-            form = (None, None, 0, None)
-        check(C.cbinfer_cbupsample_forward(ptr(x), ptr(self.outputState), ptr(form[0]), ptr(form[1]), form[2],
-                                           ptr(form[3]), ptr(work['bits']), ptr(work['copy']), nc, Hi, Wi,
-                                           self._struct(), dtype_code(x), stream_ptr(x)))
+        if self._fresh_state((1, nc, Ho, Wo), x):      # (written completely: the change information is not used)
+            form = EVERY_PIXEL
+        check(C.cbinfer_cbupsample_forward(ptr(x), ptr(self.outputState), *form_args(form), ptr(work['bits']),
+                                           ptr(work['copy']), nc, Hi, Wi, self._struct(), dtype_code(x), stream_ptr(x)))
         return self._result(work, Ho, Wo)
 
     def __repr__(self):
@@ -145,14 +134,10 @@ class CBConcat2d(CBStateModule):
     def _workspace(self, n, H, W, dev):
         """n working masks (zero between frames), the frame's mask copy, index buffer, count and the host argument
         arrays: once per operand count and map size."""
-        key = (n, H, W, dev)
-        work = self.__dict__.get('_work')
-        if work is None or work['key'] != key:
-            work = self.__dict__['_work'] = dict(
-                mask_workspace(H, W, dev, nbits=n), key=key,
-                srcs=(ctypes.c_void_p * n)(), chans=(ctypes.c_int32 * n)(), masks=(ctypes.c_void_p * n)(),
-                lists=(ctypes.c_void_p * n)(), caps=(ctypes.c_int32 * n)(), counts=(ctypes.c_void_p * n)())
-        return work
+        return self._cached_work((n, H, W, dev), lambda: dict(
+            mask_workspace(H, W, dev, nbits=n),
+            srcs=(ctypes.c_void_p * n)(), chans=(ctypes.c_int32 * n)(), masks=(ctypes.c_void_p * n)(),
+            lists=(ctypes.c_void_p * n)(), caps=(ctypes.c_int32 * n)(), counts=(ctypes.c_void_p * n)()))
 
     def forward(self, operands):
         if not isinstance(operands, (list, tuple)) or (type(operands) == tuple and operands[:1] == ('changeIndexes',)):
@@ -182,10 +167,10 @@ class CBConcat2d(CBStateModule):
             # a new state is written completely: no operand's change information is used
             self.outputState = torch.empty((1, sum(chans), H, W), dtype=t0.dtype, device=t0.device)
             self.__dict__['_channels'] = chans
-            forms = [(None, None, 0, None)] * n
+            forms = [EVERY_PIXEL] * n
         for k, ((t, _), f) in enumerate(zip(split, forms)):
             work['srcs'][k], work['chans'][k] = t.data_ptr(), chans[k]
-            work['masks'][k], work['lists'][k], work['caps'][k], work['counts'][k] = ptr(f[0]), ptr(f[1]), f[2], ptr(f[3])
+            work['masks'][k], work['lists'][k], work['caps'][k], work['counts'][k] = form_args(f)
         check(C.cbinfer_cbconcat_forward(work['srcs'], work['chans'], n, ptr(self.outputState), work['masks'],
                                          work['lists'], work['caps'], work['counts'], ptr(work['bits']),
                                          ptr(work['copy']), H, W, dtype_code(t0), stream_ptr(t0)))
@@ -200,30 +185,16 @@ _UPSAMPLERS = (nn.Upsample, nn.UpsamplingNearest2d, nn.UpsamplingBilinear2d)
 
 def insertCBUpsampling(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.Upsample / nn.UpsamplingNearest2d / nn.UpsamplingBilinear2d within
-    the library's limits that directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBPixelShuffle2d,
-    CBChannelShuffle2d, CBResize2d, CBPad2d or another CBUpsample2d (chain.operator_producers) becomes a CBUpsample2d fed by that
-    producer's changes: propChangeIndexes
-    is switched on at the producer
-    (a CBResidual's `.add`; a 2x2 CBPoolMax2d of the reference's kind also hands on the OUTPUT-resolution list,
-    downsampleIndexes).  A CBConv2d consuming the upsampled map then needs its own input copy (copyInput) unless it runs
-    in feedback mode, as behind a pool of insertCBPooling.  An upsampling beyond the limits stays the dense torch
-    operator.  Returns rootModule."""
-    for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
-        names = list(seq._modules.keys())
-        for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
-            prod, up = seq._modules[a], seq._modules[b]
-            if (type(prod) not in operator_producers(forUpsampling=True) or
-                    type(up) not in _UPSAMPLERS):
-                continue
-            try:
-                cb = CBUpsample2d(up)
-            except CBinferError:
-                continue      # (beyond the limits: stays dense)
-            hand_on_changes(prod)
-            cb.cloneOutput = cloneOutput
-            seq._modules[b] = cb
-            if pos + 2 < len(names):
-                consumer = seq._modules[names[pos + 2]]
-                if type(consumer) == CBConv2d and not consumer.feedbackLoop:
-                    consumer.copyInput = True
-    return rootModule
+    the library's limits that directly follows a producer -- chain.operator_producers(forUpsampling=True), another
+    CBUpsample2d among them and a CBConvTranspose2d not -- becomes a CBUpsample2d fed by that producer's changes:
+    propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new module hands nothing on: a
+    CBConv2d consuming the upsampled map, a 1x1 layer included, needs its own input copy (copyInput) unless it runs in
+    feedback mode, as behind a pool of insertCBPooling.  An upsampling beyond the limits stays the dense torch operator.
+    Returns rootModule."""
+    def convert(up):
+        try:
+            return CBUpsample2d(up) if type(up) in _UPSAMPLERS else None
+        except CBinferError:
+            return None      # (beyond the limits: stays dense)
+    return insert_behind_producers(rootModule, operator_producers(forUpsampling=True), convert, cloneOutput=cloneOutput,
+                                   handOn=False)

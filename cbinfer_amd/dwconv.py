@@ -132,12 +132,11 @@ class CBDepthwiseConv2d(CBDetectingLayer):
 
 def linkDepthwise(rootModule):
     """Inside every nn.Sequential of rootModule: a CBDepthwiseConv2d with dilation 1 and padding <= kernel_size / 2 that
-    directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBConvTranspose2d,
-    CBPixelShuffle2d, CBChannelShuffle2d or another CBDepthwiseConv2d takes that producer's changes (propagatedChanges
-    on the layer, propChangeIndexes on the producer)
-    and runs no detection; a CBDepthwiseConv2d directly in front of a 1x1 / stride-1 / padding-0 CBConv2d hands its
-    changes on (propChangeIndexes).  Returns rootModule."""
-    for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
+    directly follows a producer -- chain.operator_producers(), another CBDepthwiseConv2d among them -- takes that
+    producer's changes (propagatedChanges on the layer, propChangeIndexes on the producer: chain.hand_on_changes) and
+    runs no detection; a CBDepthwiseConv2d directly in front of a 1x1 / stride-1 / padding-0 CBConv2d hands its changes
+    on (propChangeIndexes).  Returns rootModule."""
+    for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
         kids = list(seq.children())
         for prod, cons in zip(kids[:-1], kids[1:]):
             if (type(cons) is CBDepthwiseConv2d and type(prod) in operator_producers() and

@@ -14,8 +14,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, stream_ptr
-from .chain import hand_back, is_1x1
-from .conv2d import CBConv2d, _padding_pair
+from .chain import hand_back, link_consumer
+from .conv2d import _padding_pair
 from .layer import CBContractingLayer, check_limits
 
 MAX_K, MAX_S, MAX_D, MAX_P = 7, 4, 8, 64
@@ -93,13 +93,9 @@ def linkGrouped(rootModule):
     """Inside every nn.Sequential of rootModule: a CBGroupedConv2d directly in front of a 1x1 / stride-1 / padding-0
     CBConv2d hands its changes on (propChangeIndexes); any other CBConv2d directly behind a CBGroupedConv2d needs its own
     input copy (copyInput) unless it runs in feedback mode.  Returns rootModule."""
-    for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
+    for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
         kids = list(seq.children())
         for prod, cons in zip(kids[:-1], kids[1:]):
-            if type(prod) is not CBGroupedConv2d:
-                continue
-            if is_1x1(cons):
-                prod.propChangeIndexes = True
-            elif type(cons) is CBConv2d and not cons.feedbackLoop:
-                cons.copyInput = True
+            if type(prod) is CBGroupedConv2d:
+                link_consumer(prod, cons)
     return rootModule

@@ -19,8 +19,10 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
-                    split_operand, state_fits)
+from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
+                    operand_changes, operator_producers, split_operand)
+from .chanreduce import CBChannelReduce2d
+from .groupconv import CBGroupedConv2d
 
 MAX_PAD = 64      # per side, either sign: cbGeom's padding bound
 MODES = {'constant': _lib.PAD_CONSTANT, 'reflect': _lib.PAD_REFLECT, 'replicate': _lib.PAD_REPLICATE,
@@ -118,19 +120,14 @@ class CBPad2d(CBStateModule):
     def _workspace(self, nc, H, W, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer and count on the OUTPUT map: once per
         input shape."""
-        key = (nc, H, W, dev)
-        work = self.__dict__.get('_work')
-        if work is None or work['key'] != key:
+        def make():
             Ho, Wo = self.out_size(H, W)
-            work = self.__dict__['_work'] = dict(mask_workspace(Ho, Wo, dev), key=key, size=(Ho, Wo))
-        return work
+            return dict(mask_workspace(Ho, Wo, dev), size=(Ho, Wo))
+        return self._cached_work((nc, H, W, dev), make)
 
     def forward(self, inp):
         x, indexes = split_operand('CBPad2d', inp, 'the input')
-        if x.dim() != 4 or x.size(0) != 1:
-            raise CBinferError("CBPad2d: the input must be a [1, C, H, W] tensor (batch 1), got %s" % (tuple(x.shape),))
-        if x.dtype not in (torch.float32, torch.float16):
-            raise CBinferError("CBPad2d: float32 and float16 tensors only, got %s" % x.dtype)
+        check_map('CBPad2d', x, note=' (batch 1)')
         nc, H, W = x.size(1), x.size(2), x.size(3)
         if self.mode == 'constant' and math.isfinite(self.value) and abs(self.value) > _FINITE_MAX[x.dtype]:
             raise CBinferError("CBPad2d: value=%r of a %dx%d %s map overflows the tensor's dtype"
@@ -139,13 +136,10 @@ class CBPad2d(CBStateModule):
         work = self._workspace(nc, H, W, x.device)
         Ho, Wo = work['size']
         form = operand_changes('CBPad2d', 'the input', indexes, H, W, x.device, work['idx'])
-        if not state_fits(self.outputState, (1, nc, Ho, Wo), x):
-            # a new state is written completely: the change information is not used
-            self.outputState = torch.empty((1, nc, Ho, Wo), dtype=x.dtype, device=x.device)
-            form = (None, None, 0, None)
-        check(C.cbinfer_cbpad_forward(ptr(x), ptr(self.outputState), ptr(form[0]), ptr(form[1]), form[2], ptr(form[3]),
-                                      ptr(work['bits']), ptr(work['copy']), nc, H, W, self._struct(), dtype_code(x),
-                                      stream_ptr(x)))
+        if self._fresh_state((1, nc, Ho, Wo), x):      # (written completely: the change information is not used)
+            form = EVERY_PIXEL
+        check(C.cbinfer_cbpad_forward(ptr(x), ptr(self.outputState), *form_args(form), ptr(work['bits']),
+                                      ptr(work['copy']), nc, H, W, self._struct(), dtype_code(x), stream_ptr(x)))
         return self._result(work, Ho, Wo)
 
     def __repr__(self):
@@ -203,16 +197,6 @@ def splitConvPadding(rootModule):
     return rootModule
 
 
-def _converted(m):
-    """The CBPad2d for `m`, or None: not one of the five pad modules, or beyond the limits."""
-    if type(m) not in PAD_MODULES:
-        return None
-    try:
-        return CBPad2d(m)
-    except CBinferError:
-        return None      # (beyond the limits: stays dense)
-
-
 def insertCBPadding(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.ReflectionPad2d, nn.ReplicationPad2d, nn.ZeroPad2d,
     nn.ConstantPad2d or nn.CircularPad2d within the library's limits that directly follows a producer --
@@ -222,24 +206,10 @@ def insertCBPadding(rootModule, cloneOutput=True):
     CBConv2d directly behind it needs its own input copy (copyInput) unless it runs in feedback mode.  A module beyond the
     limits, or behind anything else -- a pad at the front of a network has no producer; build a CBPad2d stem by hand --,
     stays the dense torch operator; the limits that depend on the map show at the first frame.  Returns rootModule."""
-    from .chanreduce import CBChannelReduce2d
-    from .conv2d import CBConv2d
-    from .groupconv import CBGroupedConv2d
-    producers = operator_producers() + (CBGroupedConv2d, CBChannelReduce2d)
-    for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
-        names = list(seq._modules.keys())
-        for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
-            prod = seq._modules[a]
-            cb = _converted(seq._modules[b]) if type(prod) in producers else None
-            if cb is None:
-                continue
-            hand_on_changes(prod)
-            cb.cloneOutput = cloneOutput
-            seq._modules[b] = cb
-            if pos + 2 < len(names):
-                consumer = seq._modules[names[pos + 2]]
-                if is_1x1(consumer):
-                    cb.propChangeIndexes = True
-                elif type(consumer) is CBConv2d and not consumer.feedbackLoop:
-                    consumer.copyInput = True
-    return rootModule
+    def convert(m):
+        try:
+            return CBPad2d(m) if type(m) in PAD_MODULES else None
+        except CBinferError:
+            return None      # (beyond the limits: stays dense)
+    return insert_behind_producers(rootModule, operator_producers() + (CBGroupedConv2d, CBChannelReduce2d), convert,
+                                   cloneOutput=cloneOutput)

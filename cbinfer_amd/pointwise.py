@@ -12,8 +12,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
-                    split_operand, state_fits)
+from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, hand_on_changes, is_1x1, mask_workspace,
+                    operand_changes, operator_producers, split_operand)
 
 # nn type (exactly, not a subclass) -> (CB_PW_* kind, p0, p1 of the instance)
 _ACTIVATIONS = {
@@ -111,21 +111,16 @@ class CBPointwise2d(CBStateModule):
     def _workspace(self, nc, H, W, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer and count, the slope of a
         one-parameter PReLU broadcast over the channels: once per map size."""
-        key = (nc, H, W, dev)
-        work = self.__dict__.get('_pwWork')
-        if work is None or work['key'] != key:
+        def make():
             slope = self.slope
             if slope is not None and slope.numel() == 1 and nc != 1:
                 slope = slope.expand(nc).contiguous()
-            work = self.__dict__['_pwWork'] = dict(mask_workspace(H, W, dev), key=key, slope=slope)
-        return work
+            return dict(mask_workspace(H, W, dev), slope=slope)
+        return self._cached_work((nc, H, W, dev), make)
 
     def forward(self, inp):
         x, indexes = split_operand('CBPointwise2d', inp, 'the input')
-        if x.dim() != 4 or x.size(0) != 1:
-            raise CBinferError("CBPointwise2d: the input must be a [1, C, H, W] tensor, got %s" % (tuple(x.shape),))
-        if x.dtype not in (torch.float32, torch.float16):
-            raise CBinferError("CBPointwise2d: float32 and float16 tensors only, got %s" % x.dtype)
+        check_map('CBPointwise2d', x)
         nc, H, W = x.size(1), x.size(2), x.size(3)
         for name in _PER_CHANNEL:
             t = getattr(self, name)
@@ -139,13 +134,11 @@ class CBPointwise2d(CBStateModule):
                 raise CBinferError("CBPointwise2d: the input is on %s, %s on %s (move the module with .to())"
                                    % (x.device, name, t.device))
         work = self._workspace(nc, H, W, x.device)
-        mask, lst, cap, count = operand_changes('CBPointwise2d', 'the input', indexes, H, W, x.device, work['idx'])
-        if not state_fits(self.outputState, x.shape, x):
-            # a new state is written completely: the operand's change information is not used
-            self.outputState = torch.empty_like(x)
-            mask, lst, cap, count = None, None, 0, None
-        check(C.cbinfer_cbpointwise_forward(ptr(x), ptr(self.outputState), ptr(mask), ptr(lst), cap, ptr(count),
-                                            ptr(work['bits']), ptr(work['copy']), nc, H, W, self.kind, self.p0, self.p1,
+        form = operand_changes('CBPointwise2d', 'the input', indexes, H, W, x.device, work['idx'])
+        if self._fresh_state(x.shape, x):      # (written completely: the operand's change information is not used)
+            form = EVERY_PIXEL
+        check(C.cbinfer_cbpointwise_forward(ptr(x), ptr(self.outputState), *form_args(form), ptr(work['bits']),
+                                            ptr(work['copy']), nc, H, W, self.kind, self.p0, self.p1,
                                             ptr(self.scale), ptr(self.shift), ptr(work['slope']), dtype_code(x),
                                             stream_ptr(x)))
         return self._result(work, H, W)
@@ -157,11 +150,9 @@ class CBPointwise2d(CBStateModule):
 
 def insertCBPointwise(rootModule):
     """Inside every nn.Sequential of rootModule, a run  [nn.BatchNorm2d] [activation]  (at least one of the two; the
-    activations of CBPointwise2d) that directly follows a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual,
-    CBUpsample2d, CBConvTranspose2d, CBDepthwiseConv2d, CBPixelShuffle2d, CBChannelShuffle2d or another CBPointwise2d
-    becomes ONE CBPointwise2d under the run's
-    first name, fed by that producer's changes: propChangeIndexes is switched on at the producer (a CBResidual's `.add`;
-    a 2x2 CBPoolMax2d of the reference's kind also hands on the OUTPUT-resolution list, downsampleIndexes).  The new
+    activations of CBPointwise2d) that directly follows a producer -- chain.operator_producers(), another CBPointwise2d
+    among them -- becomes ONE CBPointwise2d under the run's first name, fed by that producer's changes:
+    propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new
     module hands its own changes on (propChangeIndexes) only where it stands directly in front of a 1x1 / stride-1 /
     padding-0 CBConv2d -- a k x k CBConv2d that is handed indexes skips its own detection, which would be wrong here;
     linkDepthwise, insertCBUpsampling, insertCBTransposedConv and insertCBPooling(generalGeometry=True), called

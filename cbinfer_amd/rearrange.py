@@ -10,14 +10,12 @@ without a threshold.
 """
 import ctypes
 
-import torch
 import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
-                    split_operand, state_fits)
-from .conv2d import CBConv2d
+from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
+                    operand_changes, operator_producers, split_operand)
 from .groupconv import CBGroupedConv2d
 
 MAX_FACTOR = 8      # of the two pixel shuffles: CBUpsample2d's scale limit
@@ -68,32 +66,24 @@ class _CBRearrange2d(CBStateModule):
     def _workspace(self, nc, Hi, Wi, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer and count on the OUTPUT map: once per
         input shape."""
-        key = (nc, Hi, Wi, dev)
-        work = self.__dict__.get('_work')
-        if work is None or work['key'] != key:
+        def make():
             Co, Ho, Wo = self._out_shape(nc, Hi, Wi)
-            work = self.__dict__['_work'] = dict(mask_workspace(Ho, Wo, dev), key=key, shape=(Co, Ho, Wo))
-        return work
+            return dict(mask_workspace(Ho, Wo, dev), shape=(Co, Ho, Wo))
+        return self._cached_work((nc, Hi, Wi, dev), make)
 
     def forward(self, inp):
         x, indexes = split_operand(self.NAME, inp, 'the input')
-        if x.dim() != 4 or x.size(0) != 1:
-            raise CBinferError("%s: the input must be a [1, C, H, W] tensor, got %s" % (self.NAME, tuple(x.shape)))
-        if x.dtype not in (torch.float32, torch.float16):
-            raise CBinferError("%s: float32 and float16 tensors only, got %s" % (self.NAME, x.dtype))
+        check_map(self.NAME, x)
         nc, Hi, Wi = x.size(1), x.size(2), x.size(3)
         self._check_sizes(nc, Hi, Wi)
         require_device(x)
         work = self._workspace(nc, Hi, Wi, x.device)
         Co, Ho, Wo = work['shape']
         form = operand_changes(self.NAME, 'the input', indexes, Hi, Wi, x.device, work['idx'])
-        if not state_fits(self.outputState, (1, Co, Ho, Wo), x):
-            # a new state is written completely: the change information is not used
-            self.outputState = torch.empty((1, Co, Ho, Wo), dtype=x.dtype, device=x.device)
-            form = (None, None, 0, None)
-        check(C.cbinfer_cbrearrange_forward(ptr(x), ptr(self.outputState), ptr(form[0]), ptr(form[1]), form[2],
-                                            ptr(form[3]), ptr(work['bits']), ptr(work['copy']), nc, Hi, Wi,
-                                            self._struct(), dtype_code(x), stream_ptr(x)))
+        if self._fresh_state((1, Co, Ho, Wo), x):      # (written completely: the change information is not used)
+            form = EVERY_PIXEL
+        check(C.cbinfer_cbrearrange_forward(ptr(x), ptr(self.outputState), *form_args(form), ptr(work['bits']),
+                                            ptr(work['copy']), nc, Hi, Wi, self._struct(), dtype_code(x), stream_ptr(x)))
         return self._result(work, Ho, Wo)
 
 
@@ -153,18 +143,6 @@ class CBChannelShuffle2d(_CBRearrange2d):
         return 'CBChannelShuffle2d (groups=%d, propChgIdxs=%s)' % (self.factor, self.propChangeIndexes)
 
 
-def _converted(m):
-    """The change-based module for `m`, or None: not one of the three operators, or beyond the limits."""
-    try:
-        if type(m) in (nn.PixelShuffle, nn.PixelUnshuffle):
-            return CBPixelShuffle2d(m)
-        if type(m) is nn.ChannelShuffle:
-            return CBChannelShuffle2d(m)
-    except CBinferError:
-        pass      # (beyond the limits: stays dense)
-    return None
-
-
 def insertCBRearrange(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.PixelShuffle, nn.PixelUnshuffle or nn.ChannelShuffle within the
     library's limits that directly follows a producer -- chain.operator_producers(), a CBGroupedConv2d, or another
@@ -174,21 +152,14 @@ def insertCBRearrange(rootModule, cloneOutput=True):
     needs its own input copy (copyInput) unless it runs in feedback mode.  linkDepthwise, insertCBPointwise,
     insertCBUpsampling and insertCBTransposedConv, called afterwards, take the new modules as producers.  A module beyond
     the limits, or behind anything else, stays the dense torch operator.  Returns rootModule."""
-    producers = operator_producers() + (CBGroupedConv2d,)
-    for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
-        names = list(seq._modules.keys())
-        for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
-            prod = seq._modules[a]
-            cb = _converted(seq._modules[b]) if type(prod) in producers else None
-            if cb is None:
-                continue
-            hand_on_changes(prod)
-            cb.cloneOutput = cloneOutput
-            seq._modules[b] = cb
-            if pos + 2 < len(names):
-                consumer = seq._modules[names[pos + 2]]
-                if is_1x1(consumer):
-                    cb.propChangeIndexes = True
-                elif type(consumer) == CBConv2d and not consumer.feedbackLoop:
-                    consumer.copyInput = True
-    return rootModule
+    def convert(m):
+        try:
+            if type(m) in (nn.PixelShuffle, nn.PixelUnshuffle):
+                return CBPixelShuffle2d(m)
+            if type(m) is nn.ChannelShuffle:
+                return CBChannelShuffle2d(m)
+        except CBinferError:
+            pass      # (beyond the limits: stays dense)
+        return None
+    return insert_behind_producers(rootModule, operator_producers() + (CBGroupedConv2d,), convert,
+                                   cloneOutput=cloneOutput)

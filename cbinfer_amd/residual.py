@@ -11,7 +11,8 @@ import torch
 import torch.nn as nn
 
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import OPERAND_WORDS, CBStateModule, mask_workspace, operand_changes, split_operand, state_fits
+from .chain import (EVERY_PIXEL, OPERAND_WORDS, CBStateModule, form_args, mask_workspace, operand_changes,
+                    split_operand)
 from .conv2d import CBConv2d
 
 
@@ -38,11 +39,7 @@ class CBAdd2d(CBStateModule):
 
     def _workspace(self, H, W, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer and count: once per map size."""
-        key = (H, W, dev)
-        work = self.__dict__.get('_addWork')
-        if work is None or work['key'] != key:
-            work = self.__dict__['_addWork'] = dict(mask_workspace(H, W, dev), key=key)
-        return work
+        return self._cached_work((H, W, dev), lambda: mask_workspace(H, W, dev))
 
     def forward(self, a, b):
         a, ia = split_operand('CBAdd2d', a, 'operand a')
@@ -58,13 +55,11 @@ class CBAdd2d(CBStateModule):
         # (a list the producer's kernel already made is taken before its mask)
         fa, fb = (operand_changes('CBAdd2d', 'operand ' + which, ix, H, W, a.device, work['idx'], words=_ADD_WORDS,
                                   maskWhenMade=False) for which, ix in (('a', ia), ('b', ib)))
-        if not state_fits(self.outputState, a.shape, a):
-            # a new state is written completely: neither operand's change information is used
-            self.outputState = torch.empty_like(a)
-            fa = fb = (None, None, 0, None)
-        check(C.cbinfer_cbadd_forward(ptr(a), ptr(b), ptr(self.outputState), ptr(fa[0]), ptr(fa[1]), fa[2], ptr(fa[3]),
-                                      ptr(fb[0]), ptr(fb[1]), fb[2], ptr(fb[3]), ptr(work['bits']), ptr(work['copy']),
-                                      nc, H, W, int(self.relu), dtype_code(a), stream_ptr(a)))
+        if self._fresh_state(a.shape, a):      # (written completely: neither operand's change information is used)
+            fa = fb = EVERY_PIXEL
+        check(C.cbinfer_cbadd_forward(ptr(a), ptr(b), ptr(self.outputState), *form_args(fa), *form_args(fb),
+                                      ptr(work['bits']), ptr(work['copy']), nc, H, W, int(self.relu), dtype_code(a),
+                                      stream_ptr(a)))
         return self._result(work, H, W)
 
     def __repr__(self):

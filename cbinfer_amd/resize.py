@@ -21,8 +21,10 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
-from .chain import (CBStateModule, hand_on_changes, is_1x1, mask_workspace, operand_changes, operator_producers,
-                    split_operand, state_fits)
+from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
+                    operand_changes, operator_producers, split_operand)
+from .chanreduce import CBChannelReduce2d
+from .groupconv import CBGroupedConv2d
 
 MAX_RATIO = 8          # per axis, either way
 MAX_TERM = 4096        # numerator and denominator of the reduced step
@@ -140,33 +142,26 @@ class CBResize2d(CBStateModule):
     def _workspace(self, Hi, Wi, size, dev):
         """Working mask (zero between frames), the frame's mask copy, index buffer, count and the cbResize: once per map
         and output size."""
-        key = (Hi, Wi, size, dev)
-        work = self.__dict__.get('_work')
-        if work is None or work['key'] != key:
+        def make():
             geo = self.geometry(Hi, Wi, size)
             rs = _lib.Resize(*(geo + (MODES[self.mode], int(self.align_corners))))
             self.__dict__['_rsC'] = ctypes.pointer(rs)
-            work = self.__dict__['_work'] = dict(mask_workspace(geo[0], geo[1], dev), key=key, size=geo[:2])
-        return work
+            return dict(mask_workspace(geo[0], geo[1], dev), size=geo[:2])
+        return self._cached_work((Hi, Wi, size, dev), make)
 
     def forward(self, inp, size=None):
         x, indexes = split_operand('CBResize2d', inp, 'the input')
-        if x.dim() != 4 or x.size(0) != 1:
-            raise CBinferError("CBResize2d: the input must be a [1, C, H, W] tensor (batch 1), got %s" % (tuple(x.shape),))
-        if x.dtype not in (torch.float32, torch.float16):
-            raise CBinferError("CBResize2d: float32 and float16 tensors only, got %s" % x.dtype)
+        check_map('CBResize2d', x, note=' (batch 1)')
         require_device(x)
         nc, Hi, Wi = x.size(1), x.size(2), x.size(3)
         work = self._workspace(Hi, Wi, None if size is None else _pair('size', size, int), x.device)
         Ho, Wo = work['size']
         form = operand_changes('CBResize2d', 'the input', indexes, Hi, Wi, x.device, work['idx'])
-        if not state_fits(self.outputState, (1, nc, Ho, Wo), x):
-            # a new state is written completely: the change information is not used
-            self.outputState = torch.empty((1, nc, Ho, Wo), dtype=x.dtype, device=x.device)
-            form = (None, None, 0, None)
-        check(C.cbinfer_cbresize_forward(ptr(x), ptr(self.outputState), ptr(form[0]), ptr(form[1]), form[2],
-                                         ptr(form[3]), ptr(work['bits']), ptr(work['copy']), nc, Hi, Wi,
-                                         self.__dict__['_rsC'], dtype_code(x), stream_ptr(x)))
+        if self._fresh_state((1, nc, Ho, Wo), x):      # (written completely: the change information is not used)
+            form = EVERY_PIXEL
+        check(C.cbinfer_cbresize_forward(ptr(x), ptr(self.outputState), *form_args(form), ptr(work['bits']),
+                                         ptr(work['copy']), nc, Hi, Wi, self.__dict__['_rsC'], dtype_code(x),
+                                         stream_ptr(x)))
         return self._result(work, Ho, Wo)
 
     def __repr__(self):
@@ -187,27 +182,10 @@ def insertCBResize(rootModule, cloneOutput=True):
     producer's mask the two kernels are level for nearest and this one is about 20 % faster for bilinear; with a change
     LIST nearest costs about 20 % more here, because the general candidate range tests more rows per entry.  Where that
     matters call insertCBUpsampling FIRST: this pass then takes only what that one left.  Returns rootModule."""
-    from .chanreduce import CBChannelReduce2d
-    from .conv2d import CBConv2d
-    from .groupconv import CBGroupedConv2d
-    producers = operator_producers(forUpsampling=True) + (CBGroupedConv2d, CBChannelReduce2d)
-    for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
-        names = list(seq._modules.keys())
-        for pos, (a, b) in enumerate(zip(names[:-1], names[1:])):
-            prod, up = seq._modules[a], seq._modules[b]
-            if type(prod) not in producers or type(up) not in _UPSAMPLERS:
-                continue
-            try:
-                cb = CBResize2d(up)
-            except CBinferError:
-                continue      # (beyond the limits: stays dense)
-            hand_on_changes(prod)
-            cb.cloneOutput = cloneOutput
-            seq._modules[b] = cb
-            if pos + 2 < len(names):
-                consumer = seq._modules[names[pos + 2]]
-                if is_1x1(consumer):
-                    cb.propChangeIndexes = True
-                elif type(consumer) is CBConv2d and not consumer.feedbackLoop:
-                    consumer.copyInput = True
-    return rootModule
+    def convert(up):
+        try:
+            return CBResize2d(up) if type(up) in _UPSAMPLERS else None
+        except CBinferError:
+            return None      # (beyond the limits: stays dense)
+    return insert_behind_producers(rootModule, operator_producers(forUpsampling=True) +
+                                   (CBGroupedConv2d, CBChannelReduce2d), convert, cloneOutput=cloneOutput)

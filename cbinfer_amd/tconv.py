@@ -14,8 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, stream_ptr
-from .chain import hand_back, operator_producers
-from .conv2d import CBConv2d
+from .chain import hand_back, link_consumer, operator_producers
 from .layer import CBContractingLayer, check_limits
 
 MAX_K, MAX_S, MAX_D = 8, 4, 4
@@ -108,13 +107,12 @@ class CBConvTranspose2d(CBContractingLayer):
 
 def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.ConvTranspose2d within the library's limits that directly follows
-    a CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBPixelShuffle2d, CBChannelShuffle2d,
-    CBResize2d, CBPad2d or another CBConvTranspose2d (chain.operator_producers) becomes a
-    CBConvTranspose2d with `threshold` (it runs its own change detection: nothing is switched on at the producer).  An
-    nn.ReLU right behind it is absorbed (withReLU).  A CBConv2d consuming the output then needs its own input copy
-    (copyInput) unless it runs in feedback mode.  A module beyond the limits stays the dense torch operator.  Returns
-    rootModule."""
-    for seq in [m for m in rootModule.modules() if type(m) == nn.Sequential]:
+    a producer -- chain.operator_producers(), another CBConvTranspose2d among them -- becomes a CBConvTranspose2d with
+    `threshold` (it runs its own change detection: nothing is switched on at the producer).  An nn.ReLU right behind it
+    is absorbed (withReLU).  A CBConv2d consuming the output then needs its own input copy (copyInput) unless it runs in
+    feedback mode (chain.link_consumer; the layer hands nothing on by itself).  A module beyond the limits stays the
+    dense torch operator.  Returns rootModule."""
+    for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
         names = list(seq._modules.keys())
         gone = set()
         for pos in range(1, len(names)):
@@ -135,9 +133,7 @@ def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
                 gone.add(names[nxt])
                 nxt += 1
             if nxt < len(names):
-                consumer = seq._modules[names[nxt]]
-                if type(consumer) == CBConv2d and not consumer.feedbackLoop:
-                    consumer.copyInput = True
+                link_consumer(cb, seq._modules[names[nxt]], handOn=False)
         for name in gone:
             del seq._modules[name]
     return rootModule
