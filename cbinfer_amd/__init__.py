@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib                      # loads libcbinfer_hip.so; raises ImportError if not built
+from . import chain
 from .conv2d import CBConv2d
 from .conv2d import CBPoolMax2d
 from .conv2d import CBPoolAvg2d
@@ -163,7 +164,7 @@ def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
     then needs its own input copy (copyInput) unless it runs in feedback mode.  generalGeometry=True: every
     nn.MaxPool2d and nn.AvgPool2d within the library's limits (CBPoolMax2d(m, generalGeometry=True), CBPoolAvg2d) is
     converted, also directly behind a CBPointwise2d or a CBPad2d (the general pools take their mask); a pool beyond them
-    stays the dense torch operator.  Returns rootModule."""
+    stays the dense torch operator.  Both sets are rows of chain.producers().  Returns rootModule."""
     def _pair(v):
         return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
@@ -183,12 +184,12 @@ def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
             return CBPoolMax2d(pool)
         return None
 
+    producers = chain.producers('insertCBPooling(generalGeometry=True)' if generalGeometry else 'insertCBPooling')
     for seq in _sequentials(rootModule):
         names = list(seq._modules.keys())
         for a, b in zip(names[:-1], names[1:]):
             conv, pool = seq._modules[a], seq._modules[b]
-            cb = _converted(pool) if (type(conv) == CBConv2d or
-                                      (generalGeometry and type(conv) in (CBPointwise2d, CBPad2d))) else None
+            cb = _converted(pool) if type(conv) in producers else None
             if cb is not None:
                 _log('change-based pooling after %s' % a)
                 conv.propChangeIndexes = True

@@ -16,9 +16,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, require_device, stream_ptr
 from .chain import (EVERY_PIXEL, OPERAND_WORDS, CBStateModule, check_map, form_args, insert_behind_producers,
-                    mask_workspace, operand_changes, operator_producers, split_operand)
-from .chanreduce import CBChannelReduce2d
-from .groupconv import CBGroupedConv2d
+                    mask_workspace, operand_changes, producers, split_operand)
 from .residual import _sequential
 
 _OPS = {'add': _lib.BIN_ADD, 'sub': _lib.BIN_SUB, 'mul': _lib.BIN_MUL, 'maximum': _lib.BIN_MAXIMUM,
@@ -243,7 +241,7 @@ class CBGated(nn.Module):
 
 def insertCBGating(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.GLU over the channels (exactly that type, dim 1 or -3) that
-    directly follows a producer -- chain.operator_producers(), a CBGroupedConv2d or a CBChannelReduce2d -- becomes a
+    directly follows a producer -- chain.producers('insertCBGating') -- becomes a
     CBGLU2d under its name, fed by that producer's changes: propChangeIndexes is switched on at the producer
     (chain.hand_on_changes).  The new module hands its own changes on where it stands directly in front of a 1x1 /
     stride-1 / padding-0 CBConv2d; any other CBConv2d directly behind it needs its own input copy (copyInput) unless it
@@ -254,5 +252,4 @@ def insertCBGating(rootModule, cloneOutput=True):
             return CBGLU2d(glu) if type(glu) is nn.GLU else None
         except CBinferError:
             return None      # (over another dim: stays dense)
-    return insert_behind_producers(rootModule, operator_producers() + (CBGroupedConv2d, CBChannelReduce2d), convert,
-                                   cloneOutput=cloneOutput)
+    return insert_behind_producers(rootModule, producers('insertCBGating'), convert, cloneOutput=cloneOutput)

@@ -7,12 +7,13 @@ hand-back of every mask-driven module, and CBStateModule, which CBAdd2d, CBPoint
 shuffles, CBChannelReduce2d, CBResize2d, CBPad2d, CBBinary2d and CBGLU2d derive from: the flags, the keyed workspace
 cache (_cached_work) and the state step (_fresh_state).
 
-The passes: the ONE table of the modules that count as a producer (with its later additions in a second one,
-later_producer_types, and what the passes accept on top of both, chain_producers, pass_producers and
-operator_producers), what is switched on at a producer (hand_on_changes) and at the module behind a new one
-(link_consumer), and the ONE walk that puts an operator behind its producers (insert_behind_producers).
+The passes: the ONE table that says which module type counts as a producer for which pass (PRODUCERS, one row per
+module type of the package, the exceptions as data) and its accessor (producers(passName)), what is switched on at a
+producer (hand_on_changes) and at the module behind a new one (link_consumer), and the ONE walk that puts an operator
+behind its producers (insert_behind_producers).
 """
 import functools
+import importlib
 
 import torch
 import torch.nn as nn
@@ -182,57 +183,57 @@ class CBStateModule(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------- producers
-@functools.lru_cache(maxsize=None)
-def producer_types(forUpsampling=False):
-    """The module types (exactly, not a subclass) that leave every pixel outside their change list bit for bit as it
-    was and can hand that list on: what linkDepthwise, insertCBPointwise and insertCBTransposedConv accept in front of
-    their module.  CBConcat2d is none: its forward takes a list of operands and never stands in an nn.Sequential.
-    forUpsampling: insertCBUpsampling's set -- the same but for CBConvTranspose2d, which it has never accepted."""
-    from .conv2d import CBConv2d, CBPoolAvg2d, CBPoolMax2d
-    from .decoder import CBUpsample2d
-    from .dwconv import CBDepthwiseConv2d
-    from .pointwise import CBPointwise2d
-    from .residual import CBAdd2d, CBResidual
-    from .tconv import CBConvTranspose2d
-    types = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBAdd2d, CBResidual, CBUpsample2d, CBConvTranspose2d,
-             CBDepthwiseConv2d, CBPointwise2d)
-    return tuple(t for t in types if not (forUpsampling and t is CBConvTranspose2d))
+_POOLS = ('insertCBPooling', 'insertCBPooling(generalGeometry=True)')
+PASSES = ('linkDepthwise', 'insertCBPointwise', 'insertCBTransposedConv', 'insertCBUpsampling', 'insertCBRearrange',
+          'insertCBChannelOps', 'insertCBPadding', 'insertCBGating', 'insertCBResize') + _POOLS
+
+# THE table of the producers: one row per module type of the package -- (type, its module, rule, passes) --, which says
+# in front of which passes' operator the type (exactly, not a subclass) counts as a producer: one that leaves every pixel
+# outside its change list bit for bit as it was and can hand that list on.  BUT: every pass of PASSES but these; ONLY:
+# these and no other.  The order of the rows is the order of every set.
+BUT, ONLY = 'all passes but', 'only'
+PRODUCERS = (
+    ('CBConv2d', 'conv2d', BUT, ()),
+    # (insertCBPooling is the reference's hand-written rule: behind a CBConv2d, nothing else)
+    ('CBPoolMax2d', 'conv2d', BUT, _POOLS),
+    ('CBPoolAvg2d', 'conv2d', BUT, _POOLS),
+    ('CBAdd2d', 'residual', BUT, _POOLS),
+    ('CBResidual', 'residual', BUT, _POOLS),
+    ('CBUpsample2d', 'decoder', BUT, _POOLS),
+    # kept as found: never in front of an upsampling or a resize
+    ('CBConvTranspose2d', 'tconv', BUT, _POOLS + ('insertCBUpsampling', 'insertCBResize')),
+    ('CBDepthwiseConv2d', 'dwconv', BUT, _POOLS),
+    # (the general pools take the mask of CBPointwise2d and CBPad2d)
+    ('CBPointwise2d', 'pointwise', BUT, ('insertCBPooling',)),
+    ('CBPixelShuffle2d', 'rearrange', BUT, _POOLS),
+    ('CBChannelShuffle2d', 'rearrange', BUT, _POOLS),
+    ('CBResize2d', 'resize', BUT, _POOLS),
+    ('CBPad2d', 'pad', BUT, ('insertCBPooling',)),
+    ('CBBinary2d', 'binary', BUT, _POOLS),
+    ('CBGLU2d', 'binary', BUT, _POOLS),
+    ('CBGated', 'binary', BUT, _POOLS),
+    # kept as found: the passes written after it take it, the four before it (linkDepthwise, insertCBPointwise,
+    # insertCBTransposedConv, insertCBUpsampling) do not
+    ('CBGroupedConv2d', 'groupconv', ONLY, ('insertCBRearrange', 'insertCBChannelOps', 'insertCBResize',
+                                            'insertCBPadding', 'insertCBGating')),
+    # kept as found: as CBGroupedConv2d, and not for insertCBRearrange
+    ('CBChannelReduce2d', 'chanreduce', ONLY, ('insertCBChannelOps', 'insertCBResize', 'insertCBPadding',
+                                               'insertCBGating')),
+    # a producer for no pass: its forward takes a list of operands and never stands in an nn.Sequential
+    ('CBConcat2d', 'decoder', ONLY, ()),
+    # a producer for no pass, kept as found (it can hand the list it was given on: propChangeIndexes)
+    ('CBTail1x1', 'conv2d', ONLY, ()),
+)
 
 
 @functools.lru_cache(maxsize=None)
-def later_producer_types():
-    """The producers that joined after producer_types() was pinned -- CBPixelShuffle2d and CBChannelShuffle2d, which keep
-    that rule as well --: linkDepthwise, insertCBPointwise, insertCBUpsampling and insertCBTransposedConv accept
-    producer_types(...) + later_producer_types() in front of their module."""
-    from .rearrange import CBChannelShuffle2d, CBPixelShuffle2d
-    return (CBPixelShuffle2d, CBChannelShuffle2d)
-
-
-def chain_producers(forUpsampling=False):
-    """What the passes that build their producer set from the two pinned tables accept in front of their module --
-    linkDepthwise, insertCBPointwise, insertCBTransposedConv, insertCBUpsampling (forUpsampling), insertCBRearrange and
-    insertCBChannelOps, each with its own further types --: the tables, which stay as they are pinned, and CBResize2d,
-    which keeps their rule as well."""
-    from .resize import CBResize2d
-    return producer_types(forUpsampling=forUpsampling) + later_producer_types() + (CBResize2d,)
-
-
-def pass_producers(forUpsampling=False):
-    """chain_producers(...), which stays as it is pinned, and CBPad2d, which keeps the producers' rule as well: what
-    linkDepthwise, insertCBPointwise, insertCBTransposedConv, insertCBUpsampling (forUpsampling), insertCBRearrange,
-    insertCBChannelOps, insertCBResize and insertCBPadding accept in front of their module, each with its own further
-    types."""
-    from .pad import CBPad2d
-    return chain_producers(forUpsampling=forUpsampling) + (CBPad2d,)
-
-
-def operator_producers(forUpsampling=False):
-    """pass_producers(...), which stays as it is pinned, and CBBinary2d, CBGLU2d and CBGated, which keep the producers'
-    rule as well: what linkDepthwise, insertCBPointwise, insertCBTransposedConv, insertCBUpsampling (forUpsampling),
-    insertCBRearrange, insertCBChannelOps, insertCBResize, insertCBPadding and insertCBGating accept in front of their
-    module, each with its own further types."""
-    from .binary import CBBinary2d, CBGated, CBGLU2d
-    return pass_producers(forUpsampling=forUpsampling) + (CBBinary2d, CBGLU2d, CBGated)
+def producers(passName):
+    """The module types (exactly, not a subclass) that the pass `passName` of PASSES accepts in front of its module, in
+    the order of PRODUCERS.  (Imported here, at conversion time: their modules import this one.)"""
+    if passName not in PASSES:
+        raise CBinferError("chain.producers: %r is no pass of %s" % (passName, PASSES))
+    return tuple(getattr(importlib.import_module('.' + module, __package__), name)
+                 for name, module, rule, passes in PRODUCERS if (passName in passes) == (rule is ONLY))
 
 
 def hand_on_changes(prod):

@@ -16,8 +16,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
-                    operand_changes, operator_producers, split_operand)
-from .groupconv import CBGroupedConv2d
+                    operand_changes, producers, split_operand)
 
 _AFFINE = ('gamma', 'beta')
 _SOFTMAX = {nn.Softmax2d: _lib.CH_SOFTMAX, nn.Softmax: _lib.CH_SOFTMAX, nn.LogSoftmax: _lib.CH_LOGSOFTMAX}
@@ -145,14 +144,14 @@ def insertCBChannelOps(rootModule, layerNormTypes=()):
     """Inside every nn.Sequential of rootModule, an nn.Softmax2d, an nn.Softmax / nn.LogSoftmax over dim 1 (or -3), or an
     instance of one of layerNormTypes -- the user's channels-first layer-norm classes, exact types with .weight, .bias (or
     None) and .eps, as ConvNeXt's LayerNorm2d; torch has no such class of its own -- that directly follows a producer
-    (chain.operator_producers(), a CBGroupedConv2d or another CBChannelReduce2d) becomes a
+    (chain.producers('insertCBChannelOps'), another CBChannelReduce2d among them) becomes a
     CBChannelReduce2d under the same name, fed by that producer's changes: propChangeIndexes is switched on at the
     producer (chain.hand_on_changes).  The new module hands its own changes on where it stands directly in front of a
     1x1 / stride-1 / padding-0 CBConv2d; any other CBConv2d directly behind it needs its own input copy (copyInput)
     unless it runs in feedback mode, as insertCBRearrange has it.  Anything else -- a softmax over another axis, a module
-    behind a dense operator -- stays dense.  The producer tables are pinned, so linkDepthwise, insertCBPointwise,
-    insertCBUpsampling, insertCBTransposedConv and the general pools do not yet take the new module as a producer.
-    Returns rootModule."""
+    behind a dense operator -- stays dense.  linkDepthwise, insertCBPointwise, insertCBUpsampling, insertCBTransposedConv,
+    insertCBRearrange and the general pools do not take the new module as a producer (chain.PRODUCERS).  Returns
+    rootModule."""
     layerNormTypes = tuple(layerNormTypes)
 
     def convert(op):
@@ -162,4 +161,4 @@ def insertCBChannelOps(rootModule, layerNormTypes=()):
         elif type(op) not in layerNormTypes:
             return None
         return CBChannelReduce2d(op, layerNormTypes=layerNormTypes)      # (what it refuses of a layer norm is raised)
-    return insert_behind_producers(rootModule, operator_producers() + (CBGroupedConv2d, CBChannelReduce2d), convert)
+    return insert_behind_producers(rootModule, producers('insertCBChannelOps'), convert)

@@ -19,7 +19,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
-                    operand_changes, operator_producers, split_operand, state_fits)
+                    operand_changes, producers, split_operand, state_fits)
 
 MAX_SCALE = 8
 
@@ -185,7 +185,7 @@ _UPSAMPLERS = (nn.Upsample, nn.UpsamplingNearest2d, nn.UpsamplingBilinear2d)
 
 def insertCBUpsampling(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.Upsample / nn.UpsamplingNearest2d / nn.UpsamplingBilinear2d within
-    the library's limits that directly follows a producer -- chain.operator_producers(forUpsampling=True), another
+    the library's limits that directly follows a producer -- chain.producers('insertCBUpsampling'), another
     CBUpsample2d among them and a CBConvTranspose2d not -- becomes a CBUpsample2d fed by that producer's changes:
     propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new module hands nothing on: a
     CBConv2d consuming the upsampled map, a 1x1 layer included, needs its own input copy (copyInput) unless it runs in
@@ -196,5 +196,5 @@ def insertCBUpsampling(rootModule, cloneOutput=True):
             return CBUpsample2d(up) if type(up) in _UPSAMPLERS else None
         except CBinferError:
             return None      # (beyond the limits: stays dense)
-    return insert_behind_producers(rootModule, operator_producers(forUpsampling=True), convert, cloneOutput=cloneOutput,
+    return insert_behind_producers(rootModule, producers('insertCBUpsampling'), convert, cloneOutput=cloneOutput,
                                    handOn=False)

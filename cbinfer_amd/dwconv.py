@@ -14,8 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, stream_ptr
-from .chain import (PROPAGATED, hand_back, hand_on_changes, is_1x1, mask_workspace, operand_changes,
-                    operator_producers)
+from .chain import PROPAGATED, hand_back, hand_on_changes, is_1x1, mask_workspace, operand_changes, producers
 from .conv2d import _padding_pair
 from .layer import CBDetectingLayer, check_limits, frame_masks
 
@@ -132,14 +131,14 @@ class CBDepthwiseConv2d(CBDetectingLayer):
 
 def linkDepthwise(rootModule):
     """Inside every nn.Sequential of rootModule: a CBDepthwiseConv2d with dilation 1 and padding <= kernel_size / 2 that
-    directly follows a producer -- chain.operator_producers(), another CBDepthwiseConv2d among them -- takes that
+    directly follows a producer -- chain.producers('linkDepthwise'), another CBDepthwiseConv2d among them -- takes that
     producer's changes (propagatedChanges on the layer, propChangeIndexes on the producer: chain.hand_on_changes) and
     runs no detection; a CBDepthwiseConv2d directly in front of a 1x1 / stride-1 / padding-0 CBConv2d hands its changes
     on (propChangeIndexes).  Returns rootModule."""
     for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
         kids = list(seq.children())
         for prod, cons in zip(kids[:-1], kids[1:]):
-            if (type(cons) is CBDepthwiseConv2d and type(prod) in operator_producers() and
+            if (type(cons) is CBDepthwiseConv2d and type(prod) in producers('linkDepthwise') and
                     _propagated_ok(cons.kernel_size, cons.padding, cons.dilation)):
                 cons.propagatedChanges = True
                 hand_on_changes(prod)

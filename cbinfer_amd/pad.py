@@ -20,9 +20,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
-                    operand_changes, operator_producers, split_operand)
-from .chanreduce import CBChannelReduce2d
-from .groupconv import CBGroupedConv2d
+                    operand_changes, producers, split_operand)
 
 MAX_PAD = 64      # per side, either sign: cbGeom's padding bound
 MODES = {'constant': _lib.PAD_CONSTANT, 'reflect': _lib.PAD_REFLECT, 'replicate': _lib.PAD_REPLICATE,
@@ -200,7 +198,7 @@ def splitConvPadding(rootModule):
 def insertCBPadding(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.ReflectionPad2d, nn.ReplicationPad2d, nn.ZeroPad2d,
     nn.ConstantPad2d or nn.CircularPad2d within the library's limits that directly follows a producer --
-    chain.operator_producers() (another CBPad2d among them), a CBGroupedConv2d or a CBChannelReduce2d -- becomes a CBPad2d
+    chain.producers('insertCBPadding'), another CBPad2d among them -- becomes a CBPad2d
     fed by that producer's changes: propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new
     module hands its own changes on where it stands directly in front of a 1x1 / stride-1 / padding-0 CBConv2d; any other
     CBConv2d directly behind it needs its own input copy (copyInput) unless it runs in feedback mode.  A module beyond the
@@ -211,5 +209,4 @@ def insertCBPadding(rootModule, cloneOutput=True):
             return CBPad2d(m) if type(m) in PAD_MODULES else None
         except CBinferError:
             return None      # (beyond the limits: stays dense)
-    return insert_behind_producers(rootModule, operator_producers() + (CBGroupedConv2d, CBChannelReduce2d), convert,
-                                   cloneOutput=cloneOutput)
+    return insert_behind_producers(rootModule, producers('insertCBPadding'), convert, cloneOutput=cloneOutput)

@@ -13,7 +13,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, hand_on_changes, is_1x1, mask_workspace,
-                    operand_changes, operator_producers, split_operand)
+                    operand_changes, producers, split_operand)
 
 # nn type (exactly, not a subclass) -> (CB_PW_* kind, p0, p1 of the instance)
 _ACTIVATIONS = {
@@ -150,11 +150,11 @@ class CBPointwise2d(CBStateModule):
 
 def insertCBPointwise(rootModule):
     """Inside every nn.Sequential of rootModule, a run  [nn.BatchNorm2d] [activation]  (at least one of the two; the
-    activations of CBPointwise2d) that directly follows a producer -- chain.operator_producers(), another CBPointwise2d
-    among them -- becomes ONE CBPointwise2d under the run's first name, fed by that producer's changes:
-    propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new
-    module hands its own changes on (propChangeIndexes) only where it stands directly in front of a 1x1 / stride-1 /
-    padding-0 CBConv2d -- a k x k CBConv2d that is handed indexes skips its own detection, which would be wrong here;
+    activations of CBPointwise2d) that directly follows a producer -- chain.producers('insertCBPointwise'), another
+    CBPointwise2d among them -- becomes ONE CBPointwise2d under the run's first name, fed by that producer's changes:
+    propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new module hands its own changes on
+    (propChangeIndexes) only where it stands directly in front of a 1x1 / stride-1 / padding-0 CBConv2d -- a k x k
+    CBConv2d that is handed indexes skips its own detection, which would be wrong here;
     linkDepthwise, insertCBUpsampling, insertCBTransposedConv and insertCBPooling(generalGeometry=True), called
     afterwards, switch the flag on for their own consumers.  A run behind anything else, or an activation outside the
     table, stays dense.  A batch norm in training mode or without running statistics raises CBinferError, as
@@ -165,7 +165,7 @@ def insertCBPointwise(rootModule):
             names = list(seq._modules.keys())
             prod, first = seq._modules[names[pos - 1]], seq._modules[names[pos]]
             pos += 1
-            if type(prod) not in operator_producers():
+            if type(prod) not in producers('insertCBPointwise'):
                 continue
             norm = first if type(first) is nn.BatchNorm2d else None
             after = seq._modules[names[pos]] if norm is not None and pos < len(names) else first

@@ -15,8 +15,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
-                    operand_changes, operator_producers, split_operand)
-from .groupconv import CBGroupedConv2d
+                    operand_changes, producers, split_operand)
 
 MAX_FACTOR = 8      # of the two pixel shuffles: CBUpsample2d's scale limit
 
@@ -145,8 +144,8 @@ class CBChannelShuffle2d(_CBRearrange2d):
 
 def insertCBRearrange(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.PixelShuffle, nn.PixelUnshuffle or nn.ChannelShuffle within the
-    library's limits that directly follows a producer -- chain.operator_producers(), a CBGroupedConv2d, or another
-    CBPixelShuffle2d / CBChannelShuffle2d -- becomes the change-based module fed by that producer's changes:
+    library's limits that directly follows a producer -- chain.producers('insertCBRearrange'), another
+    CBPixelShuffle2d / CBChannelShuffle2d among them -- becomes the change-based module fed by that producer's changes:
     propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new module hands its own changes on
     where it stands directly in front of a 1x1 / stride-1 / padding-0 CBConv2d; any other CBConv2d consuming its output
     needs its own input copy (copyInput) unless it runs in feedback mode.  linkDepthwise, insertCBPointwise,
@@ -161,5 +160,4 @@ def insertCBRearrange(rootModule, cloneOutput=True):
         except CBinferError:
             pass      # (beyond the limits: stays dense)
         return None
-    return insert_behind_producers(rootModule, operator_producers() + (CBGroupedConv2d,), convert,
-                                   cloneOutput=cloneOutput)
+    return insert_behind_producers(rootModule, producers('insertCBRearrange'), convert, cloneOutput=cloneOutput)

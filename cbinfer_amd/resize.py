@@ -22,9 +22,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
-                    operand_changes, operator_producers, split_operand)
-from .chanreduce import CBChannelReduce2d
-from .groupconv import CBGroupedConv2d
+                    operand_changes, producers, split_operand)
 
 MAX_RATIO = 8          # per axis, either way
 MAX_TERM = 4096        # numerator and denominator of the reduced step
@@ -171,8 +169,8 @@ class CBResize2d(CBStateModule):
 
 def insertCBResize(rootModule, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.Upsample / nn.UpsamplingNearest2d / nn.UpsamplingBilinear2d that is
-    still dense and directly follows a producer -- insertCBUpsampling's set, a CBGroupedConv2d, a CBChannelReduce2d or
-    another CBResize2d -- becomes a CBResize2d when CBResize2d takes it, fed by that producer's changes:
+    still dense and directly follows a producer -- chain.producers('insertCBResize'), another CBResize2d among them and a
+    CBConvTranspose2d not -- becomes a CBResize2d when CBResize2d takes it, fed by that producer's changes:
     propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new module hands its own changes on
     where it stands directly in front of a 1x1 / stride-1 / padding-0 CBConv2d; any other CBConv2d directly behind it
     needs its own input copy (copyInput) unless it runs in feedback mode.  A module the constructor refuses stays dense;
@@ -187,5 +185,4 @@ def insertCBResize(rootModule, cloneOutput=True):
             return CBResize2d(up) if type(up) in _UPSAMPLERS else None
         except CBinferError:
             return None      # (beyond the limits: stays dense)
-    return insert_behind_producers(rootModule, operator_producers(forUpsampling=True) +
-                                   (CBGroupedConv2d, CBChannelReduce2d), convert, cloneOutput=cloneOutput)
+    return insert_behind_producers(rootModule, producers('insertCBResize'), convert, cloneOutput=cloneOutput)

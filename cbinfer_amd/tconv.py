@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, stream_ptr
-from .chain import hand_back, link_consumer, operator_producers
+from .chain import hand_back, link_consumer, producers
 from .layer import CBContractingLayer, check_limits
 
 MAX_K, MAX_S, MAX_D = 8, 4, 4
@@ -107,11 +107,11 @@ class CBConvTranspose2d(CBContractingLayer):
 
 def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
     """Inside every nn.Sequential of rootModule, an nn.ConvTranspose2d within the library's limits that directly follows
-    a producer -- chain.operator_producers(), another CBConvTranspose2d among them -- becomes a CBConvTranspose2d with
-    `threshold` (it runs its own change detection: nothing is switched on at the producer).  An nn.ReLU right behind it
-    is absorbed (withReLU).  A CBConv2d consuming the output then needs its own input copy (copyInput) unless it runs in
-    feedback mode (chain.link_consumer; the layer hands nothing on by itself).  A module beyond the limits stays the
-    dense torch operator.  Returns rootModule."""
+    a producer -- chain.producers('insertCBTransposedConv'), another CBConvTranspose2d among them -- becomes a
+    CBConvTranspose2d with `threshold` (it runs its own change detection: nothing is switched on at the producer).  An
+    nn.ReLU right behind it is absorbed (withReLU).  A CBConv2d consuming the output then needs its own input copy
+    (copyInput) unless it runs in feedback mode (chain.link_consumer; the layer hands nothing on by itself).  A module
+    beyond the limits stays the dense torch operator.  Returns rootModule."""
     for seq in [m for m in rootModule.modules() if type(m) is nn.Sequential]:
         names = list(seq._modules.keys())
         gone = set()
@@ -119,7 +119,7 @@ def insertCBTransposedConv(rootModule, threshold=1e-1, cloneOutput=True):
             prod, tc = seq._modules[names[pos - 1]], seq._modules[names[pos]]
             if names[pos - 1] in gone and pos >= 2:
                 prod = seq._modules[names[pos - 2]]
-            if type(prod) not in operator_producers() or type(tc) != nn.ConvTranspose2d:
+            if type(prod) not in producers('insertCBTransposedConv') or type(tc) != nn.ConvTranspose2d:
                 continue
             try:
                 cb = CBConvTranspose2d(tc, threshold)

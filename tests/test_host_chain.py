@@ -39,8 +39,8 @@ def conv(k=3, feedback=False, **kw):
 
 
 def _producers(pkg):
-    """name -> constructor of every kind of module a pass may find in front of its operator: chain.operator_producers(),
-    the two further ones most passes add, a pool of each kind, and a dense module."""
+    """name -> constructor of every kind of module a pass may find in front of its operator: the sixteen types every chain
+    pass but the upsamplings accepts, the two further ones most passes add, a pool of each kind, and a dense module."""
     return {
         'CBConv2d': conv,
         'CBPoolMax2d 2x2': lambda: pkg.CBPoolMax2d(nn.MaxPool2d(2)),
@@ -1452,3 +1452,85 @@ WIRING = {
             None),
     },
 }
+
+
+# ------------------------------------------------------------------------------------------------ the producer matrix
+# What every pass accepts in front of its module, by name and in order: recorded by running each pass at the commit
+# before chain.PRODUCERS was written -- watching the set it handed to the walk or tested its producer against, the types
+# it added at the call included; insertCBPooling by offering it every exported type in front of a pool.
+B = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBAdd2d', 'CBResidual', 'CBUpsample2d', 'CBConvTranspose2d',
+     'CBDepthwiseConv2d', 'CBPointwise2d', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'CBResize2d', 'CBPad2d',
+     'CBBinary2d', 'CBGLU2d', 'CBGated']
+B_NO_TRANSPOSED = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBAdd2d', 'CBResidual', 'CBUpsample2d',
+                   'CBDepthwiseConv2d', 'CBPointwise2d', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'CBResize2d',
+                   'CBPad2d', 'CBBinary2d', 'CBGLU2d', 'CBGated']
+MATRIX = {
+    'linkDepthwise': B,
+    'insertCBPointwise': B,
+    'insertCBTransposedConv': B,
+    'insertCBUpsampling': B_NO_TRANSPOSED,
+    'insertCBRearrange': B + ['CBGroupedConv2d'],
+    'insertCBChannelOps': B + ['CBGroupedConv2d', 'CBChannelReduce2d'],
+    'insertCBPadding': B + ['CBGroupedConv2d', 'CBChannelReduce2d'],
+    'insertCBGating': B + ['CBGroupedConv2d', 'CBChannelReduce2d'],
+    'insertCBResize': B_NO_TRANSPOSED + ['CBGroupedConv2d', 'CBChannelReduce2d'],
+    'insertCBPooling': ['CBConv2d'],
+    'insertCBPooling(generalGeometry=True)': ['CBConv2d', 'CBPointwise2d', 'CBPad2d'],
+}
+# the module types that wrap stateful children and keep no state of their own
+WRAPPERS = ['CBResidual', 'CBGated']
+# the layers that SequenceBatch takes or refuses by its own rule, not through batch.CHAIN_OPERATORS
+BATCH_OWN_RULE = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1']
+
+
+def _module_types():
+    """Every nn.Module subclass the package exports under a CB name."""
+    import cbinfer_amd
+    found = [getattr(cbinfer_amd, n) for n in cbinfer_amd.__all__ if n.startswith('CB')]
+    return [t for t in found if isinstance(t, type) and issubclass(t, nn.Module)]
+
+
+def test_every_pass_accepts_the_producers_recorded(pkg, chain, Err):
+    assert list(chain.PASSES) == list(MATRIX) and len(MATRIX) == 11
+    for passName, want in MATRIX.items():
+        got = chain.producers(passName)
+        assert type(got) is tuple and [t.__name__ for t in got] == want, passName
+        assert all(t is getattr(pkg, t.__name__) for t in got), passName
+    for unknown in ('linkGrouped', 'insertCBPooling(generalGeometry=False)', ''):      # (no set: never all of them)
+        with pytest.raises(Err, match="is no pass of"):
+            chain.producers(unknown)
+
+
+def test_producer_table_has_one_row_for_every_module_type(chain):
+    import cbinfer_amd
+    rows = [row[0] for row in chain.PRODUCERS]
+    assert len(set(rows)) == len(rows)
+    assert sorted(rows) == sorted(t.__name__ for t in _module_types())      # a row each, and every row exported
+    for name, module, rule, passes in chain.PRODUCERS:
+        assert getattr(getattr(cbinfer_amd, module), name) is getattr(cbinfer_amd, name)
+        assert rule in (chain.BUT, chain.ONLY) and set(passes) <= set(chain.PASSES), name
+    # a producer for no pass stands in the table as that
+    assert [row[0] for row in chain.PRODUCERS if row[2:] == (chain.ONLY, ())] == ['CBConcat2d', 'CBTail1x1']
+    assert not any(rule == chain.BUT and set(passes) == set(chain.PASSES) for _, _, rule, passes in chain.PRODUCERS)
+
+
+def test_clear_memory_reaches_every_module_type_with_state():
+    import cbinfer_amd
+    stateful = [t.__name__ for t in cbinfer_amd._STATEFUL]
+    assert len(set(stateful)) == len(stateful)
+    for t in _module_types():
+        if t.__name__ in WRAPPERS:
+            assert not hasattr(t, 'getStateTensors') and t.__name__ not in stateful
+        else:
+            assert hasattr(t, 'getStateTensors') and hasattr(t, 'clearMemory') and t.__name__ in stateful, t.__name__
+    assert set(stateful) <= set(t.__name__ for t in _module_types())
+    # the wrappers' own children are reached: what they add is a CBAdd2d / a CBBinary2d
+    assert {'CBAdd2d', 'CBBinary2d'} <= set(stateful)
+
+
+def test_batch_and_branch_group_refuse_every_chain_operator():
+    import cbinfer_amd
+    from cbinfer_amd import batch
+    refused = [t.__name__ for row in batch.CHAIN_OPERATORS for t in row[0]]
+    assert len(set(refused)) == len(refused) and not set(refused) & set(BATCH_OWN_RULE)
+    assert sorted(refused + BATCH_OWN_RULE) == sorted(t.__name__ for t in cbinfer_amd._STATEFUL)

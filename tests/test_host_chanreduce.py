@@ -285,6 +285,7 @@ def test_batch_and_branch_refusals_name_the_layer(pkg, lib):
         pkg.SequenceBatch(net, 2)
     with pytest.raises(lib.CBinferError, match=r"BranchGroup: layer '0.1' is CBChannelReduce2d"):
         pkg.BranchGroup([net])
-    # the producer tables are pinned: the new module is in neither
+    # the new module is a producer for these passes and no other (every pass's whole set: test_host_chain.py)
     from cbinfer_amd import chain
-    assert pkg.CBChannelReduce2d not in chain.producer_types() + chain.later_producer_types()
+    assert [name for name in chain.PASSES if pkg.CBChannelReduce2d in chain.producers(name)] == [
+        'insertCBChannelOps', 'insertCBPadding', 'insertCBGating', 'insertCBResize']

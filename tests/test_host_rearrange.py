@@ -261,13 +261,15 @@ def test_operators_behind_a_non_producer_or_beyond_the_limits_stay_dense(pkg):
 
 def test_the_producer_tables(pkg):
     from cbinfer_amd import chain
-    every = (pkg.CBConv2d, pkg.CBPoolMax2d, pkg.CBPoolAvg2d, pkg.CBAdd2d, pkg.CBResidual, pkg.CBUpsample2d,
-             pkg.CBConvTranspose2d, pkg.CBDepthwiseConv2d, pkg.CBPointwise2d)
-    assert chain.producer_types() == every      # unchanged, in its order
-    assert pkg.CBPixelShuffle2d not in chain.producer_types() and pkg.CBChannelShuffle2d not in chain.producer_types()
-    assert not set(chain.producer_types(forUpsampling=True)) & {pkg.CBPixelShuffle2d, pkg.CBChannelShuffle2d}
-    assert chain.later_producer_types() == (pkg.CBPixelShuffle2d, pkg.CBChannelShuffle2d)
-    assert pkg.CBGroupedConv2d not in chain.producer_types() + chain.later_producer_types()
+    # (every pass's whole set, in order: test_host_chain.py)
+    shuffles = (pkg.CBPixelShuffle2d, pkg.CBChannelShuffle2d)
+    pools = ['insertCBPooling', 'insertCBPooling(generalGeometry=True)']
+    assert [name for name in chain.PASSES if not set(shuffles) & set(chain.producers(name))] == pools
+    assert all(tuple(t for t in chain.producers(name) if t in shuffles) == shuffles
+               for name in chain.PASSES if name not in pools)
+    # a grouped convolution: for this pass and the later ones, not for the four before it
+    assert [name for name in chain.PASSES if pkg.CBGroupedConv2d in chain.producers(name)] == [
+        'insertCBRearrange', 'insertCBChannelOps', 'insertCBPadding', 'insertCBGating', 'insertCBResize']
 
 
 # ------------------------------------------------------------------------------------------------ module hygiene

@@ -350,7 +350,7 @@ def fcn_head(pkg, up):
 
 def test_insert_resize_on_heads_stacks_and_what_it_leaves(pkg, lib):
     from cbinfer_amd import chain
-    tables = (chain.producer_types(), chain.producer_types(forUpsampling=True), chain.later_producer_types())
+    matrix = [chain.producers(name) for name in chain.PASSES]
     # an FCN-type head: conv -> Upsample(size=) -> conv1x1
     net = fcn_head(pkg, nn.Upsample(size=(20, 33), mode='bilinear', align_corners=False))
     assert [type(m).__name__ for m in net] == ['CBConv2d', 'Upsample', 'CBConv2d']
@@ -394,20 +394,15 @@ def test_insert_resize_on_heads_stacks_and_what_it_leaves(pkg, lib):
     pkg.insertCBResize(net)
     assert [type(m).__name__ for m in net] == ['CBGroupedConv2d', 'CBResize2d', 'CBChannelReduce2d', 'CBResize2d']
     assert net[0].propChangeIndexes and net[1].propChangeIndexes and net[2].propChangeIndexes
-    assert tables == (chain.producer_types(), chain.producer_types(forUpsampling=True), chain.later_producer_types())
+    assert matrix == [chain.producers(name) for name in chain.PASSES]      # (what it holds: test_host_chain.py)
 
 
 def test_the_other_passes_accept_the_module_as_a_producer(pkg, lib):
     from cbinfer_amd import chain
     R = pkg.CBResize2d
-    assert R not in chain.producer_types() + chain.later_producer_types()
-    assert chain.chain_producers() == chain.producer_types() + chain.later_producer_types() + (R,)
-    assert chain.chain_producers(forUpsampling=True) == (chain.producer_types(forUpsampling=True) +
-                                                         chain.later_producer_types() + (R,))
-    assert [t.__name__ for t in chain.producer_types()] == [
-        'CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBAdd2d', 'CBResidual', 'CBUpsample2d', 'CBConvTranspose2d',
-        'CBDepthwiseConv2d', 'CBPointwise2d']
-    assert [t.__name__ for t in chain.later_producer_types()] == ['CBPixelShuffle2d', 'CBChannelShuffle2d']
+    # every pass but the two poolings (every pass's whole set, in order: test_host_chain.py)
+    assert [name for name in chain.PASSES if R not in chain.producers(name)] == [
+        'insertCBPooling', 'insertCBPooling(generalGeometry=True)']
 
     def behind(*mods):
         net = nn.Sequential(R(size=(9, 11), mode='bilinear'))
