@@ -156,7 +156,7 @@ def propChangeIndexesOf1x1(rootModule):
     return rootModule
 
 
-def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
+def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False, adaptive=False):
     """what sceneLabeling/modelLoader.py:62-78 does by hand for experiments 5/6, for any
     converted network: every 2x2/stride-2 nn.MaxPool2d that directly follows a CBConv2d inside an
     nn.Sequential becomes a CBPoolMax2d fed by that layer's change indexes (propChangeIndexes on the
@@ -164,7 +164,14 @@ def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
     then needs its own input copy (copyInput) unless it runs in feedback mode.  generalGeometry=True: every
     nn.MaxPool2d and nn.AvgPool2d within the library's limits (CBPoolMax2d(m, generalGeometry=True), CBPoolAvg2d) is
     converted, also directly behind a CBPointwise2d or a CBPad2d (the general pools take their mask); a pool beyond them
-    stays the dense torch operator.  Both sets are rows of chain.producers().  Returns rootModule."""
+    stays the dense torch operator.  Both sets are rows of chain.producers().  adaptive=True (with generalGeometry=True
+    only): an nn.AdaptiveMaxPool2d / nn.AdaptiveAvgPool2d behind the same producers is converted too -- the global pool of
+    a classifier head or a squeeze, the bins of a pyramid; one the modules refuse (return_indices=True) stays dense.
+    Returns rootModule."""
+    if adaptive and not generalGeometry:
+        raise _lib.CBinferError("insertCBPooling: adaptive=True needs generalGeometry=True (the adaptive pools are "
+                                "general-geometry modules)")
+
     def _pair(v):
         return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
@@ -173,8 +180,10 @@ def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False):
             try:
                 if type(pool) == torch.nn.MaxPool2d:
                     return CBPoolMax2d(pool, generalGeometry=True)
-                if type(pool) == torch.nn.AvgPool2d:
+                if type(pool) == torch.nn.AvgPool2d or (adaptive and type(pool) == torch.nn.AdaptiveAvgPool2d):
                     return CBPoolAvg2d(pool)
+                if adaptive and type(pool) == torch.nn.AdaptiveMaxPool2d:
+                    return CBPoolMax2d(pool, generalGeometry=True)
             except _lib.CBinferError:
                 pass      # (beyond the limits: stays dense)
             return None

@@ -100,6 +100,7 @@ class Geom(ctypes.Structure):
 _gp, _ip = ctypes.POINTER(Geom), ctypes.POINTER(ctypes.c_int)
 
 POOL_MAX, POOL_AVG_PAD, POOL_AVG_NOPAD = 0, 1, 2      # CB_POOL_*
+ADAPT_MAX, ADAPT_AVG = 0, 1                           # CB_ADAPT_*
 
 
 class Pool(ctypes.Structure):
@@ -356,6 +357,13 @@ _SIGNATURES = {
     "cbinfer_binary_changed": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "cbinfer_cbbinary_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i,
                                       _i, _i, _i, _vp]),
+    "cbinfer_adaptive_pool_supported": (_i, [_i, _i, _i, _i]),
+    "cbinfer_adaptive_pool_lanes": (_i, [_i, _i]),
+    "cbinfer_adaptive_pool_partial_elems": (_l, [_i, _i, _i, _i, _i]),
+    "cbinfer_adaptive_pool_partials": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cbinfer_adaptive_pool_changed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cbinfer_cbadaptivepool2d_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
+                                              _vp]),
     "cbinfer_conv2d_fg_cpu": (None, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i]),
 }
 

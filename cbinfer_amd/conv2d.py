@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import C, check, dtype_code, ptr, raw_stream, require_device, stream_ptr
-from .chain import PROPAGATED, hand_back, mask_workspace, operand_changes
+from .chain import EVERY_PIXEL, PROPAGATED, hand_back, mask_workspace, operand_changes, state_fits
 from .conv2d_cg import (ChangeIndexes, MaskChangeIndexes, changeDetection, changeIndexesExtr, dilateChangeIndexes,
                         genXMatrix, matrixMult, maxPool2d, newConvWorkspace, poolChangeIndexes, prepWeights, updateOutput)
 from .conv2d_fg import cbconvFG, cbconvFG_deterministic
@@ -221,15 +221,42 @@ def _check_general_pool(m, kind):
     return k, s, p, op
 
 
+_ADAPTIVE_POOLS = {'max': nn.AdaptiveMaxPool2d, 'avg': nn.AdaptiveAvgPool2d}
+
+
+def _check_adaptive_pool(m, kind, generalGeometry):
+    """The output_size of the nn.AdaptiveMaxPool2d (kind 'max') or nn.AdaptiveAvgPool2d ('avg') `m` as a pair whose
+    entries are an int >= 1 or None (the input's size on that axis).  CBinferError with a sentence otherwise."""
+    Err = _lib.CBinferError
+    name = 'CBPoolMax2d' if kind == 'max' else 'CBPoolAvg2d'
+    if not generalGeometry:
+        raise Err("%s: an %s runs on the adaptive pool of the general geometry only: pass generalGeometry=True"
+                  % (name, type(m).__name__))
+    if getattr(m, 'return_indices', False):
+        raise Err("%s: return_indices=True is not supported (the change-based pool keeps no argmax)" % name)
+    size = m.output_size
+    if not isinstance(size, (tuple, list)):
+        size = (size, size)
+    if len(size) != 2 or not all(v is None or (isinstance(v, int) and not isinstance(v, bool) and v >= 1) for v in size):
+        raise Err("%s: output_size=%r is not supported, only an int >= 1, None or a pair of them" % (name, m.output_size))
+    return tuple(size)
+
+
 class CBPoolMax2d(nn.Module):
     """Change-based max pooling: 2x2/stride-2 (reference: conv2d.py:24-84) and, with generalGeometry=True, any window,
-    stride, zero padding and ceil_mode within the library's limits (cb_pool2d.hip)."""
+    stride, zero padding and ceil_mode within the library's limits (cb_pool2d.hip) and an
+    nn.AdaptiveMaxPool2d of any output size up to the map's, the global pool included (cb_adaptpool.hip)."""
     _KIND = 'max'
 
     def __init__(self, m, generalGeometry=False):
         super(CBPoolMax2d, self).__init__()
         self.generalGeometry = bool(generalGeometry)
-        if self.generalGeometry:
+        self._adaptive = type(m) is _ADAPTIVE_POOLS[self._KIND]
+        if self._adaptive:
+            self.output_size = _check_adaptive_pool(m, self._KIND, self.generalGeometry)
+            ks, st, pd = None, None, (0, 0)
+            self._op = _lib.ADAPT_MAX if self._KIND == 'max' else _lib.ADAPT_AVG
+        elif self.generalGeometry:
             ks, st, pd, self._op = _check_general_pool(m, self._KIND)
         else:
             ks = m.kernel_size if isinstance(m.kernel_size, tuple) else (m.kernel_size,) * 2
@@ -237,13 +264,15 @@ class CBPoolMax2d(nn.Module):
             assert ks == (2, 2) and st == (2, 2)
             pd, self._op = (0, 0), _lib.POOL_MAX
         # a window the 2x2 kernel cannot take runs on cb_pool2d.hip; a 2x2/s2/p0 max pool runs as it always did
-        self._general = self.generalGeometry and (self._KIND != 'max' or (ks, st, pd) != ((2, 2), (2, 2), (0, 0)))
+        # (an adaptive pool runs on cb_adaptpool.hip: never folded, never batched, as every general pool)
+        self._general = self._adaptive or (
+            self.generalGeometry and (self._KIND != 'max' or (ks, st, pd) != ((2, 2), (2, 2), (0, 0))))
         self.padding = pd
         self._poolC = None
         self._poolWork = None
         self.stride = st
         self.kernel_size = ks
-        self.ceil_mode = m.ceil_mode
+        self.ceil_mode = getattr(m, 'ceil_mode', False)
         self.propChangeIndexes = False
         # True: a private copy of the state every frame (conv2d.py:73); False: the state itself, tagged, so that a
         # consumer that keeps a reference to it (copyInput=False) copies it then
@@ -253,23 +282,31 @@ class CBPoolMax2d(nn.Module):
         # True (fusePoolingIntoDetection): hand the consumer a LazyPool; it pools inside its change detection
         self.lazy = False
         self.register_buffer('outputState', torch.zeros(0))
+        # the row-segment partials of an adaptive pool (f32 [C, ow, H]); empty for every other pool
+        self.register_buffer('partials', torch.zeros(0))
         self.clearMemory()
 
     def clearMemory(self):
-        if not hasattr(self, 'outputState') or 'outputState' not in self._buffers:
-            self.register_buffer('outputState', torch.zeros(0))
+        for name in ('outputState', 'partials'):
+            if name not in self._buffers:
+                self.register_buffer(name, torch.zeros(0))
         self.outputState = self.outputState.new_zeros(0)
+        self.partials = self.partials.new_zeros(0)
         self.__dict__['_poolWork'] = None      # (device work buffers of the general path, not part of the state)
 
     def getStateTensors(self):
-        return [self.outputState] if hasattr(self, 'outputState') else []
+        if not hasattr(self, 'outputState'):
+            return []
+        return [self.outputState, self.partials] if self.__dict__.get('_adaptive') else [self.outputState]
 
     def _setDefaultValues(self):
         # back-fill attributes missing in modules pickled by older versions
         for name, val in (('generalGeometry', False), ('_general', False), ('padding', (0, 0)), ('_op', _lib.POOL_MAX),
-                          ('_poolC', None), ('_poolWork', None)):
+                          ('_poolC', None), ('_poolWork', None), ('_adaptive', False)):
             if name not in self.__dict__:
                 self.__dict__[name] = val
+        if 'partials' not in self._buffers:
+            self.register_buffer('partials', torch.zeros(0))
 
     def __getstate__(self):
         d = dict(self.__dict__)
@@ -326,11 +363,62 @@ class CBPoolMax2d(nn.Module):
         # (an input-resolution list means nothing behind such a pool: downsampleIndexes is ignored)
         return hand_back(self, self.outputState, work['copy'], (Ho, Wo), work)
 
+    # ---------------------------------------------------------------- adaptive and global (cb_adaptpool.hip)
+    def _adaptive_out(self, Hi, Wi):
+        """The output size on an Hi x Wi map: None is the map's own size on that axis."""
+        oh, ow = (n if v is None else v for v, n in zip(self.output_size, (Hi, Wi)))
+        if oh > Hi or ow > Wi:
+            raise _lib.CBinferError("%s: output_size=%s is larger than the %dx%d map on an axis (an adaptive pool that "
+                                    "repeats pixels is not converted)" % (self.__class__.__name__, (oh, ow), Hi, Wi))
+        if not C.cbinfer_adaptive_pool_supported(Hi, Wi, oh, ow):
+            raise _lib.CBinferError("%s: a %dx%d map pooled to %s is beyond what the library takes (output width <= 4096)"
+                                    % (self.__class__.__name__, Hi, Wi, (oh, ow)))
+        return oh, ow
+
+    def _adaptive_workspace(self, Hi, Wi, dev):
+        """The general pool's buffers on the output map and the working mask of the INPUT map (for a list operand)."""
+        key = (Hi, Wi, dev)
+        work = self.__dict__.get('_poolWork')
+        if work is None or work['key'] != key:
+            oh, ow = self._adaptive_out(Hi, Wi)
+            work = self.__dict__['_poolWork'] = dict(
+                mask_workspace(oh, ow, dev), key=key, size=(oh, ow),
+                inBits=torch.zeros(C.cbinfer_mask_words(Hi, Wi), dtype=torch.int64, device=dev))
+        return work
+
+    def _forward_adaptive(self, input, changeIndexes):
+        """A frame on cb_adaptpool.hip: cbinfer_cbadaptivepool2d_forward, two launches (three for a list), no host sync.
+        The row-segment partials that hold a listed input pixel are made again, then the output pixels whose window
+        does; the mask handed on lives on the OUTPUT map.  A frame whose state does not fit lists every pixel."""
+        nc, Hi, Wi = input.size(-3), input.size(-2), input.size(-1)
+        assert input.dim() == 4 and input.size(0) == 1
+        work = self._adaptive_workspace(Hi, Wi, input.device)
+        oh, ow = work['size']
+        assert not isinstance(changeIndexes, torch.Tensor) or changeIndexes.dim() == 1
+        if changeIndexes is None:      # (a pool always stands behind a producer)
+            raise _lib.CBinferError(PROPAGATED['words'][1] % dict(name=self.__class__.__name__))
+        form = operand_changes(self.__class__.__name__, 'pool', changeIndexes, Hi, Wi, input.device, work['idx'],
+                               **PROPAGATED)
+        if (not state_fits(self.outputState, (1, nc, oh, ow), input) or
+                not _same_shape(self.partials, (nc, ow, Hi)) or self.partials.dtype != torch.float32 or
+                self.partials.device != input.device):
+            self.outputState = torch.empty((1, nc, oh, ow), dtype=input.dtype, device=input.device)
+            self.partials = torch.empty((nc, ow, Hi), dtype=torch.float32, device=input.device)
+            form = EVERY_PIXEL      # (a new state is written completely: the operand's change information is not used)
+        mask, idx, cap, count = form
+        check(C.cbinfer_cbadaptivepool2d_forward(ptr(input), ptr(self.partials), ptr(self.outputState), ptr(mask),
+                                                 ptr(idx), cap, ptr(count), ptr(work['inBits']), ptr(work['bits']),
+                                                 ptr(work['copy']), nc, Hi, Wi, oh, ow, self._op, dtype_code(input),
+                                                 stream_ptr(input)))
+        return hand_back(self, self.outputState, work['copy'], (oh, ow), work)
+
     def forward(self, inp):
         assert type(inp) == tuple and inp[0] == 'changeIndexes'
         input = inp[1].detach().contiguous()
         changeIndexes = inp[2]
         require_device(input)
+        if self.__dict__.get('_adaptive'):
+            return self._forward_adaptive(input, changeIndexes)
         if self.__dict__.get('_general'):
             return self._forward_general(input, changeIndexes)
         nc, h, w = input.size(-3), input.size(-2), input.size(-1)
@@ -362,6 +450,9 @@ class CBPoolMax2d(nn.Module):
         return output
 
     def __repr__(self):
+        if self.__dict__.get('_adaptive'):
+            return '%s (output_size=%s, propChgIdxs=%s)' % (self.__class__.__name__, self.output_size,
+                                                            self.propChangeIndexes)
         if self.__dict__.get('generalGeometry'):
             return ('%s (k=%s, s=%s, p=%s, ceil_mode=%s, propChgIdxs=%s)' %
                     (self.__class__.__name__, self.kernel_size, self.stride, self.padding, self.ceil_mode,
@@ -373,20 +464,23 @@ class CBPoolMax2d(nn.Module):
 
 class CBPoolAvg2d(CBPoolMax2d):
     """Change-based average pooling of an nn.AvgPool2d (no counterpart in the reference): any window, stride, zero
-    padding, ceil_mode and count_include_pad within the library's limits, 2x2 included (cb_pool2d.hip).
+    padding, ceil_mode and count_include_pad within the library's limits, 2x2 included (cb_pool2d.hip, DESIGN 5.11);
+    and of an nn.AdaptiveAvgPool2d of any output size up to the map's (cb_adaptpool.hip).
     The surface is CBPoolMax2d's: propChangeIndexes, cloneOutput, outputState, clearMemory, getStateTensors.  Never
     folded into a consumer's detection (lazy stays False)."""
     _KIND = 'avg'
 
     def __init__(self, m):
         super(CBPoolAvg2d, self).__init__(m, generalGeometry=True)
-        self.count_include_pad = bool(m.count_include_pad)
+        self.count_include_pad = bool(getattr(m, 'count_include_pad', True))
 
     def __setstate__(self, state):
         super(CBPoolAvg2d, self).__setstate__(state)
         self.__dict__['generalGeometry'] = self.__dict__['_general'] = True
 
     def __repr__(self):
+        if self.__dict__.get('_adaptive'):
+            return super(CBPoolAvg2d, self).__repr__()
         return ('%s (k=%s, s=%s, p=%s, ceil_mode=%s, count_include_pad=%s, propChgIdxs=%s)' %
                 (self.__class__.__name__, self.kernel_size, self.stride, self.padding, self.ceil_mode,
                  self.count_include_pad, self.propChangeIndexes))

@@ -1,5 +1,5 @@
 // What the mask-driven element-wise operators share (cb_add.hip, cb_pointwise.hip, cb_decoder.hip, cb_pool2d.hip,
-// cb_dwconv.hip): the walk over the words of a working mask, its item loop, the grid sizing, the f32 load
+// cb_dwconv.hip, cb_adaptpool.hip): the walk over the words of a working mask, its item loop, the grid sizing, the f32 load
 // of either dtype, the list -> working mask launch and the dtype dispatch of the entry points.
 #pragma once
 #include "cb_common.h"

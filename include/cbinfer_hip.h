@@ -73,7 +73,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * reductions (CB_CH_*, cbinfer_chanreduce_supported, cbinfer_chanreduce_changed, cbinfer_cbchanreduce_forward) and the
  * resize to any size (cbResize, CB_RESIZE_*, cbinfer_resize_supported, cbinfer_cbresize_forward) and the padding (cbPad,
  * CB_PAD_*, cbinfer_pad_supported, cbinfer_pad_out_size, cbinfer_cbpad_forward) and the element-wise operators of two
- * maps (CB_BIN_*, cbinfer_binary_supported, cbinfer_binary_changed, cbinfer_cbbinary_forward). */
+ * maps (CB_BIN_*, cbinfer_binary_supported, cbinfer_binary_changed, cbinfer_cbbinary_forward) and the adaptive pools
+ * (CB_ADAPT_*, cbinfer_adaptive_pool_*, cbinfer_cbadaptivepool2d_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1432,6 +1433,81 @@ int cbinfer_cbgroupconv2d_forward(const void* input, void* prevInput, void* prev
                                   int32_t* idx, int32_t* countDev, const void* prepared, const void* bias, int C, int Hi,
                                   int Wi, int K, int groups, const cbGeom* geom, float threshold, int feedbackLoop,
                                   int copyInput, int relu, int dtype, cbStream_t stream);
+
+/* ---- change-based adaptive and global pooling: max and average (cb_adaptpool.hip) ----------------------
+ * No counterpart in the reference.  torch's nn.AdaptiveMaxPool2d / nn.AdaptiveAvgPool2d on a map: input [C, H, W] (batch
+ * 1, CB_F32 or CB_F16), output [C, oh, ow] with 1 <= oh <= H and 1 <= ow <= W.  Added under ABI 11.
+ *   windows (torch's): output row i reads the input rows lo(i) ... hi(i) - 1 with lo(i) = floor(i H / oh) and
+ *     hi(i) = ceil((i + 1) H / oh); output column j the input columns floor(j W / ow) ... ceil((j + 1) W / ow) - 1.
+ *     Neighbouring windows share a row (a column) where the size does not divide, so an input row lies in one or two
+ *     row windows: floor(y oh / H) ... ceil((y + 1) oh / H) - 1.
+ *   two levels.  Level 1, the row-segment partials, f32, caller-owned state of cbinfer_adaptive_pool_partial_elems
+ *     elements: P(c, y, j) is the sum (CB_ADAPT_AVG) or the maximum (CB_ADAPT_MAX) over the columns of window j in input
+ *     row y of channel c.  LAYOUT [C][ow][H]: element (c ow + j) H + y -- the lanes of the second launch, which run along
+ *     the rows of a window, read consecutive addresses.  Level 2: out(c, i, j) is the sum or maximum of P(c, y, j) over
+ *     the rows y of window i; the average is that sum divided by float(rows cols) in ONE IEEE f32 division; CB_F16
+ *     rounds the result to f16 once (f16 inputs are widened to f32 exactly).
+ *   order of the additions, a function of (H, W, oh, ow) alone -- not of the changed pixels, the operand's form, the
+ *     grid or the wave scheduling; every addition is one correctly rounded f32 addition, never an FMA.  Both levels
+ *     are the same reduction of values x_0 ... x_(n-1) on L lanes: s_l = +0; s_l += x_k for k = l, l + L, l + 2 L, ...
+ *     < n in ascending order (a lane without a value keeps +0); then for off = L / 2, L / 4, ..., 1: s_l += s_(l + off)
+ *     for l < off; the result is s_0.  L = cbinfer_adaptive_pool_lanes(N, o) is the smallest power of two >= the
+ *     longest window the axis can have (N / o if o divides N, else floor(N / o) + 2), at most 64.
+ *     level 1: the segment's values from left to right, L = lanes(W, ow).
+ *     level 2: the partials of the window's rows from top to bottom, L = lanes(H, oh).
+ *   maximum: a NaN in the window wins (which NaN is not specified); among equal maxima the first in row-major window
+ *     order wins, and +0 == -0 there, so the result is torch's bit for bit.  Both levels carry the position with the
+ *     value through the same lanes and tree: a later value of a lane wins only if greater, and of two equal values in
+ *     the tree the one that comes first -- further left in level 1, further up in level 2.
+ *   the average is NOT torch's bits (torch sums the window in one run); it is this specification's, which
+ *     tests/adaptpool_cases.py restates in numpy.
+ *   a frame.  The operand's changes come as its row-padded change MASK of the INPUT map (cbinfer_mask_words(H, W)
+ *     words), as an int32 LIST (flat indexes y W + x, entries outside the map are dropped), or not at all: every pixel
+ *     counts as changed then (the form of a frame that writes a new state).  P(., y, j) is recomputed, for all channels,
+ *     iff column window j of row y holds a changed pixel; output pixel (i, j) is listed and recomputed, for all
+ *     channels, iff its window holds a changed pixel; every other partial and output value keeps its bits.  After any
+ *     sequence of frames that began with an every-pixel frame, partials and output are what the last frame's input gives
+ *     alone.  The work is O(C (lengths of the dirty segments + listed outputs x rows per window)): no launch reads an
+ *     input pixel of a clean segment.
+ *   hand-on: maskCopy (cbinfer_mask_words(oh, ow) words) receives the frame's mask on the OUTPUT map every frame, all
+ *     zeros for an empty frame; outBits, the working mask of the output map (same size), and inBits, the working mask
+ *     of the input map (cbinfer_mask_words(H, W) words, needed for a list only), are zero on first use and zero again
+ *     when the frame ends.
+ *   launches: the list, if any, ORed into inBits (one launch, as in cbinfer_cbadd_forward); then
+ *     cbinfer_adaptive_pool_partials; then cbinfer_adaptive_pool_changed.  No host sync, no allocation, no waiting
+ *     between workgroups; the only atomics are 64-bit ORs into outBits.
+ * Status: a null tensor or mask buffer, C / H / W / oh / ow < 1, oh > H or ow > W, an unknown op or dtype, two of the
+ * buffers the same, both a mask and a list, a count without a list, a list without inBits, capN < 0: CB_ERR_BADARG;
+ * ow > 4096, H W, 64 C, (H + 1) oh, (W + 1) ow or the partials' element count beyond an int32: CB_ERR_UNSUPPORTED.  All arguments are checked
+ * before the first launch; a refused call launches nothing. */
+#define CB_ADAPT_MAX 0
+#define CB_ADAPT_AVG 1
+/* host, pure: 1 if the library pools an H x W map to oh x ow (the size rules above), else 0 */
+int cbinfer_adaptive_pool_supported(int H, int W, int oh, int ow);
+/* host, pure: the lanes L of the reduction along an N-long axis pooled to o (1 for a bad argument) */
+int cbinfer_adaptive_pool_lanes(int N, int o);
+/* host, pure: the elements (f32) of the partials, C H ow; 0 for a refused shape */
+long cbinfer_adaptive_pool_partial_elems(int C, int H, int W, int oh, int ow);
+/* Launch 1: partials and footprint.  The unit of work is (input row y, block of 32 channels) on a persistent grid; every
+ * unit forms the row's dirty column windows from the row's words of inputMask | inBits (either may be NULL; all != 0:
+ * every window) and recomputes its channels' partials of those windows, the lanes along x -- so each partial has ONE
+ * writer, also where a column window spans two mask words.  The first channel block of a row ORs the dirty windows into
+ * the one or two rows of outBits that hold y: one 64-bit atomicOr per dirty (row, output word).  inBits is only read. */
+int cbinfer_adaptive_pool_partials(const void* input, float* partials, const uint64_t* inputMask, const uint64_t* inBits,
+                                   int all, uint64_t* outBits, int C, int H, int W, int oh, int ow, int op, int dtype,
+                                   cbStream_t stream);
+/* Launch 2: the listed output pixels from the partials, one workgroup per word of outBits.  Every word of outBits is
+ * copied to maskCopy and zeroed; inBits != NULL: its cbinfer_mask_words(H, W) words are zeroed too.  No atomics. */
+int cbinfer_adaptive_pool_changed(const float* partials, void* output, uint64_t* inBits, uint64_t* outBits,
+                                  uint64_t* maskCopy, int C, int H, int W, int oh, int ow, int op, int dtype,
+                                  cbStream_t stream);
+/* The whole frame enqueued without a host sync: two launches in mask or every-pixel form, three in list form (capN == 0
+ * launches nothing for the list).  inputMask != NULL: mask form; changeIndexes != NULL: list form (capN entries at most,
+ * countDev the device-side length or NULL: capN is the length); both NULL: every pixel. */
+int cbinfer_cbadaptivepool2d_forward(const void* input, float* partials, void* outputState, const uint64_t* inputMask,
+                                     const int32_t* changeIndexes, int capN, const int32_t* countDev, uint64_t* inBits,
+                                     uint64_t* outBits, uint64_t* maskCopy, int C, int H, int W, int oh, int ow, int op,
+                                     int dtype, cbStream_t stream);
 
 /* replaces conv2d_fg_cpu, cbconv2d_fg_backend.cu:81-112: HOST pointers, host code, race-free. */
 void cbinfer_conv2d_fg_cpu(const float* input, const float* prevInput, float* output,
