@@ -116,6 +116,7 @@ ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2      # CB_ACT_*
 (PW_IDENTITY, PW_RELU, PW_HARDTANH, PW_LEAKY, PW_PRELU, PW_HARDSWISH, PW_HARDSIGMOID, PW_SIGMOID, PW_SILU,
  PW_TANH) = range(10)
 CH_LAYERNORM, CH_L2NORM, CH_SOFTMAX, CH_LOGSOFTMAX = range(4)      # CB_CH_*
+CC_SUM, CC_MEAN, CC_NORM, CC_MAX, CC_MIN, CC_ARGMAX, CC_ARGMIN = range(7)      # CB_CC_*
 
 
 class Upsample(ctypes.Structure):
@@ -338,6 +339,9 @@ _SIGNATURES = {
     "cbinfer_chanreduce_supported": (_i, [_i, _i, _f]),
     "cbinfer_chanreduce_changed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     "cbinfer_cbchanreduce_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    "cbinfer_chancollapse_supported": (_i, [_i, _i, _i]),
+    "cbinfer_chancollapse_changed": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "cbinfer_cbchancollapse_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "cbinfer_groupconv_supported": (_i, [_i, _i, _i, _gp]),
     "cbinfer_groupconv_prepared_weights_bytes": (_l, [_i, _i, _i, _gp, _i]),
     "cbinfer_groupconv_prep_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _gp, _i, _vp]),

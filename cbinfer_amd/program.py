@@ -81,7 +81,8 @@ class FrameProgram(object):
                                "(insertCBPointwise) for an activation or a batch norm, pycbinfer.CBPixelShuffle2d / "
                                "CBChannelShuffle2d (insertCBRearrange) for a pixel shuffle, unshuffle or channel shuffle, "
                                "pycbinfer.CBChannelReduce2d (insertCBChannelOps) for a channels-first layer norm, a "
-                               "softmax over the channels or an L2 normalisation, pycbinfer.CBResize2d (insertCBResize) "
+                               "softmax over the channels, an L2 normalisation, or an argmax, sum, mean, norm, max or min "
+                               "over the channels, pycbinfer.CBResize2d (insertCBResize) "
                                "for a resize to a size, by a fractional scale, downwards or bicubic, "
                                "pycbinfer.CBPad2d (insertCBPadding) for an explicit padding, "
                                "pycbinfer.CBBinary2d / CBGated / CBGLU2d (insertCBGating) for a product, a gate, a "

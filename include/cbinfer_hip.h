@@ -74,7 +74,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * resize to any size (cbResize, CB_RESIZE_*, cbinfer_resize_supported, cbinfer_cbresize_forward) and the padding (cbPad,
  * CB_PAD_*, cbinfer_pad_supported, cbinfer_pad_out_size, cbinfer_cbpad_forward) and the element-wise operators of two
  * maps (CB_BIN_*, cbinfer_binary_supported, cbinfer_binary_changed, cbinfer_cbbinary_forward) and the adaptive pools
- * (CB_ADAPT_*, cbinfer_adaptive_pool_*, cbinfer_cbadaptivepool2d_forward). */
+ * (CB_ADAPT_*, cbinfer_adaptive_pool_*, cbinfer_cbadaptivepool2d_forward) and the collapse of the channel axis
+ * (CB_CC_*, cbinfer_chancollapse_supported, cbinfer_chancollapse_changed, cbinfer_cbchancollapse_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -998,6 +999,61 @@ int cbinfer_chanreduce_changed(const void* x, void* out, const uint64_t* mask, i
 int cbinfer_cbchanreduce_forward(const void* x, void* outputState, const uint64_t* mask, const int32_t* list, int capN,
                                  const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int H, int W, int kind,
                                  float eps, const float* gamma, const float* beta, int dtype, cbStream_t stream);
+
+/* ---- change-based collapse of the channel axis: sum, mean, norm, max, min, argmax, argmin (cb_chancollapse.hip,
+ * DESIGN 5.27) -------------------------------------------------------------------------------------------------------
+ * The reference ends a scene-labelling frame with torch.max(y.cpu(), 1); it has no change-based form.  The output at a
+ * pixel depends on the C values at that pixel alone, so -- as for the reductions above -- recomputing at the operand's
+ * changed pixels is the dense result.  x is [C, H, W], contiguous, CB_F32 or CB_F16.  A call carries nOps = 1 .. 4 VALUE
+ * kinds (CB_CC_SUM .. CB_CC_MIN) or exactly ONE ARG kind (CB_CC_ARGMAX, CB_CC_ARGMIN), packed into the int `ops`: 4 bits
+ * per op, op k in bits 4k .. 4k+3, every bit from 4 nOps on zero.  (Plain ints: a recorded call holds no host array.)
+ *   value kinds: the state `out` is [nOps, H, W] in x's dtype, channel k is op k; every channel value is read ONCE.
+ *   arg kinds:   the state `out` is [H, W] int64.
+ *   listed pixels, masks, list form: exactly as for cbinfer_cbchanreduce_forward.
+ *   values: at listed pixels, all in f32, every operation correctly rounded in the order written, never contracted; one
+ *     rounding to f16 at the end for CB_F16 (a sum beyond the format's range is the infinity of its sign).
+ *       CB_CC_SUM      sum16(x)                              (sum16 as defined above: slices c mod 16, the fixed tree)
+ *       CB_CC_MEAN     sum16(x) / (float)C
+ *       CB_CC_NORM     sqrtf(sum16(x_c x_c))                 (torch.linalg.vector_norm(x, dim=1))
+ *       CB_CC_ARGMAX / CB_CC_ARGMIN   the smallest index c whose value is maximal / minimal under torch's CPU order: a
+ *                      NaN beats every number and the first NaN wins; +0 == -0 is a tie, the first index wins.  Taking
+ *                      the better of two (value, index) pairs under this order is associative, so the result does not
+ *                      depend on the tree: it is torch.argmax / torch.argmin (x, 1) exactly.
+ *       CB_CC_MAX / CB_CC_MIN   the value AT that index, x[argmax] / x[argmin]: torch.max(x, 1).values -- -0 where -0
+ *                      comes first in a +-0 tie, a NaN where any channel is one.
+ *     Every other pixel of `out` keeps its bits; a pixel's bits depend neither on the other listed pixels nor on the
+ *     operand's form.
+ *   hand-on: maskCopy receives the frame's mask every frame; `bits`, the working mask, is zero again when the launch
+ *     ends; bits of the row padding are never set.
+ *   labelMask (arg kinds only, may be NULL; cbinfer_mask_words(H, W) words): EVERY word is written.  A bit is set iff
+ *     the pixel is listed this frame and either every pixel is listed without change information (all form) or the new
+ *     label differs from the label `out` held before the launch.  A second mask beside maskCopy, not instead of it.
+ * All arguments are checked before the first launch.  A null tensor or mask buffer, x == out, bits == maskCopy, the
+ * operand's mask == bits or maskCopy, labelMask equal to any other argument buffer, labelMask with a value kind, both a
+ * mask and a list, a count without a list, capN < 0, nOps outside 1 .. 4, a kind above CB_CC_ARGMIN, bits of `ops` beyond
+ * its nOps kinds, an arg kind with nOps != 1, an unknown dtype, C / H / W < 1, H W or 64 C beyond an int32 return
+ * CB_ERR_BADARG and launch nothing.  There is no other limit on C. */
+#define CB_CC_SUM 0
+#define CB_CC_MEAN 1
+#define CB_CC_NORM 2
+#define CB_CC_MAX 3
+#define CB_CC_MIN 4
+#define CB_CC_ARGMAX 5
+#define CB_CC_ARGMIN 6
+/* host, pure: 1 if `ops` packs nOps (1 .. 4) value kinds or one arg kind and C >= 1, else 0 */
+int cbinfer_chancollapse_supported(int ops, int nOps, int C);
+/* The mask-driven launch.  mask: the operand's change mask, or NULL; all != 0: every pixel is listed.  The kernel ORs
+ * `bits` and mask word by word itself (or forms the full row word); without a mask the operand contributes what `bits`
+ * holds on entry.  No atomics. */
+int cbinfer_chancollapse_changed(const void* x, void* out, const uint64_t* mask, int all, uint64_t* bits,
+                                 uint64_t* maskCopy, uint64_t* labelMask, int C, int H, int W, int ops, int nOps,
+                                 int dtype, cbStream_t stream);
+/* The whole frame enqueued without a host sync.  mask != NULL: mask form, ONE launch (cbinfer_chancollapse_changed);
+ * list != NULL: list form, one launch in front, which ORs the list's bits into `bits` (capN == 0 launches nothing in
+ * front); both NULL: every pixel is listed, one launch. */
+int cbinfer_cbchancollapse_forward(const void* x, void* outputState, const uint64_t* mask, const int32_t* list, int capN,
+                                   const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, uint64_t* labelMask, int C,
+                                   int H, int W, int ops, int nOps, int dtype, cbStream_t stream);
 
 /* ---- change-based upsampling and channel concatenation for decoders (cb_decoder.hip) -------------------
  * No counterpart in the reference.  Both operators are exact for the reason the sum is: every producer leaves the pixels
