@@ -339,12 +339,14 @@ class SequenceBatch(object):
                         float(m.threshold), float(L['scale']), int(bool(m.withReLU)), ptr(L['ws'])]
                 if L.pop('detected', False):
                     # (the producing layer's row-pair launch was this frame's detection: the contraction alone)
-                    cargs = [seqs, S, ptr(L['wp']), ptr(m.bias.detach()), L['C'], L['H'], L['W'], L['K'], L['kH'],
-                             L['kW'], float(L['scale']), int(bool(m.withReLU)), ptr(L['ws']), 0]
+                    conv = dict(seqs=seqs, nSeq=S, prepared=ptr(L['wp']), bias=ptr(m.bias.detach()), C=L['C'], H=L['H'],
+                                W=L['W'], K=L['K'], kH=L['kH'], kW=L['kW'], weightScale=float(L['scale']),
+                                relu=int(bool(m.withReLU)), workspace=ptr(L['ws']), forceSplit=0, stream=st)
                     if L.get('tail') is not None:
-                        check(C.cbinfer_split_conv_tail(*(cargs + [ctypes.pointer(L['tail']), st])))
+                        fn = C.cbinfer_split_conv_tail
+                        check(fn(*fn.pack(tail=ctypes.pointer(L['tail']), **conv)))
                     else:
-                        check(C.cbinfer_split_conv(*(cargs + [st])))
+                        check(C.cbinfer_split_conv(*C.cbinfer_split_conv.pack(**conv)))
                 elif L.get('tail') is not None:
                     check(C.cbinfer_split_forward_tail(*(args + [0, ctypes.pointer(L['tail']), st])))
                 else:

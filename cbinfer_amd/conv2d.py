@@ -1192,41 +1192,42 @@ class CBConv2d(nn.Module):
             sp['stateKey'] = stateKey
         pmask = lazy.producerMask() if (lazy is not None and self._pmask_ok(rebuilt)) else None
         q = self._fill_seq(sp, work, src, pmask)
-        # (mode: bit 0 = behind a folded pool, bit 1 = not in feedback mode -- both states take every value of the frame)
-        args = [sp['seq'], 1, int(lazy is not None) | (0 if self.feedbackLoop else 2),
-                src.size(-2) if lazy is not None else 0,
-                src.size(-1) if lazy is not None else 0, ptr(wp), ptr(self.bias.detach()), Cin, H, W, K, kH, kW,
-                float(self.threshold), float(scale), int(bool(self.withReLU)), ptr(sp['ws'])]
+        # what every entry point of the family takes, by the header's parameter names ...
+        conv = dict(seqs=sp['seq'], nSeq=1, prepared=ptr(wp), bias=ptr(self.bias.detach()), C=Cin, H=H, W=W, K=K, kH=kH,
+                    kW=kW, weightScale=float(scale), relu=int(bool(self.withReLU)), workspace=ptr(sp['ws']),
+                    stream=stream_ptr(src))
+        # ... and what the frame's detection adds (mode: bit 0 = behind a folded pool, bit 1 = not in feedback mode -- both
+        # states take every value of the frame)
+        frame = dict(conv, mode=int(lazy is not None) | (0 if self.feedbackLoop else 2),
+                     pH=src.size(-2) if lazy is not None else 0, pW=src.size(-1) if lazy is not None else 0,
+                     threshold=float(self.threshold))
         # the fused 1x1 tail behind this layer (pycbinfer.fuseTail1x1) rides in the contraction's second launch
         tail = self._folded_tail(sp, H, W, dev)
-        # the contraction alone (cbinfer_split_conv[_tail]): for the frames whose detection the PRODUCING layer's
-        # launch has done already (cb_rowpair.hip; its change indexes carry this layer's token)
-        cargs = [sp['seq'], 1, ptr(wp), ptr(self.bias.detach()), Cin, H, W, K, kH, kW, float(scale),
-                 int(bool(self.withReLU)), ptr(sp['ws']), 0]
         # with a split-state consumer behind a lazy pool, the contraction in window order is its detection as well
         nextEligible, nxt, ntok, rawTok = self._window_fold(sp, tail, H, W)
-        if tail is not None:
-            fn, cfn = C.cbinfer_split_forward_tail, C.cbinfer_split_conv_tail
-            args += [0, ctypes.pointer(sp['tail']), stream_ptr(src)]
-            cargs += [ctypes.pointer(sp['tail']), stream_ptr(src)]
-        elif nxt is not None:
-            fn, cfn = C.cbinfer_split_forward_next, C.cbinfer_split_conv_next
-            args += [ctypes.pointer(nxt), stream_ptr(src)]
-            cargs = cargs[:-1] + [ctypes.pointer(nxt), stream_ptr(src)]      # (no forceSplit argument)
-        else:
-            fn, cfn = C.cbinfer_split_forward, C.cbinfer_split_conv
-            args += [stream_ptr(src)]
-            cargs += [stream_ptr(src)]
-        token = self._split_token(sp, prev)
-        done = lazy is not None and not rebuilt and getattr(lazy.indexes, 'nextDetect', None) == token
-        # (round 6: the row-pair layer in front left its state refresh to this launch's idle workgroups)
+        # fn(*args): the frame.  cfn(*cargs): the contraction alone (cbinfer_split_conv[_tail, _next]), for the frames whose
+        # detection the PRODUCING layer's launch has done already (cb_rowpair.hip; its change indexes carry this layer's token)
+        # sfn(*sargs): the contraction alone with a side job (round 6: the row-pair layer in front left its state refresh to this
+        # launch's idle workgroups)
         side = sp.get('side') or sp.setdefault('side', _lib.SideRefresh())
         sfn, sargs = None, None
-        if nxt is not None:
-            sfn, sargs = C.cbinfer_split_conv_next_refresh, cargs[:-1] + [ctypes.pointer(side), cargs[-1]]
-        elif (tail is None and sp['arith'] == 'x3' and
-              C.cbinfer_split_refresh_supported(Cin, K, kH, kW, H, W)):      # (pixel order: cbinfer_split_conv's arguments)
-            sfn, sargs = C.cbinfer_split_conv_refresh, cargs[:-2] + [ctypes.pointer(side), cargs[-1]]
+        if tail is not None:
+            fn, cfn = C.cbinfer_split_forward_tail, C.cbinfer_split_conv_tail
+            more = dict(forceSplit=0, tail=ctypes.pointer(sp['tail']))
+            args, cargs = list(fn.pack(**frame, **more)), list(cfn.pack(**conv, **more))
+        elif nxt is not None:
+            fn, cfn, sfn = C.cbinfer_split_forward_next, C.cbinfer_split_conv_next, C.cbinfer_split_conv_next_refresh
+            more = dict(next=ctypes.pointer(nxt))
+            args, cargs = list(fn.pack(**frame, **more)), list(cfn.pack(**conv, **more))
+            sargs = list(sfn.pack(side=ctypes.pointer(side), **conv, **more))
+        else:
+            fn, cfn = C.cbinfer_split_forward, C.cbinfer_split_conv
+            args, cargs = list(fn.pack(**frame)), list(cfn.pack(forceSplit=0, **conv))
+            if sp['arith'] == 'x3' and C.cbinfer_split_refresh_supported(Cin, K, kH, kW, H, W):      # (pixel order)
+                sfn = C.cbinfer_split_conv_refresh
+                sargs = list(sfn.pack(side=ctypes.pointer(side), **conv))
+        token = self._split_token(sp, prev)
+        done = lazy is not None and not rebuilt and getattr(lazy.indexes, 'nextDetect', None) == token
         pend = self.__dict__.get('_sidePending')
         if pend is not None and done and sargs is not None:
             self.__dict__.pop('_sidePending')
@@ -1746,18 +1747,22 @@ class CBConv2d(nn.Module):
         mapOut = work['map'] if (self.saveChangeMap and not have) else None
         if cap > 0:
             arith = self._arith(input)
-            args = (ptr(input), ptr(self.prevInput), ptr(self.prevOutput), None if have else ptr(work['bits']),
-                    ptr(idx), ptr(count), ptr(mapOut), ptr(self._prepared_weights(H, W, arith)),
-                    ptr(self.bias.detach()), Cin, H, W, K, kH, kW, float(self.threshold),
-                    int(bool(self.feedbackLoop)), int(bool(self.copyInput)), int(bool(self.withReLU)),
-                    int(have), cap, ptr(work['conv']),
-                    int(work['selfc'] and not have), arith, stream_ptr(input))
+            frame = dict(input=ptr(input), prevInput=ptr(self.prevInput), prevOutput=ptr(self.prevOutput),
+                         bits=None if have else ptr(work['bits']), idx=ptr(idx), countDev=ptr(count),
+                         weightsPrepared=ptr(self._prepared_weights(H, W, arith)), bias=ptr(self.bias.detach()), C=Cin, H=H,
+                         W=W, K=K, kH=kH, kW=kW, threshold=float(self.threshold), feedbackLoop=int(bool(self.feedbackLoop)),
+                         copyInput=int(bool(self.copyInput)), relu=int(bool(self.withReLU)), workspace=ptr(work['conv']),
+                         dtype=arith, stream=stream_ptr(input))
+            # (the parameter order is asked of the binding itself: this module's C may be a wrapper that notes the calls --
+            #  the tests' spies hand out plain functions -- and the call below must still go through it)
+            args = _lib.C.cbinfer_cbconv2d_forward.pack(mapOut=ptr(mapOut), haveIndexes=int(have), capN=cap,
+                                                        selfCompact=int(work['selfc'] and not have), **frame)
             check(C.cbinfer_cbconv2d_forward(*args))
             if not have and not self._inputIsLiveState:
                 if work['selfc'] and mapOut is None:
                     # replayed through the chained entry: a frame in which the layer that produced `input` rewrote
                     # nothing ends both launches at once (_upstream_count decides per frame whether that may be said)
-                    cargs = (None,) + args[:6] + args[7:19] + (args[21], args[23], args[24])
+                    cargs = _lib.C.cbinfer_cbconv2d_forward_after.pack(upstreamCount=None, **frame)
                     self._make_plan(False, input, C.cbinfer_cbconv2d_forward_after, cargs, 1)
                     if self._plan is not None:
                         self._plan['chain'] = True
