@@ -193,9 +193,14 @@ struct ConvParams {
 // The layer that produced this layer's input published a change count of zero for this frame: the detection in front
 // of this launch returned at once and left the mask empty, the frame does not exist for this layer -- no mask to read
 // or zero, no parity to flip (the mask the parity selects is still the clean one).  Its own count goes out as zero,
-// so that the layer behind it is skipped the same way.
+// so that the layer behind it is skipped the same way -- and the frame's mask COPY as empty: a module behind the layer
+// that is handed the copy as this frame's change mask (MaskChangeIndexes) would else read the frame before's.
 #define CB_UPSTREAM_IDLE_EXIT                                                          \
     if (SELFC && p.upstream && *p.upstream == 0) {                                     \
+        unsigned long long* idleCopy = p.frameMasks + 2 * (long)p.maskWords + 2;       \
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < p.maskWords;           \
+             i += gridDim.x * blockDim.x)                                              \
+            idleCopy[i] = 0ull;                                                        \
         if (blockIdx.x == 0 && threadIdx.x == 0) {                                     \
             p.countOut[0] = 0;                                                         \
             if (p.seam) p.tickets[CB_SEAM_INFO] = 0;                                   \
@@ -1614,7 +1619,8 @@ int cbinfer_conv_changed_from_mask(const void* input, uint64_t* frameMasks, int3
 }
 
 // upstreamCount (optional, device): the change count the layer that produced `input`'s source published this frame;
-// zero ends the launch at once with countOut = 0 and the masks untouched (cbinfer_cbconv2d_forward_after).
+// zero ends the launch at once with countOut = 0, the two masks untouched and the frame's mask copy empty
+// (cbinfer_cbconv2d_forward_after).
 int cbinfer_conv_changed_from_mask_after(const int32_t* upstreamCount, const void* input, uint64_t* frameMasks,
                                          int32_t* idxOut, int32_t* countOut, const void* weightsPrepared,
                                          const void* bias, void* output, int C, int H, int W, int K, int kH, int kW,

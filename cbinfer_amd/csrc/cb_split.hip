@@ -514,6 +514,10 @@ __global__ __launch_bounds__(64 * WM * WN) void cbs_conv_kernel(CbsParams p, typ
     constexpr bool HALF = AR == 1, X3 = AR == 2 || AR == 3 || AR == 4, WIN = AR == 3, SIDE = AR == 3 || AR == 4;
     // (before anything else -- the burst over the kilobyte of arguments included: an idle frame is this one load)
     if (HALF && p.upstream && *p.upstream == 0) {      // (the detection in front returned the same way: the mask is empty)
+        // (... and so is the frame's copy of it: a module behind the layer is handed the copy as this frame's change mask)
+        if (p.seq[0].maskCopy)
+            for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < p.maskWords; i += gridDim.x * blockDim.x)
+                p.seq[0].maskCopy[i] = 0ull;
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             p.seq[0].countOut[0] = 0;
             if (p.info) p.info[CBS_INFO_SK] = 1;      // (nothing for the second launch)

@@ -235,7 +235,8 @@ int cbinfer_conv_changed_from_mask(const void* input, uint64_t* frameMasks, int3
  * PRODUCING layer's contraction left its change count in this frame (its countDev).  Zero there: the producer
  * rewrote no output pixel, this layer's input is bit for bit what it compared with its state last frame, the
  * detection could find nothing -- both launches return after one scalar load, countDev receives 0 (so that the
- * next layer of the chain is skipped the same way), masks, parity, state and output stay as they are.  Non-zero
+ * next layer of the chain is skipped the same way), masks, parity, state and output stay as they are; the copy of
+ * the frame's mask behind the masks is left EMPTY, as the count is (a module handed it reads this frame's).  Non-zero
  * (or upstreamCount = NULL): cbinfer_cbconv2d_forward(selfCompact=1) exactly.  The CALLER guarantees the premise:
  * same input buffer and threshold as in this layer's previous frame, which followed the producer's previous frame;
  * no other writer to that buffer.  (cbinfer_amd/conv2d.py: CBConv2d._upstream_count checks it per frame.) */

@@ -519,6 +519,25 @@ def test_from_mask_after_idle(lib, oracle, lid):
     assert_header_at_rest(ws, lid)
 
 
+@pytest.mark.parametrize("lid", ["f32-64-w65-ws", "f32s-128-w65-seam", "f16-64-w65-ws"])
+def test_from_mask_after_idle_empties_the_mask_copy(lib, oracle, lid):
+    """The frame before left its mask in the copy behind the two masks.  An upstream count of zero goes out as a count of
+    zero AND an empty copy -- the copy is what a module behind the layer is handed as THIS frame's change mask -- and
+    touches nothing else: masks, control words, list, output, workspace."""
+    L = _layer(lib, oracle, lid)
+    m = three_frames(L.H, L.W, L.frac, 4)[0][1]
+    fr = Frame(lib, L.H, L.W)
+    fr.copy().copy_(dev(pack_mask(m, fr.wpr)))
+    assert int((fr.copy() != 0).sum()) > 0
+    ws = new_workspace(lib)
+    out = torch.full((1, L.K, L.H, L.W), FILL, dtype=L.tdtype, device="cuda")
+    snap = [t.clone() for t in (fr.buf[:fr.copy_at], fr.idx, out, ws[:4096])]
+    assert conv_from_mask(lib, L, fr, out, ws, upstream=dev(np.array([0], dtype=np.int32))) == CB_OK
+    assert fr.count.tolist() == [0] and int((fr.copy() != 0).sum()) == 0
+    for a, b in zip(snap, (fr.buf[:fr.copy_at], fr.idx, out, ws[:4096])):
+        assert torch.equal(a, b)
+
+
 @pytest.mark.parametrize("lid,dtype,K", [("f32-64-acc", "F32", 64), ("f32s-128-acc-seam", "F32S", 128),
                                          ("f32s-256-acc-seam", "F32S", 256)])
 def test_accumulate_from_mask(lib, oracle, lid, dtype, K):

@@ -1642,6 +1642,34 @@ def test_chained_layers_skip_idle_frames_bit_identically(pkg, dtype, feedback, m
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("kernels", ["list", "hsplit"])
+def test_a_skipped_frame_hands_on_an_empty_mask(pkg, kernels, monkeypatch):
+    """A chained fp16 layer whose launches end at once -- its producer rewrote nothing -- publishes a change count of
+    zero.  The mask it hands on beside that count (propChangeIndexes: a MaskChangeIndexes on the copy of the frame's
+    mask) must be empty too: the early exit used to leave the frame before's there, so a module behind the layer that
+    reads the mask (CBPointwise2d, CBUpsample2d, ...) recomputed and handed on that frame's pixels on an idle frame.
+    Found by tests/test_gpu_chain.py; in every frame the mask holds exactly the listed pixels."""
+    if kernels == "list":
+        monkeypatch.setenv("CBINFER_NO_SPLIT", "1")
+    net = _chain_net(pkg, torch.float16, False, 5)[:2]
+    net[1].propChangeIndexes = True
+    frames = _chain_frames(np.random.default_rng(7), 8, 24, 46, 81, torch.float16)
+    seen = []
+    with torch.no_grad():
+        for t, f in enumerate(frames):
+            tag, y, ix = net(f)
+            assert tag == 'changeIndexes' and ix._made and tuple(ix.size) == (46, 81)
+            assert bool(net[1].__dict__['_ranSplit']) == (kernels == "hsplit")
+            lst = ix.tensor().cpu().numpy()
+            words = ix._mask.cpu().numpy().view(np.uint64)
+            bits = np.unpackbits(words.view(np.uint8), bitorder='little').reshape(46, -1)[:, :81]
+            assert words.size == 46 * 2 and np.array_equal(np.flatnonzero(bits.reshape(-1)), lst), (kernels, t)
+            seen.append((net[1].__dict__.get('_upNow') is not None, int(net[0].lastChangeIndexes().numel()), lst.size))
+    # (an idle frame in which the skip was offered and taken, behind a frame that listed something)
+    assert any(a[2] > 0 and b == (True, 0, 0) for a, b in zip(seen[2:], seen[3:])), seen
+
+
+@pytest.mark.gpu
 def test_chained_layers_do_not_skip_what_they_must_see(pkg, monkeypatch):
     """The premises of the skip, each broken once: (a) somebody writes to the producer's output buffer through torch
     between the layers; (b) the consumer misses one of the producer's frames; (c) the consumer's state is rewritten

@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn as nn
 
+import chain_cases as cc
+
 
 @pytest.fixture(scope="module")
 def pkg():
@@ -375,6 +377,75 @@ def test_refusals_keep_their_order(pkg, Err):
                        (lambda: pkg.CBConcat2d()([x, x]), "HIP devices only")):
         with pytest.raises(Err, match=what):
             call()
+
+
+# ------------------------------------------------------------------------------------------------ the GPU cases
+def test_every_accepted_pair_has_a_gpu_case(pkg, chain):
+    """tests/chain_cases.py, which tests/test_gpu_chain.py runs on the device, covers exactly the (pass, producer type)
+    pairs the table accepts: a row added to PRODUCERS, or a pass added to PASSES, without a case there fails here by
+    name, and so does a case for a pair the table no longer accepts.  Both kinds of CBPoolMax2d wherever the type is."""
+    accepted = {(p, T.__name__) for p in chain.PASSES for T in chain.producers(p)}
+    covered = cc.pairs()
+    missing, stale = sorted(accepted - covered), sorted(covered - accepted)
+    assert not missing, "accepted by chain.PRODUCERS, no case in tests/chain_cases.py: %s" % (missing,)
+    assert not stale, "a case in tests/chain_cases.py, not accepted by chain.PRODUCERS: %s" % (stale,)
+    assert len(accepted) == 155 and tuple(cc.BEHIND) == tuple(chain.PASSES) == tuple(cc.PASSES)
+    for passName, behind in cc.BEHIND.items():
+        assert ('CBPoolMax2d 2x2' in behind) == ('CBPoolMax2d 3x3' in behind) == (
+            pkg.CBPoolMax2d in chain.producers(passName)), passName
+        assert len(set(behind)) == len(behind) and set(behind) <= set(cc.PRODUCERS), passName
+    assert len(set(cc.CASES)) == len(cc.CASES) == 155 + 9 + 3      # (+ a second pool kind, + a second general pool)
+    assert {cc.producer_type(c) for c in cc.CASES} == {name for name, _, rule, passes in chain.PRODUCERS
+                                                       if rule is chain.BUT or passes}
+
+
+@pytest.mark.parametrize("case", cc.CASES, ids=cc.case_id)
+def test_the_pass_wires_every_gpu_case(pkg, chain, case):
+    """The pass, run on the case's network, really puts its change-based operator behind the producer and switches the
+    producer's change output on where chain.hand_on_changes does -- else the GPU test would compare two dense networks.
+    And the condition of that test's listed-share cap: by numpy dilation the footprint of the one- and two-pixel frames
+    stays far below half of the operator's map."""
+    for cloneOutput in (True, False):
+        net = cc.build(pkg, case, cloneOutput=cloneOutput)
+        stem, prod, op = net.seq
+        assert type(stem) is pkg.CBConv2d and type(prod).__name__ == cc.producer_type(case), case
+        assert type(prod) in chain.producers(case.passName), case
+        assert type(op).__name__ == cc.OPS[case.op].becomes and type(op).__module__.startswith('cbinfer_amd'), case
+        assert op.cloneOutput is cloneOutput, case
+        target = cc.hand_on_target(prod)
+        assert getattr(target, 'cloneOutput', cloneOutput) is cloneOutput, case
+        assert target.propChangeIndexes == (case.passName not in cc.OWN_DETECTION), case
+        assert stem.propChangeIndexes == cc.PRODUCERS[case.producer].fed or case.passName == 'linkDepthwise', case
+        if case.producer.startswith('CBPoolMax2d'):
+            assert bool(prod.__dict__['_general']) == case.producer.endswith('3x3'), case
+            assert prod.downsampleIndexes == (case.producer.endswith('2x2') and target.propChangeIndexes), case
+        if case.passName == 'linkDepthwise':
+            assert op.propagatedChanges, case
+        if type(op) is pkg.CBPoolMax2d:
+            assert bool(op.__dict__['_general']) == (case.passName == cc.GENERAL_POOLS), case
+        assert (net.second is not None) == cc.PRODUCERS[case.producer].two
+    maps = cc.changed()
+    assert [int(m.sum()) for m in maps[:6]] == [cc.H * cc.W, 1, 2, 1, 0, 1] and maps[7].all() and maps[6].sum() > 9
+    for t in cc.LOCAL:
+        listed = cc.footprint(case, maps[t])
+        assert listed.any() and listed.mean() < 0.5, (case, t, float(listed.mean()))
+    assert not cc.footprint(case, maps[cc.IDLE]).any() and cc.footprint(case, maps[0]).all(), case
+
+
+def test_gpu_frames_are_what_the_cases_say():
+    """Eight frames: values in [0, 0.9], exact in float16; a frame differs from the one before at exactly the pixels of
+    changed(), by 0.5 in every channel -- ten times the stem's threshold in both dtypes."""
+    maps = cc.changed()
+    for dtype in (torch.float32, torch.float16):
+        fr = cc.frames(dtype)
+        assert len(fr) == len(maps) == 8 and all(tuple(f.shape) == (1, 3, cc.H, cc.W) and f.dtype == dtype for f in fr)
+        assert all(torch.equal(f.double(), g.double()) for f, g in zip(fr, cc.frames(torch.float32)))
+        assert all(0.0 <= float(f.min()) and float(f.max()) <= 0.9 for f in fr)
+        for t in range(1, 8):
+            moved = (fr[t].double() - fr[t - 1].double()).abs()[0]
+            assert bool((moved[:, torch.from_numpy(maps[t])] == 0.5).all()), t
+            assert bool((moved[:, torch.from_numpy(~maps[t])] == 0.0).all()), t
+        assert torch.equal(fr[cc.IDLE], fr[cc.IDLE - 1])
 
 
 # ------------------------------------------------------------------------------------------------ recorded
