@@ -31,6 +31,7 @@ from .chanreduce import CBChannelReduce2d, insertCBChannelOps
 from .resize import CBResize2d, insertCBResize
 from .pad import CBPad2d, insertCBPadding, splitConvPadding
 from .binary import CBBinary2d, CBGLU2d, CBGated, insertCBGating
+from .chanscale import CBChannelScale2d, CBSqueezeExcite, insertCBSqueezeExcite
 
 __version__ = "0.1.0"
 
@@ -290,10 +291,14 @@ def linkConsumers(producer, consumers):
 _STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d,
              CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d, CBChannelReduce2d,
              CBResize2d, CBPad2d, CBBinary2d, CBGLU2d)
+# The channel attention scale keeps state too.  It stands beside the table: _STATEFUL, chain.PRODUCERS and `__all__` list
+# the same module types, and the scale is no row of chain.PRODUCERS yet (a producer for no pass of its own; making it one
+# for the other passes is a follow-up).  CBSqueezeExcite is a wrapper: its pool and its scale are reached as children.
+_CHANNEL_STATE = (CBChannelScale2d,)
 
 
 def _stateful(net):
-    return [m for m in net.modules() if type(m) in _STATEFUL]
+    return [m for m in net.modules() if type(m) in _STATEFUL or type(m) in _CHANNEL_STATE]
 
 
 def clearMemory(net):
@@ -414,4 +419,6 @@ __all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CB
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',
-           'setSyncIndexes', 'tuneThresholdParameters']
+           'setSyncIndexes', 'tuneThresholdParameters', 'insertCBSqueezeExcite']
+# (CBChannelScale2d and CBSqueezeExcite are attributes of the package and of the pycbinfer alias, but no entries of
+#  `__all__`: its CB names are the rows of chain.PRODUCERS, see _CHANNEL_STATE above)

@@ -75,7 +75,9 @@ typedef void* cbStream_t; /* hipStream_t */
  * CB_PAD_*, cbinfer_pad_supported, cbinfer_pad_out_size, cbinfer_cbpad_forward) and the element-wise operators of two
  * maps (CB_BIN_*, cbinfer_binary_supported, cbinfer_binary_changed, cbinfer_cbbinary_forward) and the adaptive pools
  * (CB_ADAPT_*, cbinfer_adaptive_pool_*, cbinfer_cbadaptivepool2d_forward) and the collapse of the channel axis
- * (CB_CC_*, cbinfer_chancollapse_supported, cbinfer_chancollapse_changed, cbinfer_cbchancollapse_forward). */
+ * (CB_CC_*, cbinfer_chancollapse_supported, cbinfer_chancollapse_changed, cbinfer_cbchancollapse_forward) and the
+ * channel attention scale (CB_CS_*, cbinfer_chanscale_supported, cbinfer_chanscale_gate, cbinfer_chanscale_changed,
+ * cbinfer_cbchanscale_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1333,6 +1335,61 @@ int cbinfer_cbbinary_forward(const void* a, const void* b, void* outputState, co
                              int capA, const int32_t* countA, const uint64_t* maskB, const int32_t* listB, int capB,
                              const int32_t* countB, int bForm, int bChanges, uint64_t* bits, uint64_t* maskCopy, int C,
                              int H, int W, int op, int gate, int reverse, int dtype, cbStream_t stream);
+
+/* ---- change-based channel attention scale (cb_chanscale.hip) ---------------------------------------------
+ * No counterpart in the reference.  out[c, p] = a[c, p] * held[c]: the excite of a squeeze-and-excitation block.  a and
+ * the state `out` are [C, H, W], contiguous, one dtype (CB_F32 or CB_F16), two different tensors, 1 <= C <= 4096.  The
+ * gate vector of a frame moves a little in every frame; a channel whose gate moved by no more than `threshold` keeps the
+ * gate it last used, held[c], and only a channel that moved by more -- it TRIPPED -- has its whole plane recomputed.
+ *
+ * THIS SECTION IS THE SPECIFICATION; tests/chanscale_cases.py is its numpy twin.
+ *   s [C], f32, from one of two sources:
+ *     plain (R == 0; w1, b1, w2, b2 NULL; act CB_CS_ACT_NONE): s[c] = (float)v[c], v [C] in the dtype of `a`;
+ *     excitation (1 <= R <= 1024; act CB_CS_ACT_RELU or CB_CS_ACT_SILU): v is the pooled vector z [C] in the dtype of
+ *       `a`, w1 [R, C], w2 [C, R] f32, b1 [R] / b2 [C] f32 or NULL (then nothing is added):
+ *         hidden[r] = act(sum16_c(w1[r, c] * z[c]) + b1[r]),   s[c] = sum16_r(w2[c, r] * hidden[r]) + b2[c],
+ *       every product and sum a correctly rounded f32 operation of its own, never an FMA; sum16 is the order of
+ *       tests/chanreduce_cases.py: 16 partial sums by index mod 16, each from +0 in ascending index, then the fixed tree
+ *       p[2i] + p[2i+1];  ReLU: v < 0 ? 0 : v;  SiLU: v / (1 + expf(-v)).
+ *   gate[c] = g(s[c]) in f32: CB_CS_GATE_NONE s;  CB_CS_GATE_SIGMOID 1 / (1 + expf(-s)) (the device's expf);
+ *     CB_CS_GATE_HARDSIGMOID clamp(s + 3, 0, 6) / 6 with clamp(t, lo, hi) = t < lo ? lo : (t > hi ? hi : t).
+ *   channel c trips iff all != 0 or !(fabsf(gate[c] - held[c]) <= threshold): strictly more than the threshold, and a
+ *     NaN trips.  A tripped channel takes held[c] = gate[c]; any other keeps held[c] bit for bit, so slow drift adds up
+ *     until it trips.  tripped: ceil(C / 64) words, bit c % 64 of word c / 64, every word written every frame, the bits
+ *     beyond C zero; tripCount: their number.
+ *   values: out[c, p] = (T)((float)a[c, p] * held[c]), one f32 product, one rounding to T, written
+ *     at a listed pixel p for every channel c, and at every other pixel for the tripped channels.
+ *   Every other element of `out` keeps its bits.
+ *   listed pixels: `a` arrives as its row-padded change MASK, as an int32 LIST, or not at all (every pixel is listed), as
+ *     for the operators above; with all != 0 every pixel is listed and the operand's change information is not read.
+ *   hand-on: maskCopy receives the frame's mask every frame: the listed pixels, or every pixel of the map in a frame in
+ *     which a channel tripped (a per-pixel mask cannot name a channel); `bits`, the working mask, is zero again when the
+ *     launch ends.
+ * Bad arguments -- a null tensor or buffer, C < 1 or > 4096, R < 0 or > 1024, an unknown dtype, gate or act, an act that
+ * does not go with R, weights without R or R without weights, a negative or NaN threshold, `out` aliasing an operand,
+ * gate == held, both a mask and a list, a count without a list, a negative capacity, bits == maskCopy, the operand's
+ * mask == bits or maskCopy, H W beyond an int32 -- return CB_ERR_BADARG and launch nothing. */
+enum { CB_CS_GATE_NONE, CB_CS_GATE_SIGMOID, CB_CS_GATE_HARDSIGMOID };
+enum { CB_CS_ACT_NONE, CB_CS_ACT_RELU, CB_CS_ACT_SILU };
+/* host, pure: 1 if (gate, act, C, R) is a combination above, else 0 */
+int cbinfer_chanscale_supported(int gate, int act, int C, int R);
+/* Launch 1, ONE workgroup: s, gate, the trip decisions, held, tripped and tripCount as above.  No atomics. */
+int cbinfer_chanscale_gate(const void* v, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                           float* held, uint64_t* tripped, int32_t* tripCount, int C, int R, int gateFn, int act,
+                           float threshold, int all, int dtype, cbStream_t stream);
+/* Launch 2, the mask-driven one: reads held, tripped and tripCount as launch 1 left them on the same stream.  maskA: the
+ * operand's change mask, or NULL: the operand contributes what `bits` holds on entry; all != 0: every pixel is listed. */
+int cbinfer_chanscale_changed(const void* a, void* out, const float* held, const uint64_t* tripped,
+                              const int32_t* tripCount, const uint64_t* maskA, int all, uint64_t* bits, uint64_t* maskCopy,
+                              int C, int H, int W, int dtype, cbStream_t stream);
+/* The whole frame enqueued without a host sync: launch 1 and launch 2, an operand in list form costs one launch in
+ * front.  maskA != NULL: mask form; listA != NULL: list form (capA entries at most, countA the device-side length or
+ * NULL); both NULL: every pixel is listed.  all != 0 (a fresh state): every channel trips and every pixel is written. */
+int cbinfer_cbchanscale_forward(const void* a, const void* v, const float* w1, const float* b1, const float* w2,
+                                const float* b2, void* outputState, float* gate, float* held, uint64_t* tripped,
+                                int32_t* tripCount, const uint64_t* maskA, const int32_t* listA, int capA,
+                                const int32_t* countA, uint64_t* bits, uint64_t* maskCopy, int C, int R, int H, int W,
+                                int gateFn, int act, float threshold, int all, int dtype, cbStream_t stream);
 
 /* ---- transposed convolution (cb_tconv.hip) ------------------------------------------------------------
  * The reference has no counterpart: its CBConv2d asserts transposed == False (conv2d.py:92-104).  Input map Hi x Wi,

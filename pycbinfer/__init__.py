@@ -8,6 +8,7 @@ import sys
 
 import cbinfer_amd
 from cbinfer_amd import *            # noqa: F401,F403
+from cbinfer_amd import CBChannelScale2d, CBSqueezeExcite, chanscale      # noqa: F401  (no entries of __all__)
 from cbinfer_amd import binary, chanreduce, conv2d, conv2d_cg, conv2d_fg, decoder, dwconv, groupconv, pad, pointwise, rearrange, residual, resize, tconv
 
 sys.modules[__name__ + '.conv2d'] = conv2d
@@ -24,5 +25,6 @@ sys.modules[__name__ + '.chanreduce'] = chanreduce
 sys.modules[__name__ + '.resize'] = resize
 sys.modules[__name__ + '.pad'] = pad
 sys.modules[__name__ + '.binary'] = binary
+sys.modules[__name__ + '.chanscale'] = chanscale
 
 __all__ = cbinfer_amd.__all__
