@@ -12,8 +12,8 @@ import torch.nn as nn
 from . import _lib                      # loads libcbinfer_hip.so; raises ImportError if not built
 from . import chain
 from .conv2d import CBConv2d
-from .conv2d import CBPoolMax2d
-from .conv2d import CBPoolAvg2d
+from .pool import CBPoolMax2d
+from .pool import CBPoolAvg2d
 from .conv2d import CBTail1x1
 from .conv2d_cg import ChangeIndexes, ChannelConcat
 from .pipeline import FramePipeline

@@ -23,7 +23,8 @@ import torch
 
 from . import _lib
 from ._lib import C, CBinferError, check, ptr, stream_ptr
-from .conv2d import CBConv2d, CBPoolAvg2d, CBPoolMax2d, CBTail1x1, _switch
+from .conv2d import CBConv2d, CBTail1x1, _switch
+from .pool import CBPoolAvg2d, CBPoolMax2d
 from .residual import CBAdd2d
 from .decoder import CBConcat2d, CBUpsample2d
 from .tconv import CBConvTranspose2d

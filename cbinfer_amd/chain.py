@@ -4,8 +4,9 @@ The frame: how an operand and its change information are taken apart (split_oper
 form that lists every pixel (EVERY_PIXEL) and how a form is handed to the library (form_args), the ONE test for a state
 that no longer fits its frame (state_fits: these modules and the layers of layer.py), the mask workspace and
 hand-back of every mask-driven module, and CBStateModule, which CBAdd2d, CBPointwise2d, CBUpsample2d, CBConcat2d, the
-shuffles, CBChannelReduce2d, CBResize2d, CBPad2d, CBBinary2d and CBGLU2d derive from: the flags, the keyed workspace
-cache (_cached_work) and the state step (_fresh_state).
+shuffles, CBChannelReduce2d, CBResize2d, CBPad2d, CBBinary2d, CBGLU2d, CBChannelScale2d and the pools of pool.py
+(CBPoolMax2d, CBPoolAvg2d) derive from: the flags, the keyed workspace cache (_cached_work) and the state step
+(_fresh_state).
 
 The passes: the ONE table that says which module type counts as a producer for which pass (PRODUCERS, one row per
 module type of the package, the exceptions as data) and its accessor (producers(passName)), what is switched on at a
@@ -100,9 +101,10 @@ def form_args(form):
 
 
 # ---------------------------------------------------------------------------------------------------- state
-def state_fits(state, shape, like):
-    """Whether the state tensor `state` still serves a frame: it has `shape`, and the dtype and device of `like`."""
-    return (state is not None and tuple(state.size()) == tuple(shape) and state.dtype == like.dtype and
+def state_fits(state, shape, like, dtype=None):
+    """Whether the state tensor `state` still serves a frame: it has `shape`, and the dtype and device of `like`.
+    dtype: the state's own where it is not the frame's (the f32 partials of an adaptive pool)."""
+    return (state is not None and tuple(state.size()) == tuple(shape) and state.dtype == (dtype or like.dtype) and
             state.device == like.device)
 
 
@@ -116,16 +118,20 @@ def mask_workspace(Ho, Wo, dev, nbits=1):
                 count=torch.zeros(1, dtype=torch.int32, device=dev))
 
 
-def hand_back(module, state, copy, size, work, made=False):
-    """What a frame returns: a private copy of `state` -- or, with cloneOutput=False, the state itself, tagged, so that a
-    consumer that keeps a reference copies it then -- and with propChangeIndexes the frame's mask `copy` on the
-    size = (Ho, Wo) output map as a MaskChangeIndexes.  made: the frame's kernel already left the list and its count in
-    work['idx'] / work['count'] (CBGroupedConv2d), so a consumer that wants the list launches nothing for it."""
+def frame_output(module, state):
+    """The tensor a frame returns: a private copy of `state` -- or, with cloneOutput=False, the state itself, tagged, so
+    that a consumer that keeps a reference (a CBConv2d with copyInput=False) copies it then."""
     if getattr(module, 'cloneOutput', True):
-        output = state.clone()
-    else:
-        output = state
-        output._cbinfer_inplace_state = True
+        return state.clone()
+    state._cbinfer_inplace_state = True
+    return state
+
+
+def hand_back(module, state, copy, size, work, made=False):
+    """What a frame returns: frame_output, and with propChangeIndexes the frame's mask `copy` on the size = (Ho, Wo)
+    output map as a MaskChangeIndexes.  made: the frame's kernel already left the list and its count in work['idx'] /
+    work['count'] (CBGroupedConv2d), so a consumer that wants the list launches nothing for it."""
+    output = frame_output(module, state)
     if module.propChangeIndexes:
         return 'changeIndexes', output, MaskChangeIndexes(copy, size, work['idx'], work['count'], made=made)
     return output
@@ -169,13 +175,14 @@ class CBStateModule(nn.Module):
             work = self.__dict__[self._WORK] = dict(make(), key=key)
         return work
 
-    def _fresh_state(self, shape, like):
+    def _fresh_state(self, shape, like, fill=None):
         """Keep outputState if it still serves a frame of `shape` with the dtype and device of `like`; else allocate it
         and return True: a new state is written completely, so the caller uses no operand's change information
-        (EVERY_PIXEL)."""
+        (EVERY_PIXEL).  fill: the value of a new state whose frame does go by the operand's list (the max pools: +inf)."""
         if state_fits(self.outputState, shape, like):
             return False
-        self.outputState = torch.empty(tuple(shape), dtype=like.dtype, device=like.device)
+        state = torch.empty(tuple(shape), dtype=like.dtype, device=like.device)
+        self.outputState = state if fill is None else state.fill_(fill)
         return True
 
     def _result(self, work, Ho, Wo):
@@ -195,8 +202,8 @@ BUT, ONLY = 'all passes but', 'only'
 PRODUCERS = (
     ('CBConv2d', 'conv2d', BUT, ()),
     # (insertCBPooling is the reference's hand-written rule: behind a CBConv2d, nothing else)
-    ('CBPoolMax2d', 'conv2d', BUT, _POOLS),
-    ('CBPoolAvg2d', 'conv2d', BUT, _POOLS),
+    ('CBPoolMax2d', 'pool', BUT, _POOLS),
+    ('CBPoolAvg2d', 'pool', BUT, _POOLS),
     ('CBAdd2d', 'residual', BUT, _POOLS),
     ('CBResidual', 'residual', BUT, _POOLS),
     ('CBUpsample2d', 'decoder', BUT, _POOLS),
@@ -241,7 +248,7 @@ def hand_on_changes(prod):
     at its `.add`, a CBGated's at its `.mul`); a 2x2 CBPoolMax2d of the reference's kind also hands on the
     OUTPUT-resolution list."""
     from .binary import CBGated
-    from .conv2d import CBPoolMax2d
+    from .pool import CBPoolMax2d
     from .residual import CBResidual
     (prod.add if type(prod) is CBResidual else prod.mul if type(prod) is CBGated else prod).propChangeIndexes = True
     if type(prod) is CBPoolMax2d and not prod.__dict__.get('_general'):

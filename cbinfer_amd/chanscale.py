@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import C, CBinferError, check, dtype_code, ptr, require_device, stream_ptr
 from .chain import (EVERY_PIXEL, CBStateModule, check_map, form_args, insert_behind_producers, mask_workspace,
                     operand_changes, producers, split_operand)
-from .conv2d import CBPoolAvg2d
+from .pool import CBPoolAvg2d
 
 MAX_CHANNELS, MAX_HIDDEN = 4096, 1024
 _GATES = {None: _lib.CS_GATE_NONE, 'sigmoid': _lib.CS_GATE_SIGMOID, 'hardsigmoid': _lib.CS_GATE_HARDSIGMOID}

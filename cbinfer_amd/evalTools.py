@@ -11,7 +11,8 @@ import time
 
 import torch
 
-from . import CBConv2d, CBPoolAvg2d, CBPoolMax2d, clearMemory
+from . import CBConv2d, clearMemory
+from .pool import CBPoolAvg2d, CBPoolMax2d
 
 
 def _staged(frameset, cuda, preprocessor):

@@ -15,7 +15,7 @@ sync per layer, conv2d_cg.py:202).
 """
 import torch
 
-from .conv2d import LazyPool
+from .pool import LazyPool
 from .streams import side_stream
 
 

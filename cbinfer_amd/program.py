@@ -20,7 +20,8 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 from . import _lib
 from ._lib import CBinferError, check
-from .conv2d import CBConv2d, CBPoolMax2d, CBTail1x1
+from .conv2d import CBConv2d, CBTail1x1
+from .pool import CBPoolMax2d
 
 
 # torch operators a recorded frame may run: they launch nothing and allocate nothing (views and aliases of existing tensors)

@@ -9,11 +9,12 @@ import sys
 import cbinfer_amd
 from cbinfer_amd import *            # noqa: F401,F403
 from cbinfer_amd import CBChannelScale2d, CBSqueezeExcite, chanscale      # noqa: F401  (no entries of __all__)
-from cbinfer_amd import binary, chanreduce, conv2d, conv2d_cg, conv2d_fg, decoder, dwconv, groupconv, pad, pointwise, rearrange, residual, resize, tconv
+from cbinfer_amd import binary, chanreduce, conv2d, conv2d_cg, conv2d_fg, decoder, dwconv, groupconv, pad, pointwise, pool, rearrange, residual, resize, tconv
 
 sys.modules[__name__ + '.conv2d'] = conv2d
 sys.modules[__name__ + '.conv2d_cg'] = conv2d_cg
 sys.modules[__name__ + '.conv2d_fg'] = conv2d_fg
+sys.modules[__name__ + '.pool'] = pool
 sys.modules[__name__ + '.residual'] = residual
 sys.modules[__name__ + '.decoder'] = decoder
 sys.modules[__name__ + '.tconv'] = tconv
