@@ -361,6 +361,7 @@ int cbinfer_change_detection(const void* input, void* state, int8_t* changeMap, 
                              int dtype, cbStream_t stream) {
     CB_REQUIRE(input && state && changeMap && W > 0 && H > 0 && C > 0 && kHHalf >= 0 && kWHalf >= 0);
     if (kWHalf > 63 || H > 65535) return CB_ERR_UNSUPPORTED;
+    if (dtype != CB_F32 && dtype != CB_F16) return CB_ERR_BADARG;      // (before the map is touched)
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(changeMap, 0, (size_t)H * W, s);
     if (e != hipSuccess) return (int)e;
