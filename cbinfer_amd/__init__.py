@@ -32,6 +32,7 @@ from .resize import CBResize2d, insertCBResize
 from .pad import CBPad2d, insertCBPadding, splitConvPadding
 from .binary import CBBinary2d, CBGLU2d, CBGated, insertCBGating
 from .chanscale import CBChannelScale2d, CBSqueezeExcite, insertCBSqueezeExcite
+from .groupnorm import CBGroupNorm2d, insertCBGroupNorm
 
 __version__ = "0.1.0"
 
@@ -295,10 +296,14 @@ _STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2
 # the same module types, and the scale is no row of chain.PRODUCERS yet (a producer for no pass of its own; making it one
 # for the other passes is a follow-up).  CBSqueezeExcite is a wrapper: its pool and its scale are reached as children.
 _CHANNEL_STATE = (CBChannelScale2d,)
+# ... and so does the group norm, whose state is the map, the held statistics and the float64 partials: a third tuple
+# beside the table, for the same reason (no row of chain.PRODUCERS yet).
+_STATISTIC_STATE = (CBGroupNorm2d,)
 
 
 def _stateful(net):
-    return [m for m in net.modules() if type(m) in _STATEFUL or type(m) in _CHANNEL_STATE]
+    return [m for m in net.modules() if type(m) in _STATEFUL or type(m) in _CHANNEL_STATE or
+            type(m) in _STATISTIC_STATE]
 
 
 def clearMemory(net):
@@ -419,6 +424,6 @@ __all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CB
            'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
            'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
            'clearMemory', 'getStateTensors',
-           'setSyncIndexes', 'tuneThresholdParameters', 'insertCBSqueezeExcite']
-# (CBChannelScale2d and CBSqueezeExcite are attributes of the package and of the pycbinfer alias, but no entries of
-#  `__all__`: its CB names are the rows of chain.PRODUCERS, see _CHANNEL_STATE above)
+           'setSyncIndexes', 'tuneThresholdParameters', 'insertCBSqueezeExcite', 'insertCBGroupNorm']
+# (CBChannelScale2d, CBSqueezeExcite and CBGroupNorm2d are attributes of the package and of the pycbinfer alias, but no
+#  entries of `__all__`: its CB names are the rows of chain.PRODUCERS, see _CHANNEL_STATE and _STATISTIC_STATE above)

@@ -37,6 +37,7 @@ from .resize import CBResize2d
 from .pad import CBPad2d
 from .binary import CBBinary2d, CBGLU2d
 from .chanscale import CBChannelScale2d, CBSqueezeExcite
+from .groupnorm import CBGroupNorm2d
 
 
 # the change-based operators that have neither a batched kernel here nor a grouped launch in a BranchGroup: (types,
@@ -59,6 +60,10 @@ CHAIN_OPERATORS = (
 CHANNEL_OPERATORS = (
     ((CBSqueezeExcite, CBChannelScale2d), 'a change-based channel attention scale', 'squeeze-and-excitation'),
 )
+# ... and the group norm, likewise beside the table (cbinfer_amd._STATISTIC_STATE)
+STATISTIC_OPERATORS = (
+    ((CBGroupNorm2d,), 'a change-based group norm', 'GroupNorm and InstanceNorm'),
+)
 
 
 def _ptr_array(tensors):
@@ -79,7 +84,7 @@ class SequenceBatch(object):
             if type(m) in (CBPoolMax2d, CBPoolAvg2d) and m.__dict__.get('_general'):
                 raise CBinferError("SequenceBatch: layer %r is %r, a pool that is never folded into the next detection "
                                    "(only 2x2/stride 2 without padding is) and has no batched kernel" % (name, m))
-            for types, noun, networks in CHAIN_OPERATORS + CHANNEL_OPERATORS:
+            for types, noun, networks in CHAIN_OPERATORS + CHANNEL_OPERATORS + STATISTIC_OPERATORS:
                 if type(m) in types:
                     raise CBinferError("SequenceBatch: layer %r is %r, %s, which has no batched kernel: run %s networks "
                                        "one sequence per stream" % (name, m, noun, networks))

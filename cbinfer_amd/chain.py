@@ -4,7 +4,7 @@ The frame: how an operand and its change information are taken apart (split_oper
 form that lists every pixel (EVERY_PIXEL) and how a form is handed to the library (form_args), the ONE test for a state
 that no longer fits its frame (state_fits: these modules and the layers of layer.py), the mask workspace and
 hand-back of every mask-driven module, and CBStateModule, which CBAdd2d, CBPointwise2d, CBUpsample2d, CBConcat2d, the
-shuffles, CBChannelReduce2d, CBResize2d, CBPad2d, CBBinary2d, CBGLU2d, CBChannelScale2d and the pools of pool.py
+shuffles, CBChannelReduce2d, CBResize2d, CBPad2d, CBBinary2d, CBGLU2d, CBChannelScale2d, CBGroupNorm2d and the pools of pool.py
 (CBPoolMax2d, CBPoolAvg2d) derive from: the flags, the keyed workspace cache (_cached_work) and the state step
 (_fresh_state).
 

@@ -9,7 +9,7 @@ as plain stream launches -- the same kernels, the same order, the same arguments
 from a loop of a few ctypes calls.  The contract is a captured graph's: the network's buffers, flags and thresholds must not
 change between record and replay (the module-level decisions of the recorded frame are frozen), module bookkeeping
 (lastChangeIndexes, chain tags) is not advanced by a replay, and the network must consist of library calls only -- CBConv2d,
-lazily folded CBPoolMax2d, CBTail1x1, ChannelConcat, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d, CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d, CBChannelReduce2d, CBResize2d, CBPad2d, CBBinary2d, CBGLU2d, CBSqueezeExcite -- since a torch operator in between cannot be recorded (the recording
+lazily folded CBPoolMax2d, CBTail1x1, ChannelConcat, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d, CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d, CBChannelReduce2d, CBResize2d, CBPad2d, CBBinary2d, CBGLU2d, CBSqueezeExcite, CBGroupNorm2d -- since a torch operator in between cannot be recorded (the recording
 watches the operators that run, through a TorchDispatchMode, and refuses a frame that ran anything but views).  Re-record (`record(frame)`) after anything changed.  Outputs and states are those of the eager network, bit for
 bit (tests/test_gpu_modules.py, __graft_entry__.smoke())."""
 import ctypes
@@ -88,7 +88,8 @@ class FrameProgram(object):
                                "pycbinfer.CBPad2d (insertCBPadding) for an explicit padding, "
                                "pycbinfer.CBBinary2d / CBGated / CBGLU2d (insertCBGating) for a product, a gate, a "
                                "difference, a maximum or minimum of two maps or an nn.GLU over the channels, "
-                               "pycbinfer.CBSqueezeExcite (insertCBSqueezeExcite) for a squeeze-and-excitation block "
+                               "pycbinfer.CBSqueezeExcite (insertCBSqueezeExcite) for a squeeze-and-excitation block, "
+                               "pycbinfer.CBGroupNorm2d (insertCBGroupNorm) for a group norm or an instance norm "
                                "-- and be in its steady state (a first frame allocates)"
                                % ", ".join(sorted(set(watch.seen))))
         # where the frame's address went: integer arguments, and pointer fields of argument structures

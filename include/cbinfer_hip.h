@@ -77,7 +77,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * (CB_ADAPT_*, cbinfer_adaptive_pool_*, cbinfer_cbadaptivepool2d_forward) and the collapse of the channel axis
  * (CB_CC_*, cbinfer_chancollapse_supported, cbinfer_chancollapse_changed, cbinfer_cbchancollapse_forward) and the
  * channel attention scale (CB_CS_*, cbinfer_chanscale_supported, cbinfer_chanscale_gate, cbinfer_chanscale_changed,
- * cbinfer_cbchanscale_forward). */
+ * cbinfer_cbchanscale_forward) and the group norm (cbinfer_groupnorm_supported, cbinfer_groupnorm_partials,
+ * cbinfer_groupnorm_stats, cbinfer_groupnorm_changed, cbinfer_cbgroupnorm_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1390,6 +1391,83 @@ int cbinfer_cbchanscale_forward(const void* a, const void* v, const float* w1, c
                                 int32_t* tripCount, const uint64_t* maskA, const int32_t* listA, int capA,
                                 const int32_t* countA, uint64_t* bits, uint64_t* maskCopy, int C, int R, int H, int W,
                                 int gateFn, int act, float threshold, int all, int dtype, cbStream_t stream);
+
+/* ---- change-based group norm and instance norm (cb_groupnorm.hip) ---------------------------------------
+ * No counterpart in the reference.  torch's nn.GroupNorm on a map -- nn.InstanceNorm2d without running statistics is
+ * G == C, GroupNorm(1, C) is G == 1 --: out[c, p] = (a[c, p] - mean[g]) rstd[g] gamma[c] + beta[c] with g = c / (C / G)
+ * and the statistics taken over the (C / G) H W values of the group.  A group's (mean, rstd) moves a little in every
+ * frame of a video, so the library's threshold rule is applied to it: a group whose statistics moved by no more than
+ * `threshold` keeps the pair it last used (`held`) and is recomputed only at the operand's changed pixels; a group whose
+ * statistics moved by more -- it TRIPPED -- takes the new pair and its planes are recomputed completely.  At
+ * threshold == 0 this is the dense operator.
+ *
+ * THIS SECTION IS THE SPECIFICATION; tests/groupnorm_cases.py is its numpy twin.
+ *   operand and state: a and the state `out` are [C, H, W], contiguous, one dtype (CB_F32 or CB_F16), two different
+ *     tensors; 1 <= C <= 4096, G >= 1 divides C, batch 1, H W within an int32.  gamma / beta: f32 [C] or NULL -- NULL: no
+ *     multiplication / no addition.  eps: a HOST pointer to ONE double, read during the call (the scalar parameters of
+ *     this ABI are int, long and float); relu 0 or 1; threshold >= 0.
+ *   level 1, the segment partials, f64, caller-owned state of 2 C H wpr doubles, wpr = ceil(W / 64).  A segment is one
+ *     word of the row-padded change mask: the 64 columns tile 64 ... tile 64 + 63 of one row.  P[k][c][y][tile], element
+ *     ((k C + c) H + y) wpr + tile: the sum over the segment's columns < W of (double)x (k == 0) and of (double)x (double)x
+ *     (k == 1; exact: the square of an f32 or f16 value is an f64 number) by the FIXED butterfly over 64 lanes, lane l
+ *     holding column tile 64 + l or +0 beyond W: p_l = p_l + p_(l xor m) for m = 1, 2, 4, 8, 16, 32; the result is p_0.
+ *     Every addition is one correctly rounded f64 addition.  The statistics are f64 since E[x^2] - mean^2 in f32 cancels
+ *     on a map whose mean is large against its spread.  A frame recomputes exactly the partials of the DIRTY segments --
+ *     those whose word of the listed pixels is not zero --, for every channel; every other partial keeps its bits, and
+ *     the input pixels of a clean segment are never read.
+ *   level 2, the statistics of group g: its N = (C / G) H wpr partials are contiguous from (k C + g C / G) H wpr.  1024
+ *     lane sums s_l = +0; s_l += x_i for i = l, l + 1024, ... < N ascending; then s_l += s_(l + off) for l < off,
+ *     off = 512, 256, ..., 1; S1 (k == 0) and S2 (k == 1) are s_0.  With n = (double)((C / G) H W):
+ *       mean = S1 / n;  var = S2 / n - mean mean;  var = var < 0 ? 0 : var (a NaN stays);  rstd = 1 / sqrt(var + eps)
+ *     every operation an f64 operation of its own; mean and rstd are then rounded ONCE to f32 and written to
+ *     stats[g] / stats[G + g] every frame.
+ *   the rule, in f32, every operation rounded on its own.  held is f32 [2][G]: held[g] the mean, held[G + g] the rstd the
+ *     group last used.  Group g trips iff all != 0 (a fresh state), or !(fabsf(mean - heldMean) heldRstd <= threshold), or
+ *     !(fabsf(rstd - heldRstd) <= threshold heldRstd): strictly more than the threshold, and a NaN trips.  A tripped
+ *     group takes both new values; any other keeps both bit for bit, so slow drift adds up until it trips.  THE UNIT: the
+ *     threshold is a shift of the mean in held standard deviations and a relative change of rstd; to first order the
+ *     normalised value y of a held group is off by at most threshold (1 + |y|), before gamma.  tripped[g], one int32
+ *     per group (1 or 0), is written every frame by the group's own workgroup: nothing needs zeroing.
+ *   values: y = ((float)x - heldMean) heldRstd;  v = y gamma[c] (gamma != NULL);  v = v + beta[c] (beta != NULL);
+ *     relu: v = v < 0 ? 0 : v (-0 and a NaN stay);  out = (T)v.  Every operation is a correctly rounded f32 operation of
+ *     its own, never an FMA, and the conversion to f16 is a rounding of its own.
+ *   what is written: a listed pixel for every channel; every other pixel for the channels of the tripped groups.  Every
+ *     other element of `out` keeps its bits.
+ *   listed pixels: `a` arrives as its row-padded change MASK, as an int32 LIST, or not at all (every pixel is listed), as
+ *     for the operators above; with all != 0 every pixel is listed and the operand's change information is not read.
+ *   hand-on: maskCopy receives the frame's mask every frame: the listed pixels, or EVERY pixel of the map in a frame in
+ *     which a group tripped; `bits`, the working mask, is zero again when the frame ends.
+ * Bad arguments -- a null tensor or buffer (gamma and beta may be NULL), C < 1 or > 4096, G < 1 or not dividing C,
+ * H or W < 1, H W beyond an int32, an unknown dtype, a negative or NaN threshold, a negative or non-finite eps, relu
+ * other than 0 or 1, `out` aliasing the operand or a buffer, stats == held, both a mask and a list, a count without a
+ * list, a negative capacity, bits == maskCopy, the operand's mask == bits or maskCopy -- return CB_ERR_BADARG and launch
+ * nothing. */
+/* host, pure: 1 if 1 <= C <= 4096 and G >= 1 divides C, else 0 */
+int cbinfer_groupnorm_supported(int C, int G);
+/* Launch 1, level 1: a persistent grid over (mask word, block of 16 channels) units.  The listed word is
+ * bits[w] | maskA[w] (either may be NULL; all != 0: the full row word); both are only read.  Clean words are skipped.
+ * Lane = column, four channels in flight per wave.  A partial has ONE writer: segment = mask word.  No atomics. */
+int cbinfer_groupnorm_partials(const void* a, double* partials, const uint64_t* maskA, const uint64_t* bits, int all,
+                               int C, int H, int W, int dtype, cbStream_t stream);
+/* Launch 2, level 2 and the rule: one workgroup of 1024 threads per group; stats, held and tripped as above.  Runs
+ * every frame: an empty frame finds the same partials, hence the same statistics and no trip. */
+int cbinfer_groupnorm_stats(const double* partials, float* stats, float* held, int32_t* tripped, int C, int G, int H,
+                            int W, const double* eps, float threshold, int all, cbStream_t stream);
+/* Launch 3, the mask-driven one: reads held and tripped as launch 2 left them on the same stream.  maskA: the operand's
+ * change mask, or NULL: the operand contributes what `bits` holds on entry; all != 0: every pixel is listed. */
+int cbinfer_groupnorm_changed(const void* a, void* out, const float* gamma, const float* beta, const float* held,
+                              const int32_t* tripped, const uint64_t* maskA, int all, uint64_t* bits, uint64_t* maskCopy,
+                              int C, int G, int H, int W, int relu, int dtype, cbStream_t stream);
+/* The whole frame enqueued without a host sync: the three launches, an operand in list form costs one launch in front.
+ * maskA != NULL: mask form; listA != NULL: list form (capA entries at most, countA the device-side length or NULL); both
+ * NULL: every pixel is listed.  all != 0 (a fresh state): every group trips and every partial and pixel is written.  All
+ * arguments are checked before the first launch.  Three launches and not fewer: the readers of `held` must not share a
+ * launch with its writer, nor the readers of the partials with theirs. */
+int cbinfer_cbgroupnorm_forward(const void* a, const float* gamma, const float* beta, void* outputState, double* partials,
+                                float* stats, float* held, int32_t* tripped, const uint64_t* maskA, const int32_t* listA,
+                                int capA, const int32_t* countA, uint64_t* bits, uint64_t* maskCopy, int C, int G, int H,
+                                int W, const double* eps, int relu, float threshold, int all, int dtype,
+                                cbStream_t stream);
 
 /* ---- transposed convolution (cb_tconv.hip) ------------------------------------------------------------
  * The reference has no counterpart: its CBConv2d asserts transposed == False (conv2d.py:92-104).  Input map Hi x Wi,

@@ -9,6 +9,7 @@ import sys
 import cbinfer_amd
 from cbinfer_amd import *            # noqa: F401,F403
 from cbinfer_amd import CBChannelScale2d, CBSqueezeExcite, chanscale      # noqa: F401  (no entries of __all__)
+from cbinfer_amd import CBGroupNorm2d, groupnorm      # noqa: F401  (likewise)
 from cbinfer_amd import binary, chanreduce, conv2d, conv2d_cg, conv2d_fg, decoder, dwconv, groupconv, pad, pointwise, pool, rearrange, residual, resize, tconv
 
 sys.modules[__name__ + '.conv2d'] = conv2d
@@ -27,5 +28,6 @@ sys.modules[__name__ + '.resize'] = resize
 sys.modules[__name__ + '.pad'] = pad
 sys.modules[__name__ + '.binary'] = binary
 sys.modules[__name__ + '.chanscale'] = chanscale
+sys.modules[__name__ + '.groupnorm'] = groupnorm
 
 __all__ = cbinfer_amd.__all__
