@@ -2126,22 +2126,23 @@ struct CbsTailArgs {
     float* out[CBS_MAXSEQ];
     int C1, C2, relu1, relu2;
 };
-template <int BM, int BN>
-__global__ __launch_bounds__(64 * CB_TAIL_MAXW) void cbs_reduce_tail_kernel(CbsParams p, CbsTailArgs ta) {
-    extern __shared__ float cbs_tail_sm[];
+template <int BM, int BN, int S>
+__global__ __launch_bounds__(S == 1 ? 64 * CB_TAIL_MAXW : CB_TAIL_MAXT) void cbs_reduce_tail_kernel(CbsParams p,
+                                                                                                  CbsTailArgs ta) {
+    extern __shared__ __attribute__((aligned(16))) float cbs_tail_sm[];
     cb_touch_kernarg<sizeof(CbsParams) + sizeof(CbsTailArgs)>();
     const int C0 = p.K, C0P = (C0 + 15) / 16 * 16, C1 = ta.C1, C2 = ta.C2, HW = p.H * p.W;
-    const int t = threadIdx.x, NT = blockDim.x;
+    const int t = threadIdx.x, NT = blockDim.x;      // (64 x ceil(C1/16) row blocks x S chain sets: cb_tail_core.h)
     // Round trips to memory are what this launch consists of.  First: the launch info of the contraction, the
     // layer's biases, the second layer's matrix.  Second (per group): the slabs of the group's 16 pixel columns --
-    // their address needs no pixel index -- and the 16 pixel indices.  Third: this wave's rows of W1.
+    // their address needs no pixel index -- and the 16 pixel indices.  Third: this wave's part of W1.
     CB_TAIL_STAMP(0);
     const int SK = p.info[CBS_INFO_SK], MT = p.info[CBS_INFO_MT], CMB = MT * SK, TILE4 = BM * BN / 4;
     CBS_TILES_BEFORE(tilesBefore, p.info);
     const int GP = BN / CB_TAIL_PX, groups = tilesBefore[CBS_MAXSEQ] * GP;
     if ((int)blockIdx.x >= groups) return;
     CB_TAIL_STAMP(1);
-    const CbTailLds L = cb_tail_lds(cbs_tail_sm, C0P, C1, C2, NT);
+    const CbTailLds L = cb_tail_lds(cbs_tail_sm, C0P, C1, C2);
     __shared__ int s_pix[CB_TAIL_PX];
     for (int i = t; i < C2 * C1; i += NT) L.W2s[i] = ta.w2[i];
     for (int i = t; i < C2; i += NT) L.b2s[i] = ta.b2[i];
@@ -2174,78 +2175,83 @@ __global__ __launch_bounds__(64 * CB_TAIL_MAXW) void cbs_reduce_tail_kernel(CbsP
         if (SK > 1) {
             // X[c][px] from the slabs (SK = CBS_CHUNKS of them): thread -> (px, channel quads t/16 + i NT/16); all loads
             // of a thread in flight.  The same number of rounds for every thread, so that all reach the barrier.
+            // A thread takes U quads a round, U = 1, 2 or 4: what QN quads dealt over cstep threads come to -- the
+            // widest workgroup on the bench's 256 channels has one quad per thread, and a fixed four would request
+            // its last quad three more times.  (Four -- 80 registers of slab values -- only where the workgroup has no
+            // chain sets: more than eight waves leave a thread 128 registers.)
             const float4* sl0 = slabs + (long)ptg * CMB * TILE4 + nl0 + px;
-            const int QN = C0P / 4, rounds = (QN + 4 * cstep - 1) / (4 * cstep);
-            for (int rd = 0; rd < rounds; ++rd) {
-                const int cq0 = tq + rd * 4 * cstep;
-                float4 v[4][CBS_CHUNKS], bq[4];
+            const int QN = C0P / 4, perThread = (QN + cstep - 1) / cstep;
+            auto slabRounds = [&](auto uc) {
+                constexpr int U = decltype(uc)::value;
+                const int rounds = (QN + U * cstep - 1) / (U * cstep);
+                for (int rd = 0; rd < rounds; ++rd) {
+                    const int cq0 = tq + rd * U * cstep;
+                    float4 v[U][CBS_CHUNKS], bq[U];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int cq = min(cq0 + u * cstep, QN - 1), mt = cq / (BM / 4), mq = cq - mt * (BM / 4);
+                    for (int u = 0; u < U; ++u) {
+                        const int cq = min(cq0 + u * cstep, QN - 1), mt = cq / (BM / 4), mq = cq - mt * (BM / 4);
 #pragma unroll
-                    for (int j = 0; j < CBS_CHUNKS; ++j) v[u][j] = sl0[((long)j * MT + mt) * TILE4 + mq * BN];
-                    bq[u] = *(const float4*)(biasp + (hasBias ? min(4 * cq, p.K - 4) : 0));
-                }
-                __builtin_amdgcn_sched_barrier(0);      // (all loads requested before anything of the second half)
-                if (rd == 0) {
-                    __syncthreads();   // previous group's Hs / s_pix / Xs reads are done
-                    if (t < CB_TAIL_PX) s_pix[t] = pixMine;
-                    CB_TAIL_STAMP(2);
-                }
+                        for (int j = 0; j < CBS_CHUNKS; ++j) v[u][j] = sl0[((long)j * MT + mt) * TILE4 + mq * BN];
+                        bq[u] = *(const float4*)(biasp + (hasBias ? min(4 * cq, p.K - 4) : 0));
+                    }
+                    __builtin_amdgcn_sched_barrier(0);      // (all loads requested before anything of the second half)
+                    if (rd == 0) {
+                        __syncthreads();   // previous group's Hs / s_pix / Xs reads are done
+                        if (t < CB_TAIL_PX) s_pix[t] = pixMine;
+                        CB_TAIL_STAMP(2);
+                    }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int cq = cq0 + u * cstep;
-                    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+                    for (int u = 0; u < U; ++u) {
+                        const int cq = cq0 + u * cstep;
+                        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll
-                    for (int j = 0; j < CBS_CHUNKS; ++j) s0 += v[u][j].x, s1 += v[u][j].y, s2 += v[u][j].z, s3 += v[u][j].w;
-                    const float sv[4] = {s0, s1, s2, s3}, bv[4] = {bq[u].x, bq[u].y, bq[u].z, bq[u].w};
+                        for (int j = 0; j < CBS_CHUNKS; ++j)
+                            s0 += v[u][j].x, s1 += v[u][j].y, s2 += v[u][j].z, s3 += v[u][j].w;
+                        const float sv[4] = {s0, s1, s2, s3}, bv[4] = {bq[u].x, bq[u].y, bq[u].z, bq[u].w};
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int m = 4 * cq + e;
-                        float r = fmaf(sv[e], p.outScale, hasBias ? bv[e] : 0.f);
-                        if (p.relu) r = r <= 0.f ? 0.f : r;
-                        if (cq < QN) {
-                            if (p.accumulate) {      // (uniform; the old outputs: one more round trip, as cbs_reduce_kernel's)
-                                if (pixMine >= 0 && m < p.K) {
-                                    r += outq[(long)m * HW + pixMine];
-                                    outq[(long)m * HW + pixMine] = r;
-                                    if (relq) {
-                                        r = r <= 0.f ? 0.f : r;
-                                        relq[(long)m * HW + pixMine] = r;
+                        for (int e = 0; e < 4; ++e) {
+                            const int m = 4 * cq + e;
+                            float r = fmaf(sv[e], p.outScale, hasBias ? bv[e] : 0.f);
+                            if (p.relu) r = r <= 0.f ? 0.f : r;
+                            if (cq < QN) {
+                                if (p.accumulate) {      // (uniform; the old outputs: one more round trip, as cbs_reduce_kernel's)
+                                    if (pixMine >= 0 && m < p.K) {
+                                        r += outq[(long)m * HW + pixMine];
+                                        outq[(long)m * HW + pixMine] = r;
+                                        if (relq) {
+                                            r = r <= 0.f ? 0.f : r;
+                                            relq[(long)m * HW + pixMine] = r;
+                                        }
                                     }
+                                } else if (pixMine >= 0 && m < p.K) {
+                                    outq[(long)m * HW + pixMine] = r;
                                 }
-                            } else if (pixMine >= 0 && m < p.K) {
-                                outq[(long)m * HW + pixMine] = r;
+                                L.Xs[m * CB_TAIL_PX + px] = (m < p.K && pixMine >= 0) ? r : 0.f;
                             }
-                            L.Xs[m * CB_TAIL_PX + px] = (m < p.K && pixMine >= 0) ? r : 0.f;
                         }
                     }
                 }
-            }
+            };
+            if (perThread <= 1) slabRounds(std::integral_constant<int, 1>());      // (uniform)
+            else if (perThread <= 2 || S > 1) slabRounds(std::integral_constant<int, 2>());
+            else slabRounds(std::integral_constant<int, 4>());
         } else {
             // unsplit: the contraction's epilogue has written prevOutput; gather as the tail kernel does
             __syncthreads();
             if (t < CB_TAIL_PX) s_pix[t] = pixMine;
             const float* gsrc = relq ? relq : outq;      // (fine-grained with a relu'd copy: the tail reads the copy)
-            for (int c0 = tq; c0 < C0P; c0 += 16 * cstep) {
-                float v[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) v[u] = gsrc[(long)min(c0 + u * cstep, C0 - 1) * HW + pixLd];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    const int c = c0 + u * cstep;
-                    if (c < C0P) L.Xs[c * CB_TAIL_PX + px] = (pixMine >= 0 && c < C0) ? v[u] : 0.f;
-                }
-            }
+            cb_tail_gather<(S == 1 ? 16 : 8)>(L.Xs, gsrc, HW, pixLd, pixMine >= 0, C0, C0P, tq, px, cstep);
         }
-        // this wave's rows of W1: requested once the slab registers are free (requested earlier -- beside the slabs,
+        // this wave's part of W1: requested once the slab registers are free (requested earlier -- beside the slabs,
         // or behind their barrier -- the launch came out longer: the barrier waits for them too, and the stores of the
-        // sums queue behind them), per group -- few workgroups see a second one -- rather than kept across the loop
+        // sums queue behind them; at kernel entry, 16 registers wide since the chains have waves of their own, it came
+        // out 0.2 us longer again: the launch info and the slabs arrive later by what the request saves),
+        // per group -- few workgroups see a second one -- rather than kept across the loop
         asm volatile("" ::: "memory");
-        CbTailPre P;
-        cb_tail_preload(P, ta.w1p, ta.b1, C0P, C1);
+        CbTailPre<S> P;
+        cb_tail_preload<S>(P, ta.w1p, ta.b1, C0P, C1);
         CB_TAIL_STAMP(3);
-        cb_tail_tile(L, s_pix, P, ta.w1p, ta.out[q], C0P, C1, C2, HW, ta.relu1, ta.relu2);
+        cb_tail_tile<S>(L, s_pix, P, ta.w1p, ta.out[q], C0P, C1, C2, HW, ta.relu1, ta.relu2);
         CB_TAIL_STAMP(7);
     }
 }
@@ -2268,9 +2274,15 @@ int cbs_launch_conv(const CbsParams& p, int perCU, const CbsTailArgs* tail, hipS
         return st;
     }
     if (tail) {
-        const int waves = (tail->C1 + 15) / 16;
-        hipLaunchKernelGGL((cbs_reduce_tail_kernel<BM, BN>), dim3(2 * cb_num_cus()), dim3(64 * waves),
-                           cb_tail_lds_bytes(p.K, tail->C1, tail->C2), s, p, *tail);
+        const int S = cb_tail_chain_sets(p.K, tail->C1);
+        auto* k = S == 4 ? cbs_reduce_tail_kernel<BM, BN, 4> : S == 2 ? cbs_reduce_tail_kernel<BM, BN, 2>
+                                                                      : cbs_reduce_tail_kernel<BM, BN, 1>;
+        // (a workgroup of more than eight waves has a CU to itself -- four waves a SIMD at its registers --, and a grid of
+        //  two per CU would queue its second half: workgroups that only read the launch info and leave, one after the
+        //  other on the few CUs without a group, ending after the last group's workgroup did)
+        const int waves = (tail->C1 + 15) / 16 * S, perCU = waves > 8 ? 1 : 2;
+        hipLaunchKernelGGL(k, dim3(perCU * cb_num_cus()), dim3(64 * waves), cb_tail_lds_bytes(p.K, tail->C1, tail->C2), s, p,
+                           *tail);
         st = cb_launch_status();
     } else if (second) {
         hipLaunchKernelGGL(cbs_reduce_kernel, dim3(4 * cb_num_cus()), dim3(256), 0, s, p, BM, BN);

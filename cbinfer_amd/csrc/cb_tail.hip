@@ -6,11 +6,12 @@
 // recomputing the chain at those pixels and keeping every other output gives the dense result.
 //
 // Shape: 16 changed pixels per workgroup, so that even a few thousand pixels spread over all CUs (the
-// whole job is ~100 MFLOP: latency, not throughput, is what counts).  Wave w owns hidden channels
-// 16w..16w+15: H[16 x 16 px] = W1[16 x C0] . X[C0 x 16 px] on v_mfma_f32_16x16x4_f32 (exact f32 fma
-// chain), A fragments straight from the re-laid-out weights (one 16-byte load per four MFMAs and lane),
-// the gathered X tile staged once through LDS.  relu(H + b1) goes to LDS, and the C2 x 16 outputs of the
-// second (tiny) layer are plain f32 dot products over it.
+// whole job is ~100 MFLOP: latency, not throughput, is what counts).  Row block r owns hidden channels
+// 16r..16r+15: H[16 x 16 px] = W1[16 x C0] . X[C0 x 16 px] on v_mfma_f32_16x16x4_f32 (exact f32 fma
+// chains, four per row block, dealt over up to four waves: cb_tail_core.h), A fragments straight from the
+// re-laid-out weights (one 16-byte load per four MFMAs and lane), the gathered X tile staged once through
+// LDS.  relu(H + b1) goes to LDS, and the C2 x 16 outputs of the second (tiny) layer are plain f32 dot
+// products over it.
 #include "cb_common.h"
 #include "cb_tail_core.h"
 
@@ -40,24 +41,25 @@ struct TailSeqs {
     } seq[CBINFER_SPLIT_MAX_SEQUENCES];
 };
 
-__global__ __launch_bounds__(64 * CB_TAIL_MAXW) void cb_tail1x1_kernel(
+template <int S>
+__global__ __launch_bounds__(S == 1 ? 64 * CB_TAIL_MAXW : CB_TAIL_MAXT) void cb_tail1x1_kernel(
     TailSeqs tab, int nHost, const float* __restrict__ w1p, const float* __restrict__ b1,
     const float* __restrict__ w2, const float* __restrict__ b2, int C0, int C0P, int C1, int C2,
     int HW, int relu1, int relu2) {
-    extern __shared__ float sm[];   // Xs[C0P][16] | Hs[C1P][17] | W2s[C2][C1] | b2s[C2]
+    extern __shared__ __attribute__((aligned(16))) float sm[];   // Xs[C0P][16] | Hs[C1P][17] | W2s[C2][C1] | b2s[C2]
     cb_touch_kernarg<sizeof(TailSeqs) + 72>();
     const float* __restrict__ x = tab.seq[blockIdx.y].x;
     const int32_t* __restrict__ list = tab.seq[blockIdx.y].list;
     const int32_t* __restrict__ countDev = tab.seq[blockIdx.y].countDev;
     float* out = tab.seq[blockIdx.y].out;
     const int t = threadIdx.x, NT = blockDim.x;
-    const CbTailLds L = cb_tail_lds(sm, C0P, C1, C2, NT);
+    const CbTailLds L = cb_tail_lds(sm, C0P, C1, C2);
     float* Xs = L.Xs;
     float* W2s = L.W2s;
     float* b2s = L.b2s;
     __shared__ int s_pix[CB_TAIL_PX];
-    CbTailPre P;
-    cb_tail_preload(P, w1p, b1, C0P, C1);      // (requested beside the change count: one round trip, not two)
+    CbTailPre<S> P;
+    cb_tail_preload<S>(P, w1p, b1, C0P, C1);      // (requested beside the change count: one round trip, not two)
     const int N = countDev ? min(*countDev, nHost) : nHost;
     if ((int)blockIdx.x * CB_TAIL_PX >= N) return;
     // the second layer's (small) matrix and bias live in LDS for the life of the workgroup
@@ -73,26 +75,25 @@ __global__ __launch_bounds__(64 * CB_TAIL_MAXW) void cb_tail1x1_kernel(
             s_pix[t] = pix;
         }
         __syncthreads();
-        // gather X[c][px]: thread -> (px = t % 16, c = t / 16 + i * NT/16); 16 neighbouring lanes read the
-        // 16 pixels of one channel plane (contiguous where the changed pixels are)
         const int px = t & 15;
-        const int mypix = s_pix[px], pixLd = max(mypix, 0);
-        const int cstep = NT >> 4;
-        for (int c0 = t >> 4; c0 < C0P; c0 += 16 * cstep) {   // sixteen loads in flight per lane
-            // (never predicated -- a predicated load is a branch of its own, sixteen of them sixteen round trips:
-            //  clamped addresses, predicated uses)
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = x[(long)min(c0 + u * cstep, C0 - 1) * HW + pixLd];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const int c = c0 + u * cstep;
-                if (c < C0P) Xs[c * CB_TAIL_PX + px] = (mypix >= 0 && c < C0) ? v[u] : 0.f;
-            }
-        }
+        const int mypix = s_pix[px];
+        int tq = t >> 4;      // (an opaque copy: the gather's addresses are made per tile, not kept across the loop)
+        asm volatile("" : "+v"(tq));
+        cb_tail_gather<(S == 1 ? 16 : 8)>(Xs, x, HW, max(mypix, 0), mypix >= 0, C0, C0P, tq, px, NT >> 4);
 
-        cb_tail_tile(L, s_pix, P, w1p, out, C0P, C1, C2, HW, relu1, relu2);
+        cb_tail_tile<S>(L, s_pix, P, w1p, out, C0P, C1, C2, HW, relu1, relu2);
     }
+}
+
+// the launch: ceil(C1/16) row blocks x cb_tail_chain_sets waves per workgroup
+static void cb_tail_launch(dim3 grid, size_t lds, hipStream_t stream, const TailSeqs& tab, int numChanges,
+                           const float* w1p, const float* b1, const float* w2, const float* b2, int C0, int C1, int C2,
+                           int HW, int relu1, int relu2) {
+    const int C0P = (C0 + 15) / 16 * 16;
+    const int S = cb_tail_chain_sets(C0, C1);
+    const dim3 block(64 * ((C1 + 15) / 16) * S);
+    auto* k = S == 4 ? cb_tail1x1_kernel<4> : S == 2 ? cb_tail1x1_kernel<2> : cb_tail1x1_kernel<1>;
+    hipLaunchKernelGGL(k, grid, block, lds, stream, tab, numChanges, w1p, b1, w2, b2, C0, C0P, C1, C2, HW, relu1, relu2);
 }
 
 }  // namespace
@@ -138,14 +139,12 @@ int cbinfer_tail1x1_batched(const cbTailSeq* seqs, int nSeq, int numChanges, con
         tab.seq[q].countDev = seqs[q].countDev;
         tab.seq[q].out = seqs[q].output;
     }
-    const int C0P = (C0 + 15) / 16 * 16;
-    const int waves = (C1 + 15) / 16;
     const size_t lds = cb_tail_lds_bytes(C0, C1, C2);
     if (lds > 60 * 1024) return CB_ERR_UNSUPPORTED;
     long tiles = ((long)numChanges + CB_TAIL_PX - 1) / CB_TAIL_PX;
     if (tiles > 2048) tiles = 2048;
-    hipLaunchKernelGGL(cb_tail1x1_kernel, dim3((unsigned)tiles, nSeq), dim3(64 * waves), lds, (hipStream_t)stream,
-                       tab, numChanges, w1Prepared, b1, w2, b2, C0, C0P, C1, C2, H * W, relu1, relu2);
+    cb_tail_launch(dim3((unsigned)tiles, nSeq), lds, (hipStream_t)stream, tab, numChanges, w1Prepared, b1, w2, b2, C0, C1,
+                   C2, H * W, relu1, relu2);
     return cb_launch_status();
 }
 
@@ -159,14 +158,12 @@ int cbinfer_tail1x1(const float* input, const int32_t* changeList, int numChange
     if (numChanges == 0) return CB_OK;
     TailSeqs tab;
     tab.seq[0].x = input, tab.seq[0].list = changeList, tab.seq[0].countDev = countDev, tab.seq[0].out = output;
-    const int C0P = (C0 + 15) / 16 * 16;
-    const int waves = (C1 + 15) / 16;
     const size_t lds = cb_tail_lds_bytes(C0, C1, C2);
     if (lds > 60 * 1024) return CB_ERR_UNSUPPORTED;   // stays below the 64 KB that needs no opt-in
     long tiles = ((long)numChanges + CB_TAIL_PX - 1) / CB_TAIL_PX;
     if (tiles > 2048) tiles = 2048;   // grid-stride beyond: the capacity is H*W when the count is on the device
-    hipLaunchKernelGGL(cb_tail1x1_kernel, dim3((unsigned)tiles), dim3(64 * waves), lds, (hipStream_t)stream,
-                       tab, numChanges, w1Prepared, b1, w2, b2, C0, C0P, C1, C2, H * W, relu1, relu2);
+    cb_tail_launch(dim3((unsigned)tiles), lds, (hipStream_t)stream, tab, numChanges, w1Prepared, b1, w2, b2, C0, C1, C2,
+                   H * W, relu1, relu2);
     return cb_launch_status();
 }
 
