@@ -289,21 +289,13 @@ def linkConsumers(producer, consumers):
     return producer
 
 
-_STATEFUL = (CBConv2d, CBPoolMax2d, CBPoolAvg2d, CBTail1x1, CBAdd2d, CBUpsample2d, CBConcat2d, CBConvTranspose2d,
-             CBDepthwiseConv2d, CBPointwise2d, CBGroupedConv2d, CBPixelShuffle2d, CBChannelShuffle2d, CBChannelReduce2d,
-             CBResize2d, CBPad2d, CBBinary2d, CBGLU2d)
-# The channel attention scale keeps state too.  It stands beside the table: _STATEFUL, chain.PRODUCERS and `__all__` list
-# the same module types, and the scale is no row of chain.PRODUCERS yet (a producer for no pass of its own; making it one
-# for the other passes is a follow-up).  CBSqueezeExcite is a wrapper: its pool and its scale are reached as children.
-_CHANNEL_STATE = (CBChannelScale2d,)
-# ... and so does the group norm, whose state is the map, the held statistics and the float64 partials: a third tuple
-# beside the table, for the same reason (no row of chain.PRODUCERS yet).
-_STATISTIC_STATE = (CBGroupNorm2d,)
+# The module types of chain.PRODUCERS that keep state.  The wrappers (CBResidual, CBGated, CBSqueezeExcite) define no
+# getStateTensors: their children are reached as modules of the network.
+_STATEFUL = tuple(t for t in chain.module_types() if hasattr(t, 'getStateTensors'))
 
 
 def _stateful(net):
-    return [m for m in net.modules() if type(m) in _STATEFUL or type(m) in _CHANNEL_STATE or
-            type(m) in _STATISTIC_STATE]
+    return [m for m in net.modules() if type(m) in _STATEFUL]
 
 
 def clearMemory(net):
@@ -420,10 +412,11 @@ def tuneThresholdParameters(vidSeqReader, evalSequences, numFramesPerSeq, target
         anchor = measure()
 
 
-__all__ = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1', 'CBAdd2d', 'CBResidual', 'foldBatchNorm', 'CBUpsample2d', 'CBConcat2d', 'insertCBUpsampling', 'CBConvTranspose2d', 'insertCBTransposedConv', 'CBDepthwiseConv2d', 'linkDepthwise', 'CBPointwise2d', 'insertCBPointwise', 'CBGroupedConv2d', 'linkGrouped', 'CBPixelShuffle2d', 'CBChannelShuffle2d', 'insertCBRearrange', 'CBChannelReduce2d', 'insertCBChannelOps', 'CBResize2d', 'insertCBResize', 'CBPad2d', 'insertCBPadding', 'splitConvPadding', 'CBBinary2d', 'CBGLU2d', 'CBGated', 'insertCBGating', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline', 'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute',
-           'mergeReLURecur', 'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection',
-           'fuseDetectionIntoProducer', 'linkConsumers', 'fuseTail1x1',
-           'clearMemory', 'getStateTensors',
-           'setSyncIndexes', 'tuneThresholdParameters', 'insertCBSqueezeExcite', 'insertCBGroupNorm']
-# (CBChannelScale2d, CBSqueezeExcite and CBGroupNorm2d are attributes of the package and of the pycbinfer alias, but no
-#  entries of `__all__`: its CB names are the rows of chain.PRODUCERS, see _CHANNEL_STATE and _STATISTIC_STATE above)
+# the CB names are the rows of chain.PRODUCERS; the functions and the other classes are written out
+__all__ = [row[0] for row in chain.PRODUCERS] + [
+    'foldBatchNorm', 'insertCBUpsampling', 'insertCBTransposedConv', 'linkDepthwise', 'insertCBPointwise',
+    'linkGrouped', 'insertCBRearrange', 'insertCBChannelOps', 'insertCBResize', 'insertCBPadding', 'splitConvPadding',
+    'insertCBGating', 'insertCBSqueezeExcite', 'insertCBGroupNorm', 'ChangeIndexes', 'ChannelConcat', 'FramePipeline',
+    'SequenceBatch', 'BranchGroup', 'FrameProgram', 'convert', 'convertRecur', 'subsitute', 'mergeReLURecur',
+    'propChangeIndexesOf1x1', 'insertCBPooling', 'fusePoolingIntoDetection', 'fuseDetectionIntoProducer',
+    'linkConsumers', 'fuseTail1x1', 'clearMemory', 'getStateTensors', 'setSyncIndexes', 'tuneThresholdParameters']

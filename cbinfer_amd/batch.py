@@ -54,14 +54,8 @@ CHAIN_OPERATORS = (
     ((CBResize2d,), 'a change-based resize', 'dense-prediction'),
     ((CBPad2d,), 'a change-based padding', 'reflection-padded and restoration'),
     ((CBBinary2d, CBGLU2d), 'a change-based element-wise operator of two maps', 'gated and attention'),
-)
-# ... and the channel attention scale with its wiring module, refused in the same words.  A table of its own: the rows
-# above are the module types of cbinfer_amd._STATEFUL, which the scale stands beside (cbinfer_amd._CHANNEL_STATE).
-CHANNEL_OPERATORS = (
+    # (the wiring module stands in its row too: named_modules() reaches it before its scale, so it is named)
     ((CBSqueezeExcite, CBChannelScale2d), 'a change-based channel attention scale', 'squeeze-and-excitation'),
-)
-# ... and the group norm, likewise beside the table (cbinfer_amd._STATISTIC_STATE)
-STATISTIC_OPERATORS = (
     ((CBGroupNorm2d,), 'a change-based group norm', 'GroupNorm and InstanceNorm'),
 )
 
@@ -84,7 +78,7 @@ class SequenceBatch(object):
             if type(m) in (CBPoolMax2d, CBPoolAvg2d) and m.__dict__.get('_general'):
                 raise CBinferError("SequenceBatch: layer %r is %r, a pool that is never folded into the next detection "
                                    "(only 2x2/stride 2 without padding is) and has no batched kernel" % (name, m))
-            for types, noun, networks in CHAIN_OPERATORS + CHANNEL_OPERATORS + STATISTIC_OPERATORS:
+            for types, noun, networks in CHAIN_OPERATORS:
                 if type(m) in types:
                     raise CBinferError("SequenceBatch: layer %r is %r, %s, which has no batched kernel: run %s networks "
                                        "one sequence per stream" % (name, m, noun, networks))

@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import C, CBinferError, check
-from .batch import CHAIN_OPERATORS, CHANNEL_OPERATORS, STATISTIC_OPERATORS
+from .batch import CHAIN_OPERATORS
 from .conv2d import CBConv2d
 
 
@@ -39,7 +39,7 @@ class BranchGroup(nn.Module):
                                    "padding=%s dilation=%s%s), which has no grouped launch"
                                    % (name, tuple(m.kernel_size), tuple(m.stride), tuple(m.padding), tuple(m.dilation),
                                       '' if m.bias is not None else ', no bias'))
-            for types, noun, _ in CHAIN_OPERATORS + CHANNEL_OPERATORS + STATISTIC_OPERATORS:
+            for types, noun, _ in CHAIN_OPERATORS:
                 if type(m) in types:
                     raise CBinferError("BranchGroup: layer %r is %r, %s, which has no grouped launch" % (name, m, noun))
         self.__dict__['_pairs'] = {}

@@ -9,7 +9,8 @@ shuffles, CBChannelReduce2d, CBResize2d, CBPad2d, CBBinary2d, CBGLU2d, CBChannel
 (_fresh_state).
 
 The passes: the ONE table that says which module type counts as a producer for which pass (PRODUCERS, one row per
-module type of the package, the exceptions as data) and its accessor (producers(passName)), what is switched on at a
+module type of the package -- every one: the package's `__all__`, its state helpers and the pycbinfer aliases are read
+off it --, the exceptions as data) and its accessors (module_types(), producers(passName)), what is switched on at a
 producer (hand_on_changes) and at the module behind a new one (link_consumer), and the ONE walk that puts an operator
 behind its producers (insert_behind_producers).
 """
@@ -230,17 +231,30 @@ PRODUCERS = (
     ('CBConcat2d', 'decoder', ONLY, ()),
     # a producer for no pass, kept as found (it can hand the list it was given on: propChangeIndexes)
     ('CBTail1x1', 'conv2d', ONLY, ()),
+    # producers for no pass, kept as found: the channel attention scale and its wiring module (a wrapper: its pool and
+    # its scale keep the state) ...
+    ('CBChannelScale2d', 'chanscale', ONLY, ()),
+    ('CBSqueezeExcite', 'chanscale', ONLY, ()),
+    # ... and the group norm
+    ('CBGroupNorm2d', 'groupnorm', ONLY, ()),
 )
+
+
+@functools.lru_cache(maxsize=None)
+def module_types():
+    """The class of every row of PRODUCERS, in row order.  (Imported here, on first use: their modules import this
+    one.)"""
+    return tuple(getattr(importlib.import_module('.' + module, __package__), name) for name, module, _, _ in PRODUCERS)
 
 
 @functools.lru_cache(maxsize=None)
 def producers(passName):
     """The module types (exactly, not a subclass) that the pass `passName` of PASSES accepts in front of its module, in
-    the order of PRODUCERS.  (Imported here, at conversion time: their modules import this one.)"""
+    the order of PRODUCERS."""
     if passName not in PASSES:
         raise CBinferError("chain.producers: %r is no pass of %s" % (passName, PASSES))
-    return tuple(getattr(importlib.import_module('.' + module, __package__), name)
-                 for name, module, rule, passes in PRODUCERS if (passName in passes) == (rule is ONLY))
+    return tuple(t for t, (_, _, rule, passes) in zip(module_types(), PRODUCERS)
+                 if (passName in passes) == (rule is ONLY))
 
 
 def hand_on_changes(prod):

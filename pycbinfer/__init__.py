@@ -8,26 +8,11 @@ import sys
 
 import cbinfer_amd
 from cbinfer_amd import *            # noqa: F401,F403
-from cbinfer_amd import CBChannelScale2d, CBSqueezeExcite, chanscale      # noqa: F401  (no entries of __all__)
-from cbinfer_amd import CBGroupNorm2d, groupnorm      # noqa: F401  (likewise)
-from cbinfer_amd import binary, chanreduce, conv2d, conv2d_cg, conv2d_fg, decoder, dwconv, groupconv, pad, pointwise, pool, rearrange, residual, resize, tconv
 
-sys.modules[__name__ + '.conv2d'] = conv2d
-sys.modules[__name__ + '.conv2d_cg'] = conv2d_cg
-sys.modules[__name__ + '.conv2d_fg'] = conv2d_fg
-sys.modules[__name__ + '.pool'] = pool
-sys.modules[__name__ + '.residual'] = residual
-sys.modules[__name__ + '.decoder'] = decoder
-sys.modules[__name__ + '.tconv'] = tconv
-sys.modules[__name__ + '.dwconv'] = dwconv
-sys.modules[__name__ + '.pointwise'] = pointwise
-sys.modules[__name__ + '.groupconv'] = groupconv
-sys.modules[__name__ + '.rearrange'] = rearrange
-sys.modules[__name__ + '.chanreduce'] = chanreduce
-sys.modules[__name__ + '.resize'] = resize
-sys.modules[__name__ + '.pad'] = pad
-sys.modules[__name__ + '.binary'] = binary
-sys.modules[__name__ + '.chanscale'] = chanscale
-sys.modules[__name__ + '.groupnorm'] = groupnorm
+# every module that holds a module type of the package (the `module` column of chain.PRODUCERS) and the two of the
+# reference's function level, under the reference's name
+for _m in dict.fromkeys([row[1] for row in cbinfer_amd.chain.PRODUCERS] + ['conv2d_cg', 'conv2d_fg']):
+    sys.modules[__name__ + '.' + _m] = globals()[_m] = getattr(cbinfer_amd, _m)
+del _m
 
 __all__ = cbinfer_amd.__all__

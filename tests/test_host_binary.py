@@ -405,7 +405,8 @@ def test_batch_branch_and_program_refusals_name_the_module(pkg, lib):
     from cbinfer_amd import batch
     assert [row for row in batch.CHAIN_OPERATORS if pkg.CBBinary2d in row[0]] == [
         ((pkg.CBBinary2d, pkg.CBGLU2d), 'a change-based element-wise operator of two maps', 'gated and attention')]
-    assert batch.CHAIN_OPERATORS[-2][0] == (pkg.CBPad2d,)      # (the row was appended)
+    firsts = [row[0] for row in batch.CHAIN_OPERATORS]      # (the row was appended: it stands right behind CBPad2d's)
+    assert firsts[firsts.index((pkg.CBBinary2d, pkg.CBGLU2d)) - 1] == (pkg.CBPad2d,)
     import cbinfer_amd.program as program
     said = inspect.getsource(pkg.FrameProgram)
     assert "pycbinfer.CBBinary2d / CBGated / CBGLU2d (insertCBGating)" in said

@@ -1549,7 +1549,7 @@ MATRIX = {
     'insertCBPooling(generalGeometry=True)': ['CBConv2d', 'CBPointwise2d', 'CBPad2d'],
 }
 # the module types that wrap stateful children and keep no state of their own
-WRAPPERS = ['CBResidual', 'CBGated']
+WRAPPERS = ['CBResidual', 'CBGated', 'CBSqueezeExcite']
 # the layers that SequenceBatch takes or refuses by its own rule, not through batch.CHAIN_OPERATORS
 BATCH_OWN_RULE = ['CBConv2d', 'CBPoolMax2d', 'CBPoolAvg2d', 'CBTail1x1']
 
@@ -1581,7 +1581,8 @@ def test_producer_table_has_one_row_for_every_module_type(chain):
         assert getattr(getattr(cbinfer_amd, module), name) is getattr(cbinfer_amd, name)
         assert rule in (chain.BUT, chain.ONLY) and set(passes) <= set(chain.PASSES), name
     # a producer for no pass stands in the table as that
-    assert [row[0] for row in chain.PRODUCERS if row[2:] == (chain.ONLY, ())] == ['CBConcat2d', 'CBTail1x1']
+    assert [row[0] for row in chain.PRODUCERS if row[2:] == (chain.ONLY, ())] == [
+        'CBConcat2d', 'CBTail1x1', 'CBChannelScale2d', 'CBSqueezeExcite', 'CBGroupNorm2d']
     assert not any(rule == chain.BUT and set(passes) == set(chain.PASSES) for _, _, rule, passes in chain.PRODUCERS)
 
 
@@ -1604,4 +1605,44 @@ def test_batch_and_branch_group_refuse_every_chain_operator():
     from cbinfer_amd import batch
     refused = [t.__name__ for row in batch.CHAIN_OPERATORS for t in row[0]]
     assert len(set(refused)) == len(refused) and not set(refused) & set(BATCH_OWN_RULE)
-    assert sorted(refused + BATCH_OWN_RULE) == sorted(t.__name__ for t in cbinfer_amd._STATEFUL)
+    # (the wrapper CBSqueezeExcite keeps no state, and is refused under its own name: named_modules() reaches it before
+    #  its scale)
+    assert sorted(refused + BATCH_OWN_RULE) == sorted([t.__name__ for t in cbinfer_amd._STATEFUL] + ['CBSqueezeExcite'])
+
+
+def test_batch_refusal_rows_are_the_thirteen_recorded():
+    """batch.CHAIN_OPERATORS, row for row: the eleven rows of the table and the two that stood in tables of their own
+    beside it (the channel attention scale, the group norm), as they read before the three became one."""
+    from cbinfer_amd import batch
+    assert [(tuple(t.__name__ for t in types), noun, networks) for types, noun, networks in batch.CHAIN_OPERATORS] == [
+        (('CBAdd2d',), 'a change-based sum', 'residual'),
+        (('CBUpsample2d', 'CBConcat2d'), 'a change-based decoder operator', 'decoder'),
+        (('CBConvTranspose2d',), 'a change-based transposed convolution', 'decoder'),
+        (('CBDepthwiseConv2d',), 'a change-based depthwise convolution', 'separable'),
+        (('CBPointwise2d',), 'a change-based element-wise function', 'such'),
+        (('CBGroupedConv2d',), 'a change-based grouped convolution', 'ResNeXt-type'),
+        (('CBPixelShuffle2d', 'CBChannelShuffle2d'), 'a change-based rearrangement',
+         'super-resolution and ShuffleNet-type'),
+        (('CBChannelReduce2d',), 'a change-based per-pixel channel reduction', 'ConvNeXt-type and segmentation'),
+        (('CBResize2d',), 'a change-based resize', 'dense-prediction'),
+        (('CBPad2d',), 'a change-based padding', 'reflection-padded and restoration'),
+        (('CBBinary2d', 'CBGLU2d'), 'a change-based element-wise operator of two maps', 'gated and attention'),
+        (('CBSqueezeExcite', 'CBChannelScale2d'), 'a change-based channel attention scale', 'squeeze-and-excitation'),
+        (('CBGroupNorm2d',), 'a change-based group norm', 'GroupNorm and InstanceNorm'),
+    ]
+    assert type(batch.CHAIN_OPERATORS) is tuple and all(type(row[0]) is tuple for row in batch.CHAIN_OPERATORS)
+
+
+def test_alias_package_mirrors_the_table(chain):
+    import sys
+    import cbinfer_amd
+    import pycbinfer
+    for name, module, _, _ in chain.PRODUCERS:
+        assert getattr(pycbinfer, name) is getattr(cbinfer_amd, name)
+        assert sys.modules['pycbinfer.' + module] is getattr(pycbinfer, module) is getattr(cbinfer_amd, module)
+    for module in ('conv2d_cg', 'conv2d_fg'):
+        assert sys.modules['pycbinfer.' + module] is getattr(pycbinfer, module) is getattr(cbinfer_amd, module)
+    assert sorted(k for k in sys.modules if k.startswith('pycbinfer.')) == sorted('pycbinfer.' + m for m in (
+        'conv2d', 'conv2d_cg', 'conv2d_fg', 'pool', 'residual', 'decoder', 'tconv', 'dwconv', 'pointwise', 'groupconv',
+        'rearrange', 'chanreduce', 'resize', 'pad', 'binary', 'chanscale', 'groupnorm'))
+    assert pycbinfer.__all__ is cbinfer_amd.__all__

@@ -266,8 +266,9 @@ def test_exports_state_helpers_pickle_and_deepcopy(pkg, lib):
     assert alias is cbinfer_amd.chanscale and pkg.chanscale is alias
     for name in ('CBChannelScale2d', 'CBSqueezeExcite', 'insertCBSqueezeExcite'):
         assert getattr(pkg, name) is getattr(alias, name) is getattr(cbinfer_amd, name)
-    assert 'insertCBSqueezeExcite' in pkg.__all__
-    assert cbinfer_amd._CHANNEL_STATE == (pkg.CBChannelScale2d,)
+    assert all(n in pkg.__all__ for n in ('CBChannelScale2d', 'CBSqueezeExcite', 'insertCBSqueezeExcite'))
+    assert pkg.CBChannelScale2d in cbinfer_amd._STATEFUL and pkg.CBSqueezeExcite not in cbinfer_amd._STATEFUL
+    assert not hasattr(cbinfer_amd, '_CHANNEL_STATE')
     se = pkg.CBSqueezeExcite(0.02, nn.Conv2d(4, 2, 1), nn.Conv2d(2, 4, 1), nn.ReLU(), gate='hardsigmoid')
     assert type(se.pool) is pkg.CBPoolAvg2d and se.pool.output_size == (1, 1) and se.pool.cloneOutput is False
     assert type(se.scale) is pkg.CBChannelScale2d and (se.scale.gate, se.scale.hidden, se.threshold) == ('hardsigmoid', 2, 0.02)
@@ -300,19 +301,25 @@ def test_exports_state_helpers_pickle_and_deepcopy(pkg, lib):
 
 
 def test_the_chain_tables_are_as_they_were(pkg):
-    """The scale is a producer for no pass yet: chain.PRODUCERS and chain.PASSES have the rows and names that
-    tests/chain_cases.py and tests/test_host_chain.py write out, and insertCBSqueezeExcite walks behind the producers of
-    insertCBGating."""
+    """The scale and its wiring module are rows of chain.PRODUCERS and producers for no pass yet: chain.PASSES has the
+    names that tests/chain_cases.py and tests/test_host_chain.py write out, every pass accepts what it did, and
+    insertCBSqueezeExcite walks behind the producers of insertCBGating."""
     from cbinfer_amd import batch, chain
     import test_host_chain
     assert len(chain.PASSES) == len(chain_cases.PASSES) == len(test_host_chain.MATRIX) == 11
     assert list(chain.PASSES) == list(test_host_chain.MATRIX)
-    assert len(chain.PRODUCERS) == 20 and not any('Scale' in row[0] or 'Squeeze' in row[0] for row in chain.PRODUCERS)
+    assert len(chain.PRODUCERS) == 23
+    assert [row for row in chain.PRODUCERS if 'Scale' in row[0] or 'Squeeze' in row[0]] == [
+        ('CBChannelScale2d', 'chanscale', chain.ONLY, ()), ('CBSqueezeExcite', 'chanscale', chain.ONLY, ())]
+    for p in chain.PASSES:
+        assert pkg.CBChannelScale2d not in chain.producers(p) and pkg.CBSqueezeExcite not in chain.producers(p), p
     assert set(chain_cases.producer_type(c) for c in chain_cases.CASES) <= set(row[0] for row in chain.PRODUCERS)
     assert 'insertCBSqueezeExcite' not in chain.PASSES
     assert "producers('insertCBGating')" in inspect.getsource(pkg.insertCBSqueezeExcite)
-    assert batch.CHANNEL_OPERATORS == (((pkg.CBSqueezeExcite, pkg.CBChannelScale2d),
-                                        'a change-based channel attention scale', 'squeeze-and-excitation'),)
+    assert [row for row in batch.CHAIN_OPERATORS if {pkg.CBChannelScale2d, pkg.CBSqueezeExcite} & set(row[0])] == [
+        ((pkg.CBSqueezeExcite, pkg.CBChannelScale2d), 'a change-based channel attention scale',
+         'squeeze-and-excitation')]
+    assert not hasattr(batch, 'CHANNEL_OPERATORS')
 
 
 # ------------------------------------------------------------------------------------------------ wiring

@@ -279,16 +279,17 @@ def test_exports_state_helpers_pickle_and_deepcopy(pkg, lib):
     assert alias is cbinfer_amd.groupnorm and pkg.groupnorm is alias
     for name in ('CBGroupNorm2d', 'insertCBGroupNorm'):
         assert getattr(pkg, name) is getattr(alias, name) is getattr(cbinfer_amd, name)
-    assert 'insertCBGroupNorm' in pkg.__all__ and 'CBGroupNorm2d' not in pkg.__all__
-    # the pinned tables are as they were; the new tuples have one row each
-    assert cbinfer_amd._STATISTIC_STATE == (pkg.CBGroupNorm2d,)
-    assert cbinfer_amd._CHANNEL_STATE == (pkg.CBChannelScale2d,)
-    assert pkg.CBGroupNorm2d not in cbinfer_amd._STATEFUL and len(cbinfer_amd._STATEFUL) == 18
-    assert batch.STATISTIC_OPERATORS == (((pkg.CBGroupNorm2d,), 'a change-based group norm',
-                                          'GroupNorm and InstanceNorm'),)
-    assert len(batch.CHANNEL_OPERATORS) == 1 and len(batch.CHAIN_OPERATORS) == 11
-    assert len(chain.PRODUCERS) == 20 and len(chain.PASSES) == 11
-    assert not any(row[0] == 'CBGroupNorm2d' for row in chain.PRODUCERS)
+    assert 'insertCBGroupNorm' in pkg.__all__ and 'CBGroupNorm2d' in pkg.__all__
+    # the group norm is a row of each table; no tuple stands beside them
+    assert pkg.CBGroupNorm2d in cbinfer_amd._STATEFUL and len(cbinfer_amd._STATEFUL) == 20
+    assert not hasattr(cbinfer_amd, '_STATISTIC_STATE') and not hasattr(batch, 'STATISTIC_OPERATORS')
+    assert [row for row in batch.CHAIN_OPERATORS if pkg.CBGroupNorm2d in row[0]] == [
+        ((pkg.CBGroupNorm2d,), 'a change-based group norm', 'GroupNorm and InstanceNorm')]
+    assert len(batch.CHAIN_OPERATORS) == 13
+    assert len(chain.PRODUCERS) == 23 and len(chain.PASSES) == 11
+    assert [row for row in chain.PRODUCERS if row[0] == 'CBGroupNorm2d'] == [
+        ('CBGroupNorm2d', 'groupnorm', chain.ONLY, ())]
+    assert not any(pkg.CBGroupNorm2d in chain.producers(p) for p in chain.PASSES)
     assert issubclass(pkg.CBGroupNorm2d, chain.CBStateModule)
     net = nn.Sequential(pkg.CBGroupNorm2d(nn.GroupNorm(2, 4), 0.03, relu=True), pkg.CBGroupNorm2d(nn.InstanceNorm2d(4), 0.0))
     a, b = net[0], net[1]
