@@ -2133,45 +2133,96 @@ __global__ __launch_bounds__(S == 1 ? 64 * CB_TAIL_MAXW : CB_TAIL_MAXT) void cbs
     cb_touch_kernarg<sizeof(CbsParams) + sizeof(CbsTailArgs)>();
     const int C0 = p.K, C0P = (C0 + 15) / 16 * 16, C1 = ta.C1, C2 = ta.C2, HW = p.H * p.W;
     const int t = threadIdx.x, NT = blockDim.x;      // (64 x ceil(C1/16) row blocks x S chain sets: cb_tail_core.h)
-    // Round trips to memory are what this launch consists of.  First: the launch info of the contraction, the
-    // layer's biases, the second layer's matrix.  Second (per group): the slabs of the group's 16 pixel columns --
-    // their address needs no pixel index -- and the 16 pixel indices.  Third: this wave's part of W1.
+    // Round trips to memory are what this launch consists of.  First, ONE request burst at entry: the contraction's
+    // launch info -- read here and nowhere else: the stores below may alias it, so every later read was a trip of its
+    // own -- and this thread's elements of the second layer's matrix and bias, whose addresses depend on nothing.
+    // Second (per group), one burst again: the group's 16 pixel indices, the slabs of its 16 pixel columns -- their
+    // address needs no pixel index -- and the layer's biases.  Third: this wave's part of W1.
     CB_TAIL_STAMP(0);
-    const int SK = p.info[CBS_INFO_SK], MT = p.info[CBS_INFO_MT], CMB = MT * SK, TILE4 = BM * BN / 4;
-    CBS_TILES_BEFORE(tilesBefore, p.info);
-    const int GP = BN / CB_TAIL_PX, groups = tilesBefore[CBS_MAXSEQ] * GP;
+    constexpr int W2E = 2;      // elements of W2 per thread in the entry burst (the rest, if any: the loops in stageW2Rest)
+    constexpr int NINFO = CBS_INFO_TP + 2 * CBS_MAXSEQ;
+    static_assert(NINFO <= 64, "a launch-info word per lane");
+    const int nW2 = C2 * C1;
+    // lane i of every wave holds info word i: one request, one register, and no scalar register per word across the
+    // group loop (the words are read off the lanes where they are used)
+    const int iv = p.info[min(t & 63, NINFO - 1)];
+    float w2v[W2E];
+#pragma unroll
+    for (int e = 0; e < W2E; ++e) w2v[e] = ta.w2[min(t + e * NT, nW2 - 1)];
+    const float b2v = ta.b2[min(t, C2 - 1)];
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");      // (no request of the burst sinks below the first branch)
+    // the wait of the entry burst: for the info words only, the request in front of W2's
+    const int SK = __builtin_amdgcn_readlane(iv, CBS_INFO_SK), MT = __builtin_amdgcn_readlane(iv, CBS_INFO_MT);
+    const int CMB = MT * SK, TILE4 = BM * BN / 4;
+    int tiles = 0;
+#pragma unroll
+    for (int q_ = 0; q_ < CBS_MAXSEQ; ++q_) tiles += __builtin_amdgcn_readlane(iv, CBS_INFO_TP + q_);
+    const int GP = BN / CB_TAIL_PX, groups = tiles * GP;
     if ((int)blockIdx.x >= groups) return;
     CB_TAIL_STAMP(1);
     const CbTailLds L = cb_tail_lds(cbs_tail_sm, C0P, C1, C2);
     __shared__ int s_pix[CB_TAIL_PX];
-    for (int i = t; i < C2 * C1; i += NT) L.W2s[i] = ta.w2[i];
-    for (int i = t; i < C2; i += NT) L.b2s[i] = ta.b2[i];
+    // W2 and b2 into LDS, behind the requests of the workgroup's first group: the entry burst's values (stageW2), then
+    // what a wide second layer has beyond W2E elements per thread (stageW2Rest, behind the sums).  Their first reader
+    // stands behind cb_tail_tile's barriers.
+    auto stageW2 = [&]() {
+#pragma unroll
+        for (int e = 0; e < W2E; ++e)
+            if (t + e * NT < nW2) L.W2s[t + e * NT] = w2v[e];
+        if (t < C2) L.b2s[t] = b2v;
+    };
+    auto stageW2Rest = [&]() {
+        for (int i = t + W2E * NT; i < nW2; i += NT) L.W2s[i] = ta.w2[i];
+        for (int i = t + NT; i < C2; i += NT) L.b2s[i] = ta.b2[i];
+    };
     const float4* __restrict__ slabs = (const float4*)p.slabs;
     const bool hasBias = p.bias != nullptr;
     const float* biasp = hasBias ? p.bias : ta.b1;      // (no bias: any readable address, the values are not used)
     const int px = t & 15, cstep = NT >> 4;
-    for (int g = blockIdx.x; g < groups; g += gridDim.x) {
-        const int ptg = g / GP, gi = g - ptg * GP;
-        CBS_TILE_SEQUENCE(q, tilesBefore, p.nSeq, ptg);
-        const int nl0 = gi * CB_TAIL_PX, n0 = (ptg - tilesBefore[q]) * BN + nl0;
-        const int N = p.info[CBS_INFO_TP + CBS_MAXSEQ + q];
-        if (n0 >= N) continue;      // (uniform: a tile's last groups may be empty)
+    // Where group g lies: its tile, its sequence q, its first list slot n0 and the length N of the sequence's list
+    // (CBS_TILES_BEFORE and CBS_TILE_SEQUENCE off the lanes of iv).  n0 >= N: a tile's last groups may be empty.
+    auto locate = [&](int g, int& ptg, int& q, int& nl0, int& n0, int& N) {
+        ptg = g / GP, nl0 = (g - ptg * GP) * CB_TAIL_PX;
+        int tilesBeforeQ = 0, before = 0;
+        q = 0, N = __builtin_amdgcn_readlane(iv, CBS_INFO_TP + CBS_MAXSEQ);
+#pragma unroll
+        for (int u = 1; u < CBS_MAXSEQ; ++u) {
+            before += __builtin_amdgcn_readlane(iv, CBS_INFO_TP + u - 1);
+            if (u < p.nSeq && ptg >= before)
+                q = u, tilesBeforeQ = before, N = __builtin_amdgcn_readlane(iv, CBS_INFO_TP + CBS_MAXSEQ + u);
+        }
+        n0 = (ptg - tilesBeforeQ) * BN + nl0;
+    };
+    // One group.  FIRST: the workgroup's first one with a pixel, which also stages W2 -- a body of its own, so that the
+    // entry burst's registers and the staging's addresses are not kept across the loop over the later ones.
+    auto group = [&](int g, auto firstc) {
+        constexpr bool FIRST = decltype(firstc)::value;
+        int ptg, q, nl0, n0, N;
+        locate(g, ptg, q, nl0, n0, N);
+        if constexpr (!FIRST)
+            if (n0 >= N) return;      // (uniform)
         float* outq = p.seq[q].out;
         // fine-grained frame (accumulate: out += W * delta, cbconv2d_fg_backend.cu:37-66): the sum of the slabs JOINS
         // what the output holds, the relu'd copy (reluOut, if the layer has one) is kept beside it, and the tail's input
         // is that copy -- what the next module of the network is handed (conv2d.py:169-173)
         float* relq = p.accumulate ? p.seq[q].reluOut : nullptr;
-        int pixMine = -1;           // (thread px of every 16: the same 16 indices, no LDS hop before the scatter)
-        if (n0 + px < N) pixMine = p.seq[q].listOut[n0 + px];
+        // thread px of every 16: the same 16 indices, no LDS hop before the scatter.  Requested at a clamped address (loads
+        // are never predicated -- a predicated load is a branch, and sixteen branches in a row are sixteen round trips:
+        // clamped addresses, predicated USES); its first use stands behind the slab requests.
+        const int pixReq = p.seq[q].listOut[min(n0 + px, N - 1)];
         // (everything below that depends only on the thread index is the same in every round of this loop, and the
         //  compiler would keep it all -- some eighty registers of addresses -- alive across the loop: an opaque copy
         //  of the index makes it recompute them, a few integer instructions per use)
         int tq = t >> 4;
         asm volatile("" : "+v"(tq));
-        if ((unsigned)pixMine >= (unsigned)HW) pixMine = -1;
-        const int pixLd = max(pixMine, 0);      // (loads are never predicated -- a predicated load is a branch, and
-                                                //  sixteen branches in a row are sixteen round trips: clamped addresses,
-                                                //  predicated USES)
+        // the thread's pixel, or -1, from the index it requested: called BEHIND the group's requests (the opaque copy keeps
+        // the range check, and with it the wait for the index, from moving in front of them)
+        auto pixOf = [&](int r) {
+            asm volatile("" : "+v"(r));
+            return (n0 + px < N && (unsigned)r < (unsigned)HW) ? r : -1;
+        };
+        int pixMine = -1;
         if (SK > 1) {
             // X[c][px] from the slabs (SK = CBS_CHUNKS of them): thread -> (px, channel quads t/16 + i NT/16); all loads
             // of a thread in flight.  The same number of rounds for every thread, so that all reach the barrier.
@@ -2196,13 +2247,30 @@ __global__ __launch_bounds__(S == 1 ? 64 * CB_TAIL_MAXW : CB_TAIL_MAXT) void cbs
                     }
                     __builtin_amdgcn_sched_barrier(0);      // (all loads requested before anything of the second half)
                     if (rd == 0) {
+                        // (the end of the burst, for tests/test_host_tail_burst.py to find in the listing)
+                        if constexpr (FIRST) asm volatile("; cbs_tail_first_burst_end" ::: "memory");
+                        else asm volatile("; cbs_tail_next_burst_end" ::: "memory");
+                        __builtin_amdgcn_sched_barrier(0);      // (the index's first use, a copy, stays behind the mark)
+                        pixMine = pixOf(pixReq);
+                        if constexpr (FIRST) stageW2();
                         __syncthreads();   // previous group's Hs / s_pix / Xs reads are done
                         if (t < CB_TAIL_PX) s_pix[t] = pixMine;
                         CB_TAIL_STAMP(2);
+#ifdef CBS_STAMP
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        CB_TAIL_STAMP(8);      // (the first round's slab values are there)
+#endif
                     }
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const int cq = cq0 + u * cstep;
+                        // (every requested value is waited for HERE, on every path: summed only where its quad exists, a
+                        //  request would stay open, and the compiler puts a wait in front of every later write of such a
+                        //  register -- into the burst of the next form of this lambda, which the listing reaches from here)
+#pragma unroll
+                        for (int j = 0; j < CBS_CHUNKS; ++j)
+                            asm volatile("" ::"v"(v[u][j].x), "v"(v[u][j].y), "v"(v[u][j].z), "v"(v[u][j].w));
+                        asm volatile("" ::"v"(bq[u].x), "v"(bq[u].y), "v"(bq[u].z), "v"(bq[u].w));
                         float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll
                         for (int j = 0; j < CBS_CHUNKS; ++j)
@@ -2236,12 +2304,20 @@ __global__ __launch_bounds__(S == 1 ? 64 * CB_TAIL_MAXW : CB_TAIL_MAXT) void cbs
             else if (perThread <= 2 || S > 1) slabRounds(std::integral_constant<int, 2>());
             else slabRounds(std::integral_constant<int, 4>());
         } else {
-            // unsplit: the contraction's epilogue has written prevOutput; gather as the tail kernel does
+            // unsplit: the contraction's epilogue has written prevOutput; gather as the tail kernel does (its addresses
+            // need the pixel index: one more trip)
+            pixMine = pixOf(pixReq);
+            const int pixLd = max(pixMine, 0);
             __syncthreads();
             if (t < CB_TAIL_PX) s_pix[t] = pixMine;
             const float* gsrc = relq ? relq : outq;      // (fine-grained with a relu'd copy: the tail reads the copy)
             cb_tail_gather<(S == 1 ? 16 : 8)>(L.Xs, gsrc, HW, pixLd, pixMine >= 0, C0, C0P, tq, px, cstep);
+            // (the copies a clamped address fetched are never waited for; the compiler's wait insertion follows this path
+            //  into the other one -- they meet in blocks that branch on a flag -- and would wait in the middle of its burst)
+            __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0)
+            if constexpr (FIRST) stageW2();
         }
+        if constexpr (FIRST) stageW2Rest();
         // this wave's part of W1: requested once the slab registers are free (requested earlier -- beside the slabs,
         // or behind their barrier -- the launch came out longer: the barrier waits for them too, and the stores of the
         // sums queue behind them; at kernel entry, 16 registers wide since the chains have waves of their own, it came
@@ -2253,7 +2329,21 @@ __global__ __launch_bounds__(S == 1 ? 64 * CB_TAIL_MAXW : CB_TAIL_MAXT) void cbs
         CB_TAIL_STAMP(3);
         cb_tail_tile<S>(L, s_pix, P, ta.w1p, ta.out[q], C0P, C1, C2, HW, ta.relu1, ta.relu2);
         CB_TAIL_STAMP(7);
+        // Nothing stays open into the next group.  A value requested on a path that does not use it (a wave without a
+        // hidden row or a fragment group) is never waited for, and the compiler then puts waits in front of every later
+        // write of such a register: into the middle of the next group's burst.  (The wait for the list index at the top
+        // of the loop covered all of it before.)
+        if (g + (int)gridDim.x < groups) __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0)
+    };
+    int g = blockIdx.x;
+    for (; g < groups; g += gridDim.x) {      // (the first group with a pixel; without one there is nothing to do)
+        int ptg, q, nl0, n0, N;
+        locate(g, ptg, q, nl0, n0, N);
+        if (n0 < N) break;
     }
+    if (g >= groups) return;
+    group(g, std::true_type());
+    for (g += gridDim.x; g < groups; g += gridDim.x) group(g, std::false_type());
 }
 
 template <int BM, int BN, int WM, int WN, int PRE_CAP, bool MASK_LDS, int RING, int AR = 0>

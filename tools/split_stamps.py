@@ -34,7 +34,7 @@ def report(clear=True):
         print("  reduce + tail launch: %d workgroups stamped" % len(st))
         t0 = st[:, 0].min()
         names = ['entry', 'launch info known', 'slab columns arrived', 'X tile written', 'X tile complete (barrier)',
-                 'first layer done', 'hidden tile complete (barrier)', 'group done']
+                 'first layer done', 'hidden tile complete (barrier)', 'group done', 'first slab values arrived']
         for i, n in enumerate(names):
             v = st[:, i] >= t0
             if v.sum():
