@@ -8,8 +8,7 @@ Table 2, one 64-channel basic block (two 3x3 layers + add) at 80x120, frame time
 CBResidual run eagerly, and the same two CBConv2d layers followed by torch's add + relu.  The block's input arrives with
 its change mask, as behind a producing layer: a frame differs from the one before in two change sets of 5 % each, and the
 mask (160 words) is copied into the block's static mask buffer before every frame, in all three configurations alike.
-Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of the
-per-call time; every call of a batch takes the next of 16 change sets.  Prints markdown (profiles/add_target.md).
+The measuring method is tools/target_common.py's.  Prints markdown (profiles/add_target.md).
 usage: add_target.py [rounds]"""
 import copy
 import os
@@ -25,54 +24,10 @@ import pycbinfer  # noqa: E402
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
 from cbinfer_amd.conv2d_cg import MaskChangeIndexes  # noqa: E402
+from target_common import BATCH, SETS, change_sets, device_sets, fmt, listed_share, moving_frames, pack, rounds  # noqa: E402
 
 #          name, channels, H, W, block
 LAYERS = [("64 ch", 64, 80, 120, 8), ("128 ch", 128, 40, 60, 4), ("256 ch", 256, 20, 30, 2)]
-BATCH, SETS = 32, 16
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack(mask):
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').view(np.int64).copy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the change sets)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
 
 
 def layer(name, Cn, H, W, block, reps):
@@ -80,8 +35,7 @@ def layer(name, Cn, H, W, block, reps):
     a = torch.randn(1, Cn, H, W, device="cuda")
     b = torch.randn(1, Cn, H, W, device="cuda")
     sets = change_sets(rng, H, W, block, 0.10)
-    lists = [torch.from_numpy(np.flatnonzero(m.reshape(-1)).astype(np.int32)).cuda() for m in sets]
-    masks = [torch.from_numpy(pack(m)).cuda() for m in sets]
+    masks, lists = device_sets(sets)
     words = C.cbinfer_mask_words(H, W)
     bits = torch.zeros(words, dtype=torch.int64, device="cuda")
     mcopy = torch.zeros(words, dtype=torch.int64, device="cuda")
@@ -106,7 +60,7 @@ def layer(name, Cn, H, W, block, reps):
                                   Cn, H, W, 1, _lib.CB_F32, st))
     assert torch.equal(out, torch.relu(a + b)), "change-based frame differs from the dense operators"
     t = rounds([("mask", cb_mask), ("list", cb_list), ("dense", dense)], reps)
-    listed = statistics.mean(float(m.mean()) for m in sets) * 100.0
+    listed = listed_share(sets)
     dm = statistics.median(t["dense"]) / statistics.median(t["mask"])
     dl = statistics.median(t["dense"]) / statistics.median(t["list"])
     print("| %s @%dx%d | %.1f %% | %s | %s | %s | %.2fx / %.2fx |"
@@ -119,15 +73,8 @@ def block(reps):
     torch.manual_seed(11)
     body = nn.Sequential(nn.Conv2d(Cn, Cn, 3, padding=1), nn.ReLU(), nn.Conv2d(Cn, Cn, 3, padding=1)).eval().cuda()
     sets = change_sets(rng, H, W, blk, 0.05)
-    # frame i is the base with fresh values on set i: it differs from frame i - 1 on set i and set i - 1
-    base = torch.rand(1, Cn, H, W, device="cuda")
-    frames, masks = [], []
-    for i, m in enumerate(sets):
-        sel = torch.from_numpy(m).cuda()
-        f = base.clone()
-        f[0][:, sel] = torch.rand(Cn, int(m.sum()), device="cuda")
-        frames.append(f)
-        masks.append(torch.from_numpy(pack(m | sets[i - 1])).cuda())
+    frames = moving_frames(torch.rand(1, Cn, H, W, device="cuda"), sets, Cn, torch.float32)
+    masks = [torch.from_numpy(pack(m | sets[i - 1])).cuda() for i, m in enumerate(sets)]
     words = C.cbinfer_mask_words(H, W)
 
     def incoming():
@@ -174,7 +121,7 @@ def block(reps):
             assert torch.equal(ye, yt), "CBResidual differs from the layers with torch's add + relu"
             assert torch.equal(yp, ye), "the replayed program differs from the eager block"
         t = rounds([("replayed", replayed), ("eager", eager), ("torch", torch_add)], reps)
-    changed = statistics.mean(float((m | sets[i - 1]).mean()) for i, m in enumerate(sets)) * 100.0
+    changed = listed_share([m | sets[i - 1] for i, m in enumerate(sets)])
     print("\n## One basic block: two 3x3 64 -> 64 layers + add + ReLU @%dx%d, %.1f %% changed input pixels per frame\n"
           % (H, W, changed))
     print("| configuration | frame time |")

@@ -6,9 +6,8 @@ frame in whole blocks (32x32 frame pixels of a 480x640 / 384x1280 frame, i.e. 8 
 Operators: the gate a * sigmoid(b) (torch: two operators), the layer scale gamma[c] * x (a constant channel vector: only
 x's changes count), the difference a - b.  Per row: cbinfer_cbbinary_forward with the operands in MASK form (one launch)
 and in LIST form (one launch more per per-frame operand) -- every per-frame operand carries the frame's change set --,
-against torch's dense operator(s) on the same tensors.  Interleaved: REPS rounds of alternating batches of BATCH calls,
-device events around each batch, median [min..max] of the per-call time; every call of a batch takes the next of 16
-change sets.  Prints markdown (profiles/binary_target.md).
+against torch's dense operator(s) on the same tensors.  The measuring method is tools/target_common.py's.  Prints
+markdown (profiles/binary_target.md).
 usage: binary_target.py [rounds]"""
 import os
 import statistics
@@ -20,58 +19,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import BATCH, SETS, change_sets, device_sets, dtype_name, fmt, listed_share, rounds  # noqa: E402
 
 #          name, channels, H, W, block, second operand of the gate, operators
 ROWS = [("64 ch", 64, 96, 320, 8, 'map', ('gate', 'scale', 'sub')),
         ("256 ch", 256, 48, 160, 4, 'map', ('gate', 'scale', 'sub')),
         ("64 ch, one-channel gate", 64, 96, 320, 8, 'pixel', ('gate',)),
         ("3 ch head", 3, 480, 640, 32, 'map', ('gate', 'scale', 'sub'))]
-BATCH, SETS = 32, 16
 WHAT = {'gate': "a * sigmoid(b)", 'scale': "gamma[c] * x", 'sub': "a - b"}
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack(mask):
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').view(np.int64).copy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the change sets)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
 
 
 def row(name, Cn, H, W, block, gateForm, what, dtype, reps):
@@ -88,8 +43,7 @@ def row(name, Cn, H, W, block, gateForm, what, dtype, reps):
     gate = _lib.BIN_GATE_SIGMOID if what == 'gate' else _lib.BIN_GATE_NONE
     own = chg == _lib.BIN_B_OWN
     sets = change_sets(rng, H, W, block, 0.10)
-    lists = [torch.from_numpy(np.flatnonzero(m.reshape(-1)).astype(np.int32)).cuda() for m in sets]
-    masks = [torch.from_numpy(pack(m)).cuda() for m in sets]
+    masks, lists = device_sets(sets)
     words = C.cbinfer_mask_words(H, W)
     bits = torch.zeros(words, dtype=torch.int64, device="cuda")
     mcopy = torch.zeros(words, dtype=torch.int64, device="cuda")
@@ -125,12 +79,11 @@ def row(name, Cn, H, W, block, gateForm, what, dtype, reps):
     else:
         assert torch.equal(out, dense(0)), "change-based frame differs from the dense operator"
     t = rounds([("mask", cb_mask), ("list", cb_list), ("dense", dense)], reps)
-    listed = statistics.mean(float(m.mean()) for m in sets) * 100.0
+    listed = listed_share(sets)
     dm = statistics.median(t["dense"]) / statistics.median(t["mask"])
     dl = statistics.median(t["dense"]) / statistics.median(t["list"])
     print("| %s @%dx%d | %s | %s | %.1f %% | %s | %s | %s | %.2fx / %.2fx |"
-          % (name, H, W, WHAT[what], "fp32" if dtype == torch.float32 else "fp16", listed, fmt(t["mask"]), fmt(t["list"]),
-             fmt(t["dense"]), dm, dl))
+          % (name, H, W, WHAT[what], dtype_name(dtype), listed, fmt(t["mask"]), fmt(t["list"]), fmt(t["dense"]), dm, dl))
 
 
 def main():

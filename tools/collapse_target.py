@@ -6,10 +6,9 @@ at the four resolutions) --
   (mean, max):      64 ch @80x120, 256 ch @40x60                 against cat([x.mean(1, True), x.amax(1, True)], 1)
   norm:             128 ch @60x80                                against torch.linalg.vector_norm(x, dim=1)
 Per layer and dtype: cbinfer_cbchancollapse_forward with the operand in MASK form (one launch) and in LIST form (two
-launches) against the dense torch operator on the same tensor in the same run.  The method is tools/channel_target.py's:
-interleaved -- REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of
-the per-call time; every call of a batch takes the next of 16 change sets.  Nothing here is a promise: the table says
-what came out, the rows where the dense operator wins included.  Writes markdown (profiles/collapse_target.md).
+launches) against the dense torch operator on the same tensor in the same run.  The measuring method is
+tools/target_common.py's.  Nothing here is a promise: the table says what came out, the rows where the dense operator
+wins included.  Writes markdown (profiles/collapse_target.md).
 usage: collapse_target.py [rounds] [output.md]"""
 import os
 import statistics
@@ -23,6 +22,7 @@ sys.path.insert(0, REPO)
 import pycbinfer  # noqa: E402,F401
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import BATCH, SETS, change_sets, device_sets, dtype_name, fmt, listed_share, rounds  # noqa: E402
 
 #          name, ops, channels, H, W, block
 LAYERS = [("21 ch", ("argmax",), 21, 80, 120, 8), ("150 ch", ("argmax",), 150, 80, 120, 8),
@@ -33,59 +33,13 @@ KINDS = dict(sum=_lib.CC_SUM, mean=_lib.CC_MEAN, norm=_lib.CC_NORM, max=_lib.CC_
 DENSE = {("argmax",): ("torch.argmax(x, 1)", lambda x: torch.argmax(x, 1)),
          ("mean", "max"): ("cat([mean, amax], 1)", lambda x: torch.cat([x.mean(1, keepdim=True), x.amax(1, keepdim=True)], 1)),
          ("norm",): ("linalg.vector_norm(x, dim=1)", lambda x: torch.linalg.vector_norm(x, dim=1))}
-BATCH, SETS = 32, 16
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack(mask):
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').view(np.int64).copy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the change sets)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
 
 
 def layer(name, ops, Cn, H, W, block, dtype, reps):
     rng = np.random.default_rng(7)
     x = (torch.randn(1, Cn, H, W, device="cuda") * 3).to(dtype)
     sets = change_sets(rng, H, W, block, 0.10)
-    lists = [torch.from_numpy(np.flatnonzero(m.reshape(-1)).astype(np.int32)).cuda() for m in sets]
-    masks = [torch.from_numpy(pack(m)).cuda() for m in sets]
+    masks, lists = device_sets(sets)
     words = C.cbinfer_mask_words(H, W)
     bits = torch.zeros(words, dtype=torch.int64, device="cuda")
     mcopy = torch.zeros(words, dtype=torch.int64, device="cuda")
@@ -96,7 +50,7 @@ def layer(name, ops, Cn, H, W, block, dtype, reps):
     st = torch.cuda.current_stream().cuda_stream
     dt = _lib.dtype_code(x)
     packed = sum(KINDS[n] << (4 * k) for k, n in enumerate(ops))
-    listed = statistics.mean(float(m.mean()) for m in sets) * 100.0
+    listed = listed_share(sets)
     dname, dense_op = DENSE[ops]
 
     def call(mask, lst):
@@ -129,8 +83,8 @@ def layer(name, ops, Cn, H, W, block, dtype, reps):
     dm = statistics.median(t["dense"]) / statistics.median(t["mask"])
     dl = statistics.median(t["dense"]) / statistics.median(t["list"])
     return ("| %s @%dx%d | %s | %s | %s | %.1f %% | %s | %s | %s | %.2fx / %.2fx |"
-            % (name, H, W, "fp32" if dtype == torch.float32 else "fp16", "+".join(ops), dname, listed, fmt(t["mask"]),
-               fmt(t["list"]), fmt(t["dense"]), dm, dl))
+            % (name, H, W, dtype_name(dtype), "+".join(ops), dname, listed, fmt(t["mask"]), fmt(t["list"]),
+               fmt(t["dense"]), dm, dl))
 
 
 def main():

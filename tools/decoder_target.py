@@ -11,8 +11,7 @@ Table 2, one decoder stage at 64 ch: upsample x2 (nearest) of a 64-channel 80x12
 same run eagerly, and the same CBConv2d behind F.interpolate + torch.cat.  Both inputs of the stage arrive with their
 change masks, as behind producing layers: a frame differs from the one before in two change sets of 5 % each; the masks
 are copied into static mask buffers before every frame, in all three configurations alike.
-Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of the
-per-call time; every call of a batch takes the next of 16 change sets.  Prints markdown (profiles/decoder_target.md).
+The measuring method is tools/target_common.py's.  Prints markdown (profiles/decoder_target.md).
 usage: decoder_target.py [rounds]"""
 import copy
 import ctypes
@@ -30,54 +29,10 @@ import pycbinfer  # noqa: E402
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
 from cbinfer_amd.conv2d_cg import MaskChangeIndexes  # noqa: E402
+from target_common import BATCH, SETS, change_sets, fmt, listed_share, moving_frames, pack, rounds  # noqa: E402
 
 #          name, channels, Hi, Wi, block (input pixels)
 LAYERS = [("64 ch", 64, 80, 120, 4), ("128 ch", 128, 40, 60, 2)]
-BATCH, SETS = 32, 16
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack(mask):
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').view(np.int64).copy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the change sets)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
 
 
 def layer(name, Cn, Hi, Wi, block, reps):
@@ -137,7 +92,7 @@ def layer(name, Cn, Hi, Wi, block, reps):
     assert dev <= 8 * 2.0 ** -24 * float(x.abs().max()), "bilinear is off the float64 operator by %g" % dev
     t = rounds([("near", cb_up("nearest")), ("dnear", dense_up("nearest")), ("bil", cb_up("bilinear")),
                 ("dbil", dense_up("bilinear")), ("cat", cb_cat), ("dcat", dense_cat)], reps)
-    listed = statistics.mean(float(m.mean()) for m in sets) * 100.0
+    listed = listed_share(sets)
     for label, a, b, shape in (("upsample nearest x2", "near", "dnear", "%dx%d -> %dx%d" % (Hi, Wi, Ho, Wo)),
                                ("upsample bilinear x2", "bil", "dbil", "%dx%d -> %dx%d" % (Hi, Wi, Ho, Wo)),
                                ("concat, two operands", "cat", "dcat", "2 x %d ch @%dx%d" % (Cn, Ho, Wo))):
@@ -165,17 +120,11 @@ def stage(reps):
     conv = nn.Sequential(nn.Conv2d(2 * Cn, Cn, 1)).eval().cuda()
     lowSets = change_sets(rng, Hi, Wi, blk, 0.05)
     skipSets = change_sets(rng, Ho, Wo, 2 * blk, 0.05)
-    # frame i is the base with fresh values on set i: it differs from frame i - 1 on set i and set i - 1
     lowBase, skipBase = torch.rand(1, Cn, Hi, Wi, device="cuda"), torch.rand(1, Cn, Ho, Wo, device="cuda")
 
     def frames_of(base, sets):
-        frames, masks = [], []
-        for i, m in enumerate(sets):
-            f = base.clone()
-            f[0][:, torch.from_numpy(m).cuda()] = torch.rand(base.size(1), int(m.sum()), device="cuda")
-            frames.append(f)
-            masks.append(torch.from_numpy(pack(m | sets[i - 1])).cuda())
-        return frames, masks
+        return (moving_frames(base, sets, Cn, torch.float32),
+                [torch.from_numpy(pack(m | sets[i - 1])).cuda() for i, m in enumerate(sets)])
     lowFrames, lowMasks = frames_of(lowBase, lowSets)
     skipFrames, skipMasks = frames_of(skipBase, skipSets)
 

@@ -11,8 +11,8 @@ layer of a ConvNeXt-type block and a dilated layer of a DeepLab-type head.  Per 
 Achieved bytes/s against the ALGORITHMIC bytes of a frame: (input pixels under a tap of a listed output pixel x C +
 listed output pixels x K) x element size, plus 2 C Hi Wi x element size for the form with its own detection (input and
 state are read once each).
-Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of the
-per-call time; every call of a batch takes the next of 16 frames.  Prints markdown (profiles/dw_target.md).
+The measuring method is tools/target_common.py's, with two warm-up batches per run; every call of a batch takes the next
+of 16 frames.  Prints markdown (profiles/dw_target.md).
 usage: dw_target.py [rounds]"""
 import ctypes
 import os
@@ -26,6 +26,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import BATCH, SETS, change_sets, dtype_name, fmt, listed_share, moving_frames, pack, rounds  # noqa: E402
 
 #          name, C, k, s, p, d, Hi, Wi, block (input pixels)
 LAYERS = [("32ch 3x3 s1", 32, 3, 1, 1, 1, 160, 240, 8),
@@ -35,38 +36,7 @@ LAYERS = [("32ch 3x3 s1", 32, 3, 1, 1, 1, 160, 240, 8),
           ("960ch 3x3 s1", 960, 3, 1, 1, 1, 10, 15, 1),
           ("96ch 7x7 s1 p3", 96, 7, 1, 3, 1, 80, 120, 4),
           ("256ch 3x3 d2 p2", 256, 3, 1, 2, 2, 40, 60, 2)]
-BATCH, SETS, TH = 32, 16, 0.05
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack_mask(m):
-    """bool [H, W] -> int64 [H * wpr]: bit x % 64 of word row * wpr + x / 64."""
-    H, W = m.shape
-    wpr = (W + 63) // 64
-    p = np.zeros((H, wpr * 64), dtype=np.uint8)
-    p[:, :W] = m
-    return np.packbits(p.reshape(H, wpr, 64), axis=-1, bitorder="little").view("<u8").reshape(-1).view(np.int64)
+TH = 0.05
 
 
 def maps_of(changed, k, s, p, d):
@@ -78,21 +48,6 @@ def maps_of(changed, k, s, p, d):
     read = torch.zeros(Hi, Wi, dtype=torch.bool)      # (rows and columns behind the last window are never read)
     read[:back.shape[2], :back.shape[3]] = back[0, 0, :Hi, :Wi] > 0
     return listed[0, 0].numpy(), read.numpy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the frames)
-        timed(fn, BATCH)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
 
 
 def layer(name, Cn, k, s, p, d, Hi, Wi, block, dtype, reps):
@@ -107,17 +62,14 @@ def layer(name, Cn, k, s, p, d, Hi, Wi, block, dtype, reps):
     w = (torch.randn(Cn, 1, k, k, device="cuda") / k).to(dtype)
     b = torch.randn(Cn, device="cuda").to(dtype)
     sets = change_sets(rng, Hi, Wi, block, 0.05)
-    base = torch.rand(1, Cn, Hi, Wi, device="cuda").to(dtype)
-    frames, masks, nbytes = [], [], []
+    frames = moving_frames(torch.rand(1, Cn, Hi, Wi, device="cuda").to(dtype), sets, Cn, dtype)
+    masks, nbytes = [], []
     for i, m in enumerate(sets):
-        f = base.clone()
-        f[0][:, torch.from_numpy(m).cuda()] = torch.rand(Cn, int(m.sum()), device="cuda").to(dtype)
-        frames.append(f)
         moved = m | sets[i - 1]
-        masks.append(torch.from_numpy(pack_mask(moved)).cuda())
+        masks.append(torch.from_numpy(pack(moved)).cuda())
         listed, read = maps_of(moved, k, s, p, d)
         nbytes.append((int(read.sum()) * Cn + int(listed.sum()) * Cn) * es)
-    changed = statistics.mean(float((m | sets[i - 1]).mean()) for i, m in enumerate(sets)) * 100.0
+    changed = listed_share([m | sets[i - 1] for i, m in enumerate(sets)])
     listedShare = statistics.mean(float(maps_of(m | sets[i - 1], k, s, p, d)[0].mean()) for i, m in enumerate(sets)) * 100.0
     algo = statistics.mean(nbytes)
     propagated = d == 1 and 2 * p <= k
@@ -162,11 +114,11 @@ def layer(name, Cn, k, s, p, d, Hi, Wi, block, dtype, reps):
             prop(i)
         assert off(P['out'], frames[0]) <= 1.0, "the propagated frame is off the float64 layer"
         runs.insert(1, ("prop", prop))
-    t = rounds(runs, reps)
+    t = rounds(runs, reps, warm=2)
     med = {key: statistics.median(v) for key, v in t.items()}
     detect = 2 * Cn * Hi * Wi * es
     row = "| %s | %dx%d -> %dx%d | %s | %.1f %% / %.1f %% | %s | %s | %.2fx | %.0f |" % (
-        name, Hi, Wi, Ho, Wo, "fp16" if es == 2 else "fp32", changed, listedShare, fmt(t["dense"]), fmt(t["own"]),
+        name, Hi, Wi, Ho, Wo, dtype_name(dtype), changed, listedShare, fmt(t["dense"]), fmt(t["own"]),
         med["dense"] / med["own"], (algo + detect) / med["own"] * 1e-3)
     if propagated:
         row += " %s | %.2fx | %.0f |" % (fmt(t["prop"]), med["dense"] / med["prop"], algo / med["prop"] * 1e-3)

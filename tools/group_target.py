@@ -11,8 +11,8 @@ change set i, so it differs from frame i - 1 on two sets of 5 % each).  The grou
   groups=1     the same shape as ONE group through the general-geometry frame (cbinfer_cbconv2d_forward_geom, G times
                the multiply-adds, no row padding): what the grouped form's padding costs against it.
 useful / issued: Kg / KgP * Ckkg / CkkgP, the share of the MFMA work that is not padding.
-Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of the
-per-call time; every call of a batch takes the next of 16 frames.  Prints markdown (profiles/group_target.md).
+The measuring method is tools/target_common.py's, with two warm-up batches per run; every call of a batch takes the next
+of 16 frames.  Prints markdown (profiles/group_target.md).
 usage: group_target.py [rounds]"""
 import ctypes
 import os
@@ -28,50 +28,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import cbinfer_amd  # noqa: E402
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import BATCH, SETS, change_sets, dtype_name, fmt, listed_share, moving_frames, rounds  # noqa: E402
 
 #          name, C, K, G, s, Hi, Wi, block (input pixels)
 LAYERS = [("128->128 G=32 3x3", 128, 128, 32, 1, 80, 120, 4),
           ("256->256 G=32 3x3 s2", 256, 256, 32, 2, 80, 120, 4),
           ("240->240 G=10 3x3", 240, 240, 10, 1, 40, 60, 2),
           ("1024->1024 G=32 3x3", 1024, 1024, 32, 1, 20, 30, 2)]
-BATCH, SETS, TH = 32, 16, 0.05
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the frames)
-        timed(fn, BATCH)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
+TH = 0.05
 
 
 def layer(name, Cn, K, G, s, Hi, Wi, block, dtype, reps):
@@ -90,17 +54,14 @@ def layer(name, Cn, K, G, s, Hi, Wi, block, dtype, reps):
     w, b = conv.weight.detach(), conv.bias.detach()
     w1 = (torch.randn(K, Cn, k, k, device="cuda") / (3.0 * Cn ** 0.5)).to(dtype)      # the same shape as one group
     sets = change_sets(rng, Hi, Wi, block, 0.05)
-    base = torch.rand(1, Cn, Hi, Wi, device="cuda").to(dtype)
+    frames = moving_frames(torch.rand(1, Cn, Hi, Wi, device="cuda").to(dtype), sets, Cn, dtype)
     one = torch.ones(1, 1, k, k)
-    frames, lists = [], []
+    lists = []
     for i, m in enumerate(sets):
-        f = base.clone()
-        f[0][:, torch.from_numpy(m).cuda()] = torch.rand(Cn, int(m.sum()), device="cuda").to(dtype)
-        frames.append(f)
         moved = torch.from_numpy((m | sets[i - 1]).astype(np.float32))[None, None]
         listed = (F.conv2d(moved, one, stride=s, padding=p, dilation=d) > 0)[0, 0]
         lists.append(torch.nonzero(listed.reshape(-1)).reshape(-1).int().cuda())
-    changed = statistics.mean(float((m | sets[i - 1]).mean()) for i, m in enumerate(sets)) * 100.0
+    changed = listed_share([m | sets[i - 1] for i, m in enumerate(sets)])
     listedShare = statistics.mean(float(l.numel()) for l in lists) / (Ho * Wo) * 100.0
 
     def state():
@@ -156,12 +117,12 @@ def layer(name, Cn, K, G, s, Hi, Wi, block, dtype, reps):
     assert float(((A['out'].cpu().double() - want).abs() / bound).max()) <= 1.0, "the frame is off the float64 layer"
 
     t = rounds([("detect", detect), ("contract", contract), ("frame", frame), ("module", module), ("dense", dense),
-                ("groups=1", ungrouped)], reps)
+                ("groups=1", ungrouped)], reps, warm=2)
     med = {key: statistics.median(v) for key, v in t.items()}
     rows = 16 if Kg <= 16 else 32 if Kg <= 32 else 64
     KgP, CkkgP = (Kg + rows - 1) // rows * rows, (Ckkg + 31) // 32 * 32
     print("| %s | %dx%d -> %dx%d | %s | %.1f %% / %.1f %% | %d | %.3f | %s | %s | %s | %s | %s | %.2fx | %s | %.2fx |" % (
-        name, Hi, Wi, Ho, Wo, "fp16" if half else "fp32", changed, listedShare, rows,
+        name, Hi, Wi, Ho, Wo, dtype_name(dtype), changed, listedShare, rows,
         (Kg / float(KgP)) * (Ckkg / float(CkkgP)), fmt(t["dense"]), fmt(t["detect"]), fmt(t["contract"]), fmt(t["frame"]),
         fmt(t["module"]), med["dense"] / med["frame"], fmt(t["groups=1"]), med["groups=1"] / med["frame"]), flush=True)
 

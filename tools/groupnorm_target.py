@@ -7,9 +7,8 @@ Per norm and dtype the frame -- ONE cbinfer_cbgroupnorm_forward with the affine 
 operand in LIST form -- at a threshold at which no group trips (100) and at one at which every group whose statistics moved
 trips (0), the operand in mask form and in list form, against torch's dense F.group_norm + relu on the same frames in the
 same process.  Frame i is a base frame with fresh values on change set i, so it differs from frame i - 1 on two sets of
-5 % each; the mask / the list says so.  Interleaved: REPS rounds of alternating batches of BATCH calls, device events
-around each batch, median [min..max] of the per-frame time; every call of a batch takes the next of 16 frames.  Prints
-markdown (profiles/groupnorm_target.md).
+5 % each; the mask / the list says so.  The measuring method is tools/target_common.py's; every call of a batch takes the
+next of 16 frames.  Prints markdown (profiles/groupnorm_target.md).
 usage: groupnorm_target.py [rounds]"""
 import ctypes
 import os
@@ -23,55 +22,12 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import BATCH, SETS, change_sets, dtype_name, fmt, listed_share, pack, rounds  # noqa: E402
 
 #        name, channels, groups, H, W, block
 NORMS = [("GroupNorm(32, 256)", 256, 32, 80, 120, 4), ("InstanceNorm2d(64)", 64, 64, 96, 320, 4),
          ("GroupNorm(1, 64)", 64, 1, 320, 480, 8)]
-BATCH, SETS, EPS = 32, 16, 1e-5
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack(mask):
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').view(np.int64).copy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the frames)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
+EPS = 1e-5
 
 
 class Norm(object):
@@ -143,13 +99,13 @@ def norm(name, Cn, G, H, W, blk, dtype, reps):
             assert torch.allclose(runs[(0.0, form)].out.float(), want.float(), rtol=tol, atol=tol), "differs from dense"
     t = rounds([((th, form), lambda i, n=n, form=form: call(n, form, i)) for (th, form), n in runs.items()] +
                [("dense", dense)], reps)
-    changed = statistics.mean(float((m | sets[i - 1]).mean()) for i, m in enumerate(sets)) * 100.0
+    changed = listed_share([m | sets[i - 1] for i, m in enumerate(sets)])
     med = {k: statistics.median(v) for k, v in t.items()}
     print("| %s @%dx%d | %s | %.1f %% | %s | %s | %s (%.0f of %d tripped) | %s | %s | %.2fx / %.2fx | %.2fx / %.2fx |"
-          % (name, H, W, "fp32" if dtype == torch.float32 else "fp16", changed, fmt(t[(100.0, "mask")]),
-             fmt(t[(100.0, "list")]), fmt(t[(0.0, "mask")]), statistics.mean(tripped), G, fmt(t[(0.0, "list")]),
-             fmt(t["dense"]), med["dense"] / med[(100.0, "mask")], med["dense"] / med[(100.0, "list")],
-             med["dense"] / med[(0.0, "mask")], med["dense"] / med[(0.0, "list")]))
+          % (name, H, W, dtype_name(dtype), changed, fmt(t[(100.0, "mask")]), fmt(t[(100.0, "list")]),
+             fmt(t[(0.0, "mask")]), statistics.mean(tripped), G, fmt(t[(0.0, "list")]), fmt(t["dense"]),
+             med["dense"] / med[(100.0, "mask")], med["dense"] / med[(100.0, "list")], med["dense"] / med[(0.0, "mask")],
+             med["dense"] / med[(0.0, "list")]))
 
 
 def main():

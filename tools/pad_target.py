@@ -10,8 +10,7 @@ launch in front) against torch's dense F.pad on the same device tensor.
 Table 2, the chain 3x3 conv 64 -> 64 + ReLU -> ReflectionPad2d(1) -> valid 3x3 conv 64 -> 64 @96x320, threshold 0.05,
 frame time of: the chain with CBPad2d replayed by FrameProgram, the same run eagerly, and the same converted layers with
 torch's dense pad in the middle (the layer behind it then runs its own detection on the padded map).
-Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of the
-per-call time; every call of a batch takes the next of 16 change sets.  Prints markdown (profiles/pad_target.md).
+The measuring method is tools/target_common.py's.  Prints markdown (profiles/pad_target.md).
 usage: pad_target.py [rounds]"""
 import copy
 import ctypes
@@ -28,7 +27,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pycbinfer  # noqa: E402
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
-from decoder_target import BATCH, SETS, change_sets, fmt, pack, rounds  # noqa: E402
+from target_common import (BATCH, SETS, change_sets, device_sets, dtype_name, fmt, listed_share,  # noqa: E402
+                           moving_frames, rounds)
 
 #         name, channels, H, W, mode, (left, right, top, bottom)
 CASES = [("monodepth2-type layer", 64, 96, 320, "reflect", (1, 1, 1, 1)),
@@ -45,8 +45,7 @@ def case(name, Cn, H, W, mode, pads, tdt, reps):
     rng = np.random.default_rng(7)
     x = torch.randn(1, Cn, H, W, device="cuda").to(tdt)
     sets = change_sets(rng, H, W, BLOCK, 0.10)
-    masks = [torch.from_numpy(pack(m)).cuda() for m in sets]
-    lists = [torch.from_numpy(np.flatnonzero(m.reshape(-1)).astype(np.int32)).cuda() for m in sets]
+    masks, lists = device_sets(sets)
     left, right, top, bottom = pads
     Ho, Wo = H + top + bottom, W + left + right
     p = ctypes.pointer(_lib.Pad(MODES[mode], left, right, top, bottom, 0.0))
@@ -72,10 +71,10 @@ def case(name, Cn, H, W, mode, pads, tdt, reps):
     assert torch.equal(out, dense(0)), "the padded map differs from F.pad"
     t = rounds([("mask", lambda i: run(i, "mask")), ("list", lambda i: run(i, "list")), ("dense", dense)], reps)
     med = {k: statistics.median(v) for k, v in t.items()}
-    listed = statistics.mean(float(m.mean()) for m in sets) * 100.0
+    listed = listed_share(sets)
     print("| %s, %d ch @%dx%d %s %s | %s | %.1f %% | %s | %s | %s | %.2fx / %.2fx |"
-          % (name, Cn, H, W, mode, pads, "fp32" if tdt == torch.float32 else "fp16", listed, fmt(t["mask"]), fmt(t["list"]),
-             fmt(t["dense"]), med["dense"] / med["mask"], med["dense"] / med["list"]))
+          % (name, Cn, H, W, mode, pads, dtype_name(tdt), listed, fmt(t["mask"]), fmt(t["list"]), fmt(t["dense"]),
+             med["dense"] / med["mask"], med["dense"] / med["list"]))
 
 
 def chain(tdt, reps):
@@ -85,14 +84,7 @@ def chain(tdt, reps):
     src = nn.Sequential(nn.Conv2d(Cn, Cn, 3, padding=1), nn.ReLU(), nn.ReflectionPad2d(1), nn.Conv2d(Cn, Cn, 3))
     src = src.eval().cuda().to(tdt)
     sets = change_sets(rng, H, W, BLOCK, 0.05)
-    # frame i is the base with fresh values on set i: it differs from frame i - 1 on set i and set i - 1
-    base = torch.rand(1, Cn, H, W, device="cuda").to(tdt)
-    frames = []
-    for m in sets:
-        sel = torch.from_numpy(m).cuda()
-        f = base.clone()
-        f[0][:, sel] = torch.rand(Cn, int(m.sum()), device="cuda").to(tdt)
-        frames.append(f)
+    frames = moving_frames(torch.rand(1, Cn, H, W, device="cuda").to(tdt), sets, Cn, tdt)
 
     def converted(padding):
         net = pycbinfer.convert(copy.deepcopy(src), threshold=0.05, generalGeometry=True)
@@ -125,9 +117,9 @@ def chain(tdt, reps):
             assert torch.equal(yp, ye), "the replayed program differs from the eager chain"
             assert float((ye.float() - yt.float()).abs().max()) < 1.0, "the chain differs from the one with torch's pad"
         t = rounds([("replayed", replayed), ("eager", eager), ("torch", torch_pad)], reps)
-    changed = statistics.mean(float((m | sets[i - 1]).mean()) for i, m in enumerate(sets)) * 100.0
-    print("| %s | %.1f %% | %s | %s | %s |" % ("fp32" if tdt == torch.float32 else "fp16", changed, fmt(t["replayed"]),
-                                              fmt(t["eager"]), fmt(t["torch"])))
+    changed = listed_share([m | sets[i - 1] for i, m in enumerate(sets)])
+    print("| %s | %.1f %% | %s | %s | %s |" % (dtype_name(tdt), changed, fmt(t["replayed"]), fmt(t["eager"]),
+                                              fmt(t["torch"])))
 
 
 def main():

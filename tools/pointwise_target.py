@@ -10,8 +10,7 @@ Table 2, the chain of tests/test_gpu_pointwise.py at 80x120 with 64 -> 144 -> 14
 Hardswish -> 3x3 depthwise -> BN + ReLU6 -> 1x1 CBConv2d), frame time of: the chain with CBPointwise2d replayed by
 FrameProgram, the same run eagerly, and the same converted layers with torch's dense Hardswish / BatchNorm2d / ReLU6
 between them (each layer then runs its own change detection).
-Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of the
-per-call time; every call of a batch takes the next of 16 change sets.  Prints markdown (profiles/pointwise_target.md).
+The measuring method is tools/target_common.py's.  Prints markdown (profiles/pointwise_target.md).
 usage: pointwise_target.py [rounds]"""
 import copy
 import os
@@ -27,54 +26,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pycbinfer  # noqa: E402
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import (BATCH, SETS, change_sets, device_sets, dtype_name, fmt, listed_share,  # noqa: E402
+                           moving_frames, rounds)
 
 #          name, channels, H, W, block
 LAYERS = [("64 ch", 64, 80, 120, 8), ("144 ch", 144, 80, 120, 8), ("256 ch", 256, 20, 30, 2)]
-BATCH, SETS = 32, 16
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack(mask):
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').view(np.int64).copy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the change sets)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
 
 
 def batch_norm(Cn, seed, dev="cuda"):
@@ -103,15 +59,14 @@ def layer(name, Cn, H, W, block, dtype, reps):
     rng = np.random.default_rng(7)
     x = (torch.randn(1, Cn, H, W, device="cuda") * 3).to(dtype)
     sets = change_sets(rng, H, W, block, 0.10)
-    lists = [torch.from_numpy(np.flatnonzero(m.reshape(-1)).astype(np.int32)).cuda() for m in sets]
-    masks = [torch.from_numpy(pack(m)).cuda() for m in sets]
+    masks, lists = device_sets(sets)
     words = C.cbinfer_mask_words(H, W)
     bits = torch.zeros(words, dtype=torch.int64, device="cuda")
     mcopy = torch.zeros(words, dtype=torch.int64, device="cuda")
     out = torch.empty_like(x)
     st = torch.cuda.current_stream().cuda_stream
     dt = _lib.dtype_code(x)
-    listed = statistics.mean(float(m.mean()) for m in sets) * 100.0
+    listed = listed_share(sets)
     for fname, m, dense_op, ulps in functions(Cn, dtype):
         def call(mask, lst, m=m):
             check(C.cbinfer_cbpointwise_forward(ptr(x), ptr(out), ptr(mask), ptr(lst), lst.numel() if lst is not None else 0,
@@ -138,8 +93,7 @@ def layer(name, Cn, H, W, block, dtype, reps):
         dm = statistics.median(t["dense"]) / statistics.median(t["mask"])
         dl = statistics.median(t["dense"]) / statistics.median(t["list"])
         print("| %s @%dx%d | %s | %s | %.1f %% | %s | %s | %s | %.2fx / %.2fx |"
-              % (name, H, W, "fp32" if dtype == torch.float32 else "fp16", fname, listed, fmt(t["mask"]), fmt(t["list"]),
-                 fmt(t["dense"]), dm, dl))
+              % (name, H, W, dtype_name(dtype), fname, listed, fmt(t["mask"]), fmt(t["list"]), fmt(t["dense"]), dm, dl))
 
 
 def chain(dtype, reps):
@@ -153,14 +107,7 @@ def chain(dtype, reps):
         src.add_module(name, mod)
     src = src.eval().cuda().to(dtype)
     sets = change_sets(rng, H, W, blk, 0.05)
-    # frame i is the base with fresh values on set i: it differs from frame i - 1 on set i and set i - 1
-    base = torch.rand(1, 64, H, W, device="cuda").to(dtype)
-    frames = []
-    for m in sets:
-        sel = torch.from_numpy(m).cuda()
-        f = base.clone()
-        f[0][:, sel] = torch.rand(64, int(m.sum()), device="cuda").to(dtype)
-        frames.append(f)
+    frames = moving_frames(torch.rand(1, 64, H, W, device="cuda").to(dtype), sets, 64, dtype)
 
     def converted(pointwise):
         net = pycbinfer.convert(copy.deepcopy(src), threshold=0.05, depthwise=True)
@@ -196,9 +143,9 @@ def chain(dtype, reps):
             assert torch.equal(yp, ye), "the replayed program differs from the eager chain"
             assert float((ye.float() - yt.float()).abs().max()) < 1.0, "the chain differs from the one with torch activations"
         t = rounds([("replayed", replayed), ("eager", eager), ("torch", torch_acts)], reps)
-    changed = statistics.mean(float((m | sets[i - 1]).mean()) for i, m in enumerate(sets)) * 100.0
-    print("| %s | %.1f %% | %s | %s | %s |" % ("fp32" if dtype == torch.float32 else "fp16", changed, fmt(t["replayed"]),
-                                              fmt(t["eager"]), fmt(t["torch"])))
+    changed = listed_share([m | sets[i - 1] for i, m in enumerate(sets)])
+    print("| %s | %.1f %% | %s | %s | %s |" % (dtype_name(dtype), changed, fmt(t["replayed"]), fmt(t["eager"]),
+                                              fmt(t["torch"])))
 
 
 def main():

@@ -4,11 +4,12 @@
   stem pool    64 ch  160x240  3x3 stride 2 pad 1 max
   ceil pool    16 ch  320x480  3x3 stride 2 ceil_mode max
   transition  256 ch   40x60   2x2 average
-Per layer, interleaved -- REPS rounds of alternating batches of BATCH calls, device events around each batch, median
-[min..max] of the per-call time: the frame of cbinfer_cbpool2d_forward (both launches) fed the change LIST and fed the
-change MASK, torch's dense F.max_pool2d / F.avg_pool2d on the same tensor, and, for a 2x2/stride-2 window, the existing
-cbinfer_max_pool2d launch on the same list (it computes the maximum, not the average: the window is what is compared).
-Every call of a batch takes the next of 16 change sets.  Prints markdown (profiles/pool_target.md).
+Per layer: the frame of cbinfer_cbpool2d_forward (both launches) fed the change LIST and fed the change MASK, torch's
+dense F.max_pool2d / F.avg_pool2d on the same tensor, and, for a 2x2/stride-2 window, the existing cbinfer_max_pool2d
+launch on the same list (it computes the maximum, not the average: the window is what is compared).
+The measuring method is tools/target_common.py's: one warm-up batch per run in front of the rounds.  (This tool used to
+warm up with one extra call in front of every timed batch instead; tables recorded that way say so.)
+Prints markdown (profiles/pool_target.md).
 usage: pool_target.py [rounds]"""
 import ctypes
 import os
@@ -23,47 +24,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pycbinfer  # noqa: E402,F401
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import BATCH, SETS, change_sets, device_sets, fmt, listed_share, rounds  # noqa: E402
 
 #          name, channels, H, W, window, stride, padding, ceil, op, block
 LAYERS = [("stem pool 64 ch 3x3 s2 p1 max", 64, 160, 240, 3, 2, 1, False, "max", 16),
           ("ceil pool 16 ch 3x3 s2 ceil max", 16, 320, 480, 3, 2, 0, True, "max", 32),
           ("transition 256 ch 2x2 avg", 256, 40, 60, 2, 2, 0, False, "avg", 4)]
-BATCH, SETS = 32, 16
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (one warm-up)"""
-    fn(0)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block):
-    """SETS bool maps with 10 % of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(0.10 * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack(mask):
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').view(np.int64).copy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
 
 
 def layer(name, Cn, H, W, k, s, p, ceil, op, block, reps):
@@ -74,9 +40,8 @@ def layer(name, Cn, H, W, k, s, p, ceil, op, block, reps):
     check(C.cbinfer_pool_out_size(H, W, gp, ctypes.byref(ho), ctypes.byref(wo)))
     Ho, Wo = ho.value, wo.value
     x = torch.rand(1, Cn, H, W, device="cuda")
-    sets = change_sets(rng, H, W, block)
-    lists = [torch.from_numpy(np.flatnonzero(m.reshape(-1)).astype(np.int32)).cuda() for m in sets]
-    masks = [torch.from_numpy(pack(m)).cuda() for m in sets]
+    sets = change_sets(rng, H, W, block, 0.10)
+    masks, lists = device_sets(sets)
     words = C.cbinfer_mask_words(Ho, Wo)
     bits = torch.zeros(words, dtype=torch.int64, device="cuda")
     copy = torch.zeros(words, dtype=torch.int64, device="cuda")
@@ -112,11 +77,8 @@ def layer(name, Cn, H, W, k, s, p, ceil, op, block, reps):
     if (k, s, p) == (2, 2, 0):
         out2 = torch.full((1, Cn, Ho, Wo), float('inf'), device="cuda")
         runs.append(("old", old_2x2))
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    listed = statistics.mean(float(m.mean()) for m in sets) * 100.0
+    t = rounds(runs, reps)
+    listed = listed_share(sets)
     dl = statistics.median(t["dense"]) / statistics.median(t["list"])
     dm = statistics.median(t["dense"]) / statistics.median(t["mask"])
     print("| %s @%dx%d -> %dx%d | %.1f %% | %s | %s | %s | %.2fx / %.2fx | %s |"

@@ -8,8 +8,7 @@ Three columns: cbinfer_cbrearrange_forward with the input in MASK form (one laun
 device tensor (made contiguous, as a consumer needs it); and cbinfer_cbupsample_forward, nearest, writing the SAME output
 shape from the same footprint (x2 from the low resolution for the shuffle, x1 otherwise) -- the yardstick of a word walk
 with the same store traffic.  Nothing gates on these times.
-Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of the
-per-call time; every call of a batch takes the next of 16 change sets.  Prints markdown (profiles/rearrange_target.md).
+The measuring method is tools/target_common.py's.  Prints markdown (profiles/rearrange_target.md).
 usage: rearrange_target.py [rounds]"""
 import ctypes
 import os
@@ -24,56 +23,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pycbinfer  # noqa: E402,F401
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import BATCH, SETS, change_sets, dtype_name, fmt, listed_share, pack, rounds  # noqa: E402
 
 #        name, kind, factor, input (C, H, W), block (input pixels)
 CASES = [("pixel shuffle x2", _lib.REARRANGE_SHUFFLE, 2, (256, 160, 240), 4),
          ("pixel unshuffle x2", _lib.REARRANGE_UNSHUFFLE, 2, (64, 320, 480), 8),
          ("channel shuffle, 3 groups", _lib.REARRANGE_CHANNELS, 3, (240, 40, 60), 2)]
-BATCH, SETS = 32, 16
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack(mask):
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').view(np.int64).copy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: one pass over the change sets, twice)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
 
 
 def dense_op(kind, f, x):
@@ -130,10 +85,10 @@ def case(name, kind, f, shape, block, dtype, share, reps):
     yard(1)
     assert torch.equal(ucopy, mcopy), "the yardstick walks another footprint"
     t = rounds([("cb", cb), ("dense", dense), ("yard", yard)], reps)
-    listed = statistics.mean(float(m.mean()) for m in sets) * 100.0
+    listed = listed_share(sets)
     print("| %s | %s | %d ch @%dx%d -> %d ch @%dx%d | %.1f %% | %s | %s | %s | %.2fx |"
-          % (name, "fp32" if dtype == torch.float32 else "fp16", Cn, H, W, Co, Ho, Wo, listed, fmt(t["cb"]),
-             fmt(t["dense"]), fmt(t["yard"]), statistics.median(t["dense"]) / statistics.median(t["cb"])))
+          % (name, dtype_name(dtype), Cn, H, W, Co, Ho, Wo, listed, fmt(t["cb"]), fmt(t["dense"]), fmt(t["yard"]),
+             statistics.median(t["dense"]) / statistics.median(t["cb"])))
 
 
 def main():

@@ -8,8 +8,7 @@ fp32 and fp16, against torch's dense F.interpolate on the same device tensor --
   a super-resolution head       3 ch @ 160x240  -> 640x960  bicubic.
 The x2 cases (the FPN step, and the same map with bilinear) are also run through cbinfer_cbupsample_forward, the
 integer-scale kernel, on the same input and the same change sets.
-Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of the
-per-call time; every call of a batch takes the next of 16 change sets.  Prints markdown (profiles/resize_target.md).
+The measuring method is tools/target_common.py's.  Prints markdown (profiles/resize_target.md).
 usage: resize_target.py [rounds]"""
 import ctypes
 import fractions
@@ -25,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pycbinfer  # noqa: E402,F401
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
-from decoder_target import BATCH, SETS, change_sets, fmt, pack, rounds  # noqa: E402
+from target_common import BATCH, SETS, change_sets, device_sets, dtype_name, fmt, listed_share, rounds  # noqa: E402
 
 #         name, channels, Hi, Wi, Ho, Wo, mode, also through the integer-scale kernel
 CASES = [("segmentation head", 19, 60, 80, 480, 640, "bilinear", False),
@@ -40,8 +39,7 @@ def case(name, Cn, Hi, Wi, Ho, Wo, mode, integer, tdt, share, reps):
     rng = np.random.default_rng(7)
     x = torch.randn(1, Cn, Hi, Wi, device="cuda").to(tdt)
     sets = change_sets(rng, Hi, Wi, 4, share)
-    masks = [torch.from_numpy(pack(m)).cuda() for m in sets]
-    lists = [torch.from_numpy(np.flatnonzero(m.reshape(-1)).astype(np.int32)).cuda() for m in sets]
+    masks, lists = device_sets(sets)
     words = C.cbinfer_mask_words(Ho, Wo)
     st = torch.cuda.current_stream().cuda_stream
     dt = _lib.dtype_code(x)
@@ -82,9 +80,9 @@ def case(name, Cn, Hi, Wi, Ho, Wo, mode, integer, tdt, share, reps):
         runs += [("umask", lambda i: upsample(i, "mask")), ("ulist", lambda i: upsample(i, "list"))]
     t = rounds(runs, reps)
     med = {k: statistics.median(v) for k, v in t.items()}
-    listed = statistics.mean(float(m.mean()) for m in sets) * 100.0
+    listed = listed_share(sets)
     label = "%s, %d ch @%dx%d -> %dx%d %s" % (name, Cn, Hi, Wi, Ho, Wo, mode)
-    dname = "fp32" if tdt == torch.float32 else "fp16"
+    dname = dtype_name(tdt)
     for form in ("mask", "list"):
         ukey = "u" + form
         print("| %s | %s | %.0f %% | %s | %s | %s | %.2fx | %s | %s |"

@@ -7,9 +7,8 @@ cbinfer_cbchanscale_forward (the fused excitation and the scale: two launches), 
 which no channel trips (2: a sigmoid gate cannot move that far) and at one at which every channel that moved trips (0),
 against torch's dense block on the same frames in the same process: adaptive_avg_pool2d, two 1x1 convolutions, ReLU,
 sigmoid, multiply.  Frame i is a base frame with fresh values on change set i, so it differs from frame i - 1 on two sets
-of 5 % each; the mask says so.  Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each
-batch, median [min..max] of the per-frame time; every call of a batch takes the next of 16 frames.  Prints markdown
-(profiles/se_target.md).
+of 5 % each; the mask says so.  The measuring method is tools/target_common.py's; every call of a batch takes the next
+of 16 frames.  Prints markdown (profiles/se_target.md).
 usage: se_target.py [rounds]"""
 import os
 import statistics
@@ -22,55 +21,11 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import BATCH, SETS, change_sets, dtype_name, fmt, listed_share, pack, rounds  # noqa: E402
 
 #          name, channels, hidden, H, W, block
 BLOCKS = [("MobileNetV3-type", 96, 24, 40, 60, 2), ("EfficientNet-type", 144, 6, 80, 120, 4),
           ("SE-ResNet-type", 256, 16, 80, 120, 4)]
-BATCH, SETS = 32, 16
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
-
-
-def pack(mask):
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').view(np.int64).copy()
-
-
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the frames)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
 
 
 class Block(object):
@@ -142,11 +97,11 @@ def block(name, Cn, R, H, W, blk, dtype, reps):
         assert torch.allclose(trip.out.float(), want.float(), rtol=tol, atol=tol), "the block differs from the dense one"
     t = rounds([("hold", lambda i: hold.frame(frames[i % SETS], masks[i % SETS])),
                 ("trip", lambda i: trip.frame(frames[i % SETS], masks[i % SETS])), ("dense", dense)], reps)
-    changed = statistics.mean(float((m | sets[i - 1]).mean()) for i, m in enumerate(sets)) * 100.0
+    changed = listed_share([m | sets[i - 1] for i, m in enumerate(sets)])
     med = {k: statistics.median(v) for k, v in t.items()}
     print("| %s C %d R %d @%dx%d | %s | %.1f %% | %s | %s (%.0f of %d tripped) | %s | %.2fx / %.2fx |"
-          % (name, Cn, R, H, W, "fp32" if dtype == torch.float32 else "fp16", changed, fmt(t["hold"]), fmt(t["trip"]),
-             statistics.mean(tripped), Cn, fmt(t["dense"]), med["dense"] / med["hold"], med["dense"] / med["trip"]))
+          % (name, Cn, R, H, W, dtype_name(dtype), changed, fmt(t["hold"]), fmt(t["trip"]), statistics.mean(tripped), Cn,
+             fmt(t["dense"]), med["dense"] / med["hold"], med["dense"] / med["trip"]))
 
 
 def main():

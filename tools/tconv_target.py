@@ -13,8 +13,8 @@ Per layer:
   yardstick    cbg_conv_kernel (cbinfer_conv_changed_geom, list mode) on a stride-1 layer with the SAME filter size on
                C / (sH sW) channels -- the same useful depth C kH kW / (sH sW) = mean C taps(phase) --, the same K, the
                same output map and the same list: what the gather contraction costs without the phase split.
-Interleaved: REPS rounds of alternating batches of BATCH calls, device events around each batch, median [min..max] of the
-per-call time; every call of a batch takes the next of 16 frames.  Prints markdown (profiles/tconv_target.md).
+The measuring method is tools/target_common.py's, with two warm-up batches per run; every call of a batch takes the next
+of 16 frames.  Prints markdown (profiles/tconv_target.md).
 usage: tconv_target.py [rounds]"""
 import ctypes
 import os
@@ -28,34 +28,13 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cbinfer_amd import _lib  # noqa: E402
 from cbinfer_amd._lib import C, check, ptr  # noqa: E402
+from target_common import BATCH, SETS, change_sets, fmt, listed_share, moving_frames, rounds  # noqa: E402
 
 #          name, C, K, (k, s, p, op), Hi, Wi, block (input pixels)
 LAYERS = [("128->64 2x2 s2", 128, 64, (2, 2, 0, 0), 80, 120, 4),
           ("128->64 4x4 s2 p1", 128, 64, (4, 2, 1, 0), 80, 120, 4),
           ("256->128 3x3 s2 p1 op1", 256, 128, (3, 2, 1, 1), 40, 60, 2)]
-BATCH, SETS, TH = 32, 16, 0.05
-
-
-def timed(fn, n):
-    """mean device time of fn(i) in us over n back-to-back calls (the caller has warmed fn up)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for i in range(n):
-        fn(i)
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / n
-
-
-def change_sets(rng, H, W, block, share):
-    """SETS bool maps with `share` of the block x block tiles set."""
-    by, bx = (H + block - 1) // block, (W + block - 1) // block
-    out = []
-    for _ in range(SETS):
-        tiles = np.zeros(by * bx, dtype=bool)
-        tiles[rng.choice(by * bx, size=max(1, round(share * by * bx)), replace=False)] = True
-        out.append(np.kron(tiles.reshape(by, bx), np.ones((block, block), dtype=bool))[:H, :W])
-    return out
+TH = 0.05
 
 
 def footprint(changed, k, s, p, Ho, Wo):
@@ -70,21 +49,6 @@ def footprint(changed, k, s, p, Ho, Wo):
     return listed
 
 
-def fmt(v):
-    return "%.1f [%.1f..%.1f]" % (statistics.median(v), min(v), max(v))
-
-
-def rounds(runs, reps):
-    for _, fn in runs:      # (warm-up: two passes over the frames)
-        timed(fn, BATCH)
-        timed(fn, BATCH)
-    t = {key: [] for key, _ in runs}
-    for _ in range(reps):
-        for key, fn in runs:
-            t[key].append(timed(fn, BATCH))
-    return t
-
-
 def layer(name, Cn, K, ksp, Hi, Wi, block, reps):
     k, s, p, op = ksp
     rng = np.random.default_rng(7)
@@ -97,15 +61,12 @@ def layer(name, Cn, K, ksp, Hi, Wi, block, reps):
     w = torch.randn(Cn, K, k, k, device="cuda") / (Cn * k * k / (s * s)) ** 0.5
     b = torch.randn(K, device="cuda")
     sets = change_sets(rng, Hi, Wi, block, 0.05)
-    base = torch.rand(1, Cn, Hi, Wi, device="cuda")
-    frames, lists = [], []
+    frames = moving_frames(torch.rand(1, Cn, Hi, Wi, device="cuda"), sets, Cn, torch.float32)
+    lists = []
     for i, m in enumerate(sets):
-        f = base.clone()
-        f[0][:, torch.from_numpy(m).cuda()] = torch.rand(Cn, int(m.sum()), device="cuda")
-        frames.append(f)
         px = np.flatnonzero(footprint(m | sets[i - 1], k, s, p, Ho, Wo).reshape(-1)).astype(np.int32)
         lists.append(torch.from_numpy(px).cuda())
-    changed = statistics.mean(float((m | sets[i - 1]).mean()) for i, m in enumerate(sets)) * 100.0
+    changed = listed_share([m | sets[i - 1] for i, m in enumerate(sets)])
     listed = statistics.mean(t.numel() for t in lists) / float(Ho * Wo) * 100.0
 
     arith = _lib.CB_F32S
@@ -169,7 +130,8 @@ def layer(name, Cn, K, ksp, Hi, Wi, block, reps):
     err0 = (L['out'].double() - want0).abs().view(K, -1)[:, sel]
     assert bool((err0 <= 64 * 2.0 ** -24 * mag0.view(K, -1)[:, sel]).all()), "the list-mode contraction is off"
 
-    t = rounds([("frame", frame), ("dense", dense), ("det", detection), ("con", contraction), ("yard", yardstick)], reps)
+    t = rounds([("frame", frame), ("dense", dense), ("det", detection), ("con", contraction), ("yard", yardstick)], reps,
+               warm=2)
     med = {key: statistics.median(v) for key, v in t.items()}
     print("| %s | %dx%d -> %dx%d | %.1f %% / %.1f %% | %s | %s | %.2fx | %s | %s | %s | %.2fx |"
           % (name, Hi, Wi, Ho, Wo, changed, listed, fmt(t["frame"]), fmt(t["dense"]), med["dense"] / med["frame"],
