@@ -35,6 +35,17 @@ __device__ __forceinline__ float cbw_act(float v, float p0, float p1, float slop
         case CB_PW_SIGMOID: return 1.f / (1.f + expf(-v));
         case CB_PW_SILU: return v / (1.f + expf(-v));
         case CB_PW_TANH: return tanhf(v);
+        // the six kinds of DESIGN 5.30: the device's erff / tanhf / expm1f / expf / log1pf, each bounded there
+        case CB_PW_GELU: return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+        case CB_PW_GELU_TANH:
+            return 0.5f * v * (1.f + tanhf(0.79788456080286535588f * (v + 0.044715f * (v * v * v))));
+        case CB_PW_ELU: return v > 0.f ? v : p0 * expm1f(v * p1);      // (CELU: p1 = 1 / alpha)
+        case CB_PW_SELU: return v > 0.f ? 1.0507009873554805f * v : 1.7580993408473766f * expm1f(v);
+        case CB_PW_SOFTPLUS: {
+            const float t = v * p0;
+            return t > p1 ? v : log1pf(expf(t)) / p0;
+        }
+        case CB_PW_MISH: return v * tanhf(log1pf(expf(v)));
         default: return v;      // CB_PW_IDENTITY: the affine alone
     }
 }
@@ -88,6 +99,12 @@ void cbw_launch(const void* x, void* out, const uint64_t* mask, int all, uint64_
         CBW_GO(CB_PW_SIGMOID);
         CBW_GO(CB_PW_SILU);
         CBW_GO(CB_PW_TANH);
+        CBW_GO(CB_PW_GELU);
+        CBW_GO(CB_PW_GELU_TANH);
+        CBW_GO(CB_PW_ELU);
+        CBW_GO(CB_PW_SELU);
+        CBW_GO(CB_PW_SOFTPLUS);
+        CBW_GO(CB_PW_MISH);
     }
 #undef CBW_GO
 }
@@ -106,8 +123,12 @@ bool cbw_args_ok(const void* x, const void* out, const uint64_t* mask, const uin
 }  // namespace
 
 int cbinfer_pointwise_supported(int kind, float p0, float p1) {
-    if (kind < CB_PW_IDENTITY || kind > CB_PW_TANH) return 0;
+    // (10..15 are unassigned)
+    if (!(kind >= CB_PW_IDENTITY && kind <= CB_PW_TANH) && !(kind >= CB_PW_GELU && kind <= CB_PW_MISH)) return 0;
     if (kind == CB_PW_HARDTANH && !(p0 <= p1)) return 0;      // (also a NaN bound)
+    // finite: t - t == 0 fails for an infinity and a NaN
+    if (kind == CB_PW_ELU && !(p0 - p0 == 0.f && p1 - p1 == 0.f)) return 0;
+    if (kind == CB_PW_SOFTPLUS && (!(p0 - p0 == 0.f) || p0 == 0.f || p1 != p1)) return 0;
     return 1;
 }
 

@@ -5,7 +5,8 @@ eval-mode nn.BatchNorm2d that foldBatchNorm cannot fold (BN -> ReLU -> conv, a B
 torch operator -- it recomputes the whole map, drops the producer's change information and cannot be recorded by a
 FrameProgram.  Every producer of this package leaves the pixels outside its change list bit for bit as they were, so
 f(x) can differ from last frame's only at the producer's changed pixels: CBPointwise2d recomputes it there and is the
-dense result exactly, without a threshold.
+dense result exactly, without a threshold.  GELU, ELU / CELU / SELU, Softplus and Mish are taken with transcendental=True
+(DESIGN 5.30).
 """
 import torch
 import torch.nn as nn
@@ -28,7 +29,42 @@ _ACTIVATIONS = {
     nn.SiLU: lambda m: (_lib.PW_SILU, 0.0, 0.0),
     nn.Tanh: lambda m: (_lib.PW_TANH, 0.0, 0.0),
 }
+
+
+def _gelu(m):
+    if m.approximate not in ('none', 'tanh'):
+        raise CBinferError("CBPointwise2d: act=%r: approximate=%r is not supported, only 'none' and 'tanh'"
+                           % (m, m.approximate))
+    return (_lib.PW_GELU if m.approximate == 'none' else _lib.PW_GELU_TANH), 0.0, 0.0
+
+
+def _celu(m):
+    if float(m.alpha) == 0.0:
+        raise CBinferError("CBPointwise2d: act=%r: alpha=0 is not supported (CELU divides by it)" % (m,))
+    # (1 / alpha rounded to float32 once, as the kernel takes it)
+    return _lib.PW_ELU, float(m.alpha), float(torch.tensor(1.0 / float(m.alpha), dtype=torch.float32))
+
+
+def _softplus(m):
+    if float(m.beta) == 0.0:
+        raise CBinferError("CBPointwise2d: act=%r: beta=0 is not supported (Softplus divides by it)" % (m,))
+    return _lib.PW_SOFTPLUS, float(m.beta), float(m.threshold)
+
+
+# the types `transcendental=True` adds: the device's erff / tanhf / expm1f / expf / log1pf, no bit-for-bit twin
+_TRANSCENDENTAL = {
+    nn.GELU: _gelu,
+    nn.ELU: lambda m: (_lib.PW_ELU, float(m.alpha), 1.0),
+    nn.CELU: _celu,
+    nn.SELU: lambda m: (_lib.PW_SELU, 0.0, 0.0),
+    nn.Softplus: _softplus,
+    nn.Mish: lambda m: (_lib.PW_MISH, 0.0, 0.0),
+}
 _PER_CHANNEL = ('scale', 'shift', 'slope')
+
+
+def _table(transcendental):
+    return {**_ACTIVATIONS, **_TRANSCENDENTAL} if transcendental else _ACTIVATIONS
 
 
 def _bn_affine(norm):
@@ -60,7 +96,9 @@ class CBPointwise2d(CBStateModule):
     x scale[c] + shift[c] (two roundings).  At least one of the two.  scale / shift / slope are computed HERE and kept as
     float32 buffers (pickled, moved by .to(), kept float32 by .half()): later edits of the source modules are not
     followed.  The first seven activations are torch's CPU operators bit for bit, fp32 and fp16; Sigmoid, SiLU and Tanh
-    call the device's expf / tanhf (DESIGN 5.16 has the bound).
+    call the device's expf / tanhf (DESIGN 5.16 has the bound).  transcendental=True adds exactly nn.GELU (approximate
+    'none' or 'tanh'), nn.ELU, nn.CELU (alpha != 0), nn.SELU, nn.Softplus (beta != 0) and nn.Mish, each bounded against
+    its formula in float64; without it they are refused as before.
 
     forward(x): a [1, C, H, W] tensor or the ('changeIndexes', tensor, indexes) tuple of a producer with
     propChangeIndexes.  A bare tensor carries no change information: every pixel is recomputed.  A MaskChangeIndexes
@@ -70,7 +108,7 @@ class CBPointwise2d(CBStateModule):
 
     _WORK = '_pwWork'
 
-    def __init__(self, act=None, norm=None):
+    def __init__(self, act=None, norm=None, transcendental=False):
         super(CBPointwise2d, self).__init__()
         if act is None and norm is None:
             raise CBinferError("CBPointwise2d: act=None and norm=None: at least one of the two must be given")
@@ -78,12 +116,16 @@ class CBPointwise2d(CBStateModule):
         self.actName = None
         scale = shift = slope = None
         if act is not None:
-            if type(act) not in _ACTIVATIONS:
+            table = _table(transcendental)
+            if type(act) not in table:
                 raise CBinferError("CBPointwise2d: act=%s is not supported, only an instance of exactly %s"
-                                   % (type(act).__name__, ", ".join("nn." + t.__name__ for t in _ACTIVATIONS)))
-            self.kind, self.p0, self.p1 = _ACTIVATIONS[type(act)](act)
+                                   % (type(act).__name__, ", ".join("nn." + t.__name__ for t in table)))
+            self.kind, self.p0, self.p1 = table[type(act)](act)
             self.actName = type(act).__name__
             if not C.cbinfer_pointwise_supported(self.kind, self.p0, self.p1):
+                if self.kind != _lib.PW_HARDTANH:
+                    raise CBinferError("CBPointwise2d: act=%r: the parameters %r, %r are not usable"
+                                       % (act, self.p0, self.p1))
                 raise CBinferError("CBPointwise2d: act=%r: min_val=%r is above max_val=%r" % (act, self.p0, self.p1))
             if self.kind == _lib.PW_PRELU:
                 slope = act.weight.detach().float().reshape(-1).clone()      # (an fp16 weight converts exactly)
@@ -148,10 +190,10 @@ class CBPointwise2d(CBStateModule):
             self.actName, self.p0, self.p1, self.scale is not None, self.propChangeIndexes)
 
 
-def insertCBPointwise(rootModule):
+def insertCBPointwise(rootModule, transcendental=False):
     """Inside every nn.Sequential of rootModule, a run  [nn.BatchNorm2d] [activation]  (at least one of the two; the
-    activations of CBPointwise2d) that directly follows a producer -- chain.producers('insertCBPointwise'), another
-    CBPointwise2d among them -- becomes ONE CBPointwise2d under the run's first name, fed by that producer's changes:
+    activations of CBPointwise2d, with transcendental=True those it adds) that directly follows a producer --
+    chain.producers('insertCBPointwise'), another CBPointwise2d among them -- becomes ONE CBPointwise2d under the run's first name, fed by that producer's changes:
     propChangeIndexes is switched on at the producer (chain.hand_on_changes).  The new module hands its own changes on
     (propChangeIndexes) only where it stands directly in front of a 1x1 / stride-1 / padding-0 CBConv2d -- a k x k
     CBConv2d that is handed indexes skips its own detection, which would be wrong here;
@@ -169,10 +211,10 @@ def insertCBPointwise(rootModule):
                 continue
             norm = first if type(first) is nn.BatchNorm2d else None
             after = seq._modules[names[pos]] if norm is not None and pos < len(names) else first
-            act = after if type(after) in _ACTIVATIONS else None
+            act = after if type(after) in _table(transcendental) else None
             if norm is None and act is None:
                 continue
-            cb = CBPointwise2d(act=act, norm=norm)
+            cb = CBPointwise2d(act=act, norm=norm, transcendental=transcendental)
             hand_on_changes(prod)
             seq._modules[names[pos - 1]] = cb
             if norm is not None and act is not None:

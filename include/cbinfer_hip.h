@@ -914,15 +914,24 @@ int cbinfer_cbadd_forward(const void* a, const void* b, void* outputState, const
  *       CB_PW_SIGMOID      1 / (1 + expf(-v))
  *       CB_PW_SILU         v / (1 + expf(-v))
  *       CB_PW_TANH         tanhf(v)
- *     The first seven are torch's CPU operators bit for bit; the last three call the device's expf / tanhf.  Every other
- *     pixel of `out` keeps its bits; a pixel's bits depend neither on the other listed pixels nor on the operand's form.
+ *       CB_PW_GELU         0.5 v (1 + erff(v 0.70710678118654752440f))                    (nn.GELU, approximate='none')
+ *       CB_PW_GELU_TANH    0.5 v (1 + tanhf(0.79788456080286535588f (v + 0.044715f (v v v))))       (approximate='tanh')
+ *       CB_PW_ELU          v > 0 ? v : p0 expm1f(v p1)        (ELU: p0 = alpha, p1 = 1; CELU: p0 = alpha, p1 = 1 / alpha)
+ *       CB_PW_SELU         v > 0 ? 1.0507009873554805f v : 1.7580993408473766f expm1f(v)
+ *       CB_PW_SOFTPLUS     t = v p0; t > p1 ? v : log1pf(expf(t)) / p0                     (p0 = beta, p1 = threshold)
+ *       CB_PW_MISH         v tanhf(log1pf(expf(v)))
+ *     The first seven are torch's CPU operators bit for bit; the others call the device's expf / tanhf / erff / expm1f /
+ *     log1pf and are bounded against the same formula in float64.  The kinds 10..15 are unassigned
+ *     and refused: the second group starts at 16.  Every other pixel of `out` keeps its bits; a pixel's bits depend
+ *     neither on the other listed pixels nor on the operand's form.
  *   hand-on: maskCopy receives the frame's mask every frame (all zeros for an empty frame: cbinfer_compact_bits makes
  *     the ascending list from it on demand); `bits`, the working mask (cbinfer_mask_words(H, W) words, zero on first
  *     use), is zero again when the launch ends.
  * All arguments are checked before the first launch.  A null tensor or mask buffer, x == out, bits == maskCopy, the
  * operand's mask == bits or maskCopy, both a mask and a list, a count without a list, capN < 0, an unknown kind or dtype,
- * CB_PW_HARDTANH with p0 > p1, CB_PW_PRELU without slope, scale without shift or the reverse, C / H / W < 1, H W or 64 C
- * beyond an int32 return CB_ERR_BADARG and launch nothing. */
+ * CB_PW_HARDTANH with p0 > p1, CB_PW_ELU with a non-finite p0 or p1, CB_PW_SOFTPLUS with p0 zero or non-finite or p1 a
+ * NaN, CB_PW_PRELU without slope, scale without shift or the reverse, C / H / W < 1, H W or 64 C beyond an int32 return
+ * CB_ERR_BADARG and launch nothing. */
 #define CB_PW_IDENTITY 0
 #define CB_PW_RELU 1
 #define CB_PW_HARDTANH 2
@@ -933,7 +942,14 @@ int cbinfer_cbadd_forward(const void* a, const void* b, void* outputState, const
 #define CB_PW_SIGMOID 7
 #define CB_PW_SILU 8
 #define CB_PW_TANH 9
-/* host, pure: 1 if `kind` is one of CB_PW_* and its parameters are usable (CB_PW_HARDTANH: p0 <= p1), else 0 */
+#define CB_PW_GELU 16
+#define CB_PW_GELU_TANH 17
+#define CB_PW_ELU 18
+#define CB_PW_SELU 19
+#define CB_PW_SOFTPLUS 20
+#define CB_PW_MISH 21
+/* host, pure: 1 if `kind` is one of CB_PW_* and its parameters are usable (CB_PW_HARDTANH: p0 <= p1; CB_PW_ELU: p0 and
+ * p1 finite; CB_PW_SOFTPLUS: p0 finite and not zero, p1 no NaN), else 0 */
 int cbinfer_pointwise_supported(int kind, float p0, float p1);
 /* The mask-driven launch.  mask: the operand's change mask, or NULL; all != 0: every pixel is listed.  The kernel ORs
  * `bits` and mask word by word itself (or forms the full row word); without a mask the operand contributes what `bits`
