@@ -12,7 +12,7 @@ import torch.nn as nn
 from . import _lib                      # loads libcbinfer_hip.so; raises ImportError if not built
 from . import chain
 from .conv2d import CBConv2d
-from .pool import CBPoolMax2d
+from .pool import CBPoolMax2d, computes_suppression
 from .pool import CBPoolAvg2d
 from .conv2d import CBTail1x1
 from .conv2d_cg import ChangeIndexes, ChannelConcat
@@ -158,7 +158,7 @@ def propChangeIndexesOf1x1(rootModule):
     return rootModule
 
 
-def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False, adaptive=False):
+def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False, adaptive=False, nmsTypes=None):
     """what sceneLabeling/modelLoader.py:62-78 does by hand for experiments 5/6, for any
     converted network: every 2x2/stride-2 nn.MaxPool2d that directly follows a CBConv2d inside an
     nn.Sequential becomes a CBPoolMax2d fed by that layer's change indexes (propChangeIndexes on the
@@ -169,15 +169,51 @@ def insertCBPooling(rootModule, cloneOutput=True, generalGeometry=False, adaptiv
     stays the dense torch operator.  Both sets are rows of chain.producers().  adaptive=True (with generalGeometry=True
     only): an nn.AdaptiveMaxPool2d / nn.AdaptiveAvgPool2d behind the same producers is converted too -- the global pool of
     a classifier head or a squeeze, the bins of a pyramid; one the modules refuse (return_indices=True) stays dense.
+
+    nmsTypes (with generalGeometry=True only): {class: keywords}, a class of the user's that computes peak suppression --
+    torch has no module for it -- and the keywords of the CBPoolMax2d that replaces it, e.g.
+    {SimpleNMS: dict(kernel_size=3, suppress='window', floor=0.1)}; peakList=N may be among them.  A module of EXACTLY
+    such a type behind the same producers becomes CBPoolMax2d(nn.MaxPool2d(k, 1, k // 2), generalGeometry=True, ...).
+    Before a type's first module is converted it is run against the rule in dense torch operators
+    (pool.suppression_formula) on a small CPU tensor with plateaus and values below the floor: a class whose forward is
+    something else is refused by name (CBinferError), never converted silently.
     Returns rootModule."""
     if adaptive and not generalGeometry:
         raise _lib.CBinferError("insertCBPooling: adaptive=True needs generalGeometry=True (the adaptive pools are "
                                 "general-geometry modules)")
+    if nmsTypes is not None and not generalGeometry:
+        raise _lib.CBinferError("insertCBPooling: nmsTypes needs generalGeometry=True (peak suppression is a "
+                                "general-geometry module)")
+    nmsTypes = dict(nmsTypes or {})
+    for t, kw in nmsTypes.items():
+        if not (isinstance(t, type) and isinstance(kw, dict) and {'kernel_size', 'suppress'} <= set(kw) and
+                set(kw) <= {'kernel_size', 'suppress', 'floor', 'peakList'}):
+            raise _lib.CBinferError("insertCBPooling: nmsTypes maps a class to the keywords kernel_size, suppress and, "
+                                    "if wanted, floor and peakList, got %r: %r" % (t, kw))
+    checkedNms = set()
+
+    def _suppressing(m):
+        kw = dict(nmsTypes[type(m)])
+        k = _pair(kw.pop('kernel_size'))
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in k) or len(k) != 2:
+            raise _lib.CBinferError("insertCBPooling: nmsTypes[%s]: kernel_size=%r is not an int or a pair of ints"
+                                    % (type(m).__name__, k))
+        cb = CBPoolMax2d(torch.nn.MaxPool2d(k, 1, (k[0] // 2, k[1] // 2)), generalGeometry=True, **kw)
+        if type(m) not in checkedNms:
+            if not computes_suppression(m, k, kw['suppress'], kw.get('floor')):
+                raise _lib.CBinferError(
+                    "insertCBPooling: %s does not compute peak suppression with kernel_size=%s, suppress=%r, floor=%r "
+                    "(checked bit for bit on a CPU tensor with plateaus and values below the floor): it is not "
+                    "converted" % (type(m).__name__, k, kw['suppress'], kw.get('floor')))
+            checkedNms.add(type(m))
+        return cb
 
     def _pair(v):
         return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
     def _converted(pool):
+        if type(pool) in nmsTypes:
+            return _suppressing(pool)
         if generalGeometry:
             try:
                 if type(pool) == torch.nn.MaxPool2d:

@@ -78,7 +78,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * (CB_CC_*, cbinfer_chancollapse_supported, cbinfer_chancollapse_changed, cbinfer_cbchancollapse_forward) and the
  * channel attention scale (CB_CS_*, cbinfer_chanscale_supported, cbinfer_chanscale_gate, cbinfer_chanscale_changed,
  * cbinfer_cbchanscale_forward) and the group norm (cbinfer_groupnorm_supported, cbinfer_groupnorm_partials,
- * cbinfer_groupnorm_stats, cbinfer_groupnorm_changed, cbinfer_cbgroupnorm_forward). */
+ * cbinfer_groupnorm_stats, cbinfer_groupnorm_changed, cbinfer_cbgroupnorm_forward) and the peak suppression (cbPeaks,
+ * cbinfer_peaks_supported, cbinfer_peaks_changed, cbinfer_cbpeaks_forward, cbinfer_peaks_list). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1716,6 +1717,71 @@ int cbinfer_cbadaptivepool2d_forward(const void* input, float* partials, void* o
                                      const int32_t* changeIndexes, int capN, const int32_t* countDev, uint64_t* inBits,
                                      uint64_t* outBits, uint64_t* maskCopy, int C, int H, int W, int oh, int ow, int op,
                                      int dtype, cbStream_t stream);
+
+/* ---- change-based peak suppression and peak lists (cb_peaks.hip) ----------------------------------------
+ * No counterpart in the reference's library: its pose detector copies the full-resolution heat maps to the host and
+ * searches the peaks there.  Torch has no module for the operator either; keypoint heads write it as
+ * heat * (max_pool2d(heat, 3, 1, 1) == heat).  Added under ABI 11.
+ *   the rule.  The operand is a map v [C, H, W] (batch 1, CB_F32 or CB_F16), the window kH x kW with each of kH, kW one of
+ *     3, 5, 7 on its own axis, rH = kH / 2, rW = kW / 2.
+ *     1. neighbourhood N(y, x).  cross == 0 ("window"): every in-map pixel (y + dy, x + dx) with |dy| <= rH and
+ *        |dx| <= rW, the centre included.  cross == 1 (3 x 3 only): the centre and its in-map 4-neighbours.  Pixels
+ *        outside the map do not take part: the -inf padding of a max pool.
+ *     2. keep(c, y, x) holds iff v[c, y, x] >= v[c, n] by IEEE comparison for every n of N -- a NaN at the centre or at
+ *        any neighbour gives false, +0 and -0 are equal -- and, with hasFloor, (float)v[c, y, x] >= floor (an f32).
+ *     3. out[c, y, x] has the bits of v[c, y, x] where keep holds and is +0 elsewhere.
+ *     4. peakBits holds one bit per pixel and channel: C cbinfer_mask_words(H, W) words, channel c's at
+ *        c cbinfer_mask_words(H, W), each in the row-padded layout of every mask here.  The bit equals keep; the bits of
+ *        the row padding are never set.
+ *     5. the peak list names the pixels with keep ascending in (c, y, x) -- the order of peakMap[c].nonzero() taken
+ *        channel after channel: int32 entries (c, y, x), three per peak, and scores v[c, y, x] in the map's dtype; count
+ *        is the TRUE number of peaks and channelStart[0 .. C] the TRUE offsets of the channels (channelStart[C] ==
+ *        count).  With a capacity capN < count the first capN entries in that order are written and nothing beyond them.
+ *     For cross == 0 this is torch.where((F.max_pool2d(x, k, 1, k // 2) == x) & (x >= floor), x, 0) bit for bit (torch's
+ *     pool lets a NaN win, so the equality fails exactly where rule 2 does); on NaN-free non-negative maps also the
+ *     product above.  At interior pixels cross == 1 is the four-neighbour test with a threshold of the reference's pose
+ *     detector, which crops a border ring where this rule uses the in-map neighbours.
+ *   a frame.  The operand's changes come as its row-padded change MASK (cbinfer_mask_words(H, W) words), as an int32
+ *     LIST (flat indexes y W + x; entries outside the map are dropped, duplicates and any order are fine), or not at
+ *     all: every pixel counts as changed then (the form of a frame that writes a new state).  Listed and recomputed, for
+ *     all channels, are the pixels of the FOOTPRINT: those whose kH x kW window (stride 1, padding k / 2) holds a changed
+ *     pixel -- cross == 1 uses the 3 x 3 footprint too, a superset of what it needs, which is still the dense result.
+ *     out and peakBits keep their bits at every other pixel.  A pixel's bits depend neither on the other listed pixels
+ *     nor on the operand's form.
+ *   hand-on: maskCopy (cbinfer_mask_words(H, W) words) receives the footprint every frame, all zeros for an empty frame;
+ *     `bits`, the working mask (same size, zero on first use), is zero again when the frame ends.
+ *   launches: mask or every-pixel form ONE (the footprint of a mask is gathered inside the walk); list form one more in
+ *     front (cbinfer_pool_footprint with the window as a stride-1 CB_POOL_MAX pool: 64-bit atomicOr into `bits`).  The
+ *     suppression launch has no atomics: the unit of work is (mask word, channel), one wave each, whose 64-bit ballot of
+ *     keep becomes the word of peakBits, (old & ~word) | (ballot & word), stored by one lane.
+ * Status: a null tensor or mask buffer, x == out, C / H / W < 1, an unknown dtype, two of the mask buffers the same,
+ * both a mask and a list, a count without a list, capN < 0: CB_ERR_BADARG; a window that is even or outside 3 .. 7, cross
+ * with another window than 3 x 3, a floor that is not finite, H W or 64 C beyond an int32: CB_ERR_UNSUPPORTED.  All
+ * arguments are checked before the first launch; a refused call launches nothing. */
+typedef struct cbPeaks {
+    int kH, kW, cross, hasFloor;
+    float floor;
+} cbPeaks;
+/* host, pure: 1 if the library takes the window, kind and floor (cross and hasFloor are 0 or 1), else 0 */
+int cbinfer_peaks_supported(const cbPeaks* peaks);
+/* The suppression launch.  mask (may be NULL): the OPERAND's change mask of this frame, whose footprint the launch
+ * gathers; all != 0: every pixel is listed; otherwise, or in addition, the footprint stands in `bits` already. */
+int cbinfer_peaks_changed(const void* x, void* out, uint64_t* peakBits, const uint64_t* mask, int all, uint64_t* bits,
+                          uint64_t* maskCopy, int C, int H, int W, const cbPeaks* peaks, int dtype, cbStream_t stream);
+/* The whole frame enqueued without a host sync.  mask != NULL: mask form; list != NULL: list form (capN entries at most,
+ * countDev the device-side length or NULL: capN is the length); both NULL: every pixel. */
+int cbinfer_cbpeaks_forward(const void* x, void* outputState, uint64_t* peakBits, const uint64_t* mask,
+                            const int32_t* list, int capN, const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy,
+                            int C, int H, int W, const cbPeaks* peaks, int dtype, cbStream_t stream);
+/* The ordered peak list from peakBits, three launches: the peaks of every (channel, row) into work (int32, C H + 1
+ * entries); their exclusive scan in place by ONE workgroup, which also stores count and channelStart (C + 1 entries);
+ * the entries and scores, one thread per word of peakBits.  No workgroup waits for another one inside a launch and no
+ * atomic decides an entry's position.  Every word of peakBits is read every frame: 1 / 32 of the map's bytes in CB_F32.
+ * entries (3 capN int32) and scores (capN of the map's dtype) may be NULL when capN == 0.  Status: a null x, peakBits,
+ * work, count or channelStart, entries or scores missing with capN > 0, C / H / W < 1, capN < 0, an unknown dtype:
+ * CB_ERR_BADARG; C H W beyond an int32: CB_ERR_UNSUPPORTED. */
+int cbinfer_peaks_list(const void* x, const uint64_t* peakBits, int32_t* work, int32_t* entries, void* scores, int capN,
+                       int32_t* count, int32_t* channelStart, int C, int H, int W, int dtype, cbStream_t stream);
 
 /* replaces conv2d_fg_cpu, cbconv2d_fg_backend.cu:81-112: HOST pointers, host code, race-free. */
 void cbinfer_conv2d_fg_cpu(const float* input, const float* prevInput, float* output,
