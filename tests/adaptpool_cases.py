@@ -6,6 +6,7 @@ reduction (L strided lane sums from +0, then a tree; the maximum keeps the first
 rounding to f16.  numpy's float32 addition and division are correctly rounded and never fused, so the twin's bits are
 the specification's."""
 import numpy as np
+from optest import bits_of, np_dtype, pack      # noqa: F401  (handed on to the tests)
 
 OPS = ("max", "avg")
 DTYPES = ("f32", "f16")
@@ -22,10 +23,6 @@ CASES = {
     "none_axis": (3, 6, 200, (None, 1)),          # None axis; four words per row
 }
 CASE_IDS = list(CASES)
-
-
-def np_dtype(dtype):
-    return np.float32 if dtype == "f32" else np.float16
 
 
 def lo(i, N, o):
@@ -168,16 +165,3 @@ def frames(cid, dtype, seed=0):
         xs.append(x)
     return xs, sets
 
-
-def pack(mask):
-    """A bool [H, W] map as the library's row-padded bit mask (uint64 words)."""
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').copy()
-
-
-def bits_of(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint16)

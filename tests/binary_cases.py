@@ -3,6 +3,7 @@ cb_binary.hip), shared by tests/test_host_binary.py and tests/test_gpu_binary.py
 of include/cbinfer_hip.h: both operands to float32 (exact), ONE float32 operation, explicit comparisons for maximum /
 minimum, a gate value rounded to the operand dtype before the product, one rounding to float16."""
 import numpy as np
+from optest import pack      # noqa: F401  (handed on to the tests)
 
 OPS = ('add', 'sub', 'mul', 'maximum', 'minimum')
 GATES = (None, 'sigmoid', 'hardsigmoid')
@@ -81,15 +82,6 @@ def pairs(dtype):
     s = specials(dtype)
     a, b = np.meshgrid(s, s, indexing='ij')
     return a.reshape(-1).copy(), b.reshape(-1).copy()
-
-
-def pack(mask):
-    """A bool [H, W] map as the library's row-padded bit mask (uint64 words)."""
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').copy()
 
 
 def frame_sets(rng, H, W):

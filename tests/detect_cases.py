@@ -24,6 +24,8 @@ import zlib
 
 import numpy as np
 
+from optest import pack, raw      # noqa: F401  (handed on to the tests)
+
 F32, F16 = "f32", "f16"
 NP = {F32: np.float32, F16: np.float16}
 UINT = {np.dtype(np.float32): np.uint32, np.dtype(np.float16): np.uint16}
@@ -111,15 +113,6 @@ def fg_rule(inp, prev, th, refresh):
     if refresh:
         new[differs] = inp[differs]
     return delta, pred, new
-
-
-def pack_mask(m):
-    """[H, W] bool -> the row-padded mask's uint64 words."""
-    H, W = m.shape
-    wpr = (W + 63) // 64
-    p = np.zeros((H, wpr * 64), dtype=np.uint8)
-    p[:, :W] = m
-    return np.ascontiguousarray(np.packbits(p, axis=1, bitorder="little")).view(np.uint64).reshape(-1)
 
 
 def unpack_mask(words, H, W):

@@ -21,6 +21,7 @@ from collections import namedtuple
 import numpy as np
 
 from splitconv_cases import dilate, rows, singles
+from optest import mask_words      # noqa: F401  (handed on to the tests)
 
 ASSUMED_CUS = 256        # the CU count the claimed cells of CASES are written for (MI355X)
 GROUP_MAX, NEXT_MAX = 2, 2                          # CBINFER_HGROUP_MAX, CBINFER_HNEXT_MAX
@@ -63,10 +64,6 @@ def geom(C, H, W, kH, kW):
 def supported(C, K, kH, kW):
     return (64 <= C <= 1024 and 1 <= K <= 1024 and kH % 2 == 1 and kW % 2 == 1 and 1 <= kH <= 15 and 1 <= kW <= 15
             and geom(C, 64, 64, kH, kW)["nStages"] >= 1)
-
-
-def mask_words(H, W):
-    return H * ((W + 63) // 64)
 
 
 def tile_height(K):      # cbs_bm

@@ -14,6 +14,7 @@ import zlib
 from collections import namedtuple
 
 import numpy as np
+from optest import mask_words      # noqa: F401  (handed on to the tests)
 
 ASSUMED_CUS = 256        # the CU count the claimed cells of CASES are written for (MI355X)
 MAXSEQ = 8               # CBINFER_SPLIT_MAX_SEQUENCES
@@ -22,10 +23,6 @@ ROW_MAXROWS = 256        # CB_ROW_MAXROWS
 PAIR_MAXCAND = 4         # CBP_MAXCAND
 PAIR_MAXWORDS = 1 << 20  # CBP_MAXWORDS
 REFERENCE_BUDGET = 1.0e9      # multiply-adds of a case's float64 reference
-
-
-def mask_words(H, W):
-    return H * ((W + 63) // 64)
 
 
 # -------------------------------------------------------------------------------------------------------------------

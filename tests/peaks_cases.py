@@ -6,6 +6,7 @@ The twin compares every pixel with every neighbour of its neighbourhood, one off
 (a NaN on either side gives False, +0 >= -0 and -0 >= +0 are True); float16 maps are compared in float32, which is
 exact.  There is no maximum in it and no pooling: that the rule equals torch's max_pool2d formula is a test."""
 import numpy as np
+from optest import bits_of, np_dtype, pack      # noqa: F401  (handed on to the tests)
 
 DTYPES = ("f32", "f16")
 FORMS = ("all", "mask", "list")
@@ -28,16 +29,6 @@ WINDOWS = {
     "w3x7": (3, 7, 0, 0.1),
 }
 WINDOW_IDS = list(WINDOWS)
-
-
-def np_dtype(dtype):
-    return np.float32 if dtype == "f32" else np.float16
-
-
-def bits_of(a):
-    """The integer view of a float array."""
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint16)
 
 
 # ------------------------------------------------------------------------------------------------ the rule
@@ -79,15 +70,6 @@ def twin(v, window):
     kH, kW, cross, floor = WINDOWS[window]
     k = keep(v, kH, kW, cross, floor)
     return suppressed(v, k), k
-
-
-def pack(mask):
-    """A bool [H, W] map as the library's row-padded bit mask (uint64 words)."""
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').copy()
 
 
 def peak_bits(k):

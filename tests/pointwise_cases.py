@@ -7,6 +7,7 @@ operator, so the twin written here IS the specification:
   rule 3  only listed pixels are written; the frame's mask is handed on, padding bits never set.
 No GPU is needed to import this file."""
 import numpy as np
+from optest import bits_of, pack      # noqa: F401  (handed on to the tests)
 
 F32 = np.float32
 (IDENTITY, RELU, HARDTANH, LEAKY, PRELU, HARDSWISH, HARDSIGMOID, SIGMOID, SILU, TANH) = range(10)
@@ -123,20 +124,6 @@ def patterns(rng, H, W):
         edge[0, W - 1] = edge[H - 1, 0] = True
     return [("full", ~Z), ("empty", Z), ("one bit", one), ("last column", last), ("word boundary", edge),
             ("random", rng.random((H, W)) < 0.1)]
-
-
-def pack(mask):
-    """A bool [H, W] map as the library's row-padded bit mask (uint64 words)."""
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').copy()
-
-
-def bits_of(a):
-    """The integer view of a float array."""
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint16)
 
 
 def same_bits(got, want):

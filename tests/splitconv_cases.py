@@ -13,6 +13,7 @@ import zlib
 from collections import namedtuple
 
 import numpy as np
+from optest import mask_words      # noqa: F401  (handed on to the tests)
 
 ASSUMED_CUS = 256        # the CU count the claimed cells of CASES are written for (MI355X)
 MAXSEQ = 8               # CBS_MAXSEQ
@@ -56,10 +57,6 @@ def geom(C, kH, kW):
 def supported(C, K, kH, kW):
     return (C in (16, 32, 64) and 1 <= K <= 1024 and kH % 2 == 1 and kW % 2 == 1 and 1 <= kH <= 15 and 1 <= kW <= 15
             and geom(C, kH, kW)["nStages"] >= 4)
-
-
-def mask_words(H, W):
-    return H * ((W + 63) // 64)
 
 
 def tile_height(K):

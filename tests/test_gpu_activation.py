@@ -10,26 +10,15 @@ import torch
 import torch.nn as nn
 
 import activation_cases as ac
-from test_gpu_chanreduce import LayerNorm2d, LayerSpy, chain_frames, raw, set_clone
-from test_gpu_pointwise import FILL, dev, dev_words, host_words, operand_args, stream
+from optest import (chain_frames, dev, dev_words, host_words, LayerSpy, lib,      # noqa: F401  (fixtures)
+                    operand_args, gpu_pkg as pkg, raw, share_of, stream, walk_frames)
+from test_gpu_chanreduce import LayerNorm2d, set_clone
+from test_gpu_pointwise import FILL
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [np.float32, np.float16]
 WORST = {}      # (case name, dtype name) -> [worst err / bound, worst err / |ref|] seen against float64
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 def code_of(lib, dtype):
@@ -48,42 +37,21 @@ def run_frames(lib, shape, dtype, form, kind, p0, p1, rng):
     """The six mask patterns as consecutive frames through cbinfer_cbpointwise_forward, as run_frames of
     tests/test_gpu_pointwise.py: before every frame x gets new values at the frame's pixels AND at one pixel outside
     them; the listed values are judged against the float64 formula, unlisted pixels must keep their bits, maskCopy be
-    the frame's mask, the working mask zero."""
+    the frame's mask, the working mask zero (optest.walk_frames)."""
     C, ptr = lib.C, lib.ptr
     Cn, H, W = shape
-    words = C.cbinfer_mask_words(H, W)
     special = np.array(ac.SPECIAL, dtype=dtype)
-    x = ac.values(rng, shape, dtype, 20.0, special)
     out = np.empty(shape, dtype=dtype)
     ac.bits_of(out)[...] = FILL[dtype] & (0xFFFFFFFF if dtype == np.float32 else 0xFFFF)
-    dout = dev(out)
-    bits = torch.zeros(words, dtype=torch.int64, device="cuda")
-    mcopy = torch.full((words,), -1, dtype=torch.int64, device="cuda")
-    sawUnlisted = 0
-    for t, (label, S) in enumerate(ac.patterns(rng, H, W)):
-        where = (shape, np.dtype(dtype).name, form, ac.case_name(kind, p0, p1), label)
-        fresh = ac.values(rng, shape, dtype, 20.0, special)
-        x[:, S] = fresh[:, S]
-        free = np.flatnonzero(~S.reshape(-1))
-        p = 0
-        if len(free):      # an operand altered where the list does not say so: a dense operator would pick it up
-            p = int(free[len(free) // 2])
-            x[:, p // W, p % W] = fresh[:, p // W, p % W]
-        listed = np.ones((H, W), dtype=bool) if form == "all" else S
-        dx = dev(x)
-        mask, lst, cap, cnt = operand_args(form, S, t, p)
-        st = C.cbinfer_cbpointwise_forward(ptr(dx), ptr(dout), ptr(mask), ptr(lst), cap, ptr(cnt), ptr(bits), ptr(mcopy),
-                                           Cn, H, W, kind, p0, p1, None, None, None, code_of(lib, dtype), stream())
-        assert st == 0, where
-        got = dout.cpu().numpy()
+
+    def call(dx, dout, mask, lst, cap, cnt, bits, mcopy):
+        return C.cbinfer_cbpointwise_forward(ptr(dx), ptr(dout), ptr(mask), ptr(lst), cap, ptr(cnt), ptr(bits), ptr(mcopy),
+                                             Cn, H, W, kind, p0, p1, None, None, None, code_of(lib, dtype), stream())
+
+    def check(x, got, listed, where):
         note(x[:, listed], got[:, listed], kind, p0, p1, where)
-        assert np.array_equal(ac.bits_of(got)[:, ~listed], ac.bits_of(out)[:, ~listed]), where
-        if len(free) and not listed.all():
-            sawUnlisted += 1
-        assert np.array_equal(host_words(mcopy), ac.pack(listed)), where
-        assert int(bits.ne(0).sum().item()) == 0, where
-        out = got
-    return sawUnlisted
+    return walk_frames(lib, shape, dtype, form, lambda: ac.patterns(rng, H, W), call, check, out,
+                       lambda: ac.values(rng, shape, dtype, 20.0, special), what=(ac.case_name(kind, p0, p1),))
 
 
 @pytest.mark.parametrize("form", ac.FORMS)
@@ -139,7 +107,7 @@ def test_a_pixel_does_not_depend_on_the_list_the_form_or_the_run(lib, dtype):
                 dout = torch.zeros((Cn, H, W), dtype=dx.dtype, device="cuda")
                 bits = torch.zeros(words, dtype=torch.int64, device="cuda")
                 mcopy = torch.zeros(words, dtype=torch.int64, device="cuda")
-                mask, lst, cap, cnt = operand_args(form, S, rep)
+                mask, lst, cap, cnt = operand_args(form, S, 0, bool(rep % 2))
                 st = C.cbinfer_cbpointwise_forward(ptr(dx), ptr(dout), ptr(mask), ptr(lst), cap, ptr(cnt), ptr(bits),
                                                    ptr(mcopy), Cn, H, W, kind, p0, p1, ptr(dscale), ptr(dshift), None,
                                                    code_of(lib, dtype), stream())
@@ -266,10 +234,6 @@ def convnext_body(pkg, tdt, transcendental=True):
     return net
 
 
-def share_of(module):
-    return float(np.unpackbits(host_words(module._pwWork['copy']).view(np.uint8)).sum()) / (20 * 70)
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16"])
 def test_convnext_chain_equals_the_chain_that_recomputes_every_pixel(pkg, lib, dtype, monkeypatch):
     """Six frames of moving blocks: the chain with the GELU as a CBPointwise2d against a deep copy -- made before the
@@ -304,7 +268,7 @@ def test_convnext_chain_equals_the_chain_that_recomputes_every_pixel(pkg, lib, d
             for name in ('stem', 'dw', 'pw1', 'pw2'):
                 assert torch.equal(raw(getattr(net, name).prevOutput), raw(getattr(dense, name).prevOutput)), (name, t)
             assert torch.equal(raw(net.norm.outputState), raw(dense.norm.outputState)), t
-            share.append(share_of(net.gelu))
+            share.append(share_of(net.gelu._pwWork['copy'], 20, 70))
     for h in hooks:
         h.remove()
     print("listed share per frame:", ["%.2f" % s for s in share], {k: v for k, v in spy.calls.items() if k != 'dense'})

@@ -13,21 +13,9 @@ import torch.nn.functional as F
 
 import adaptpool_cases as ac
 from adaptpool_cases import CASE_IDS, CASES, DTYPES, OPS
+from optest import dev_words, host_words, lib, gpu_pkg as pkg, stream      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 @pytest.fixture(scope="module")
@@ -43,18 +31,6 @@ def walks():
             cache[key + (op,)] = [ac.twin(x, CASES[cid][3], op) for x in cache[key][0]]
         return cache[key] + (cache[key + (op,)],)
     return get
-
-
-def dev_words(words):
-    return torch.from_numpy(words.view(np.int64)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def op_code(lib, op):

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 import torch.nn as nn
+from optest import (dev_words, host_words, lib, operand_args, pack, gpu_pkg as pkg,      # noqa: F401  (fixtures)
+                    raw, stream)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,45 +22,6 @@ TH = 0.05
 SHAPES = [(1, 3, 64), (5, 5, 70), (67, 9, 130), (3, 2, 1), (1, 2100, 9)]
 STRIDED = (1, 2100, 9)      # more mask words than workgroups: the grid-stride leg of the word walk
 FORMS = ["mask", "list", "all"]
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
-
-
-def pack(mask):
-    """A bool [H, W] map as the library's row-padded bit mask (uint64 words)."""
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').copy()
-
-
-def dev_words(words):
-    return torch.from_numpy(words.view(np.int64)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def raw(t):
-    """The bits of a float tensor."""
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def twin(a, b, relu):
@@ -84,23 +47,6 @@ def frame_sets(rng, H, W):
     return [("empty", Z, Z), ("single", at((H // 2, W // 2)), Z), ("full word", word, Z),
             ("last column", Z, at((H - 1, W - 1))), ("both corners", at((0, 0)), at((H - 1, W - 1))),
             ("disjoint", A, B), ("overlapping", A2, B2), ("empty again", Z, Z)]
-
-
-def operand_args(form, changed, junk, useCount):
-    """(mask, list, capacity, device count) of cbinfer_cbadd_forward for one operand; the tensors are kept alive by the
-    caller.  List form: unsorted, with a duplicate and entries outside the map; with a device count the buffer holds
-    entries behind it that must not be read."""
-    H, W = changed.shape
-    if form == "all":
-        return None, None, 0, None
-    if form == "mask":
-        return dev_words(pack(changed)), None, 0, None
-    idx = np.flatnonzero(changed.reshape(-1)).astype(np.int32)[::-1]
-    idx = np.concatenate([idx, idx[:1], np.array([H * W, -1, H * W + 77], dtype=np.int32)])
-    if useCount:
-        buf = torch.from_numpy(np.concatenate([idx, np.full(5, junk, dtype=np.int32)])).cuda()
-        return None, buf, buf.numel(), torch.tensor([len(idx)], dtype=torch.int32, device="cuda")
-    return None, torch.from_numpy(idx.copy()).cuda(), len(idx), None
 
 
 def refresh(t, changed, rng):
@@ -141,6 +87,8 @@ def test_every_operand_form_through_the_c_abi(lib, shape, dtype):
                 assert torch.equal(out, twin(a, b, relu)), (fa, fb, relu, "first frame")
                 assert np.array_equal(host_words(mcopy), pack(np.ones((H, W), dtype=bool)))
                 assert int(bits.ne(0).sum().item()) == 0
+                # (two operands, two lists, a first frame without either: this loop stays here -- optest.walk_frames
+                # walks one operand -- and takes the operand forms from optest)
                 for t, (label, SA, SB) in enumerate(frame_sets(rng, H, W)):
                     where = (shape, dtype, relu, fa, fb, label)
                     prev = out.clone()
@@ -152,8 +100,8 @@ def test_every_operand_form_through_the_c_abi(lib, shape, dtype):
                         p = int(free[len(free) // 2])
                         (a if t % 2 else b)[0, :, p // W, p % W] += 3.0
                     listed = np.ones((H, W), dtype=bool) if "all" in (fa, fb) else (SA | SB)
-                    ma, la, ca, na = operand_args(fa, SA, 0, useCount=True)
-                    mb, lb, cb, nb = operand_args(fb, SB, H * W - 1, useCount=False)
+                    ma, la, ca, na = operand_args(fa, SA, 0, use_count=True)
+                    mb, lb, cb, nb = operand_args(fb, SB, H * W - 1, use_count=False)
                     check(C.cbinfer_cbadd_forward(ptr(a), ptr(b), ptr(out), ptr(ma), ptr(la), ca, ptr(na), ptr(mb), ptr(lb),
                                                   cb, ptr(nb), ptr(bits), ptr(mcopy), Cn, H, W, relu, lib.dtype_code(a),
                                                   stream()))

@@ -5,15 +5,9 @@ arithmetic; only the enumeration of the work items differs)."""
 import numpy as np
 import pytest
 import torch
+from optest import gpu_pkg as pkg      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
 
 
 def _nets(pkg, n, size):

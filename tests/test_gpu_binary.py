@@ -17,50 +17,14 @@ import torch.nn.functional as F
 
 import binary_cases as bc
 from test_gpu_rearrange import net_frames
+from optest import (bits_of, dev, dev_words, free_pixel, host_words, lib, operand_args,      # noqa: F401  (fixtures)
+                    gpu_pkg as pkg, raw, stream)
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [np.float32, np.float16]
 CHANGE_FORMS = ["mask", "list", "all"]
 WORST = {}
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
-
-
-def dev(x):
-    return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def dev_words(words):
-    return torch.from_numpy(words.view(np.int64)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def raw(t):
-    """The bits of a float tensor."""
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def bits_of(x):
-    return x.view(np.uint32 if x.dtype == np.float32 else np.uint16)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def values(rng, shape, dtype, span=1.0, special=None, lim=None):
@@ -71,23 +35,6 @@ def values(rng, shape, dtype, span=1.0, special=None, lim=None):
         pick = rng.random(shape) < 1.0 / 16
         v[pick] = special[rng.integers(0, len(special), int(pick.sum()))]
     return v
-
-
-def operand_args(form, changed, junk, useCount):
-    """(mask, list, capacity, device count) of one operand; the tensors are kept alive by the caller.  List form: unsorted,
-    with a duplicate and entries outside the map; with a device count the buffer holds entries behind it that must not
-    be read."""
-    H, W = changed.shape
-    if form == "all":
-        return None, None, 0, None
-    if form == "mask":
-        return dev_words(bc.pack(changed)), None, 0, None
-    idx = np.flatnonzero(changed.reshape(-1)).astype(np.int32)[::-1]
-    idx = np.concatenate([idx, idx[:1], np.array([H * W, -1, H * W + 77], dtype=np.int32)])
-    if useCount:
-        buf = torch.from_numpy(np.concatenate([idx, np.full(5, junk, dtype=np.int32)])).cuda()
-        return None, buf, buf.numel(), torch.tensor([len(idx)], dtype=torch.int32, device="cuda")
-    return None, torch.from_numpy(idx.copy()).cuda(), len(idx), None
 
 
 def plans(form, pairs):
@@ -160,6 +107,8 @@ def run_frames(lib, shape, dtype, form, fn, plan, rng, check, span=1.0, special=
     assert np.array_equal(host_words(mcopy), bc.pack(everything))
     assert int(bits.ne(0).sum().item()) == 0
     saw = 0
+    # (two operands, two lists, a first frame without either: this loop stays here -- optest.walk_frames walks one
+    # operand -- and takes the operand forms from optest)
     for t, (label, SA, SB) in enumerate(bc.frame_sets(rng, H, W)):
         where = (shape, dtype, form, fn, plan, label)
         prev = out
@@ -172,8 +121,7 @@ def run_frames(lib, shape, dtype, form, fn, plan, rng, check, span=1.0, special=
             b[...] = values(rng, b.shape, dtype, bspan, bspecial, blim)      # a per-frame vector / scalar: every pixel
         union = SA | SB if ownPixels else SA
         # an operand altered where NEITHER list says so: a dense operator would pick it up
-        free = np.flatnonzero(~union.reshape(-1))
-        p = int(free[len(free) // 2]) if len(free) else None
+        p = free_pixel(union, middle=True)
         if p is not None:
             tgt = b if (ownPixels and t % 2) else a
             v = tgt[:, p // W, p % W]
@@ -184,8 +132,8 @@ def run_frames(lib, shape, dtype, form, fn, plan, rng, check, span=1.0, special=
         da.copy_(dev(a))
         if db is not None:
             db.copy_(dev(b))
-        argsA = operand_args(fa, SA, 0, useCount=True)
-        argsB = operand_args(fb, SB, H * W - 1, useCount=False) if ownPixels else none
+        argsA = operand_args(fa, SA, 0, use_count=True)
+        argsB = operand_args(fb, SB, H * W - 1, use_count=False) if ownPixels else none
         call(argsA, argsB)
         out = dout.cpu().numpy()
         check(a, b, out, listed, where)
@@ -398,8 +346,8 @@ def test_the_state_does_not_depend_on_the_change_forms(lib, dtype, form, shape):
                     da.copy_(dev(a))
                     if db is not None:
                         db.copy_(dev(b))
-                (ma, la, ca, na) = none if not t else operand_args(cf, SA, 0, useCount=True)
-                (mb, lb, cb, nb) = none if not (t and own) else operand_args(cf, SB, H * W - 1, useCount=False)
+                (ma, la, ca, na) = none if not t else operand_args(cf, SA, 0, use_count=True)
+                (mb, lb, cb, nb) = none if not (t and own) else operand_args(cf, SB, H * W - 1, use_count=False)
                 st = C.cbinfer_cbbinary_forward(ptr(da), ptr(db), ptr(dout), ptr(ma), ptr(la), ca, ptr(na), ptr(mb), ptr(lb),
                                                 cb, ptr(nb), bc.FORMS.index(form), lib.BIN_B_OWN if own else lib.BIN_B_NONE,
                                                 ptr(bits), ptr(mcopy), Cn, H, W, code, bc.GATES.index(gate), int(reverse), dt,

@@ -20,27 +20,15 @@ import torch
 import torch.nn.functional as F
 
 import chain_cases as cc
-from test_gpu_pad import host_words, operand_of, pack, raw
+from test_gpu_pad import operand_of
 from test_gpu_tconv import bound_of, tconv64
+from optest import host_words, lib, pack, gpu_pkg as pkg, raw      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = {'f32': torch.float32, 'f16': torch.float16}
 HANDED = ('as handed', 'list made first')
 _FRAMES = {}
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 def frames(dtype):

@@ -10,6 +10,8 @@ import torch
 import torch.nn as nn
 
 import chancollapse_cases as cc
+from optest import (chain_frames, dev, dev_words, host_words, LayerSpy, lib,      # noqa: F401  (fixtures)
+                    operand_args, gpu_pkg as pkg, raw, stream, walk_frames)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,64 +22,14 @@ WORST = {}      # (kind name, dtype name) -> worst err / bound seen against floa
 ALL_CALLS = [(k,) for k in range(7)] + [(cc.SUM, cc.MEAN, cc.NORM, cc.MAX), (cc.MEAN, cc.MAX), (cc.MIN, cc.MAX)]
 
 
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def dev_words(words):
-    return torch.from_numpy(words.view(np.int64)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def raw(t):
-    """The bits of a tensor."""
-    return t.view({torch.float32: torch.int32, torch.float16: torch.int16}.get(t.dtype, t.dtype))
-
-
 def is_arg(kinds):
     return kinds[0] in cc.ARG_KINDS
 
 
-def operand_args(form, changed, t, junk=0):
-    """(mask, list, capacity, device count) of cbinfer_cbchancollapse_forward; the tensors are kept alive by the caller.
-    List form: unsorted, with a duplicate and entries outside the map; on every other frame with a device count in
-    front of entries (`junk`, a pixel that is not listed) that must not be read."""
-    H, W = changed.shape
-    if form == "all":
-        return None, None, 0, None
-    if form == "mask":
-        return dev_words(cc.pack(changed)), None, 0, None
-    idx = np.flatnonzero(changed.reshape(-1)).astype(np.int32)[::-1]
-    idx = np.concatenate([idx, idx[:1], np.array([H * W, -1, H * W + 77], dtype=np.int32)])
-    if t % 2:
-        buf = dev(np.concatenate([idx, np.full(5, junk, dtype=np.int32)]))
-        return None, buf, buf.numel(), torch.tensor([len(idx)], dtype=torch.int32, device="cuda")
-    return None, dev(idx.copy()), len(idx), None
-
-
-def forward(lib, dx, dout, form, S, t, junk, bits, mcopy, label, kinds):
+def forward(lib, dx, dout, args, bits, mcopy, label, kinds):
+    """cbinfer_cbchancollapse_forward with the operand `args` = (mask, list, capacity, device count)."""
     Cn, H, W = dx.shape
-    mask, lst, cap, cnt = operand_args(form, S, t, junk)
+    mask, lst, cap, cnt = args
     ptr = lib.ptr
     return lib.C.cbinfer_cbchancollapse_forward(ptr(dx), ptr(dout), ptr(mask), ptr(lst), cap, ptr(cnt), ptr(bits),
                                                 ptr(mcopy), ptr(label), Cn, H, W, cc.packed(kinds), len(kinds),
@@ -93,51 +45,33 @@ def new_state(kinds, H, W, dtype):
     return out
 
 
-def state_bits(a):
-    return a if a.dtype == np.int64 else cc.bits_of(a)
-
-
 def run_frames(lib, shape, dtype, form, kinds, rng, values, check):
     """The six mask patterns as consecutive frames through cbinfer_cbchancollapse_forward.  Before every frame x gets new
     values at the frame's pixels AND at one pixel outside them; check(x, got, listed, where) judges the values at the
     listed pixels; unlisted pixels must keep their bits, maskCopy be the frame's mask, the working mask zero; an arg
     launch's label mask -- full of stale bits before every launch -- must be listed & (all form | new != old), in every
-    word.  Returns (frames with an unlisted pixel, x at the listed pixels of all frames [C, n])."""
+    word.  The walk is optest.walk_frames; the label mask rides in its call and check.  Returns (frames with an unlisted
+    pixel, x at the listed pixels of all frames [C, n])."""
     Cn, H, W = shape
     words = lib.C.cbinfer_mask_words(H, W)
-    x = values(rng, shape, dtype)
-    out = new_state(kinds, H, W, dtype)
-    dout = dev(out)
-    bits = torch.zeros(words, dtype=torch.int64, device="cuda")
-    mcopy = torch.full((words,), -1, dtype=torch.int64, device="cuda")
-    sawUnlisted, seen = 0, []
-    for t, (name, S) in enumerate(cc.patterns(rng, H, W)):
-        where = (shape, np.dtype(dtype).name, form, [cc.NAMES[k] for k in kinds], name)
-        fresh = values(rng, shape, dtype)
-        x[:, S] = fresh[:, S]
-        free = np.flatnonzero(~S.reshape(-1))
-        p = 0
-        if len(free):      # an operand altered where the list does not say so: a dense operator would pick it up
-            p = int(free[len(free) // 2])
-            x[:, p // W, p % W] = fresh[:, p // W, p % W]
-        listed = np.ones((H, W), dtype=bool) if form == "all" else S
-        label = torch.full((words,), -1, dtype=torch.int64, device="cuda") if is_arg(kinds) else None
-        st = forward(lib, dev(x), dout, form, S, t, p, bits, mcopy, label, kinds)
-        assert st == 0, where
-        got = dout.cpu().numpy()
-        check(x, got, listed, where)
-        keep = (slice(None), ~listed) if got.ndim == 3 else (~listed,)
-        assert np.array_equal(state_bits(got)[keep], state_bits(out)[keep]), where
-        if len(free) and not listed.all():
-            sawUnlisted += 1
-        assert np.array_equal(host_words(mcopy), cc.pack(listed)), where
-        assert int(bits.ne(0).sum().item()) == 0, where
+    label = torch.empty(words, dtype=torch.int64, device="cuda") if is_arg(kinds) else None
+    prev, seen = [new_state(kinds, H, W, dtype)], []
+
+    def call(dx, dout, mask, lst, cap, cnt, bits, mcopy):
         if label is not None:
-            moved = listed & (np.ones((H, W), dtype=bool) if form == "all" else got != out)
+            label.fill_(-1)
+        return forward(lib, dx, dout, (mask, lst, cap, cnt), bits, mcopy, label, kinds)
+
+    def judge(x, got, listed, where):
+        check(x, got, listed, where)
+        if label is not None:
+            moved = listed & (np.ones((H, W), dtype=bool) if form == "all" else got != prev[0])
             assert np.array_equal(host_words(label), cc.pack(moved)), where
         seen.append(x[:, listed].copy())
-        out = got
-    return sawUnlisted, np.concatenate(seen, axis=1)
+        prev[0] = got
+    saw = walk_frames(lib, shape, dtype, form, lambda: cc.patterns(rng, H, W), call, judge, prev[0],
+                      lambda: values(rng, shape, dtype), what=([cc.NAMES[k] for k in kinds],))
+    return saw, np.concatenate(seen, axis=1)
 
 
 def check_float_kinds(kinds):
@@ -252,12 +186,12 @@ def test_label_mask_is_empty_where_scores_move_and_labels_stay(lib):
     mcopy = torch.zeros(words, dtype=torch.int64, device="cuda")
     label = torch.full((words,), -1, dtype=torch.int64, device="cuda")
     full = np.ones((H, W), dtype=bool)
-    assert forward(lib, dev(x), dout, "all", full, 0, 0, bits, mcopy, label, (cc.ARGMAX,)) == 0
+    assert forward(lib, dev(x), dout, operand_args("all", full), bits, mcopy, label, (cc.ARGMAX,)) == 0
     assert np.array_equal(host_words(label), cc.pack(full))
     first = dout.cpu().numpy()
     assert np.array_equal(first, x.argmax(axis=0))
     label.fill_(-1)
-    assert forward(lib, dev(x * 2), dout, "mask", full, 0, 0, bits, mcopy, label, (cc.ARGMAX,)) == 0
+    assert forward(lib, dev(x * 2), dout, operand_args("mask", full), bits, mcopy, label, (cc.ARGMAX,)) == 0
     assert int(label.ne(0).sum()) == 0 and np.array_equal(host_words(mcopy), cc.pack(full))
     assert np.array_equal(dout.cpu().numpy(), first)
     x2 = x * 2
@@ -268,7 +202,7 @@ def test_label_mask_is_empty_where_scores_move_and_labels_stay(lib):
     for y, xx in movedPixels:
         S[y, xx] = True
     label.fill_(-1)
-    assert forward(lib, dev(x2), dout, "list", S, 0, 0, bits, mcopy, label, (cc.ARGMAX,)) == 0
+    assert forward(lib, dev(x2), dout, operand_args("list", S), bits, mcopy, label, (cc.ARGMAX,)) == 0
     want = np.zeros((H, W), dtype=bool)
     for y, xx in movedPixels:
         want[y, xx] = True
@@ -305,10 +239,10 @@ def test_a_pixel_does_not_depend_on_the_list_the_form_or_the_run(lib, dtype):
                 dout = dev(new_state(kinds, H, W, dtype))
                 bits = torch.zeros(words, dtype=torch.int64, device="cuda")
                 mcopy = torch.zeros(words, dtype=torch.int64, device="cuda")
-                assert forward(lib, dx, dout, form, S, rep, 0, bits, mcopy, None, kinds) == 0
-                seen.append(state_bits(dout[..., py, px].cpu().numpy()).copy())
+                assert forward(lib, dx, dout, operand_args(form, S, 0, bool(rep % 2)), bits, mcopy, None, kinds) == 0
+                seen.append(cc.bits_of(dout[..., py, px].cpu().numpy()).copy())
         assert all(np.array_equal(s, seen[0]) for s in seen[1:]), kinds
-        want = cc.twin_arg(x[:, py, px:px + 1], kinds[0])[0] if is_arg(kinds) else state_bits(
+        want = cc.twin_arg(x[:, py, px:px + 1], kinds[0])[0] if is_arg(kinds) else cc.bits_of(
             cc.twin_values(x[:, py, px:px + 1], kinds)[:, 0])
         assert np.array_equal(seen[0], want), kinds
 
@@ -401,7 +335,7 @@ def test_module_forms_flags_and_errors(pkg, lib, dtype):
                 assert np.array_equal(got[sel], want[sel]), (op, t)
             else:
                 assert cc.same_bits(got[sel], want[sel]), (op, t)
-            assert np.array_equal(state_bits(got)[..., ~S], state_bits(prev)[..., ~S]), (op, t)
+            assert np.array_equal(cc.bits_of(got)[..., ~S], cc.bits_of(prev)[..., ~S]), (op, t)
             assert np.array_equal(host_words(m._chWork['copy']), cc.pack(S))
             handed = S & (got != prev).reshape(-1, H, W)[0] if m.labelChanges else S
             assert np.array_equal(host_words(ix._mask), cc.pack(handed)), (op, t)
@@ -509,39 +443,6 @@ def set_clone(net, cloneOutput):
     return net
 
 
-def chain_frames(rng, n, npdt, H=20, W=70):
-    """n frames [1, 8, H, W]; a frame differs from the one before in two moved blocks only."""
-    base = (rng.random((1, 8, H, W)) * 2 - 1).astype(npdt)
-    frames = []
-    for i in range(n):
-        new = base.copy()
-        if i:
-            for _ in range(2):
-                y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                blk = new[:, :, y0:y0 + 4, x0:x0 + 7]
-                blk[...] = (rng.random(blk.shape) * 2 - 1).astype(npdt)
-        frames.append(dev(new))
-        base = new
-    return frames
-
-
-class CallSpy(object):
-    """Counts the launching library calls made through it (the library object's attributes are read-only)."""
-
-    def __init__(self, real):
-        self.__dict__.update(real=real, calls={})
-
-    def __getattr__(self, name):
-        fn = getattr(self.real, name)
-        if not getattr(fn, 'launcher', False):
-            return fn
-
-        def counted(*a):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*a)
-        return counted
-
-
 def tensor_of(y):
     return y[1] if type(y) == tuple else y
 
@@ -557,7 +458,7 @@ def test_segmentation_head_labels_are_the_argmax_of_the_producers_state(pkg, lib
     net = segmentation_head(pkg, tdt)
     dense = copy.deepcopy(net)
     dense.label = DenseTwin(net.label)
-    spy = CallSpy(lib.C)
+    spy = LayerSpy(lib.C)
     monkeypatch.setattr(chmod, 'C', spy)
     share = []
     with torch.no_grad():
@@ -579,7 +480,7 @@ def test_segmentation_head_labels_are_the_argmax_of_the_producers_state(pkg, lib
             share.append(float(listed.sum()) / (20 * 70))
             prev = now
     assert share[0] == 1.0 and 0 < min(share[1:]) and max(share[1:]) < 0.5, share
-    assert spy.calls == {'cbinfer_cbchancollapse_forward': 6}
+    assert spy.calls == {None: {'cbinfer_cbchancollapse_forward': 6}}
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16"])
@@ -592,7 +493,7 @@ def test_spatial_attention_equals_the_chain_with_the_dense_twin(pkg, lib, dtype,
     net = attention_block(pkg, tdt)
     dense = copy.deepcopy(net)
     dense.att.gate._modules['0'] = DenseTwin(net.att.gate[0])
-    spy = CallSpy(lib.C)
+    spy = LayerSpy(lib.C)
     monkeypatch.setattr(chmod, 'C', spy)
     with torch.no_grad():
         for t, f in enumerate(chain_frames(np.random.default_rng(21), 6, dtype)):
@@ -602,7 +503,7 @@ def test_spatial_attention_equals_the_chain_with_the_dense_twin(pkg, lib, dtype,
             assert tuple(pooled.shape) == (1, 2, 20, 70) and state_equals(pooled, module_twin(net.att.gate[0], f[0].cpu().numpy())), t
             for a, b in ((net.att.gate[1], dense.att.gate[1]), (net.att.body[0], dense.att.body[0])):
                 assert torch.equal(raw(a.prevOutput), raw(b.prevOutput)), t
-    assert spy.calls == {'cbinfer_cbchancollapse_forward': 6}
+    assert spy.calls == {None: {'cbinfer_cbchancollapse_forward': 6}}
 
 
 @pytest.mark.parametrize("chain", ["segmentation", "attention"])

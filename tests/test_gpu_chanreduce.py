@@ -11,6 +11,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import chanreduce_cases as cc
+from optest import (chain_frames, dev, dev_words, host_words, LayerSpy, lib,      # noqa: F401  (fixtures)
+                    operand_args, gpu_pkg as pkg, raw, share_of, stream, walk_frames)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,19 +21,6 @@ WORST = {}      # (kind name, dtype name) -> worst err / bound seen against floa
 FILL = {np.float32: 0x5BCD5BCD, np.float16: 0x5BCD}
 EXACT = [(cc.LAYERNORM, False), (cc.LAYERNORM, True), (cc.L2NORM, False)]
 INEXACT = [(cc.SOFTMAX, False), (cc.LOGSOFTMAX, False)]
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 class LayerNorm2d(nn.Module):
@@ -47,47 +36,10 @@ class LayerNorm2d(nn.Module):
         return F.layer_norm(x.permute(0, 2, 3, 1), (self.C,), self.weight, self.bias, self.eps).permute(0, 3, 1, 2)
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def dev_words(words):
-    return torch.from_numpy(words.view(np.int64)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def raw(t):
-    """The bits of a float tensor."""
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def operand_args(form, changed, t, junk=0):
-    """(mask, list, capacity, device count) of cbinfer_cbchanreduce_forward; the tensors are kept alive by the caller.
-    List form: unsorted, with a duplicate and entries outside the map; on every other frame with a device count in
-    front of entries (`junk`, a pixel that is not listed) that must not be read."""
-    H, W = changed.shape
-    if form == "all":
-        return None, None, 0, None
-    if form == "mask":
-        return dev_words(cc.pack(changed)), None, 0, None
-    idx = np.flatnonzero(changed.reshape(-1)).astype(np.int32)[::-1]
-    idx = np.concatenate([idx, idx[:1], np.array([H * W, -1, H * W + 77], dtype=np.int32)])
-    if t % 2:
-        buf = dev(np.concatenate([idx, np.full(5, junk, dtype=np.int32)]))
-        return None, buf, buf.numel(), torch.tensor([len(idx)], dtype=torch.int32, device="cuda")
-    return None, dev(idx.copy()), len(idx), None
-
-
-def forward(lib, dx, dout, form, S, t, junk, bits, mcopy, kind, eps, dgamma, dbeta):
+def forward(lib, dx, dout, args, bits, mcopy, kind, eps, dgamma, dbeta):
+    """cbinfer_cbchanreduce_forward with the operand `args` = (mask, list, capacity, device count)."""
     Cn, H, W = dx.shape
-    mask, lst, cap, cnt = operand_args(form, S, t, junk)
+    mask, lst, cap, cnt = args
     ptr = lib.ptr
     return lib.C.cbinfer_cbchanreduce_forward(ptr(dx), ptr(dout), ptr(mask), ptr(lst), cap, ptr(cnt), ptr(bits), ptr(mcopy),
                                               Cn, H, W, kind, eps, ptr(dgamma), ptr(dbeta),
@@ -98,45 +50,28 @@ def run_frames(lib, shape, dtype, form, kind, affine, rng, check):
     """The six mask patterns as consecutive frames through cbinfer_cbchanreduce_forward.  Before every frame x gets new
     values at the frame's pixels AND at one pixel outside them; check(x, out, listed, where, gamma, beta) judges the
     values at the listed pixels; unlisted pixels must keep their bits, maskCopy be the frame's mask, the working mask
-    zero.  Returns (frames with an unlisted pixel, listed pixels, listed pixels whose channels are all finite)."""
+    zero (optest.walk_frames); three quarters of the listed pixels must be finite.  Returns the number of frames with an
+    unlisted pixel."""
     Cn, H, W = shape
-    words = lib.C.cbinfer_mask_words(H, W)
-    assert words == H * ((W + 63) // 64)
     gamma, beta = cc.affine(rng, Cn)
     dgamma, dbeta = (dev(gamma), dev(beta)) if affine else (None, None)
     eps = cc.EPS[kind]
-    x = cc.values(rng, shape, dtype)
     out = np.empty(shape, dtype=dtype)
     cc.bits_of(out)[...] = FILL[dtype]
-    dout = dev(out)
-    bits = torch.zeros(words, dtype=torch.int64, device="cuda")
-    mcopy = torch.full((words,), -1, dtype=torch.int64, device="cuda")
-    sawUnlisted = nListed = nFinite = 0
-    for t, (label, S) in enumerate(cc.patterns(rng, H, W)):
-        where = (shape, np.dtype(dtype).name, form, cc.NAMES[kind], affine, label)
-        fresh = cc.values(rng, shape, dtype)
-        x[:, S] = fresh[:, S]
-        free = np.flatnonzero(~S.reshape(-1))
-        p = 0
-        if len(free):      # an operand altered where the list does not say so: a dense operator would pick it up
-            p = int(free[len(free) // 2])
-            x[:, p // W, p % W] = fresh[:, p // W, p % W]
-        listed = np.ones((H, W), dtype=bool) if form == "all" else S
-        st = forward(lib, dev(x), dout, form, S, t, p, bits, mcopy, kind, eps, dgamma, dbeta)
-        assert st == 0, where
-        got = dout.cpu().numpy()
+    n = {'listed': 0, 'finite': 0}
+
+    def call(dx, dout, mask, lst, cap, cnt, bits, mcopy):
+        return forward(lib, dx, dout, (mask, lst, cap, cnt), bits, mcopy, kind, eps, dgamma, dbeta)
+
+    def judge(x, got, listed, where):
         check(x, got, listed, where, gamma if affine else None, beta if affine else None)
-        assert np.array_equal(cc.bits_of(got)[:, ~listed], cc.bits_of(out)[:, ~listed]), where
-        if len(free) and not listed.all():
-            sawUnlisted += 1
-        assert np.array_equal(host_words(mcopy), cc.pack(listed)), where
-        assert int(bits.ne(0).sum().item()) == 0, where
-        nListed += int(listed.sum())
-        nFinite += int(cc.finite_pixels(x)[listed].sum())
-        out = got
+        n['listed'] += int(listed.sum())
+        n['finite'] += int(cc.finite_pixels(x)[listed].sum())
+    saw = walk_frames(lib, shape, dtype, form, lambda: cc.patterns(rng, H, W), call, judge, out,
+                      lambda: cc.values(rng, shape, dtype), what=(cc.NAMES[kind], affine))
     # (the bit and bound checks must see finite pixels: the special values are placed per pixel)
-    assert 4 * nFinite >= 3 * nListed, (shape, nFinite, nListed)
-    return sawUnlisted
+    assert 4 * n['finite'] >= 3 * n['listed'], (shape, n)
+    return saw
 
 
 def check_twin(kind):
@@ -256,8 +191,8 @@ def test_a_pixel_does_not_depend_on_the_list_the_form_or_the_run(lib, dtype):
                 bits = torch.zeros(words, dtype=torch.int64, device="cuda")
                 mcopy = torch.zeros(words, dtype=torch.int64, device="cuda")
                 aff = kind == cc.LAYERNORM
-                st = forward(lib, dx, dout, form, S, rep, 0, bits, mcopy, kind, cc.EPS[kind], dgamma if aff else None,
-                             dbeta if aff else None)
+                st = forward(lib, dx, dout, operand_args(form, S, 0, bool(rep % 2)), bits, mcopy, kind, cc.EPS[kind],
+                             dgamma if aff else None, dbeta if aff else None)
                 assert st == 0
                 seen.append(cc.bits_of(dout[:, py, px].cpu().numpy()).copy())
         assert all(np.array_equal(s, seen[0]) for s in seen[1:]), cc.NAMES[kind]
@@ -446,45 +381,6 @@ def set_clone(net, cloneOutput):
     return net
 
 
-def chain_frames(rng, n, npdt, H=20, W=70):
-    """n frames [1, 8, H, W]; a frame differs from the one before in two moved blocks only."""
-    base = (rng.random((1, 8, H, W)) * 2 - 1).astype(npdt)
-    frames = []
-    for i in range(n):
-        new = base.copy()
-        if i:
-            for _ in range(2):
-                y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                blk = new[:, :, y0:y0 + 4, x0:x0 + 7]
-                blk[...] = (rng.random(blk.shape) * 2 - 1).astype(npdt)
-        frames.append(dev(new))
-        base = new
-    return frames
-
-
-class LayerSpy(object):
-    """Notes the library calls made while each named layer runs (the library object's attributes are read-only
-    function pointers)."""
-
-    def __init__(self, real):
-        self.__dict__.update(real=real, calls={}, layer=[None])
-
-    def __getattr__(self, name):
-        fn = getattr(self.real, name)
-        if not getattr(fn, 'launcher', False):
-            return fn
-
-        def counted(*a):
-            per = self.calls.setdefault(self.layer[0], {})
-            per[name] = per.get(name, 0) + 1
-            return fn(*a)
-        return counted
-
-
-def share_of(module):
-    return float(np.unpackbits(host_words(module._chWork['copy']).view(np.uint8)).sum()) / (20 * 70)
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16"])
 def test_convnext_chain_equals_the_chain_with_the_dense_twin(pkg, lib, dtype, monkeypatch):
     """Six frames of moving blocks: the chain with a CBChannelReduce2d against a deep copy -- made before the first frame
@@ -517,7 +413,7 @@ def test_convnext_chain_equals_the_chain_with_the_dense_twin(pkg, lib, dtype, mo
             assert cc.same_bits(net.norm.outputState[0].cpu().numpy(), ref), t
             for name in ('expand', 'dw', 'project'):
                 assert torch.equal(raw(getattr(net, name).prevOutput), raw(getattr(dense, name).prevOutput)), (name, t)
-            share.append(share_of(net.norm))
+            share.append(share_of(net.norm._chWork['copy'], 20, 70))
     for h in hooks:
         h.remove()
     print("listed share per frame:", ["%.2f" % s for s in share], {k: v for k, v in spy.calls.items() if k != 'dense'})
@@ -543,7 +439,7 @@ def test_segmentation_head_state_is_the_softmax_of_the_producers_state(pkg, lib,
             assert torch.equal(raw(y), raw(net.prob.outputState))
             logits = net.head.prevOutput[0].cpu().numpy()
             assert module_agrees(net.prob, logits, net.prob.outputState[0].cpu().numpy()), t
-            share.append(share_of(net.prob))
+            share.append(share_of(net.prob._chWork['copy'], 20, 70))
     assert share[0] == 1.0 and 0 < min(share[1:]) and max(share[1:]) < 0.5, share
 
 

@@ -11,59 +11,13 @@ import torch
 import torch.nn as nn
 
 import chanscale_cases as cs
+from optest import dev, free_pixel, host_words, lib, operand, gpu_pkg as pkg, raw      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [np.float32, np.float16]
 WORST = {}      # what -> worst err / bound seen against float64
 TH = 0.25       # the threshold of the frame tests: exact in float32, as are the gates built around it
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def raw(t):
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def operand(pkg, form, x, listed, t):
-    """The operand a module is handed: bare ('all'), with its mask as a MaskChangeIndexes, or with an int32 list --
-    unsorted, with a duplicate and entries outside the map; on every other frame a ChangeIndexes with a device count in
-    front of entries that must not be read."""
-    from cbinfer_amd.conv2d_cg import ChangeIndexes, MaskChangeIndexes
-    H, W = listed.shape
-    if form == "all":
-        return x
-    if form == "mask":
-        words = torch.from_numpy(cs.pack(listed).view(np.int64)).cuda()
-        return ('changeIndexes', x, MaskChangeIndexes(words, (H, W), torch.empty(H * W, dtype=torch.int32, device="cuda"),
-                                                      torch.zeros(1, dtype=torch.int32, device="cuda")))
-    idx = np.flatnonzero(listed.reshape(-1)).astype(np.int32)[::-1]
-    idx = np.concatenate([idx, idx[:1], np.array([H * W, -1, H * W + 77], dtype=np.int32)])
-    if t % 2:
-        free = np.flatnonzero(~listed.reshape(-1))
-        junk = int(free[0]) if len(free) else 0
-        buf = dev(np.concatenate([idx, np.full(5, junk, dtype=np.int32)]))
-        return ('changeIndexes', x, ChangeIndexes(buf, torch.tensor([len(idx)], dtype=torch.int32, device="cuda"), (H, W)))
-    return ('changeIndexes', x, dev(idx.copy()))
 
 
 def pixel_patterns(rng, H, W):
@@ -148,7 +102,7 @@ def test_frames_equal_the_twin_bit_for_bit(pkg, dtype, form):
                     p = int(free[len(free) // 2])
                     a[:, p // W, p % W] = fresh_vals[:, p // W, p % W]
             listed = np.ones((H, W), dtype=bool) if form == "all" else S
-            out = m(operand(pkg, form, dev(a).reshape(1, Cn, H, W), S, t), dev(v).reshape(1, Cn, 1, 1))
+            out = m(operand(form, dev(a).reshape(1, Cn, H, W), S, free_pixel(S) or 0, bool(t % 2)), dev(v).reshape(1, Cn, 1, 1))
             assert type(out) is tuple and out[0] == 'changeIndexes' and out[1].dtype == tdt, where
             assert out[2].size == (H, W) and out[2]._mask is m._csWork['copy'], where
             held, prev, tripped = check_frame(m, a, v, held, prev, listed, t == 0, out[1], where)
@@ -185,7 +139,7 @@ def test_gates_against_float64_and_frames_with_a_gate(pkg, dtype, gate):
         for t, v in enumerate((v0, (v0.astype(np.float32) * 1.001).astype(dtype), big)):
             S = rng.random((H, W)) < 0.1
             a[:, S] = cs.pc.values(rng, shape, dtype, span=4.0)[:, S]
-            m(operand(pkg, "mask", dev(a).reshape(1, Cn, H, W), S, t), dev(v).reshape(1, Cn, 1, 1))
+            m(operand("mask", dev(a).reshape(1, Cn, H, W), S, free_pixel(S) or 0, bool(t % 2)), dev(v).reshape(1, Cn, 1, 1))
             where = (shape, np.dtype(dtype).name, gate, t)
             g = m._csWork['gate'].cpu().numpy()
             ref = cs.gate64(v.astype(np.float32), gate)
@@ -232,7 +186,7 @@ def test_fused_excitation_against_the_twin_and_float64(pkg, dtype, act):
                 if t:
                     z = (z.astype(np.float32) + rng.uniform(-0.05, 0.05, Cn).astype(np.float32)).astype(dtype)
                 S = rng.random((H, W)) < 0.1
-                m(operand(pkg, "mask", dev(a).reshape(1, Cn, H, W), S, t), dev(z).reshape(1, Cn, 1, 1))
+                m(operand("mask", dev(a).reshape(1, Cn, H, W), S, free_pixel(S) or 0, bool(t % 2)), dev(z).reshape(1, Cn, 1, 1))
                 where = (Cn, R, bias, np.dtype(dtype).name, act, t)
                 s = m._csWork['gate'].cpu().numpy()
                 if act == 'relu':

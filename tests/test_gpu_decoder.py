@@ -16,6 +16,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from test_host_decoder import twin_corner_max, twin_footprint, twin_upsample
+from optest import (dev_words, free_pixel, host_words, hostile_list, lib, pack,      # noqa: F401  (fixtures)
+                    gpu_pkg as pkg, raw, stream)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,45 +28,6 @@ UP_SHAPES = [(1, 1, 1, 8, 8), (5, 3, 32, 1, 2), (5, 4, 13, 2, 5), (3, 5, 23, 3, 
              (1, 1050, 9, 2, 1)]
 UP_STRIDED = (1, 1050, 9, 2, 1)      # more output mask words than workgroups: the grid-stride leg of the word walk
 SENTINEL = 0x5BCD
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
-
-
-def pack(mask):
-    """A bool [H, W] map as the library's row-padded bit mask (uint64 words)."""
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    return np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8').copy()
-
-
-def dev_words(words):
-    return torch.from_numpy(words.view(np.int64)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def raw(t):
-    """The bits of a float tensor."""
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def sel_of(mask):
@@ -79,15 +42,7 @@ def up_struct(lib, sH, sW, mode, align):
 def list_args(changed, useCount):
     """(list, capacity, device count) of an int32 change list: unsorted, with a duplicate and entries outside the map;
     with a device count the buffer holds entries behind it that must not be read."""
-    H, W = changed.shape
-    idx = np.flatnonzero(changed.reshape(-1)).astype(np.int32)[::-1]
-    idx = np.concatenate([idx, idx[:1], np.array([H * W, -1, H * W + 77], dtype=np.int32)])
-    if useCount:
-        free = np.flatnonzero(~changed.reshape(-1))
-        junk = int(free[0]) if len(free) else 0
-        buf = torch.from_numpy(np.concatenate([idx, np.full(5, junk, dtype=np.int32)])).cuda()
-        return buf, buf.numel(), torch.tensor([len(idx)], dtype=torch.int32, device="cuda")
-    return torch.from_numpy(idx.copy()).cuda(), len(idx), None
+    return hostile_list(changed, free_pixel(changed) or 0, useCount)
 
 
 def refresh(t, changed, rng):

@@ -21,18 +21,12 @@ import torch
 import detect_cases as dc
 import refgpu
 from detect_cases import CASES, F16, F32
+from optest import gpu_lib as lib, raw      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 IDS = [c.id for c in CASES]
 GUARD = 64
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
 
 
 def dev(a):
@@ -82,7 +76,7 @@ class Frame(object):
         self.before = rng.integers(0, 2 ** 62, total).astype(np.int64)
         self.pre = [rng.random((H, W)) < 0.04 for _ in range(2)]
         for k in (0, 1):
-            self.before[k * self.nw:(k + 1) * self.nw] = dc.pack_mask(self.pre[k]).view(np.int64)
+            self.before[k * self.nw:(k + 1) * self.nw] = dc.pack(self.pre[k]).view(np.int64)
         self.before[2 * self.nw:2 * self.nw + 1].view(np.int32)[:] = (parity, 0)
         self.g = Guarded(self.before)
 
@@ -300,7 +294,7 @@ def test_compaction_of_a_bit_mask(lib, name, H, W, content):
     C_ = lib.C
     m = dc.compact_mask(H, W, content)
     want = np.flatnonzero(m).astype(np.int32)
-    words = dc.pack_mask(m)
+    words = dc.pack(m)
     bits = dev(words)
     for extras in (False, True):      # with and without the byte map and the cleared other mask
         idx, cnt = Guarded(np.full(H * W, -7, dtype=np.int32)), Guarded(np.array([-1], dtype=np.int32))

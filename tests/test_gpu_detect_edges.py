@@ -20,23 +20,13 @@ import ctypes
 import numpy as np
 import pytest
 import torch
+from optest import dev, gpu_lib as lib, raw      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 H = 5
 WIDTHS = (64, 65, 130)
 TH, BASE, SPIKE = 0.1, 0.25, 1.0      # (all exact in f16)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def pixels(W):

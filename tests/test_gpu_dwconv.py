@@ -25,41 +25,17 @@ import torch.nn.functional as F
 
 import dwconv_cases as dc
 from dwconv_cases import ARITH, CASE_BY_ID, CASES, GEOMS
-from test_gpu_geom import bits_of, footprint, frames_for
+from test_gpu_geom import footprint, frames_for
 from test_gpu_geomconv import Masks
-from test_gpu_listconv import dev, pack_mask, stream
+from test_gpu_listconv import pack_mask
 from test_host_dwconv import cgeom, conv64
+from optest import bits_of, dev, gpu_lib as lib, npdtype, pkg, raw, stream, tdtype      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 FILL = 77.0
 TH = 0.05
 WORST = {}       # dtype -> worst err / mag seen (printed; a measurement, not a bar)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-def tdtype(dtype):
-    return torch.float16 if dtype == "F16" else torch.float32
-
-
-def npdtype(dtype):
-    return np.float16 if dtype == "F16" else np.float32
-
-
-def raw(t):
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
 
 
 def bound_of(dtype, n, want, mag):

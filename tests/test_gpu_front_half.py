@@ -12,21 +12,11 @@ import math
 import numpy as np
 import pytest
 import torch
+from optest import dev, gpu_lib as lib      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 FP32_TOL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 class Layer(object):

@@ -20,6 +20,7 @@ import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from optest import bits_of, dev, npdtype, gpu_pkg as pkg      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,13 +48,6 @@ GEOMS = {
 NAMES = list(GEOMS)
 RING = ("3x3p3", "2x2s2p2", "1x1p64")      # geometries with unreachable output pixels
 DTYPES = [torch.float32, torch.float16]
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
 
 
 def out_size(n, k, s, p, d):
@@ -127,11 +121,6 @@ class Twin(object):
         if self.relu:
             ref = torch.relu(ref)
         return np.flatnonzero(listed.reshape(-1)).astype(np.int32), listed, ref.numpy()
-
-
-def bits_of(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint16)
 
 
 def frames_for(rng, C, Hi, Wi, n, npdtype, th=TH):

@@ -25,29 +25,15 @@ import torch.nn.functional as F
 
 import geomconv_cases as gc
 from geomconv_cases import ARITH, CASE_BY_ID, CASES, case_form, case_out_hw, case_pixels, cell_of
-from test_gpu_geom import GEOMS, Twin, _c_abi_buffers, bits_of, footprint, frames_for, make_conv, out_size
-from test_gpu_listconv import dev, half_tol, pack_mask, stream
+from test_gpu_geom import GEOMS, Twin, _c_abi_buffers, footprint, frames_for, make_conv, out_size
+from test_gpu_listconv import half_tol, pack_mask
+from optest import bits_of, dev, gpu_lib as lib, npdtype, stream, tdtype      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 FILL = 77.0
 TH = 0.05
 WORST = {}       # arithmetic -> worst err / mag seen (printed; a measurement, not a bar)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
-
-
-def tdtype(arith):
-    return torch.float16 if arith == "F16" else torch.float32
-
-
-def npdtype(arith):
-    return np.float16 if arith == "F16" else np.float32
 
 
 class Data(object):

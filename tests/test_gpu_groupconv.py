@@ -24,37 +24,17 @@ import torch.nn.functional as F
 
 import groupconv_cases as gc
 from groupconv_cases import ARITH, CASE_BY_ID, CASES, SHAPES
-from test_gpu_dwconv import Spy, raw
-from test_gpu_geom import GEOMS, Twin, bits_of, footprint, frames_for, out_size
+from test_gpu_dwconv import Spy
+from test_gpu_geom import GEOMS, Twin, footprint, frames_for, out_size
 from test_gpu_geomconv import Masks
-from test_gpu_listconv import dev, half_tol, stream
+from test_gpu_listconv import half_tol
+from optest import bits_of, dev, gpu_lib as lib, npdtype, pkg, raw, stream, tdtype      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 FILL = 77.0
 TH = 0.05
 WORST = {}       # arithmetic -> worst err / mag seen (printed; a measurement, not a bar)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-def tdtype(arith):
-    return torch.float16 if arith == "F16" else torch.float32
-
-
-def npdtype(arith):
-    return np.float16 if arith == "F16" else np.float32
 
 
 def bound_of(arith, Ckkg, want, mag):

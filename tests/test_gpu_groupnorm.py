@@ -13,6 +13,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import groupnorm_cases as gn
+from optest import (chain_frames, dev, free_pixel, host_words, lib, operand,      # noqa: F401  (fixtures)
+                    gpu_pkg as pkg, raw)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,59 +26,12 @@ TH = 0.05       # the threshold of the frame tests
 SHAPES = [(Cn, G, H, W) for (Cn, G) in gn.CASES for (H, W) in gn.MAPS] + [(4, 2, 2100, 9)]
 
 
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def raw(t):
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
 def tdt_of(dtype):
     return torch.float32 if dtype == np.float32 else torch.float16
 
 
 def worst(key, value):
     WORST[key] = max(WORST.get(key, 0.0), float(value))
-
-
-def operand(form, x, listed, t):
-    """The operand a module is handed: bare ('all'), with its mask as a MaskChangeIndexes, or with an int32 list --
-    unsorted, with a duplicate and entries outside the map; on every other frame a ChangeIndexes with a device count in
-    front of entries that must not be read."""
-    from cbinfer_amd.conv2d_cg import ChangeIndexes, MaskChangeIndexes
-    H, W = listed.shape
-    if form == "all":
-        return x
-    if form == "mask":
-        words = torch.from_numpy(gn.pack(listed).view(np.int64)).cuda()
-        return ('changeIndexes', x, MaskChangeIndexes(words, (H, W), torch.empty(H * W, dtype=torch.int32, device="cuda"),
-                                                      torch.zeros(1, dtype=torch.int32, device="cuda")))
-    idx = np.flatnonzero(listed.reshape(-1)).astype(np.int32)[::-1]
-    idx = np.concatenate([idx, idx[:1], np.array([H * W, -1, H * W + 77], dtype=np.int32)])
-    if t % 2:
-        free = np.flatnonzero(~listed.reshape(-1))
-        junk = int(free[0]) if len(free) else 0
-        buf = dev(np.concatenate([idx, np.full(5, junk, dtype=np.int32)]))
-        return ('changeIndexes', x, ChangeIndexes(buf, torch.tensor([len(idx)], dtype=torch.int32, device="cuda"), (H, W)))
-    return ('changeIndexes', x, dev(idx.copy()))
 
 
 def module_for(pkg, Cn, G, aff, relu, threshold, rng):
@@ -158,7 +113,7 @@ def test_frames_equal_the_twin_bit_for_bit(pkg, dtype, form):
             listed = np.ones((H, W), dtype=bool) if form == "all" else S
             holding = np.repeat(~np.isin(np.arange(G), seq[t]), Cn // G)
             x = dev(poisoned(a, listed, holding) if t and form != "all" else a).reshape(1, Cn, H, W)
-            out = m(operand(form, x, S, t))
+            out = m(operand(form, x, S, free_pixel(S) or 0, bool(t % 2)))
             assert type(out) is tuple and out[0] == 'changeIndexes' and out[1].dtype == tdt_of(dtype), where
             assert out[2].size == (H, W) and out[2]._mask is m._gnWork['copy'], where
             P, held, prev, tripped = check_frame(m, a, P, held, prev, listed, t == 0, out[1], where, G, gamma, beta)
@@ -182,7 +137,7 @@ def test_threshold_zero_against_float64(pkg, dtype):
             S = rng.random((H, W)) < 0.1
             if t:
                 a[:, S] = (rng.standard_normal((Cn, int(S.sum()))) * 2).astype(dtype)
-            m(operand("mask", dev(a).reshape(1, Cn, H, W), S, t))
+            m(operand("mask", dev(a).reshape(1, Cn, H, W), S, free_pixel(S) or 0, bool(t % 2)))
             want = reference(a, G, gamma, beta, relu)
             got = m.outputState[0].cpu().numpy().astype(np.float64)
             err, bound = np.abs(got - want), gn.bound(a, G, gn.EPS, gamma, beta, relu)
@@ -211,7 +166,7 @@ def test_large_mean_holds_the_same_bound(pkg):
             S = rng.random((H, W)) < 0.1
             if t:
                 a[:, S] = (1000.0 + rng.standard_normal((Cn, int(S.sum())))).astype(np.float32)
-            m(operand("mask", dev(a).reshape(1, Cn, H, W), S, t))
+            m(operand("mask", dev(a).reshape(1, Cn, H, W), S, free_pixel(S) or 0, bool(t % 2)))
             want = reference(a, G, gamma, beta, False)
             bound = gn.bound(a, G, gn.EPS, gamma, beta, False)
             err = np.abs(m.outputState[0].cpu().numpy().astype(np.float64) - want)
@@ -242,7 +197,7 @@ def test_holding_keeps_unlisted_elements_and_stays_within_the_threshold(pkg, dty
             delta = np.repeat(0.2 * TH * std * (H * W) / S.sum(), Cg)
             a[:, S] = (a[:, S].astype(np.float64) + delta[:, None]).astype(dtype)
             before = m.outputState[0].cpu().numpy().copy()
-            m(operand("mask", dev(a).reshape(1, Cn, H, W), S, t))
+            m(operand("mask", dev(a).reshape(1, Cn, H, W), S, free_pixel(S) or 0, bool(t % 2)))
             where = ((Cn, G, H, W), np.dtype(dtype).name, t)
             assert m.lastTrippedGroups() == [], where
             after = m.outputState[0].cpu().numpy()
@@ -288,22 +243,6 @@ def make_chain(pkg, kind, tdt, threshold, cloneOutput):
     return net, head64
 
 
-def chain_frames(rng, n, npdt, H=12, W=70):
-    """n frames [1, 4, H, W]; a frame differs from the one before in two moved blocks only."""
-    base = (rng.random((1, 4, H, W)) * 2 - 1).astype(npdt)
-    frames = []
-    for i in range(n):
-        new = base.copy()
-        if i:
-            for _ in range(2):
-                y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                blk = new[:, :, y0:y0 + 4, x0:x0 + 7]
-                blk[...] = (rng.random(blk.shape) * 2 - 1).astype(npdt)
-        frames.append(dev(new))
-        base = new
-    return frames
-
-
 @pytest.mark.parametrize("kind", ["gn", "in"])
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16"])
 def test_chain_at_threshold_zero_is_the_dense_network(pkg, dtype, kind):
@@ -319,7 +258,7 @@ def test_chain_at_threshold_zero_is_the_dense_network(pkg, dtype, kind):
     pad = head64.padding
     K = int(head64.weight[0].numel())
     with torch.no_grad():
-        for t, f in enumerate(chain_frames(np.random.default_rng(73), 5, dtype)):
+        for t, f in enumerate(chain_frames(np.random.default_rng(73), 5, dtype, H=12, C=4)):
             y = net(f)
             x = net.stem.prevOutput[0].cpu().numpy()
             want = reference(x, norm.num_groups, gamma, beta, norm.relu)
@@ -346,7 +285,7 @@ def test_chain_records_as_a_launch_program(pkg, lib, dtype, kind):
     cbinfer_cbgroupnorm_forward --, four replayed frames equal the eager network in outputs and in every state, held and
     partials included, bit for bit."""
     net, _ = make_chain(pkg, kind, tdt_of(dtype), 0.01, False)
-    frames = chain_frames(np.random.default_rng(79), 8, dtype)
+    frames = chain_frames(np.random.default_rng(79), 8, dtype, H=12, C=4)
     with torch.no_grad():
         for f in frames[:4]:
             net(f)

@@ -8,15 +8,9 @@ import numpy as np
 import pytest
 import torch
 import torch.nn as nn
+from optest import gpu_pkg as pkg      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
 
 
 def video(rng, C, H, W, n, frac, blk=6):

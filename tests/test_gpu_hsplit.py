@@ -54,8 +54,8 @@ import torch
 import hsplit_cases as hc
 from hsplit_cases import CASES, CASE_BY_ID, TH, cell_of
 from test_gpu_detect_edges import pool2
-from test_gpu_split import dev
 from test_gpu_splitconv import cus, mask_bits, reference
+from optest import dev, gpu_lib as lib, raw      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -65,13 +65,6 @@ RAN = set()       # ids of the cases whose frames test ran to its end
 IDS = [c.id for c in CASES]
 # (bias, relu): bias alone (no output clamped: every one tells of the arithmetic), ReLU alone, neither
 EPILOGUES = [(True, False), (False, True), (False, False)]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
 
 
 def bits16(a):

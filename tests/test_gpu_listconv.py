@@ -15,6 +15,7 @@ import torch
 
 from listconv_cases import (ACCUMULATE_IDS, ARITH, CASE_BY_ID, CASES, CLEAR_BITS_IDS, OUT_OF_MAP_IDS, case_form,
                             case_pixels, cell_of, list_form)
+from optest import dev, np_dtype, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -40,18 +41,6 @@ def lib():
 
 def cus():
     return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def np_dtype(dtype):
-    return np.float16 if dtype == "F16" else np.float32
 
 
 def make_tensors(seed, dtype, K, C, kH, kW, H, W):

@@ -47,6 +47,7 @@ import torch
 
 import maskconv_cases as mc
 from maskconv_cases import CASES, CASE_BY_ID
+from optest import dev, gpu_lib as lib, pack      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -63,13 +64,6 @@ SLOT_IDS = [c.id for c in CASES if "slots" in dict(c.opt)]
 assert len(PLAIN_IDS) + len(PAIR_IDS) + len(DET_IDS) + len(SLOT_IDS) == len(CASES)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
-
-
 def cus():
     return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
 
@@ -78,18 +72,6 @@ def assert_claimed_cell(c):
     got = mc.case_cell(c, cus())
     assert got == c.cell, ("%s: on a card with %d CUs this shape lands in %s, not in the cell %s it was written for"
                            % (c.id, cus(), got, c.cell))
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def pack_mask(m):
-    H, W = m.shape
-    wpr = (W + 63) // 64
-    bits = np.zeros((H, wpr * 64), np.uint8)
-    bits[:, :W] = m
-    return np.packbits(bits, axis=1, bitorder="little").view(np.int64).reshape(-1)
 
 
 def unpack_mask(words, H, W):
@@ -152,7 +134,7 @@ class Seq(object):
         H, W = mask.shape
         words = H * ((W + 63) // 64)
         self.state, self.out = dev(state), dev(out0)
-        self.bits = dev(pack_mask(mask))
+        self.bits = dev(pack(mask).view(np.int64))
         self.arrive = torch.zeros(words, dtype=torch.int32, device="cuda")
         self.copy = torch.full((words,), -1, dtype=torch.int64, device="cuda")
         self.relu = dev(relu0) if relu0 is not None else None
@@ -373,7 +355,7 @@ def run_config(lib, c, d, wq, bias, relu, masks=None, check=True, fold_rng=None,
             rest = np.ones(H * W, bool)
             rest[idx] = False
             assert np.array_equal(now[:, rest].view(np.int32), before[:, rest].view(np.int32)), what
-        assert np.array_equal(s.copy.cpu().numpy(), pack_mask(masks[q])), what + ": the mask copy"
+        assert np.array_equal(s.copy.cpu().numpy(), pack(masks[q]).view(np.int64)), what + ": the mask copy"
         assert int(s.bits.abs().sum().item()) == 0 and int(s.arrive.abs().sum().item()) == 0, what
         if s.relu is not None:
             r = s.relu.cpu().numpy().reshape(K, -1)
@@ -506,7 +488,7 @@ def test_rowpairs_with_their_own_detection_against_float64(lib, oracle, cid):
         y, mag = d.ref[0]
         check_outputs(c, what, now, d.out0[0].reshape(K, -1), d.idx[0], y, mag,
                       d.b.astype(np.float64)[None] if bias else None, relu)
-        assert np.array_equal(s.copy.cpu().numpy(), pack_mask(mask)), what + ": the mask copy"
+        assert np.array_equal(s.copy.cpu().numpy(), pack(mask).view(np.int64)), what + ": the mask copy"
         assert np.array_equal(s.state.cpu().numpy(), state0), what + ": the state is refreshed by a later launch"
         if fold:
             a, b = check_fold(lib, c, what, s, mask, now.reshape(K, H, W))

@@ -7,17 +7,11 @@ import numpy as np
 import pytest
 import torch
 import torch.nn as nn
+from optest import gpu_pkg as pkg      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 FP32_TOL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer          # the drop-in alias
-    assert torch.cuda.is_available()
-    return pycbinfer
 
 
 def golden_net(d, k):

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 import torch
+from optest import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +23,6 @@ def cb():
     from cbinfer_amd import conv2d_cg, conv2d_fg
     assert torch.cuda.is_available()
     return cbinfer_amd, conv2d_cg, conv2d_fg
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def rand_case(rng, C, H, W, frac, th=0.1, blocks=False):

@@ -19,27 +19,15 @@ import torch.nn.functional as F
 
 import pad_cases as pc
 from rearrange_cases import special_values
-from test_gpu_decoder import SENTINEL, dev_words, host_words, input_frames, list_args, pack, raw, refresh, sel_of, stream
+from test_gpu_decoder import SENTINEL, input_frames, list_args, refresh, sel_of
 from test_gpu_geom import bound_for
 from test_gpu_rearrange import net_frames
+from optest import dev_words, host_words, lib, pack, gpu_pkg as pkg, raw, stream      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float32, torch.float16]
 VALUE = -3.5      # of the constant-mode cases: a border that is not the zero of a fresh buffer
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 def torch_pad(mode, pads, x, value=VALUE):

@@ -13,24 +13,13 @@ import torch.nn.functional as F
 
 import peaks_cases as pc
 from peaks_cases import DTYPES, FORMS, SHAPES, WINDOW_IDS, WINDOWS
+from optest import (dev, dev_words, free_pixel, host_words, lib, operand_args,      # noqa: F401  (fixtures)
+                    gpu_pkg as pkg, raw, stream)
 
 pytestmark = pytest.mark.gpu
 
 # a state no result has: NaNs (a suppressed map holds none)
 FILL = {"f32": 0x7fc12345, "f16": 0x7e55}
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 @pytest.fixture(scope="module")
@@ -48,44 +37,9 @@ def walks():
     return get
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def dev_words(words):
-    return torch.from_numpy(words.view(np.int64)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def peaks_struct(lib, window):
     kH, kW, cross, floor = WINDOWS[window]
     return lib.Peaks(kH, kW, cross, int(floor is not None), floor or 0.0)
-
-
-def operand_args(form, S, L, t):
-    """(mask, list, capacity, device count) of cbinfer_cbpeaks_forward.  List form: unsorted, with a duplicate and
-    entries outside the map; on every other frame with a device count in front of junk -- a pixel outside the
-    footprint L, where there is one -- that must not be read."""
-    H, W = S.shape
-    if form == "all":
-        return None, None, 0, None
-    if form == "mask":
-        return dev_words(pc.pack(S)), None, 0, None
-    idx = np.flatnonzero(S.reshape(-1)).astype(np.int32)[::-1]
-    idx = np.concatenate([idx, idx[:1], np.array([H * W, -1, H * W + 77], dtype=np.int32)])
-    if t % 2:
-        free = np.flatnonzero(~L.reshape(-1))
-        junk = int(free[len(free) // 2]) if len(free) else 0
-        buf = dev(np.concatenate([idx, np.full(5, junk, dtype=np.int32)]))
-        return None, buf, buf.numel(), torch.tensor([len(idx)], dtype=torch.int32, device="cuda")
-    return None, dev(idx.copy()), len(idx), None
 
 
 class State(object):
@@ -116,7 +70,8 @@ class State(object):
         lib, ptr = self.lib, self.lib.ptr
         Cn, H, W = self.shape
         L = pc.listed(S, self.window, form)
-        mask, lst, cap, cnt = operand_args(form, S, L, t)
+        # (every other frame: a device count in front of junk -- a pixel outside the footprint L, where there is one)
+        mask, lst, cap, cnt = operand_args(form, S, free_pixel(L, middle=True) or 0, bool(t % 2))
         self.x = dev(x)
         self.entries.fill_(-7)
         code = lib.CB_F32 if self.dtype == "f32" else lib.CB_F16
@@ -271,10 +226,6 @@ def same_state_and_list(a, b):
     n = int(ca.item())
     return bool(torch.equal(ca, cb) and torch.equal(fa, fb) and torch.equal(ea[:n], eb[:n]) and
                 torch.equal(raw(sa[:n]), raw(sb[:n])))
-
-
-def raw(t):
-    return t.view({torch.float32: torch.int32, torch.float16: torch.int16}.get(t.dtype, t.dtype))
 
 
 def unpack(words, H, W):

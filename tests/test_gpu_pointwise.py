@@ -11,105 +11,38 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import pointwise_cases as pc
+from optest import (chain_frames, dev, dev_words, host_words, LayerSpy, lib,      # noqa: F401  (fixtures)
+                    operand_args, gpu_pkg as pkg, raw, share_of, stream, walk_frames)
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [np.float32, np.float16]
 WORST = {}      # (kind name, dtype name) -> worst err / |ref| seen against float64
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def dev_words(words):
-    return torch.from_numpy(words.view(np.int64)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def operand_args(form, changed, t, junk=0):
-    """(mask, list, capacity, device count) of cbinfer_cbpointwise_forward; the tensors are kept alive by the caller.
-    List form: unsorted, with a duplicate and entries outside the map; on every other frame with a device count in
-    front of entries (`junk`, a pixel that is not listed) that must not be read."""
-    H, W = changed.shape
-    if form == "all":
-        return None, None, 0, None
-    if form == "mask":
-        return dev_words(pc.pack(changed)), None, 0, None
-    idx = np.flatnonzero(changed.reshape(-1)).astype(np.int32)[::-1]
-    idx = np.concatenate([idx, idx[:1], np.array([H * W, -1, H * W + 77], dtype=np.int32)])
-    if t % 2:
-        buf = dev(np.concatenate([idx, np.full(5, junk, dtype=np.int32)]))
-        return None, buf, buf.numel(), torch.tensor([len(idx)], dtype=torch.int32, device="cuda")
-    return None, dev(idx.copy()), len(idx), None
-
-
 FILL = {np.float32: 0x5BCD5BCD, np.float16: 0x5BCD}
 
 
 def run_frames(lib, shape, dtype, form, kind, p0, p1, affine, rng, check, span=8.0, special=None):
     """The six mask patterns as consecutive frames through cbinfer_cbpointwise_forward.  Before every frame x gets new
     values at the frame's pixels AND at one pixel outside them; check(x, out at the listed pixels [C, n], where) judges
-    the values; unlisted pixels must keep their bits, maskCopy be the frame's mask, the working mask zero."""
+    the values; unlisted pixels must keep their bits, maskCopy be the frame's mask, the working mask zero: the walk of
+    optest.walk_frames, the per-channel parameters drawn in front of it."""
     C, ptr = lib.C, lib.ptr
     Cn, H, W = shape
-    words = C.cbinfer_mask_words(H, W)
-    assert words == H * ((W + 63) // 64)
     scale, shift, slope = pc.per_channel(rng, Cn)
     dscale, dshift, dslope = (dev(v) for v in (scale, shift, slope))
-    x = pc.values(rng, shape, dtype, span, special)
     out = np.empty(shape, dtype=dtype)
     pc.bits_of(out)[...] = FILL[dtype] & (0xFFFFFFFF if dtype == np.float32 else 0xFFFF)
-    dout = dev(out)
-    bits = torch.zeros(words, dtype=torch.int64, device="cuda")
-    mcopy = torch.full((words,), -1, dtype=torch.int64, device="cuda")
-    sawUnlisted = 0
-    for t, (label, S) in enumerate(pc.patterns(rng, H, W)):
-        where = (shape, np.dtype(dtype).name, form, pc.NAMES[kind], affine, label)
-        fresh = pc.values(rng, shape, dtype, span, special)
-        x[:, S] = fresh[:, S]
-        free = np.flatnonzero(~S.reshape(-1))
-        p = 0
-        if len(free):      # an operand altered where the list does not say so: a dense operator would pick it up
-            p = int(free[len(free) // 2])
-            x[:, p // W, p % W] = fresh[:, p // W, p % W]
-        listed = np.ones((H, W), dtype=bool) if form == "all" else S
-        dx = dev(x)
-        mask, lst, cap, cnt = operand_args(form, S, t, p)
-        st = C.cbinfer_cbpointwise_forward(ptr(dx), ptr(dout), ptr(mask), ptr(lst), cap, ptr(cnt), ptr(bits), ptr(mcopy),
-                                           Cn, H, W, kind, p0, p1, ptr(dscale) if affine else None,
-                                           ptr(dshift) if affine else None, ptr(dslope) if kind == pc.PRELU else None,
-                                           lib.CB_F32 if dtype == np.float32 else lib.CB_F16, stream())
-        assert st == 0, where
-        got = dout.cpu().numpy()
+
+    def call(dx, dout, mask, lst, cap, cnt, bits, mcopy):
+        return C.cbinfer_cbpointwise_forward(ptr(dx), ptr(dout), ptr(mask), ptr(lst), cap, ptr(cnt), ptr(bits), ptr(mcopy),
+                                             Cn, H, W, kind, p0, p1, ptr(dscale) if affine else None,
+                                             ptr(dshift) if affine else None, ptr(dslope) if kind == pc.PRELU else None,
+                                             lib.CB_F32 if dtype == np.float32 else lib.CB_F16, stream())
+
+    def judge(x, got, listed, where):
         check(x, got, listed, where, scale if affine else None, shift if affine else None, slope)
-        assert np.array_equal(pc.bits_of(got)[:, ~listed], pc.bits_of(out)[:, ~listed]), where
-        if len(free) and not listed.all():
-            sawUnlisted += 1
-        assert np.array_equal(host_words(mcopy), pc.pack(listed)), where
-        assert int(bits.ne(0).sum().item()) == 0, where
-        out = got
-    return sawUnlisted
+    return walk_frames(lib, shape, dtype, form, lambda: pc.patterns(rng, H, W), call, judge, out,
+                       lambda: pc.values(rng, shape, dtype, span, special), what=(pc.NAMES[kind], affine))
 
 
 @pytest.mark.parametrize("form", pc.FORMS)
@@ -206,7 +139,7 @@ def test_a_pixel_does_not_depend_on_the_list_the_form_or_the_run(lib, dtype):
                 dout = torch.zeros((Cn, H, W), dtype=dx.dtype, device="cuda")
                 bits = torch.zeros(words, dtype=torch.int64, device="cuda")
                 mcopy = torch.zeros(words, dtype=torch.int64, device="cuda")
-                mask, lst, cap, cnt = operand_args(form, S, rep)
+                mask, lst, cap, cnt = operand_args(form, S, 0, bool(rep % 2))
                 st = C.cbinfer_cbpointwise_forward(ptr(dx), ptr(dout), ptr(mask), ptr(lst), cap, ptr(cnt), ptr(bits),
                                                    ptr(mcopy), Cn, H, W, kind, p0, p1, ptr(dscale), ptr(dshift),
                                                    ptr(dslope) if kind == pc.PRELU else None,
@@ -277,7 +210,7 @@ def test_module_forms_flags_and_errors(pkg, lib, dtype):
         empty = torch.zeros(0, dtype=torch.int32, device="cuda")
         tag, y, ix = m(('changeIndexes', dev(x)[None], empty))      # first frame
         assert tag == 'changeIndexes' and pc.same_bits(m.outputState[0].cpu().numpy(), module_twin(m, x))
-        assert y is not m.outputState and torch.equal(pc_raw(y), pc_raw(m.outputState))
+        assert y is not m.outputState and torch.equal(raw(y), raw(m.outputState))
         assert isinstance(ix, MaskChangeIndexes) and ix.size == (H, W) and not ix._made
         assert ix.tensor().numel() == H * W
         for t in range(4):
@@ -340,16 +273,11 @@ def test_module_forms_flags_and_errors(pkg, lib, dtype):
                 copy.deepcopy(m).cpu()(dx)
         before = m.outputState.clone()
         torch.cuda.synchronize()
-        assert torch.equal(pc_raw(m.outputState), pc_raw(before))
+        assert torch.equal(raw(m.outputState), raw(before))
         m.clearMemory()
         assert m.outputState.numel() == 0 and m._pwWork is None
         out = m(dx)
         assert pc.same_bits(out[0].cpu().numpy(), module_twin(m, x2))
-
-
-def pc_raw(t):
-    """The bits of a float tensor."""
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
 
 
 # ------------------------------------------------------------------------------------------------ a MobileNetV3-type chain
@@ -406,41 +334,6 @@ def link_chain(pkg, net, cloneOutput):
     return net
 
 
-def chain_frames(rng, n, npdt, H=20, W=70):
-    """n frames [1, 8, H, W]; a frame differs from the one before in two moved blocks only."""
-    base = (rng.random((1, 8, H, W)) * 2 - 1).astype(npdt)
-    frames = []
-    for i in range(n):
-        new = base.copy()
-        if i:
-            for _ in range(2):
-                y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                blk = new[:, :, y0:y0 + 4, x0:x0 + 7]
-                blk[...] = (rng.random(blk.shape) * 2 - 1).astype(npdt)
-        frames.append(dev(new))
-        base = new
-    return frames
-
-
-class LayerSpy(object):
-    """Notes the library calls made while each named layer runs (the library object's attributes are read-only
-    function pointers)."""
-
-    def __init__(self, real):
-        self.__dict__.update(real=real, calls={}, layer=[None])
-
-    def __getattr__(self, name):
-        fn = getattr(self.real, name)
-        if not getattr(fn, 'launcher', False):
-            return fn
-
-        def counted(*a):
-            per = self.calls.setdefault(self.layer[0], {})
-            per[name] = per.get(name, 0) + 1
-            return fn(*a)
-        return counted
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f16"])
 def test_chain_equals_the_chain_with_dense_activations(pkg, lib, dtype, monkeypatch):
     """Six frames: the chain with CBPointwise2d modules against the same chain -- a deep copy made before the first
@@ -470,15 +363,15 @@ def test_chain_equals_the_chain_with_dense_activations(pkg, lib, dtype, monkeypa
             y = net(f)
             spy.layer[0] = 'dense'
             yd = dense(f)
-            assert tuple(y.shape) == (1, 8, 20, 70) and torch.equal(pc_raw(y), pc_raw(yd)), t
+            assert tuple(y.shape) == (1, 8, 20, 70) and torch.equal(raw(y), raw(yd)), t
             for name in ('hs', 'bn'):
                 state = getattr(net, name).outputState
                 src = net.expand.prevOutput if name == 'hs' else net.dw.prevOutput
                 ref = module_twin(getattr(net, name), src[0].cpu().numpy())
                 assert pc.same_bits(state[0].cpu().numpy(), ref), (name, t)
-            assert torch.equal(pc_raw(net.dw.prevOutput), pc_raw(dense.dw.prevOutput)), t
-            assert torch.equal(pc_raw(net.project.prevOutput), pc_raw(dense.project.prevOutput)), t
-            share.append(float(np.unpackbits(host_words(net.bn._pwWork['copy']).view(np.uint8)).sum()) / (20 * 70))
+            assert torch.equal(raw(net.dw.prevOutput), raw(dense.dw.prevOutput)), t
+            assert torch.equal(raw(net.project.prevOutput), raw(dense.project.prevOutput)), t
+            share.append(share_of(net.bn._pwWork['copy'], 20, 70))
     for h in hooks:
         h.remove()
     print("listed share per frame:", ["%.2f" % s for s in share], {k: v for k, v in spy.calls.items() if k != 'dense'})
@@ -503,7 +396,7 @@ def test_chain_records_as_a_launch_program(pkg, lib, dtype):
         prog = pkg.FrameProgram(net)
         for t, f in enumerate(frames[4:]):
             yp, ye = prog(f), eager(f)
-            assert torch.equal(pc_raw(yp), pc_raw(ye)), t
+            assert torch.equal(raw(yp), raw(ye)), t
             for ta, tb in zip(pkg.getStateTensors(net), pkg.getStateTensors(eager)):
                 assert torch.equal(ta, tb), t
         raws = [fn for fn, _ in prog.calls]

@@ -16,6 +16,8 @@ import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from optest import (bits_of, dev_words, host_words, lib, npdtype, pack, gpu_pkg as pkg,      # noqa: F401  (fixtures)
+                    stream)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,19 +40,6 @@ WINDOWS = {
 STRIDED = ("2x2s2p0", (4200, 9))      # 2100 output mask words, more than workgroups: the grid-stride leg of the kernel
 NAMES = list(WINDOWS)
 OPS = ["max", "avg_pad", "avg_nopad"]
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 # ------------------------------------------------------------------------------------------------ the twin
@@ -106,37 +95,10 @@ def cpu_pool(x, win, op):
     return F.avg_pool2d(x, k, s, p, ceil_mode=ceil, count_include_pad=(op == "avg_pad"))
 
 
-def pack(mask):
-    """A bool [H, W] map as the library's row-padded bit mask (uint64 words, int64 tensor on the device)."""
-    H, W = mask.shape
-    wpr = (W + 63) // 64
-    pad = np.zeros((H, wpr * 64), dtype=bool)
-    pad[:, :W] = mask
-    words = np.packbits(pad.reshape(H, wpr, 64), axis=-1, bitorder='little').reshape(-1).view('<u8')
-    return words.copy()
-
-
-def dev_words(words):
-    return torch.from_numpy(words.view(np.int64)).cuda()
-
-
-def host_words(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def bits_of(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint16)
-
-
 def pool_struct(lib, win, op="max"):
     (kH, kW), (sH, sW), (pH, pW), ceil = win
     code = {"max": lib.POOL_MAX, "avg_pad": lib.POOL_AVG_PAD, "avg_nopad": lib.POOL_AVG_NOPAD}[op]
     return lib.Pool(kH, kW, sH, sW, pH, pW, int(ceil), code)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ------------------------------------------------------------------------------------------------ launch 1

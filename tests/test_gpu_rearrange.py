@@ -17,24 +17,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import rearrange_cases as rc
-from test_gpu_decoder import SENTINEL, dev_words, host_words, input_frames, list_args, pack, raw, refresh, sel_of, stream
+from test_gpu_decoder import SENTINEL, input_frames, list_args, refresh, sel_of
+from optest import dev_words, host_words, lib, pack, gpu_pkg as pkg, raw, stream      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float32, torch.float16]
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 def torch_op(kind, f, x):

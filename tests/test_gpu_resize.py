@@ -15,7 +15,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import resize_cases as rc
-from test_gpu_decoder import SENTINEL, dev_words, host_words, input_frames, list_args, pack, raw, refresh, sel_of, stream
+from test_gpu_decoder import SENTINEL, input_frames, list_args, refresh, sel_of
+from optest import bits_of, dev_words, host_words, lib, pack, gpu_pkg as pkg, raw, stream      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,25 +28,8 @@ def case_id(c):
     return rc.shape_id(c[:5]) if c[5] is None else "%dx%dx%d-by-%s" % (c[:3] + (c[5],))
 
 
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    assert torch.cuda.is_available()
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
-
-
 def struct_of(lib, rs):
     return ctypes.pointer(lib.Resize(*rs))
-
-
-def bits_of(a):
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint16)
 
 
 def host(t):

@@ -9,29 +9,11 @@ import numpy as np
 import pytest
 import torch
 import torch.nn as nn
+from optest import dev, gpu_lib as lib, pack      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 FP32_TOL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def pack_mask(m):
-    H, W = m.shape
-    wpr = (W + 63) // 64
-    bits = np.zeros((H, wpr * 64), np.uint8)
-    bits[:, :W] = m
-    return np.packbits(bits, axis=1, bitorder="little").view(np.int64).reshape(-1)
 
 
 @pytest.mark.parametrize("C,K,k,H,W", [(3, 16, 7, 64, 96), (3, 16, 7, 37, 131), (4, 16, 3, 45, 70), (1, 9, 5, 20, 64),
@@ -57,12 +39,12 @@ def test_rowpairs_contraction_vs_oracle(lib, oracle, C, K, k, H, W):
     wp = torch.empty(C_.cbinfer_rowconv_prepared_bytes(C, K, k, k), dtype=torch.uint8, device="cuda")
     lib.check(C_.cbinfer_rowconv_prep_weights(dev(w).data_ptr(), wp.data_ptr(), K, C, k, k, None))
     words = C_.cbinfer_mask_words(H, W)
-    bits, copy = dev(pack_mask(m)), torch.zeros(words, dtype=torch.int64, device="cuda")
+    bits, copy = dev(pack(m).view(np.int64)), torch.zeros(words, dtype=torch.int64, device="cuda")
     ctl = torch.zeros(words, dtype=torch.int32, device="cuda")
     out0 = rng.standard_normal((1, K, H, W)).astype(np.float32)
     out, xd, bd = dev(out0), dev(x), dev(b)
     for relu in (0, 1):
-        bits.copy_(dev(pack_mask(m)))
+        bits.copy_(dev(pack(m).view(np.int64)))
         out.copy_(dev(out0))
         lib.check(C_.cbinfer_conv_changed_rowpairs(xd.data_ptr(), bits.data_ptr(), ctl.data_ptr(), copy.data_ptr(),
                                                    wp.data_ptr(), bd.data_ptr(), out.data_ptr(), C, H, W, K, k, k, relu,
@@ -77,7 +59,7 @@ def test_rowpairs_contraction_vs_oracle(lib, oracle, C, K, k, H, W):
         keep[idx] = False
         assert np.array_equal(got.reshape(K, -1)[:, keep], out0.reshape(K, -1)[:, keep])
         assert int(bits.abs().sum().item()) == 0 and int(ctl.abs().sum().item()) == 0
-        assert np.array_equal(copy.cpu().numpy(), pack_mask(m))
+        assert np.array_equal(copy.cpu().numpy(), pack(m).view(np.int64))
     # an empty mask: nothing happens (and the kernel exits cleanly)
     lib.check(C_.cbinfer_conv_changed_rowpairs(xd.data_ptr(), bits.data_ptr(), ctl.data_ptr(), copy.data_ptr(),
                                                wp.data_ptr(), bd.data_ptr(), out.data_ptr(), C, H, W, K, k, k, 0, None,

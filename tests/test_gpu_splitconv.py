@@ -27,7 +27,8 @@ import torch
 
 import splitconv_cases as sc
 from splitconv_cases import CASES, CASE_BY_ID, case_form, cell_of
-from test_gpu_split import Layer, dev
+from test_gpu_split import Layer
+from optest import dev, gpu_lib as lib      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -42,13 +43,6 @@ CONV_IDS = [c.id for c in CASES if c.mode == "conv"]
 TAIL_IDS = [c.id for c in CASES if c.mode == "tail"]
 FG_IDS = [c.id for c in CASES if c.mode == "fg"]
 assert len(CONV_IDS) + len(TAIL_IDS) + len(FG_IDS) == len(CASES)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
 
 
 def cus():

@@ -23,7 +23,8 @@ import pytest
 import torch
 
 import test_gpu_tail_waves as W
-from test_gpu_split import Layer, dev
+from test_gpu_split import Layer
+from optest import dev, gpu_lib as lib      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -72,13 +73,6 @@ FG_CASE = W.Case(1, 64, 256, 8, 17)
 def digest(a):
     a = np.ascontiguousarray(a)
     return hashlib.sha256(str(a.dtype).encode() + str(a.shape).encode() + a.tobytes()).hexdigest()
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
 
 
 @pytest.fixture(scope="module")

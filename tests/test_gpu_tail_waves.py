@@ -26,7 +26,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_split import Layer, dev
+from test_gpu_split import Layer
+from optest import dev, gpu_lib as lib      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -72,13 +73,6 @@ assert {tail_form(c)[0] for c in CASES} == {1, 2, 3, 4, 5, 8}
 assert {tail_form(c)[1] for c in CASES} == {1, 2, 4} and any(tail_form(c)[2] for c in CASES)
 FG_CASE = Case(1, 64, 256, 8, 130)            # (bias 0, relu 0: the fine-grained frame has neither)
 GOLDEN_NAME = "tail_waves.npz"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
 
 
 @pytest.fixture(scope="module")

@@ -25,37 +25,17 @@ import torch.nn.functional as F
 
 import tconv_cases as tc
 from tconv_cases import ARITH, CASE_BY_ID, CASES, case_form, case_out_hw, case_pixels, case_tags
-from test_gpu_geom import bits_of, footprint as geom_footprint, frames_for
+from test_gpu_geom import footprint as geom_footprint, frames_for
 from test_gpu_geomconv import Masks, detection_frame
-from test_gpu_listconv import dev, half_tol, pack_mask, stream
+from test_gpu_listconv import half_tol, pack_mask
 from test_host_tconv import tgeom, twin_footprint, twin_reachable
+from optest import bits_of, dev, gpu_lib as lib, npdtype, pkg, raw, stream, tdtype      # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 FILL = 77.0
 TH = 0.05
 WORST = {}       # arithmetic -> worst err / mag seen (printed; a measurement, not a bar)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    assert torch.cuda.is_available()
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-def tdtype(arith):
-    return torch.float16 if arith == "F16" else torch.float32
-
-
-def npdtype(arith):
-    return np.float16 if arith == "F16" else np.float32
 
 
 def tconv64(x, w, b, geom):
@@ -542,10 +522,6 @@ def stage_frames(n, seed):
             base[:, :, y0:y0 + 5, x0:x0 + 9] = rng.random(base[:, :, y0:y0 + 5, x0:x0 + 9].shape) * 0.9
         out.append(torch.from_numpy(base.astype(np.float32)).cuda())
     return out
-
-
-def raw(t):
-    return t.view(torch.int32)
 
 
 def test_decoder_stage_records_as_a_launch_program(pkg, lib):

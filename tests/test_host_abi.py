@@ -6,6 +6,7 @@ import os
 import subprocess
 
 import pytest
+from optest import lib, raw      # noqa: F401  (fixtures)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,12 +25,6 @@ template <class R, class... A> constexpr bool sig(R (*)(A...), const char* kinds
     return same(is, kinds);
 }
 """
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 def kind(t):

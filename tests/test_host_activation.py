@@ -12,18 +12,7 @@ import torch.nn.functional as F
 
 import activation_cases as ac
 from test_host_chanreduce import LayerNorm2d, _names
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 
 def test_float64_formulas_are_torchs_operators():

@@ -14,18 +14,7 @@ import torch.nn.functional as F
 
 import adaptpool_cases as ac
 from adaptpool_cases import CASE_IDS, CASES, DTYPES
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 
 def torch_pool(x, size, op):

@@ -13,18 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import binary_cases as bc
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, names_of, pkg      # noqa: F401  (fixtures)
 
 
 # ------------------------------------------------------------------------------------------------ the twin
@@ -274,10 +263,6 @@ def test_exports_state_helpers_pickle_and_deepcopy(pkg, lib):
 
 
 # ------------------------------------------------------------------------------------------------ wiring
-def names_of(net):
-    return [type(m).__name__ for m in net]
-
-
 def test_insert_gating_wiring_and_what_it_leaves(pkg, lib):
     torch.manual_seed(1)
     seq = nn.Sequential(nn.Conv2d(3, 8, 3, padding=1), nn.GLU(1), nn.Conv2d(4, 8, 1), nn.GLU(-3), nn.Conv2d(4, 6, 3, padding=1),

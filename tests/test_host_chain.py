@@ -9,12 +9,7 @@ import torch
 import torch.nn as nn
 
 import chain_cases as cc
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
+from optest import pkg      # noqa: F401  (fixtures)
 
 
 @pytest.fixture(scope="module")

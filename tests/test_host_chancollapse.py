@@ -11,18 +11,7 @@ import torch.nn as nn
 
 import chancollapse_cases as cc
 import chanreduce_cases as cr
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 
 class ChannelPool(nn.Module):

@@ -14,18 +14,7 @@ import torch.nn.functional as F
 
 import chain_cases
 import chanscale_cases as cs
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, names_of, pkg      # noqa: F401  (fixtures)
 
 
 class SE(nn.Module):
@@ -323,10 +312,6 @@ def test_the_chain_tables_are_as_they_were(pkg):
 
 
 # ------------------------------------------------------------------------------------------------ wiring
-def names_of(net):
-    return [type(m).__name__ for m in net]
-
-
 def test_insert_squeeze_excite_wiring_and_what_it_leaves(pkg, lib):
     torch.manual_seed(1)
     seq = nn.Sequential(nn.Conv2d(3, 8, 3, padding=1), SE(8, 2), nn.Conv2d(8, 8, 1), SE(8, 4, nn.SiLU, nn.Hardsigmoid, True),

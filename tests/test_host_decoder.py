@@ -10,18 +10,7 @@ import numpy as np
 import pytest
 import torch
 import torch.nn as nn
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 
 # ------------------------------------------------------------------------------------------------ the twin

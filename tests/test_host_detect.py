@@ -43,7 +43,7 @@ def test_constants_are_the_librarys():
     assert (_lib.CB_OK, _lib.CB_ERR_BADARG, _lib.CB_ERR_UNSUPPORTED) == (dc.OK, dc.BADARG, dc.UNSUPPORTED)
     assert (_lib.CB_F32, _lib.CB_F16) == (dc.CODE[F32], dc.CODE[F16])
     for H, W in dc.SIZES:
-        assert _lib.C.cbinfer_mask_words(H, W) == dc.pack_mask(np.zeros((H, W), dtype=bool)).size
+        assert _lib.C.cbinfer_mask_words(H, W) == dc.pack(np.zeros((H, W), dtype=bool)).size
 
 
 def test_classifier_on_the_named_channel_counts():
@@ -224,14 +224,14 @@ def test_every_window_position_decides_somewhere():
 # the other kernels' rules
 # ---------------------------------------------------------------------------------------------------------------------
 def test_compaction_rule_and_masks(oracle):
-    words = {name: dc.pack_mask(dc.compact_mask(H, W, "full")).size for name, H, W in dc.COMPACT_MASKS}
+    words = {name: dc.pack(dc.compact_mask(H, W, "full")).size for name, H, W in dc.COMPACT_MASKS}
     assert [words[n] for n in ("1w", "63w", "64w", "65w", "130w")] == [1, 63, 64, 65, 130]
     assert words["1920w"] > 1856 and words["3968w"] > 3904      # one and two rounds of the eight-deep prefix loop
     for name, H, W in dc.COMPACT_MASKS:
         for content in dc.COMPACT_CONTENTS:
             m = dc.compact_mask(H, W, content)
             assert np.array_equal(oracle.changeIndexesExtr(m.astype(np.int8)), np.flatnonzero(m)), (name, content)
-            back = dc.unpack_mask(dc.pack_mask(m), H, W)
+            back = dc.unpack_mask(dc.pack(m), H, W)
             assert np.array_equal(back[:, :W], m) and not back[:, W:].any()
     assert dc.compact_mask(2, 4150, "last-bit").sum() == 1
 

@@ -15,18 +15,7 @@ import torch.nn.functional as F
 
 import dwconv_cases as dc
 from dwconv_cases import CASES, GEOMS
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 
 def cgeom(lib, geom):

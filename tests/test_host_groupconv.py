@@ -16,21 +16,10 @@ import torch.nn as nn
 
 import groupconv_cases as gc
 from groupconv_cases import CASES, SHAPES
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "cbinfer_amd", "csrc")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 def cgeom(lib, geom):

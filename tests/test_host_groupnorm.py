@@ -12,18 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import groupnorm_cases as gn
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, names_of, pkg      # noqa: F401  (fixtures)
 
 
 def torch64(a, G, gamma, beta, relu, instance=False):
@@ -317,10 +306,6 @@ def test_exports_state_helpers_pickle_and_deepcopy(pkg, lib):
         assert m.outputState.numel() == 0 and m.held.numel() == 0 and m.partials.numel() == 0 and m._gnWork is None
         assert m.held.dtype == torch.float32 and m.partials.dtype == torch.float64
     assert a.gamma.numel() == 4      # (the affine is no state)
-
-
-def names_of(net):
-    return [type(m).__name__ for m in net]
 
 
 def test_insert_pass_wiring(pkg, lib):

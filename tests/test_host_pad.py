@@ -15,24 +15,9 @@ import torch.nn.functional as F
 
 import pad_cases as pc
 from rearrange_cases import same_bits, special_values
+from optest import lib, names_of, pkg      # noqa: F401  (fixtures)
 
 VALUES = (0.0, -0.0, 0.1, -3.5, float('inf'))
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
-
-
-def names_of(net):
-    return [type(m).__name__ for m in net]
 
 
 # ------------------------------------------------------------------------------------------------ the twin

@@ -15,18 +15,7 @@ import torch.nn.functional as F
 
 import peaks_cases as pc
 from peaks_cases import DTYPES, SHAPES, WINDOW_IDS, WINDOWS
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 
 @pytest.fixture(autouse=True, scope="module")

@@ -12,18 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import pointwise_cases as pc
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 
 N = 250000

@@ -7,18 +7,7 @@ import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 
 def test_constructors_and_limits(pkg, lib):

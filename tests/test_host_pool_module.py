@@ -8,17 +8,12 @@ import pickle
 import pytest
 import torch
 import torch.nn as nn
+from optest import pkg      # noqa: F401  (fixtures)
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'pool_modules_parent.pkl')
 # what test_host_pool.test_pickle_round_trip compares, and the members of the other forms
 ATTRS = ('kernel_size', 'stride', 'padding', 'ceil_mode', '_op', '_general', 'generalGeometry', 'propChangeIndexes',
          'cloneOutput', '_adaptive', 'downsampleIndexes', 'lazy')
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
 
 
 def _modules(pkg):

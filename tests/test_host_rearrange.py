@@ -13,18 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import rearrange_cases as rc
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, names_of, pkg      # noqa: F401  (fixtures)
 
 
 def torch_op(kind, f, x):
@@ -185,10 +174,6 @@ def test_c_entry_point_checks_its_arguments(lib):
 
 
 # ------------------------------------------------------------------------------------------------ insertCBRearrange
-def names_of(net):
-    return [type(m).__name__ for m in net]
-
-
 def test_insert_rearrange_on_espcn_type_stacks(pkg):
     torch.manual_seed(1)
     seq = nn.Sequential(nn.Conv2d(3, 8, 3, padding=1), nn.ReLU(), nn.Conv2d(8, 16, 3, padding=1), nn.PixelShuffle(2),

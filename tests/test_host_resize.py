@@ -13,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import resize_cases as rc
+from optest import dev, lib, pkg      # noqa: F401  (fixtures)
 
 U24 = 2.0 ** -24      # the largest relative error of one f32 rounding
 # Sums of the absolute rounding errors of an axis' weights, in units of U24, from one rounding per operation:
@@ -35,18 +36,6 @@ def f32_bar_units(mode):
     S, E, T = S_WEIGHTS[mode], E_WEIGHTS[mode], TERMS[mode]
     units = 2 * S * E + 2 * T * S * S
     return 8.0 if mode == rc.BILINEAR else max(540.0, units)
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
 
 
 def all_cases(mode, align):

@@ -15,18 +15,7 @@ import torch.nn.functional as F
 
 import tconv_cases as tc
 from tconv_cases import CASES, case_form, case_out_hw, case_pixels, case_tags
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import pycbinfer
-    return pycbinfer
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from cbinfer_amd import _lib
-    return _lib
+from optest import lib, pkg      # noqa: F401  (fixtures)
 
 
 # ------------------------------------------------------------------------------------------------ the twin
