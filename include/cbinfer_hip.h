@@ -79,7 +79,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * channel attention scale (CB_CS_*, cbinfer_chanscale_supported, cbinfer_chanscale_gate, cbinfer_chanscale_changed,
  * cbinfer_cbchanscale_forward) and the group norm (cbinfer_groupnorm_supported, cbinfer_groupnorm_partials,
  * cbinfer_groupnorm_stats, cbinfer_groupnorm_changed, cbinfer_cbgroupnorm_forward) and the peak suppression (cbPeaks,
- * cbinfer_peaks_supported, cbinfer_peaks_changed, cbinfer_cbpeaks_forward, cbinfer_peaks_list). */
+ * cbinfer_peaks_supported, cbinfer_peaks_changed, cbinfer_cbpeaks_forward, cbinfer_peaks_list) and the grid sampling
+ * (cbWarp, CB_WARP_*, cbinfer_warp_supported, cbinfer_cbwarp_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1189,6 +1190,79 @@ int cbinfer_resize_supported(const cbResize* rs, int Hi, int Wi);
 int cbinfer_cbresize_forward(const void* input, void* outputState, const uint64_t* inputMask, const int32_t* list,
                              int capN, const int32_t* countDev, uint64_t* bits, uint64_t* maskCopy, int C, int Hi, int Wi,
                              const cbResize* rs, int dtype, cbStream_t stream);
+
+/* ---- change-based grid sampling (cb_warp.hip) ------------------------------------------------------------
+ * No counterpart in the reference.  F.grid_sample of a [C, Hi, Wi] map through a coordinate field on the Ho x Wo output
+ * map: a fixed warp (homography, rectification, affine grid) or a flow field.  An output pixel reads 1, 2x2 or 4x4 input
+ * pixels at a position given by ITS OWN coordinate pair, so -- every producer leaves the pixels outside its change list
+ * bit for bit as they were -- it can differ from last frame's only where its coordinate pair changed or one of its taps
+ * did.  The coordinates are data and cannot be inverted: the frame is driven from the OUTPUT side, every output pixel
+ * tests the change bits of its own taps.  input [C, Hi, Wi] and the state `out` [C, Ho, Wo] are contiguous, CB_F32 or
+ * CB_F16 (dtype), two different tensors; the coordinates have a dtype of their own (coordDtype), loaded exactly to f32:
+ *   CB_WARP_GRID  coords [Ho, Wo, 2], normalised (x, y) pairs, torch's layout;
+ *   CB_WARP_FLOW  coords [2, Ho, Wo], plane 0 = dx, plane 1 = dy in input pixels.
+ *
+ * THIS SECTION IS THE SPECIFICATION of the f32 arithmetic: every operation written below is rounded on its own (round
+ * to nearest even, never an FMA), in exactly this order; the result is rounded to the dtype once.
+ *   source coordinate of an axis with n input pixels, g the pixel's normalised coordinate, o its own output coordinate:
+ *     GRID, alignCorners == 0:  s = ((g + 1) * (float)n - 1) * 0.5
+ *     GRID, alignCorners == 1:  s = ((g + 1) * 0.5) * (float)(n - 1)
+ *     FLOW:                     s = (float)o + d        (no unnormalisation; alignCorners only places the reflection)
+ *     then s = !(s > -L) ? -L : (s > L ? L : s) with L = 2^20: clamped before any integer conversion, a NaN goes to -L.
+ *   padding of a COORDINATE (nearest and bilinear; bicubic leaves the centre alone):
+ *     CB_WARP_ZEROS       s as it is;
+ *     CB_WARP_BORDER      clip(s) = s < 0 ? 0 : (s > (float)(n - 1) ? (float)(n - 1) : s);
+ *     CB_WARP_REFLECTION  lo = 0, span = (float)(n - 1) with alignCorners, lo = -0.5, span = (float)n without;
+ *                         span == 0: s = 0; else a = fabsf(s - lo), e = fmodf(a, span) (exact), k = (int)((a - e) / span)
+ *                         (an exact integer), s = k odd ? (span - e) + lo : e + lo; then clip(s).
+ *   taps and weights per axis; a tap index i is IN THE MAP iff 0 <= i < n, and a tap of a pixel counts iff both its
+ *   indexes are in the map.  An address is formed only from an index in the map:
+ *     CB_WARP_NEAREST   one tap i = (int)rintf(s).
+ *     CB_WARP_BILINEAR  f = floorf(s), the taps i0 = (int)f and i0 + 1 with w0 = (f + 1) - s, w1 = s - f.
+ *     CB_WARP_BICUBIC   f = floorf(s), t = s - f, the taps (int)f - 1 .. (int)f + 2 with the weights of the resize section
+ *                       above (A = -0.75): far(t + 1), near(t), near(1 - t), far(2 - t); each tap INDEX i is padded:
+ *                       ZEROS as it is; BORDER clamped to [0, n - 1]; REFLECTION in integers -- n == 1: 0; with
+ *                       alignCorners i = |i|, m = i mod 2 (n - 1), i = m > n - 1 ? 2 (n - 1) - m : m; without
+ *                       i = i < 0 ? -1 - i : i, m = i mod 2 n, i = m >= n ? 2 n - 1 - m : m.
+ *   values: nearest copies the tap bit for bit, +0 where it does not count.  Otherwise, from acc = +0:
+ *     BILINEAR  the weights wnw = wx0 * wy0, wne = wx1 * wy0, wsw = wx0 * wy1, wse = wx1 * wy1; acc = acc + w * p for
+ *               the taps that count, in the order nw, ne, sw, se (four products, the sums left to right);
+ *     BICUBIC   rows over x first: r_k = sum over j ascending of wx_j * p(k, j), from +0, over the taps that count;
+ *               then out = sum over k ascending of wy_k * r_k, from +0, over all four rows.
+ *   A tap that does not count contributes NOTHING -- it is not multiplied by zero, and no value is read for it.
+ *   A pixel's bits therefore depend neither on the other listed pixels nor on the operands' forms.
+ *   listed pixels: (oy, ox) is listed iff its coordinate pair is listed or any tap of it that counts is listed in the
+ *     input's changes -- a zero weight does not matter.  Each operand X arrives as its row-padded change MASK (input: on
+ *     the Hi x Wi map; coordinates: on the Ho x Wo map), as an int32 LIST of flat indexes on that map (capX entries at
+ *     most, countX the device-side length or NULL: capX is the length; entries outside the map are dropped; an empty
+ *     list: the operand did not change, which is how a constant grid arrives), or not at all: then EVERY output pixel is
+ *     listed and neither operand's change information is read.
+ *   launches: a list costs one launch in front (cbinfer_pool_footprint with a 1x1 window): the input's into `inBits`,
+ *     the working mask of the INPUT map, the coordinates' into `bits`, the working mask of the OUTPUT map; then ONE
+ *     launch for the frame; an input list costs one launch behind it, which stores zero to the words of `inBits` the
+ *     list named.  No host sync, memset, allocation or data atomics.
+ *   hand-on: maskCopy (cbinfer_mask_words(Ho, Wo) words) receives the frame's mask every frame; `inBits`
+ *     (cbinfer_mask_words(Hi, Wi) words) and `bits` (cbinfer_mask_words(Ho, Wo) words), zero on first use, are zero
+ *     again when the frame ends.  Unlisted pixels keep their bits; bits of the row padding are never set.
+ * Limits (cbinfer_warp_supported): Hi, Wi, Ho, Wo in 1 .. 2^15 - 1; mode, padding, coordKind one of the enumerators;
+ * alignCorners 0 or 1; coordDtype CB_F32 or CB_F16.
+ * Bad arguments (a null tensor or mask buffer, outputState == input or coords, C < 1, an unknown dtype, a cbWarp beyond
+ * the limits, a capacity < 0, both a mask and a list for one operand, a count without a list, two of inBits / bits /
+ * maskCopy equal, an operand's mask equal to one of them, 64 C beyond an int32) return CB_ERR_BADARG and launch nothing. */
+enum { CB_WARP_NEAREST, CB_WARP_BILINEAR, CB_WARP_BICUBIC };
+enum { CB_WARP_ZEROS, CB_WARP_BORDER, CB_WARP_REFLECTION };
+enum { CB_WARP_GRID, CB_WARP_FLOW };
+typedef struct cbWarp {
+    int Ho, Wo, mode, padding, alignCorners, coordKind, coordDtype;
+} cbWarp;
+/* host, pure: 1 if the sampling of an Hi x Wi map is within the limits above, else 0 */
+int cbinfer_warp_supported(const cbWarp* warp, int Hi, int Wi);
+/* The whole frame of a change-based grid sampling enqueued without a host sync. */
+int cbinfer_cbwarp_forward(const void* input, const void* coords, void* outputState, const uint64_t* inputMask,
+                           const int32_t* inputList, int inputCap, const int32_t* inputCount, const uint64_t* coordMask,
+                           const int32_t* coordList, int coordCap, const int32_t* coordCount, uint64_t* inBits,
+                           uint64_t* bits, uint64_t* maskCopy, int C, int Hi, int Wi, const cbWarp* warp, int dtype,
+                           cbStream_t stream);
 
 /* ---- change-based pixel shuffle, pixel unshuffle and channel shuffle (cb_rearrange.hip) -----------------
  * No counterpart in the reference.  The three operators compute nothing: values are copied bit for bit, never converted,
