@@ -1,5 +1,5 @@
-"""Change-based element-wise operators of two maps: CBBinary2d, CBGLU2d, CBGated and insertCBGating (cb_binary.hip,
-DESIGN 5.25).
+"""Change-based operators of two maps: CBBinary2d, CBGLU2d, CBGated and insertCBGating (cb_binary.hip),
+and CBBinary2d('correlate'), the correlation layer / cost volume of flow and stereo networks (cb_corr.hip).
 
 The reference has no element-wise operator of two maps, and CBAdd2d is the sum alone: a gate `feat * sigmoid(gate)`, a
 layer scale `gamma[c] * x`, a residual by difference `x - net(x)`, an element-wise maximum or an nn.GLU over the
@@ -8,6 +8,7 @@ cannot be recorded by a FrameProgram.  Every producer of this package leaves the
 bit as they were, so op(a, b) can differ from last frame's only at the UNION of the two lists, and a constant operand (a
 parameter) never changes: the modules here recompute it there and are the dense result exactly, without a threshold.
 """
+import ctypes
 import numbers
 
 import torch
@@ -22,6 +23,40 @@ from .residual import _sequential
 _OPS = {'add': _lib.BIN_ADD, 'sub': _lib.BIN_SUB, 'mul': _lib.BIN_MUL, 'maximum': _lib.BIN_MAXIMUM,
         'minimum': _lib.BIN_MINIMUM}
 _GATES = {None: _lib.BIN_GATE_NONE, 'sigmoid': _lib.BIN_GATE_SIGMOID, 'hardsigmoid': _lib.BIN_GATE_HARDSIGMOID}
+# the correlation layer has entry points of its own and no CB_BIN_* code (cb_corr.hip)
+CORRELATE = 'correlate'
+MAX_DISPLACEMENT, MAX_STEP, MAX_CORR_CHANNELS = 64, 8, 512
+
+
+def correlation_window(displacement, step):
+    """(y0, y1, x0, x1, Dy, Dx) of CBBinary2d('correlate', displacement=, step=): displacement an int r (both axes
+    -r .. r), a pair (ry, rx) or ((y0, y1), (x0, x1)); CBinferError naming the setting beyond the library's limits."""
+    def whole(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    d = displacement
+    if whole(d):
+        d = (d, d)
+    ok = isinstance(d, (tuple, list)) and len(d) == 2
+    if ok and all(whole(v) for v in d):
+        d = ((-d[0], d[0]), (-d[1], d[1]))
+    ok = ok and all(isinstance(r, (tuple, list)) and len(r) == 2 and all(whole(v) for v in r) for r in d)
+    if not ok:
+        raise CBinferError("CBBinary2d: displacement=%r must be an int r, a pair (ry, rx) or ((y0, y1), (x0, x1))"
+                           % (displacement,))
+    (y0, y1), (x0, x1) = ((int(v) for v in r) for r in d)
+    if not whole(step) or not 1 <= step <= MAX_STEP:
+        raise CBinferError("CBBinary2d: step=%r must be an int in 1 .. %d" % (step, MAX_STEP))
+    if y0 > y1 or x0 > x1 or max(abs(v) for v in (y0, y1, x0, x1)) > MAX_DISPLACEMENT:
+        raise CBinferError("CBBinary2d: displacement=%r: every range must be ascending and within -%d .. %d"
+                           % (displacement, MAX_DISPLACEMENT, MAX_DISPLACEMENT))
+    if (y1 - y0) % step or (x1 - x0) % step:
+        raise CBinferError("CBBinary2d: step=%d must divide both range lengths of displacement=%r (%d and %d)"
+                           % (step, displacement, y1 - y0, x1 - x0))
+    Dy, Dx = (y1 - y0) // step + 1, (x1 - x0) // step + 1
+    if Dy * Dx > MAX_CORR_CHANNELS:
+        raise CBinferError("CBBinary2d: displacement=%r with step=%d gives %d x %d = %d output channels, the limit is %d"
+                           % (displacement, step, Dy, Dx, Dy * Dx, MAX_CORR_CHANNELS))
+    return y0, y1, x0, x1, Dy, Dx
 
 
 # operand_changes' refusals in these modules' words (which: 'operand a' / 'operand b')
@@ -38,7 +73,7 @@ class _CBBinaryBase(CBStateModule):
     def _set_function(self, name, op, gate, reverse):
         if op not in _OPS:
             raise CBinferError("%s: op=%r is not supported, only one of %s"
-                               % (name, op, ", ".join(repr(k) for k in _OPS)))
+                               % (name, op, ", ".join(repr(k) for k in list(_OPS) + [CORRELATE])))
         if gate not in _GATES:
             raise CBinferError("%s: gate=%r is not supported, only None, 'sigmoid' or 'hardsigmoid'" % (name, gate))
         self.op, self.gate, self.reverse = op, gate, bool(reverse)
@@ -86,11 +121,36 @@ class CBBinary2d(_CBBinaryBase):
     x * torch.tensor(v, dtype=x.dtype), which can differ in the last bit from torch's x * v.
 
     The flags are CBAdd2d's: propChangeIndexes hands on the union as a MaskChangeIndexes; cloneOutput=False hands out the
-    state itself, tagged, and the frame is then free of torch operators."""
+    state itself, tagged, and the frame is then free of torch operators.
 
-    def __init__(self, op, other=None, gate=None, reverse=False):
+    op='correlate' -- CBBinary2d('correlate', displacement=4, step=1, normalize=True) -- is the correlation layer (cost
+    volume) of FlowNet / PWC-Net / DispNet-type networks on the matrix cores (cb_corr.hip): a and b are
+    [1, C, H, W] maps of one shape, dtype and device, the state is [1, Dy Dx, H, W],
+        out[i Dx + j, y, x] = (1/C) sum_c a[c, y, x] b[c, y + y0 + i step, x + x0 + j step],
+    a tap outside the map contributing nothing; normalize=False is the plain sum.  displacement: an int r (both axes
+    -r .. r), a pair (ry, rx), or ((y0, y1), (x0, x1)) for one-sided ranges (stereo: ((0, 0), (-40, 0))); step divides
+    both range lengths; every |displacement| <= 64, step <= 8, Dy Dx <= 512.  A pixel is recomputed iff a changed there or
+    b changed at one of its window's taps -- the handed-on mask is that footprint.  `other`, `gate` and `reverse` do not
+    go with it, and displacement / step / normalize go with no other op.  It has no conversion pass: an operator of two
+    inputs never stands in an nn.Sequential, it is wired by hand as the per-frame flow of CBResize2d is."""
+
+    def __init__(self, op, other=None, gate=None, reverse=False, displacement=None, step=None, normalize=None):
         super(CBBinary2d, self).__init__()
-        self._set_function('CBBinary2d', op, gate, reverse)
+        window = dict(displacement=displacement, step=step, normalize=normalize)
+        if op == CORRELATE:
+            for key, given in (('other', other is not None), ('gate', gate is not None), ('reverse', bool(reverse))):
+                if given:
+                    raise CBinferError("CBBinary2d: %s= does not go with op='correlate'" % key)
+            self.op, self.gate, self.reverse = op, None, False
+            self.displacement = 4 if displacement is None else displacement
+            self.step = 1 if step is None else step
+            self.normalize = True if normalize is None else bool(normalize)
+            self.window = correlation_window(self.displacement, self.step)
+        else:
+            for key, value in window.items():
+                if value is not None:
+                    raise CBinferError("CBBinary2d: %s= goes with op='correlate' only, not with op=%r" % (key, op))
+            self._set_function('CBBinary2d', op, gate, reverse)
         self.otherNumber = None
         self.hasOther = other is not None
         buf = None
@@ -140,7 +200,39 @@ class CBBinary2d(_CBBinaryBase):
         raise CBinferError("CBBinary2d: the constant operand `other` has shape %s, operand a is %s"
                            % (shape, tuple(a.shape)))
 
+    def _correlate(self, a, b):
+        name = 'CBBinary2d'
+        if b is None:
+            raise CBinferError("CBBinary2d: forward(a, b) takes two operands")
+        a, ia = split_operand(name, a, 'operand a')
+        check_map(name, a, 'operand a')
+        b, ib = split_operand(name, b, 'operand b')
+        if tuple(b.shape) != tuple(a.shape) or b.dtype != a.dtype or b.device != a.device:
+            raise CBinferError("CBBinary2d: the operands differ: a is %s %s on %s, b is %s %s on %s"
+                               % (tuple(a.shape), a.dtype, a.device, tuple(b.shape), b.dtype, b.device))
+        require_device(a, b)
+        nc, H, W = a.size(1), a.size(2), a.size(3)
+        y0, y1, x0, x1, Dy, Dx = self.window
+
+        def make():
+            corr = _lib.Corr(y0, y1, x0, x1, self.step, int(self.normalize))
+            if not C.cbinfer_correlation_supported(ctypes.byref(corr), nc, H, W):
+                raise CBinferError("CBBinary2d: correlating %s maps is beyond the library's limits" % (tuple(a.shape),))
+            work = mask_workspace(H, W, a.device, nbits=2)      # (the output's working mask, then b's)
+            return dict(work, corr=ctypes.pointer(corr), bBits=work['bits'][work['copy'].numel():])
+        work = self._cached_work((CORRELATE, nc, H, W, a.device), make)
+        fa = operand_changes(name, 'operand a', ia, H, W, a.device, work['idx'], words=_WORDS, maskWhenMade=False)
+        fb = operand_changes(name, 'operand b', ib, H, W, a.device, work['idx'], words=_WORDS, maskWhenMade=False)
+        if self._fresh_state((1, Dy * Dx, H, W), a):      # (written completely: no change information is used)
+            fa = fb = EVERY_PIXEL
+        check(C.cbinfer_cbcorrelation_forward(ptr(a), ptr(b), ptr(self.outputState), *form_args(fa), *form_args(fb),
+                                              ptr(work['bBits']), ptr(work['bits']), ptr(work['copy']), nc, H, W,
+                                              work['corr'], _lib.dtype_code(a), stream_ptr(a)))
+        return self._result(work, H, W)
+
     def forward(self, a, b=None):
+        if self.op == CORRELATE:
+            return self._correlate(a, b)
         if self.hasOther and b is not None:
             raise CBinferError("CBBinary2d: the module has a constant operand `other`: forward(a) takes one argument")
         if not self.hasOther and b is None:
@@ -173,6 +265,9 @@ class CBBinary2d(_CBBinaryBase):
         return self._frame('CBBinary2d', a, ia, b, ib, form, _lib.BIN_B_OWN, nc, H, W)
 
     def __repr__(self):
+        if self.op == CORRELATE:
+            return 'CBBinary2d (op=correlate, displacement=%r, step=%d, normalize=%s, propChgIdxs=%s)' % (
+                self.displacement, self.step, self.normalize, self.propChangeIndexes)
         other = ('number %r' % self.otherNumber if self.otherNumber is not None else
                  tuple(self.other.shape) if self.other is not None else None)
         return 'CBBinary2d (op=%s, gate=%s, reverse=%s, other=%s, propChgIdxs=%s)' % (

@@ -80,7 +80,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_cbchanscale_forward) and the group norm (cbinfer_groupnorm_supported, cbinfer_groupnorm_partials,
  * cbinfer_groupnorm_stats, cbinfer_groupnorm_changed, cbinfer_cbgroupnorm_forward) and the peak suppression (cbPeaks,
  * cbinfer_peaks_supported, cbinfer_peaks_changed, cbinfer_cbpeaks_forward, cbinfer_peaks_list) and the grid sampling
- * (cbWarp, CB_WARP_*, cbinfer_warp_supported, cbinfer_cbwarp_forward). */
+ * (cbWarp, CB_WARP_*, cbinfer_warp_supported, cbinfer_cbwarp_forward) and the correlation layer (cbCorr,
+ * cbinfer_correlation_supported, cbinfer_cbcorrelation_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1263,6 +1264,56 @@ int cbinfer_cbwarp_forward(const void* input, const void* coords, void* outputSt
                            const int32_t* coordList, int coordCap, const int32_t* coordCount, uint64_t* inBits,
                            uint64_t* bits, uint64_t* maskCopy, int C, int Hi, int Wi, const cbWarp* warp, int dtype,
                            cbStream_t stream);
+
+/* ---- change-based correlation layer / cost volume (cb_corr.hip) -------------------------------------------
+ * No counterpart in the reference.  The correlation layer of FlowNet / PWC-Net / DispNet-type networks: two maps a and
+ * b [C, H, W] and a window of displacements, y0 .. y1 and x0 .. x1 in steps of `step`,
+ *   Dy = (y1 - y0) / step + 1,   Dx = (x1 - x0) / step + 1,   the state `out` is [Dy Dx, H, W],
+ *   out[i Dx + j, y, x] = scale * sum over c of a[c, y, x] * b[c, y + y0 + i step, x + x0 + j step],
+ * channel i Dx + j holding displacement (y0 + i step, x0 + j step): dy-major, dx fastest.  ZERO PADDING: a tap whose
+ * row or column lies outside the map contributes nothing (the channel of a pixel all of whose taps lie outside is +0).
+ * scale = (float)1 / (float)C with normalize != 0 -- float32(1/C), as FlowNet's and PWC-Net's correlation divide --,
+ * else 1.  a, b and `out` are contiguous, one dtype (CB_F32 or CB_F16), three different tensors.
+ *
+ * THIS SECTION IS THE SPECIFICATION.
+ *   listed pixels -- the exact footprint: pixel p = (y, x) is listed iff a changed at p, or b changed at a pixel
+ *     p + (y0 + i step, x0 + j step), 0 <= i < Dy, 0 <= j < Dx, that lies in the map.  With step > 1 this is the sparse
+ *     set of those taps, NOT its bounding rectangle.  Every producer leaves the pixels outside its change list bit for
+ *     bit as they were, so no other pixel of the result can differ from last frame's: no threshold is involved.  Each
+ *     operand X arrives as its row-padded change MASK (cbinfer_mask_words(H, W) words), as an int32 LIST of flat indexes
+ *     y W + x (capX entries at most, countX the device-side length or NULL: capX is the length; entries outside the map
+ *     are dropped; an empty list: the operand did not change), or not at all: then EVERY pixel is listed and neither
+ *     operand's change information is read.
+ *   arithmetic: the operands go to the matrix unit as they are (f32: v_mfma_f32_16x16x4_f32, the exact-f32 form; f16:
+ *     v_mfma_f32_16x16x32_f16, whose products are exact in f32); products and sums in f32 on the matrix unit, k ascending
+ *     in the kernel's fixed chunks of 16 (f32) or 32 (f16) channels, a channel tail and every tap outside the map filled
+ *     with +0; then ONE f32 multiply by scale; then ONE rounding to the dtype.  DESIGN 5.33 has the error bound.
+ *   unit of work: a non-empty word of the frame's mask -- a row and 64 columns -- is four groups of 16 columns; a group
+ *     with a listed pixel is computed whole and only its listed pixels are stored.  A pixel's bits therefore depend on
+ *     its own operand values and on x mod 16 alone, never on the other listed pixels or on the operands' forms.
+ *   launches: a list costs one launch in front (cbinfer_pool_footprint with a 1x1 window): a's into `bits`, b's into
+ *     `bBits`, a working mask of its own; then ONE launch for the frame; a list of b costs one launch behind it, which
+ *     stores zero to the words of `bBits` the list named (the frame launch reads b's mask from every workgroup and cannot
+ *     clear it itself).  No host sync, memset, allocation or data atomics beyond the footprint launch's.
+ *   hand-on: maskCopy (cbinfer_mask_words(H, W) words) receives the frame's mask every frame; `bits` and `bBits` (as
+ *     many words each, zero on first use) are zero again when the frame ends.  Unlisted pixels keep their bits; bits of
+ *     the row padding are never set.
+ * Limits (cbinfer_correlation_supported): -64 <= y0 <= y1 <= 64, -64 <= x0 <= x1 <= 64, 1 <= step <= 8 dividing y1 - y0
+ * and x1 - x0, Dy Dx <= 512, normalize 0 or 1, C, H, W >= 1, H W and 64 C within an int32.
+ * Bad arguments (a null tensor or mask buffer, outputState == a or b, an unknown dtype, a cbCorr beyond the limits, a
+ * capacity < 0, both a mask and a list for one operand, a count without a list, two of bBits / bits / maskCopy equal, an
+ * operand's mask equal to one of them) return CB_ERR_BADARG and launch nothing. */
+typedef struct cbCorr {
+    int y0, y1, x0, x1, step, normalize;
+} cbCorr;
+/* host, pure: 1 if the correlation of two [C, H, W] maps is within the limits above, else 0 */
+int cbinfer_correlation_supported(const cbCorr* corr, int C, int H, int W);
+/* The whole frame of a change-based correlation enqueued without a host sync. */
+int cbinfer_cbcorrelation_forward(const void* a, const void* b, void* outputState, const uint64_t* maskA,
+                                  const int32_t* listA, int capA, const int32_t* countA, const uint64_t* maskB,
+                                  const int32_t* listB, int capB, const int32_t* countB, uint64_t* bBits, uint64_t* bits,
+                                  uint64_t* maskCopy, int C, int H, int W, const cbCorr* corr, int dtype,
+                                  cbStream_t stream);
 
 /* ---- change-based pixel shuffle, pixel unshuffle and channel shuffle (cb_rearrange.hip) -----------------
  * No counterpart in the reference.  The three operators compute nothing: values are copied bit for bit, never converted,

@@ -8,7 +8,13 @@ x's changes count), the difference a - b.  Per row: cbinfer_cbbinary_forward wit
 and in LIST form (one launch more per per-frame operand) -- every per-frame operand carries the frame's change set --,
 against torch's dense operator(s) on the same tensors.  The measuring method is tools/target_common.py's.  Prints
 markdown (profiles/binary_target.md).
-usage: binary_target.py [rounds]"""
+
+`binary_target.py correlate` measures the correlation layer instead (cb_corr.hip, cbinfer_cbcorrelation_forward;
+profiles/correlation_target.md): PWC-Net pyramid levels (radius 4), FlowNetC (radius 20, step 2) and a one-sided stereo
+range, fp32 and fp16, 10 % changed pixels in BOTH operands, mask form and list form, against the faster of two dense
+torch formulations on the same tensors -- the shifted-product loop with mean(1), and unfold + einsum.
+usage: binary_target.py [correlate] [rounds]"""
+import ctypes
 import os
 import statistics
 import sys
@@ -86,9 +92,95 @@ def row(name, Cn, H, W, block, gateForm, what, dtype, reps):
           % (name, H, W, WHAT[what], dtype_name(dtype), listed, fmt(t["mask"]), fmt(t["list"]), fmt(t["dense"]), dm, dl))
 
 
+#               name, channels, H, W, block, displacement ((y0, y1), (x0, x1)), step
+CORR_ROWS = [("PWC level, 196 ch", 196, 48, 160, 4, ((-4, 4), (-4, 4)), 1),
+             ("PWC level, 128 ch", 128, 64, 208, 4, ((-4, 4), (-4, 4)), 1),
+             ("PWC level, 64 ch", 64, 96, 320, 8, ((-4, 4), (-4, 4)), 1),
+             ("FlowNetC, 256 ch", 256, 48, 64, 4, ((-20, 20), (-20, 20)), 2),
+             ("stereo, 64 ch", 64, 96, 320, 8, ((0, 0), (-40, 0)), 1)]
+
+
+def corr_row(name, Cn, H, W, block, disp, step, dtype, reps):
+    import torch.nn.functional as F
+    rng = np.random.default_rng(7)
+    torch.manual_seed(7)
+    a, b = (torch.randn(1, Cn, H, W, device="cuda").to(dtype) for _ in range(2))
+    (y0, y1), (x0, x1) = disp
+    taps = [(dy, dx) for dy in range(y0, y1 + 1, step) for dx in range(x0, x1 + 1, step)]
+    # (left, right, top, bottom) zero padding that every tap's window needs
+    pads = (max(0, -x0), max(0, x1), max(0, -y0), max(0, y1))
+    corr = ctypes.pointer(_lib.Corr(y0, y1, x0, x1, step, 1))
+    assert C.cbinfer_correlation_supported(corr, Cn, H, W)
+    sets = change_sets(rng, H, W, block, 0.10)
+    masks, lists = device_sets(sets)
+    words = C.cbinfer_mask_words(H, W)
+    bbits, bits, mcopy = (torch.zeros(words, dtype=torch.int64, device="cuda") for _ in range(3))
+    out = torch.empty(1, len(taps), H, W, device="cuda", dtype=dtype)
+    st = torch.cuda.current_stream().cuda_stream
+    dt = _lib.dtype_code(a)
+
+    def loop(i):
+        bp = F.pad(b, pads)
+        return torch.stack([(a * bp[:, :, pads[2] + dy:pads[2] + dy + H, pads[0] + dx:pads[0] + dx + W]).mean(1)
+                            for dy, dx in taps], dim=1)
+
+    def unfold(i):
+        kh, kw = (y1 - y0) // step + 1, (x1 - x0) // step + 1
+        cols = F.unfold(F.pad(b, pads), (kh, kw), dilation=step).view(Cn, kh * kw, H, W)
+        return (torch.einsum('chw,cdhw->dhw', a[0], cols) / Cn)[None]
+
+    def frame(ma, la, mb, lb):
+        check(C.cbinfer_cbcorrelation_forward(ptr(a), ptr(b), ptr(out), ptr(ma), ptr(la),
+                                              la.numel() if la is not None else 0, None, ptr(mb), ptr(lb),
+                                              lb.numel() if lb is not None else 0, None, ptr(bbits), ptr(bits), ptr(mcopy),
+                                              Cn, H, W, corr, dt, st))
+
+    # results first: every pixel listed, against the float64 formula within the bound of DESIGN 5.33
+    frame(None, None, None, None)
+    bp = F.pad(b.double(), pads)
+    for k, (dy, dx) in enumerate(taps[::max(1, len(taps) // 7)]):
+        prod = a.double() * bp[:, :, pads[2] + dy:pads[2] + dy + H, pads[0] + dx:pads[0] + dx + W]
+        ref, bar = prod.mean(1), (Cn + 2) * 2.0 ** -24 * prod.abs().mean(1)
+        if dtype == torch.float16:
+            bar = bar + 2.0 ** -11 * ref.abs() + 2.0 ** -25
+        got = out[:, taps.index((dy, dx))].double()
+        assert bool(((got - ref).abs() <= bar).all()), "correlation beyond its bound"
+        assert torch.allclose(loop(0)[:, taps.index((dy, dx))].double(), ref, atol=1e-2), "dense loop"
+        assert torch.allclose(unfold(0)[:, taps.index((dy, dx))].double(), ref, atol=1e-2), "dense unfold"
+    t = rounds([("mask", lambda i: frame(masks[i % SETS], None, masks[i % SETS], None)),
+                ("list", lambda i: frame(None, lists[i % SETS], None, lists[i % SETS])),
+                ("loop", loop), ("unfold", unfold)], reps)
+    frame(masks[0], None, masks[0], None)
+    listed = float(np.unpackbits(mcopy.cpu().numpy().view(np.uint8)).sum()) / (H * W) * 100.0
+    dense = min(statistics.median(t["loop"]), statistics.median(t["unfold"]))
+    ratios = [dense / statistics.median(t[k]) for k in ("mask", "list")]
+    # (a case where the module loses to the dense operator is written in capitals, as in the other tables)
+    verdict = "%.2fx / %.2fx" % tuple(ratios) + (" LOSES" if min(ratios) < 1.0 else "")
+    print("| %s @%dx%d | %d ch out | %s | %.1f %% / %.1f %% | %s | %s | %s | %s | %s |"
+          % (name, H, W, len(taps), dtype_name(dtype), listed_share(sets), listed, fmt(t["mask"]), fmt(t["list"]),
+             fmt(t["loop"]), fmt(t["unfold"]), verdict))
+
+
+def corr_main(reps):
+    print("# Change-based correlation layer at 10 % changed pixels in both operands\n")
+    print("%s, torch %s; times in us per call, median [min..max] over %d interleaved rounds of %d calls; the dense "
+          "baseline of a row is the faster of its two torch formulations\n"
+          % (torch.cuda.get_device_name(0), torch.__version__, reps, BATCH))
+    print("| layer | window | dtype | changed / listed pixels | cbinfer_cbcorrelation_forward, mask form | list form | "
+          "dense torch, shifted products | dense torch, unfold + einsum | dense / mask form, dense / list form |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for name, Cn, H, W, block, disp, step in CORR_ROWS:
+        for dtype in (torch.float32, torch.float16):
+            corr_row(name, Cn, H, W, block, disp, step, dtype, reps)
+
+
 def main():
-    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 15
+    args = sys.argv[1:]
+    correlate = bool(args) and args[0] == "correlate"
+    reps = int(args[correlate]) if len(args) > correlate else 15
     assert torch.cuda.is_available(), "binary_target.py needs a GPU"
+    if correlate:
+        return corr_main(reps)
     print("# Change-based element-wise operators of two maps at 10 % changed pixels\n")
     print("%s, torch %s; times in us per call, median [min..max] over %d interleaved rounds of %d calls\n"
           % (torch.cuda.get_device_name(0), torch.__version__, reps, BATCH))
