@@ -1,5 +1,7 @@
 """Change-based operators of two maps: CBBinary2d, CBGLU2d, CBGated and insertCBGating (cb_binary.hip),
-and CBBinary2d('correlate'), the correlation layer / cost volume of flow and stereo networks (cb_corr.hip).
+CBBinary2d('correlate'), the correlation layer / cost volume of flow and stereo networks (cb_corr.hip), and
+CBBinary2d('aggregate'), the per-pixel kernel application that takes such a volume back to a feature map (cb_aggr.hip,
+DESIGN 5.34).
 
 The reference has no element-wise operator of two maps, and CBAdd2d is the sum alone: a gate `feat * sigmoid(gate)`, a
 layer scale `gamma[c] * x`, a residual by difference `x - net(x)`, an element-wise maximum or an nn.GLU over the
@@ -23,14 +25,16 @@ from .residual import _sequential
 _OPS = {'add': _lib.BIN_ADD, 'sub': _lib.BIN_SUB, 'mul': _lib.BIN_MUL, 'maximum': _lib.BIN_MAXIMUM,
         'minimum': _lib.BIN_MINIMUM}
 _GATES = {None: _lib.BIN_GATE_NONE, 'sigmoid': _lib.BIN_GATE_SIGMOID, 'hardsigmoid': _lib.BIN_GATE_HARDSIGMOID}
-# the correlation layer has entry points of its own and no CB_BIN_* code (cb_corr.hip)
-CORRELATE = 'correlate'
-MAX_DISPLACEMENT, MAX_STEP, MAX_CORR_CHANNELS = 64, 8, 512
+# the correlation layer and the per-pixel kernel application have entry points of their own and no CB_BIN_* code
+# (cb_corr.hip, cb_aggr.hip)
+CORRELATE, AGGREGATE = 'correlate', 'aggregate'
+MAX_DISPLACEMENT, MAX_STEP, MAX_CORR_CHANNELS, MAX_WEIGHT_PLANES = 64, 8, 512, 4096
 
 
-def correlation_window(displacement, step):
-    """(y0, y1, x0, x1, Dy, Dx) of CBBinary2d('correlate', displacement=, step=): displacement an int r (both axes
-    -r .. r), a pair (ry, rx) or ((y0, y1), (x0, x1)); CBinferError naming the setting beyond the library's limits."""
+def correlation_window(displacement, step, what="output channels"):
+    """(y0, y1, x0, x1, Dy, Dx) of CBBinary2d('correlate' / 'aggregate', displacement=, step=): displacement an int r
+    (both axes -r .. r), a pair (ry, rx) or ((y0, y1), (x0, x1)); CBinferError naming the setting beyond the library's
+    limits.  what: the name of the Dy Dx things the window makes in the limit's message."""
     def whole(v):
         return isinstance(v, numbers.Integral) and not isinstance(v, bool)
     d = displacement
@@ -54,8 +58,8 @@ def correlation_window(displacement, step):
                            % (step, displacement, y1 - y0, x1 - x0))
     Dy, Dx = (y1 - y0) // step + 1, (x1 - x0) // step + 1
     if Dy * Dx > MAX_CORR_CHANNELS:
-        raise CBinferError("CBBinary2d: displacement=%r with step=%d gives %d x %d = %d output channels, the limit is %d"
-                           % (displacement, step, Dy, Dx, Dy * Dx, MAX_CORR_CHANNELS))
+        raise CBinferError("CBBinary2d: displacement=%r with step=%d gives %d x %d = %d %s, the limit is %d"
+                           % (displacement, step, Dy, Dx, Dy * Dx, what, MAX_CORR_CHANNELS))
     return y0, y1, x0, x1, Dy, Dx
 
 
@@ -73,7 +77,7 @@ class _CBBinaryBase(CBStateModule):
     def _set_function(self, name, op, gate, reverse):
         if op not in _OPS:
             raise CBinferError("%s: op=%r is not supported, only one of %s"
-                               % (name, op, ", ".join(repr(k) for k in list(_OPS) + [CORRELATE])))
+                               % (name, op, ", ".join(repr(k) for k in list(_OPS) + [CORRELATE, AGGREGATE])))
         if gate not in _GATES:
             raise CBinferError("%s: gate=%r is not supported, only None, 'sigmoid' or 'hardsigmoid'" % (name, gate))
         self.op, self.gate, self.reverse = op, gate, bool(reverse)
@@ -132,24 +136,51 @@ class CBBinary2d(_CBBinaryBase):
     both range lengths; every |displacement| <= 64, step <= 8, Dy Dx <= 512.  A pixel is recomputed iff a changed there or
     b changed at one of its window's taps -- the handed-on mask is that footprint.  `other`, `gate` and `reverse` do not
     go with it, and displacement / step / normalize go with no other op.  It has no conversion pass: an operator of two
-    inputs never stands in an nn.Sequential, it is wired by hand as the per-frame flow of CBResize2d is."""
+    inputs never stands in an nn.Sequential, it is wired by hand as the per-frame flow of CBResize2d is.
 
-    def __init__(self, op, other=None, gate=None, reverse=False, displacement=None, step=None, normalize=None):
+    op='aggregate' -- CBBinary2d('aggregate', displacement=4, step=1, groups=1), forward(w, v) -- is the operator that
+    consumes such a volume (cb_aggr.hip): the attn . V half of local attention, the kernel application of
+    kernel-prediction networks, CARAFE's reassembly, involution (groups = C / 16) and dynamic filters, on the matrix
+    cores.  w is [1, G T, H, W] with T = Dy Dx taps and G = groups dividing C, v [1, C, H, W] of the same H, W, dtype and
+    device, the state is [1, C, H, W],
+        out[c, y, x] = sum_{i, j} w[g(c) T + i Dx + j, y, x] v[c, y + y0 + i step, x + x0 + j step],   g(c) = c // (C // G),
+    a tap outside the map contributing nothing: the plane order of w is correlate's, so correlate -> softmax -> aggregate
+    needs nothing in between.  displacement / step as for 'correlate' (T <= 512, G T <= 4096).  A pixel is recomputed iff
+    w changed there or v changed at one of its window's taps.  Both operands must hold FINITE values (a 16-pixel group
+    multiplies the columns outside a pixel's own window by zero).  `other`, `gate`, `reverse` and `normalize` do not go
+    with it, `groups` goes with no other op; it has no conversion pass either."""
+
+    def __init__(self, op, other=None, gate=None, reverse=False, displacement=None, step=None, normalize=None,
+                 groups=None):
         super(CBBinary2d, self).__init__()
         window = dict(displacement=displacement, step=step, normalize=normalize)
-        if op == CORRELATE:
-            for key, given in (('other', other is not None), ('gate', gate is not None), ('reverse', bool(reverse))):
+        if op in (CORRELATE, AGGREGATE):
+            refused = (('other', other is not None), ('gate', gate is not None), ('reverse', bool(reverse)),
+                       ('groups', groups is not None) if op == CORRELATE else ('normalize', normalize is not None))
+            for key, given in refused:
                 if given:
-                    raise CBinferError("CBBinary2d: %s= does not go with op='correlate'" % key)
+                    raise CBinferError("CBBinary2d: %s= does not go with op=%r" % (key, op))
             self.op, self.gate, self.reverse = op, None, False
             self.displacement = 4 if displacement is None else displacement
             self.step = 1 if step is None else step
-            self.normalize = True if normalize is None else bool(normalize)
-            self.window = correlation_window(self.displacement, self.step)
+            if op == CORRELATE:
+                self.normalize = True if normalize is None else bool(normalize)
+                self.window = correlation_window(self.displacement, self.step)
+            else:
+                self.groups = 1 if groups is None else groups
+                self.window = correlation_window(self.displacement, self.step, "taps")
+                taps = self.window[4] * self.window[5]
+                if (not isinstance(self.groups, numbers.Integral) or isinstance(self.groups, bool) or
+                        not 1 <= self.groups <= MAX_WEIGHT_PLANES // taps):
+                    raise CBinferError("CBBinary2d: groups=%r must be an int >= 1 with groups x %d taps within %d weight "
+                                       "planes" % (self.groups, taps, MAX_WEIGHT_PLANES))
         else:
             for key, value in window.items():
                 if value is not None:
-                    raise CBinferError("CBBinary2d: %s= goes with op='correlate' only, not with op=%r" % (key, op))
+                    raise CBinferError("CBBinary2d: %s= goes with op='correlate' only, not with op=%r (displacement= and "
+                                       "step= with op='aggregate' as well)" % (key, op))
+            if groups is not None:
+                raise CBinferError("CBBinary2d: groups= goes with op='aggregate' only, not with op=%r" % (op,))
             self._set_function('CBBinary2d', op, gate, reverse)
         self.otherNumber = None
         self.hasOther = other is not None
@@ -230,9 +261,47 @@ class CBBinary2d(_CBBinaryBase):
                                               work['corr'], _lib.dtype_code(a), stream_ptr(a)))
         return self._result(work, H, W)
 
+    def _aggregate(self, w, v):
+        name = 'CBBinary2d'
+        if v is None:
+            raise CBinferError("CBBinary2d: forward(w, v) takes two operands")
+        w, iw = split_operand(name, w, 'operand w')
+        check_map(name, w, 'operand w')
+        v, iv = split_operand(name, v, 'operand v')
+        check_map(name, v, 'operand v')
+        if tuple(v.shape[2:]) != tuple(w.shape[2:]) or v.dtype != w.dtype or v.device != w.device:
+            raise CBinferError("CBBinary2d: the operands differ: w is %s %s on %s, v is %s %s on %s"
+                               % (tuple(w.shape), w.dtype, w.device, tuple(v.shape), v.dtype, v.device))
+        y0, y1, x0, x1, Dy, Dx = self.window
+        nc, H, W = v.size(1), v.size(2), v.size(3)
+        if w.size(1) != self.groups * Dy * Dx:
+            raise CBinferError("CBBinary2d: operand w has %d channels, groups=%d x %d x %d taps take %d"
+                               % (w.size(1), self.groups, Dy, Dx, self.groups * Dy * Dx))
+        if nc % self.groups:
+            raise CBinferError("CBBinary2d: groups=%d does not divide the %d channels of operand v" % (self.groups, nc))
+        require_device(w, v)
+
+        def make():
+            aggr = _lib.Aggr(y0, y1, x0, x1, self.step, self.groups)
+            if not C.cbinfer_aggregate_supported(ctypes.byref(aggr), nc, H, W):
+                raise CBinferError("CBBinary2d: aggregating %s maps is beyond the library's limits" % (tuple(v.shape),))
+            work = mask_workspace(H, W, w.device, nbits=2)      # (the output's working mask, then v's)
+            return dict(work, aggr=ctypes.pointer(aggr), vBits=work['bits'][work['copy'].numel():])
+        work = self._cached_work((AGGREGATE, nc, H, W, w.device), make)
+        fw = operand_changes(name, 'operand w', iw, H, W, w.device, work['idx'], words=_WORDS, maskWhenMade=False)
+        fv = operand_changes(name, 'operand v', iv, H, W, w.device, work['idx'], words=_WORDS, maskWhenMade=False)
+        if self._fresh_state((1, nc, H, W), v):      # (written completely: no change information is used)
+            fw = fv = EVERY_PIXEL
+        check(C.cbinfer_cbaggregate_forward(ptr(w), ptr(v), ptr(self.outputState), *form_args(fw), *form_args(fv),
+                                            ptr(work['vBits']), ptr(work['bits']), ptr(work['copy']), nc, H, W,
+                                            work['aggr'], _lib.dtype_code(w), stream_ptr(w)))
+        return self._result(work, H, W)
+
     def forward(self, a, b=None):
         if self.op == CORRELATE:
             return self._correlate(a, b)
+        if self.op == AGGREGATE:
+            return self._aggregate(a, b)
         if self.hasOther and b is not None:
             raise CBinferError("CBBinary2d: the module has a constant operand `other`: forward(a) takes one argument")
         if not self.hasOther and b is None:
@@ -268,6 +337,9 @@ class CBBinary2d(_CBBinaryBase):
         if self.op == CORRELATE:
             return 'CBBinary2d (op=correlate, displacement=%r, step=%d, normalize=%s, propChgIdxs=%s)' % (
                 self.displacement, self.step, self.normalize, self.propChangeIndexes)
+        if self.op == AGGREGATE:
+            return 'CBBinary2d (op=aggregate, displacement=%r, step=%d, groups=%d, propChgIdxs=%s)' % (
+                self.displacement, self.step, self.groups, self.propChangeIndexes)
         other = ('number %r' % self.otherNumber if self.otherNumber is not None else
                  tuple(self.other.shape) if self.other is not None else None)
         return 'CBBinary2d (op=%s, gate=%s, reverse=%s, other=%s, propChgIdxs=%s)' % (

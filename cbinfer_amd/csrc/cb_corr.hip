@@ -6,7 +6,7 @@
 // changed at one of the window's taps: recomputing there is the dense result exactly, without a threshold.  Unlike the
 // grid sampling this IS a contraction -- per displacement row a banded product of a^T with a strip of b over the
 // channel axis -- and runs on the matrix unit.  A frame is
-//   per operand in LIST form, one launch in front (cb_list_to_bits of cb_maskwalk.h): a's list into the working mask of
+//   per operand in LIST form, one launch in front (cbw_lists_to_bits of cb_window.h): a's list into the working mask of
 //              the output, b's into a working mask of its own;
 //   one launch, the whole-word walk of cb_maskwalk.h (cb_walk_word_units) over the output mask.  makeWord: a's mask
 //              word ORed with the windows of b's mask at every displacement -- the (i, j) shifts dealt over the 64 lanes
@@ -27,16 +27,12 @@
 //   for b in LIST form, one launch behind: zero to the words of b's working mask that the list named (the frame launch
 //              reads that mask from every workgroup, so it cannot clear it itself).
 // No host sync, memset, allocation, data atomics or inline assembly; all stores are plain vector stores.
-#include "cb_maskwalk.h"
+#include "cb_window.h"
 
 // (the one f32 operation outside the matrix unit is the multiply by the scale: nothing to contract, and it stays so)
 #pragma clang fp contract(off)
 
 namespace {
-
-#define CBC_MAXDISP 64
-#define CBC_MAXSTEP 8
-#define CBC_MAXCHAN 512
 
 struct cbc_geo {
     int C, H, W, y0, x0, step, Dy, Dx, NT;
@@ -105,33 +101,12 @@ __global__ __launch_bounds__(256) void cbc_corr_kernel(const T* __restrict__ a, 
     __shared__ float sBand[4][DXMAX][17];      // per wave [channel][pixel], a row padded by one bank
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long HW = (long)g.H * g.W;
+    const cbw_window win = {g.y0, g.x0, g.step, g.Dy, g.Dx};
     cb_walk_word_units(
         bits, maskCopy, words, g.W, wpr, all,
         [&](long w, int y, int tile) -> unsigned long long {
             if (all) return 0ull;
-            unsigned long long word = maskA ? maskA[w] : 0ull;
-            if (maskB) {      // (uniform over the workgroup)
-                unsigned long long m = 0ull;
-                const int shifts = g.Dy * g.Dx;
-                for (int e = lane; e < shifts; e += 64) {
-                    const int i = e / g.Dx, j = e - i * g.Dx;
-                    const int yy = y + g.y0 + i * g.step;
-                    if (yy < 0 || yy >= g.H) continue;
-                    // the 64 bits of b's mask row yy from column xs on: bit x' is the tap of pixel 64 tile + x'
-                    const int xs = tile * 64 + g.x0 + j * g.step;      // (>= -64)
-                    const int wi = xs >> 6, sh = xs & 63;
-                    const unsigned long long* row = maskB + (long)yy * wpr;
-                    const unsigned long long lo = (wi >= 0 && wi < wpr) ? row[wi] : 0ull;
-                    const unsigned long long hi = (sh != 0 && wi + 1 >= 0 && wi + 1 < wpr) ? row[wi + 1] : 0ull;
-                    m |= (lo >> sh) | (sh != 0 ? hi << (64 - sh) : 0ull);
-                }
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) m |= __shfl_xor(m, o);
-                const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)m);
-                const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(m >> 32));
-                word |= ((unsigned long long)hi << 32) | lo;
-            }
-            return word;
+            return cbw_footprint_word(maskA, maskB, w, y, tile, g.H, wpr, win, lane);
         },
         [&](unsigned long long word, int y, int tile) {
             const int xw = tile * 64;
@@ -207,20 +182,6 @@ __global__ __launch_bounds__(256) void cbc_corr_kernel(const T* __restrict__ a, 
         });
 }
 
-// behind a frame whose b came as a list: zero to the words of b's working mask that the list named (plain stores of
-// one value: entries that share a word do not matter)
-__global__ __launch_bounds__(256) void cbc_clear_list_kernel(const int32_t* __restrict__ list, int nHost,
-                                                            const int32_t* __restrict__ countDev, int H, int W, int wpr,
-                                                            unsigned long long* __restrict__ bBits) {
-    const int N = countDev ? min(*countDev, nHost) : nHost;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long)gridDim.x * blockDim.x) {
-        const int pos = list[i];
-        if ((unsigned)pos >= (unsigned)(H * W)) continue;      // (an out-of-map entry set no bit)
-        const int y = pos / W, x = pos - y * W;
-        bBits[(long)y * wpr + (x >> 6)] = 0ull;
-    }
-}
-
 template <typename T>
 void cbc_launch(const void* a, const void* b, void* out, const uint64_t* maskA, const uint64_t* maskB, int all,
                 uint64_t* bits, uint64_t* maskCopy, const cbc_geo& g, hipStream_t s) {
@@ -240,20 +201,13 @@ void cbc_launch(const void* a, const void* b, void* out, const uint64_t* maskA, 
 #undef CBC_GO
 }
 
-inline bool cbc_range_ok(int lo, int hi, int step) {
-    return lo >= -CBC_MAXDISP && hi <= CBC_MAXDISP && lo <= hi && (hi - lo) % step == 0;
-}
-
 }  // namespace
 
 int cbinfer_correlation_supported(const cbCorr* c, int C, int H, int W) {
     if (!c) return 0;
-    if (!(c->step >= 1 && c->step <= CBC_MAXSTEP && cbc_range_ok(c->y0, c->y1, c->step) &&
-          cbc_range_ok(c->x0, c->x1, c->step) && (c->normalize == 0 || c->normalize == 1)))
-        return 0;
-    const int Dy = (c->y1 - c->y0) / c->step + 1, Dx = (c->x1 - c->x0) / c->step + 1;
+    if (!(cbw_window_ok(c->y0, c->y1, c->x0, c->x1, c->step) && (c->normalize == 0 || c->normalize == 1))) return 0;
     // (a list addresses a pixel with an int32; C is within the other operators' limit)
-    return Dy * Dx <= CBC_MAXCHAN && C >= 1 && H >= 1 && W >= 1 && (long)H * W < (1l << 31) && (long)C * 64 < (1l << 31);
+    return C >= 1 && H >= 1 && W >= 1 && (long)H * W < (1l << 31) && (long)C * 64 < (1l << 31);
 }
 
 int cbinfer_cbcorrelation_forward(const void* a, const void* b, void* outputState, const uint64_t* maskA,
@@ -262,14 +216,11 @@ int cbinfer_cbcorrelation_forward(const void* a, const void* b, void* outputStat
                                   uint64_t* maskCopy, int C, int H, int W, const cbCorr* corr, int dtype,
                                   cbStream_t stream) {
     // (every argument is checked before the first launch)
+    const cbw_forms f = {maskA, listA, capA, countA, maskB, listB, capB, countB, bBits, bits, maskCopy};
     CB_REQUIRE(a && b && outputState && outputState != a && outputState != b);
-    CB_REQUIRE(bBits && bits && maskCopy && bBits != bits && bBits != maskCopy && bits != maskCopy);
+    CB_REQUIRE(cbw_forms_ok(f));
     CB_REQUIRE(dtype == CB_F32 || dtype == CB_F16);
     CB_REQUIRE(cbinfer_correlation_supported(corr, C, H, W));
-    CB_REQUIRE(capA >= 0 && !(maskA && listA) && (listA || !countA));
-    CB_REQUIRE(capB >= 0 && !(maskB && listB) && (listB || !countB));
-    CB_REQUIRE(maskA != bBits && maskA != bits && maskA != maskCopy);
-    CB_REQUIRE(maskB != bBits && maskB != bits && maskB != maskCopy);
     cbc_geo g;
     g.C = C, g.H = H, g.W = W, g.y0 = corr->y0, g.x0 = corr->x0, g.step = corr->step;
     g.Dy = (corr->y1 - corr->y0) / corr->step + 1;
@@ -277,25 +228,12 @@ int cbinfer_cbcorrelation_forward(const void* a, const void* b, void* outputStat
     g.NT = (16 + corr->x1 - corr->x0 + 15) / 16;      // (at most 9)
     g.scale = corr->normalize ? 1.f / (float)C : 1.f;
     const hipStream_t s = (hipStream_t)stream;
-    // an operand with neither mask nor list lists every pixel: the other's changes are not needed then
-    const int all = (!maskA && !listA) || (!maskB && !listB);
-    const bool bList = !all && listB && capB > 0;
-    if (!all && listA) {
-        const int st = cb_list_to_bits(listA, capA, countA, H, W, bits, stream);
-        if (st != CB_OK) return st;
-    }
-    if (bList) {
-        const int st = cb_list_to_bits(listB, capB, countB, H, W, bBits, stream);
-        if (st != CB_OK) return st;
-    }
-    const uint64_t* mA = all ? nullptr : maskA;
-    const uint64_t* mB = all ? nullptr : (maskB ? maskB : (bList ? bBits : nullptr));
-    cb_dispatch_dtype(dtype, [&](auto t) { cbc_launch<decltype(t)>(a, b, outputState, mA, mB, all, bits, maskCopy, g, s); });
-    const int st = cb_launch_status();
-    if (st != CB_OK || !bList) return st;
-    long blocks = ((long)capB + 255) / 256;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    hipLaunchKernelGGL(cbc_clear_list_kernel, dim3((unsigned)blocks), dim3(256), 0, s, listB, capB, countB, H, W,
-                       (W + 63) / 64, (unsigned long long*)bBits);
-    return cb_launch_status();
+    cbw_frame fr;
+    int st = cbw_lists_to_bits(f, H, W, stream, &fr);
+    if (st != CB_OK) return st;
+    cb_dispatch_dtype(dtype, [&](auto t) {
+        cbc_launch<decltype(t)>(a, b, outputState, fr.mA, fr.mB, fr.all, bits, maskCopy, g, s);
+    });
+    st = cb_launch_status();
+    return (st != CB_OK || !fr.bList) ? st : cbw_clear_list(f, H, W, s);
 }

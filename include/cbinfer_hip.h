@@ -81,7 +81,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_groupnorm_stats, cbinfer_groupnorm_changed, cbinfer_cbgroupnorm_forward) and the peak suppression (cbPeaks,
  * cbinfer_peaks_supported, cbinfer_peaks_changed, cbinfer_cbpeaks_forward, cbinfer_peaks_list) and the grid sampling
  * (cbWarp, CB_WARP_*, cbinfer_warp_supported, cbinfer_cbwarp_forward) and the correlation layer (cbCorr,
- * cbinfer_correlation_supported, cbinfer_cbcorrelation_forward). */
+ * cbinfer_correlation_supported, cbinfer_cbcorrelation_forward) and the per-pixel kernel application (cbAggr,
+ * cbinfer_aggregate_supported, cbinfer_cbaggregate_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1314,6 +1315,52 @@ int cbinfer_cbcorrelation_forward(const void* a, const void* b, void* outputStat
                                   const int32_t* listB, int capB, const int32_t* countB, uint64_t* bBits, uint64_t* bits,
                                   uint64_t* maskCopy, int C, int H, int W, const cbCorr* corr, int dtype,
                                   cbStream_t stream);
+
+/* ---- change-based per-pixel kernel application (cb_aggr.hip) ---------------------------------------------
+ * No counterpart in the reference.  The operator that takes a volume of per-pixel weights back to a feature map: the
+ * attn . V half of neighbourhood / local attention, the kernel application of kernel-prediction networks, CARAFE's
+ * reassembly, involution, dynamic-filter layers.  A window of displacements as the correlation layer's, T = Dy Dx taps,
+ * G = groups >= 1 dividing C; w is [G T, H, W], v and the state `out` are [C, H, W],
+ *   out[c, y, x] = sum over i < Dy, j < Dx of w[g(c) T + i Dx + j, y, x] * v[c, y + y0 + i step, x + x0 + j step],
+ * g(c) = c / (C / G): channel c uses the weight planes of its group, in the correlation layer's plane order (dy-major, dx
+ * fastest) -- a cost volume normalised per pixel is a valid w as it stands.  ZERO PADDING: a tap whose row or column lies
+ * outside the map contributes nothing (a pixel all of whose taps lie outside is +0).  w, v and `out` are contiguous, one
+ * dtype (CB_F32 or CB_F16), three different tensors.
+ *
+ * THIS SECTION IS THE SPECIFICATION.
+ *   FINITE OPERANDS: a 16-pixel group multiplies every column of the strip of v that its windows span, the columns
+ *     outside a pixel's own window by +0.  The contract therefore requires finite values in w and v; a non-finite v is
+ *     outside the specification (0 * inf would reach pixels whose window does not hold it).
+ *   listed pixels -- the exact footprint of the correlation layer with a := w, b := v: pixel p = (y, x) is listed iff w
+ *     changed at p, or v changed at a pixel p + (y0 + i step, x0 + j step) that lies in the map (with step > 1 the sparse
+ *     set, not its rectangle).  The three operand forms -- mask, list with or without a device count, none: EVERY pixel is
+ *     listed -- mean what they mean there.
+ *   arithmetic: the operands go to the matrix unit as they are (f32: v_mfma_f32_16x16x4_f32; f16:
+ *     v_mfma_f32_16x16x32_f16, whose products are exact in f32); products and sums in f32 on the matrix unit, displacement
+ *     rows ascending, columns ascending within a row; off-band weights, columns outside the map and the channel tail are
+ *     filled with +0; then ONE rounding to the dtype.  There is no scale.  DESIGN 5.34 has the error bound.
+ *   unit of work: a non-empty word of the frame's mask is four groups of 16 pixels; a group with a listed pixel is
+ *     computed whole and only its listed pixels are stored.  A pixel's bits therefore depend on its own operand values
+ *     and on x mod 16 alone, never on the other listed pixels or on the operands' forms.
+ *   launches and hand-on: as the correlation layer's, with w's list into `bits` and v's into `vBits`: one launch in front
+ *     per list, ONE launch for the frame, one launch behind it for a list of v; maskCopy receives the frame's mask every
+ *     frame, `bits` and `vBits` (cbinfer_mask_words(H, W) words each, zero on first use) are zero again when the frame
+ *     ends.  No host sync, memset, allocation or data atomics beyond the footprint launch's.
+ * Limits (cbinfer_aggregate_supported): -64 <= y0 <= y1 <= 64, -64 <= x0 <= x1 <= 64, 1 <= step <= 8 dividing y1 - y0 and
+ * x1 - x0, T <= 512, groups >= 1 dividing C, G T <= 4096, C, H, W >= 1, H W and 64 max(C, G T) within an int32.
+ * Bad arguments -- the correlation layer's list, with outputState == w or v and a cbAggr beyond the limits -- return
+ * CB_ERR_BADARG and launch nothing. */
+typedef struct cbAggr {
+    int y0, y1, x0, x1, step, groups;
+} cbAggr;
+/* host, pure: 1 if the kernel application on a [C, H, W] map is within the limits above, else 0 */
+int cbinfer_aggregate_supported(const cbAggr* aggr, int C, int H, int W);
+/* The whole frame of a change-based per-pixel kernel application enqueued without a host sync. */
+int cbinfer_cbaggregate_forward(const void* w, const void* v, void* outputState, const uint64_t* maskW,
+                                const int32_t* listW, int capW, const int32_t* countW, const uint64_t* maskV,
+                                const int32_t* listV, int capV, const int32_t* countV, uint64_t* vBits, uint64_t* bits,
+                                uint64_t* maskCopy, int C, int H, int W, const cbAggr* aggr, int dtype,
+                                cbStream_t stream);
 
 /* ---- change-based pixel shuffle, pixel unshuffle and channel shuffle (cb_rearrange.hip) -----------------
  * No counterpart in the reference.  The three operators compute nothing: values are copied bit for bit, never converted,
