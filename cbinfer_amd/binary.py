@@ -1,7 +1,8 @@
 """Change-based operators of two maps: CBBinary2d, CBGLU2d, CBGated and insertCBGating (cb_binary.hip),
 CBBinary2d('correlate'), the correlation layer / cost volume of flow and stereo networks (cb_corr.hip), and
 CBBinary2d('aggregate'), the per-pixel kernel application that takes such a volume back to a feature map (cb_aggr.hip,
-DESIGN 5.34).
+DESIGN 5.34), and CBBinary2d('deform'), the deformable convolution of a feature map and an offset field (cb_deform.hip,
+DESIGN 5.35).
 
 The reference has no element-wise operator of two maps, and CBAdd2d is the sum alone: a gate `feat * sigmoid(gate)`, a
 layer scale `gamma[c] * x`, a residual by difference `x - net(x)`, an element-wise maximum or an nn.GLU over the
@@ -25,9 +26,11 @@ from .residual import _sequential
 _OPS = {'add': _lib.BIN_ADD, 'sub': _lib.BIN_SUB, 'mul': _lib.BIN_MUL, 'maximum': _lib.BIN_MAXIMUM,
         'minimum': _lib.BIN_MINIMUM}
 _GATES = {None: _lib.BIN_GATE_NONE, 'sigmoid': _lib.BIN_GATE_SIGMOID, 'hardsigmoid': _lib.BIN_GATE_HARDSIGMOID}
-# the correlation layer and the per-pixel kernel application have entry points of their own and no CB_BIN_* code
-# (cb_corr.hip, cb_aggr.hip)
-CORRELATE, AGGREGATE = 'correlate', 'aggregate'
+# the correlation layer, the per-pixel kernel application and the deformable convolution have entry points of their own
+# and no CB_BIN_* code (cb_corr.hip, cb_aggr.hip, cb_deform.hip)
+CORRELATE, AGGREGATE, DEFORM = 'correlate', 'aggregate', 'deform'
+_MODULATIONS = {None: _lib.DEFORM_NONE, 'planes': _lib.DEFORM_PLANES, 'sigmoid': _lib.DEFORM_SIGMOID}
+_DEFORM_KEYS = ('weight', 'bias', 'stride', 'padding', 'dilation', 'offsetGroups', 'modulation', 'relu')
 MAX_DISPLACEMENT, MAX_STEP, MAX_CORR_CHANNELS, MAX_WEIGHT_PLANES = 64, 8, 512, 4096
 
 
@@ -77,7 +80,7 @@ class _CBBinaryBase(CBStateModule):
     def _set_function(self, name, op, gate, reverse):
         if op not in _OPS:
             raise CBinferError("%s: op=%r is not supported, only one of %s"
-                               % (name, op, ", ".join(repr(k) for k in list(_OPS) + [CORRELATE, AGGREGATE])))
+                               % (name, op, ", ".join(repr(k) for k in list(_OPS) + [CORRELATE, AGGREGATE, DEFORM])))
         if gate not in _GATES:
             raise CBinferError("%s: gate=%r is not supported, only None, 'sigmoid' or 'hardsigmoid'" % (name, gate))
         self.op, self.gate, self.reverse = op, gate, bool(reverse)
@@ -148,12 +151,46 @@ class CBBinary2d(_CBBinaryBase):
     needs nothing in between.  displacement / step as for 'correlate' (T <= 512, G T <= 4096).  A pixel is recomputed iff
     w changed there or v changed at one of its window's taps.  Both operands must hold FINITE values (a 16-pixel group
     multiplies the columns outside a pixel's own window by zero).  `other`, `gate`, `reverse` and `normalize` do not go
-    with it, `groups` goes with no other op; it has no conversion pass either."""
+    with it, `groups` goes with no other op; it has no conversion pass either.
+
+    op='deform' -- CBBinary2d('deform', weight=W, bias=None, stride=1, padding=0, dilation=1, offsetGroups=1,
+    modulation=None, relu=False), forward(x, field) -- is the deformable convolution (DCNv1 / DCNv2:
+    torchvision.ops.deform_conv2d, mmcv's ModulatedDeformConv2d) on the matrix cores (cb_deform.hip).  W is
+    [K, C, kH, kW] and bias [K] or None, both COPIED into buffers that follow .to() / .half(); x is [1, C, Hi, Wi], the
+    state [1, K, Ho, Wo] with the convolution's output size.  field is [1, F, Ho, Wo], float32 or float16 whatever x is:
+    first the 2 Go T offset planes (T = kH kW, Go = offsetGroups dividing C; plane 2 (g T + t) is dy, the next one dx for
+    tap t = ky kW + kx: torchvision's and mmcv's layout), then by modulation= nothing (None, F = 2 Go T), Go T multiplier
+    planes ('planes', F = 3 Go T: torchvision's mask behind the offsets) or the same planes before their sigmoid
+    ('sigmoid': mmcv's DCNv2 block, whose conv_offset output is this field as it stands),
+        out[k, oy, ox] = bias[k] + sum_{c, t} W[k, c, t] m[g(c) T + t, oy, ox]
+                                              S(x[c], oy sH - pH + ky dH + dy, ox sW - pW + kx dW + dx),
+    S the bilinear sample in which a tap outside the map contributes nothing.  A pixel is recomputed iff the field changed
+    there or x changed at one of its taps that count; the handed-on mask is that footprint on the OUTPUT map.  One weight
+    group only; the keywords of the other ops do not go with it and its own go with no other op; it has no conversion
+    pass either."""
 
     def __init__(self, op, other=None, gate=None, reverse=False, displacement=None, step=None, normalize=None,
-                 groups=None):
+                 groups=None, weight=None, bias=None, stride=None, padding=None, dilation=None, offsetGroups=None,
+                 modulation=None, relu=False):
         super(CBBinary2d, self).__init__()
         window = dict(displacement=displacement, step=step, normalize=normalize)
+        own = dict(zip(_DEFORM_KEYS, (weight, bias, stride, padding, dilation, offsetGroups, modulation, relu or None)))
+        if op == DEFORM:
+            refused = dict(window, other=other, gate=gate, reverse=reverse or None)
+            for key, value in refused.items():
+                if value is not None:
+                    raise CBinferError("CBBinary2d: %s= does not go with op=%r" % (key, op))
+            if groups not in (None, 1):
+                raise CBinferError("CBBinary2d: groups=%r: op='deform' takes one weight group only (offsetGroups= are the "
+                                   "offset field's groups)" % (groups,))
+            self.op, self.gate, self.reverse = op, None, False
+            self._set_deform(weight, bias, stride, padding, dilation, offsetGroups, modulation, relu)
+            self._buffers['outputState'] = self._buffers.pop('outputState')
+            self.otherNumber, self.hasOther, self._deformPrep = None, False, None
+            return
+        for key, value in own.items():
+            if value is not None:
+                raise CBinferError("CBBinary2d: %s= goes with op='deform' only, not with op=%r" % (key, op))
         if op in (CORRELATE, AGGREGATE):
             refused = (('other', other is not None), ('gate', gate is not None), ('reverse', bool(reverse)),
                        ('groups', groups is not None) if op == CORRELATE else ('normalize', normalize is not None))
@@ -231,6 +268,103 @@ class CBBinary2d(_CBBinaryBase):
         raise CBinferError("CBBinary2d: the constant operand `other` has shape %s, operand a is %s"
                            % (shape, tuple(a.shape)))
 
+    def _set_deform(self, weight, bias, stride, padding, dilation, offsetGroups, modulation, relu):
+        def whole(n):
+            return isinstance(n, numbers.Integral) and not isinstance(n, bool)
+
+        def pair(key, v, default):
+            v = default if v is None else v
+            v = (v, v) if whole(v) else v
+            if not (isinstance(v, (tuple, list)) and len(v) == 2 and all(whole(n) for n in v)):
+                raise CBinferError("CBBinary2d: %s=%r must be an int or a pair of ints" % (key, v))
+            return int(v[0]), int(v[1])
+        if not torch.is_tensor(weight) or weight.dim() != 4 or weight.numel() == 0:
+            raise CBinferError("CBBinary2d: op='deform' takes weight=, a [K, C, kH, kW] tensor, got %s"
+                               % (tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__,))
+        if weight.dtype not in (torch.float32, torch.float16):
+            raise CBinferError("CBBinary2d: weight must be a float32 or float16 tensor, got %s" % weight.dtype)
+        K, Cin, kH, kW = weight.shape
+        if bias is not None and (not torch.is_tensor(bias) or tuple(bias.shape) != (K,) or bias.dtype != weight.dtype):
+            raise CBinferError("CBBinary2d: bias must be a [%d] tensor of the weight's dtype or None" % K)
+        if modulation not in _MODULATIONS:
+            raise CBinferError("CBBinary2d: modulation=%r is not supported, only None, 'planes' or 'sigmoid'"
+                               % (modulation,))
+        Go = 1 if offsetGroups is None else offsetGroups
+        if not whole(Go) or not 1 <= Go <= 16:
+            raise CBinferError("CBBinary2d: offsetGroups=%r must be an int in 1 .. 16" % (offsetGroups,))
+        if Cin % Go:
+            raise CBinferError("CBBinary2d: offsetGroups=%d does not divide the %d input channels of weight" % (Go, Cin))
+        self.stride, self.padding, self.dilation = (pair('stride', stride, 1), pair('padding', padding, 0),
+                                                    pair('dilation', dilation, 1))
+        self.offsetGroups, self.modulation, self.relu = int(Go), modulation, bool(relu)
+        self.register_buffer('weight', weight.detach().clone().contiguous())
+        self.register_buffer('bias', None if bias is None else bias.detach().clone().contiguous())
+        if C.cbinfer_deform_prepared_weights_bytes(K, Cin, ctypes.byref(self._deform_struct(_lib.CB_F32)),
+                                                   _lib.CB_F32) <= 0:
+            raise CBinferError("CBBinary2d: kernel %dx%d stride=%s padding=%s dilation=%s is beyond what the library takes "
+                               "(per axis: filter <= 7, stride <= 4, dilation <= 8, padding <= 64)"
+                               % (kH, kW, self.stride, self.padding, self.dilation))
+
+    def _deform_struct(self, fieldCode):
+        kH, kW = self.weight.shape[2:]
+        geom = _lib.Geom(kH, kW, *(self.stride + self.padding + self.dilation))
+        return _lib.Deform(geom, self.offsetGroups, _MODULATIONS[self.modulation], fieldCode, int(self.relu))
+
+    def _deform_forward(self, x, field):
+        name = 'CBBinary2d'
+        if field is None:
+            raise CBinferError("CBBinary2d: forward(x, field) takes two operands")
+        x, ix = split_operand(name, x, 'operand x')
+        check_map(name, x, 'operand x')
+        field, ifield = split_operand(name, field, 'the field')
+        check_map(name, field, 'the field')
+        w = self.weight
+        K, Cin, kH, kW = w.shape
+        if x.size(1) != Cin:
+            raise CBinferError("CBBinary2d: operand x has %d channels, the weight takes %d" % (x.size(1), Cin))
+        if w.dtype != x.dtype or w.device != x.device or field.device != x.device:
+            raise CBinferError("CBBinary2d: operand x is %s on %s, the weight %s on %s, the field on %s (move the module "
+                               "with .to() / .half())" % (x.dtype, x.device, w.dtype, w.device, field.device))
+        Hi, Wi = x.size(2), x.size(3)
+        planes = (2 if self.modulation is None else 3) * self.offsetGroups * kH * kW
+        if field.size(1) != planes:
+            raise CBinferError("CBBinary2d: the field has %d channels, offsetGroups=%d x %d x %d taps with modulation=%r "
+                               "take %d" % (field.size(1), self.offsetGroups, kH, kW, self.modulation, planes))
+        d = self._deform_struct(_lib.dtype_code(field))
+        Ho, Wo = ctypes.c_int(), ctypes.c_int()
+        if (C.cbinfer_geom_out_size(Hi, Wi, ctypes.byref(d.geom), ctypes.byref(Ho), ctypes.byref(Wo)) != 0 or
+                not C.cbinfer_deform_supported(ctypes.byref(d), Cin, Hi, Wi, K)):
+            raise CBinferError("CBBinary2d: the deformable convolution of a %s map to %d channels is beyond the "
+                               "library's limits" % (tuple(x.shape), K))
+        Ho, Wo = Ho.value, Wo.value
+        if tuple(field.shape[2:]) != (Ho, Wo):
+            raise CBinferError("CBBinary2d: the field is a %dx%d map, the output map of a %dx%d input is %dx%d"
+                               % (field.size(2), field.size(3), Hi, Wi, Ho, Wo))
+        require_device(x, field)
+
+        def make():
+            # (the output's working mask, x's on its own map, the shared split-k workspace with its zero counters)
+            return dict(mask_workspace(Ho, Wo, x.device), deform=ctypes.pointer(d),
+                        inBits=torch.zeros(C.cbinfer_mask_words(Hi, Wi), dtype=torch.int64, device=x.device),
+                        conv=torch.zeros(C.cbinfer_geom_workspace_bytes(), dtype=torch.uint8, device=x.device))
+        work = self._cached_work((DEFORM, Cin, Hi, Wi, field.dtype, x.device), make)
+        key = (w.data_ptr(), w._version, w.dtype, w.device)
+        if self._deformPrep is None or self._deformPrep[0] != key:
+            code = _lib.dtype_code(w)
+            wp = torch.empty(C.cbinfer_deform_prepared_weights_bytes(K, Cin, work['deform'], code), dtype=torch.uint8,
+                             device=w.device)
+            check(C.cbinfer_deform_prep_weights(ptr(w), ptr(wp), K, Cin, work['deform'], code, stream_ptr(w)))
+            self._deformPrep = (key, wp)
+        fx = operand_changes(name, 'operand x', ix, Hi, Wi, x.device, work['idx'], words=_WORDS, maskWhenMade=False)
+        ff = operand_changes(name, 'the field', ifield, Ho, Wo, x.device, work['idx'], words=_WORDS, maskWhenMade=False)
+        if self._fresh_state((1, K, Ho, Wo), x):      # (written completely: no change information is used)
+            fx = ff = EVERY_PIXEL
+        check(C.cbinfer_cbdeform_forward(ptr(x), ptr(field), ptr(self._deformPrep[1]), ptr(self.bias),
+                                         ptr(self.outputState), *form_args(fx), *form_args(ff), ptr(work['inBits']),
+                                         ptr(work['bits']), ptr(work['copy']), ptr(work['conv']), Cin, Hi, Wi, K,
+                                         work['deform'], _lib.dtype_code(x), stream_ptr(x)))
+        return self._result(work, Ho, Wo)
+
     def _correlate(self, a, b):
         name = 'CBBinary2d'
         if b is None:
@@ -302,6 +436,8 @@ class CBBinary2d(_CBBinaryBase):
             return self._correlate(a, b)
         if self.op == AGGREGATE:
             return self._aggregate(a, b)
+        if self.op == DEFORM:
+            return self._deform_forward(a, b)
         if self.hasOther and b is not None:
             raise CBinferError("CBBinary2d: the module has a constant operand `other`: forward(a) takes one argument")
         if not self.hasOther and b is None:
@@ -340,6 +476,12 @@ class CBBinary2d(_CBBinaryBase):
         if self.op == AGGREGATE:
             return 'CBBinary2d (op=aggregate, displacement=%r, step=%d, groups=%d, propChgIdxs=%s)' % (
                 self.displacement, self.step, self.groups, self.propChangeIndexes)
+        if self.op == DEFORM:
+            K, Cin, kH, kW = self.weight.shape
+            return ('CBBinary2d (op=deform, %d -> %d, kernel=%dx%d, stride=%s, padding=%s, dilation=%s, offsetGroups=%d, '
+                    'modulation=%s, bias=%s, relu=%s, propChgIdxs=%s)' % (
+                        Cin, K, kH, kW, self.stride, self.padding, self.dilation, self.offsetGroups, self.modulation,
+                        self.bias is not None, self.relu, self.propChangeIndexes))
         other = ('number %r' % self.otherNumber if self.otherNumber is not None else
                  tuple(self.other.shape) if self.other is not None else None)
         return 'CBBinary2d (op=%s, gate=%s, reverse=%s, other=%s, propChgIdxs=%s)' % (

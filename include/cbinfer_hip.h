@@ -82,7 +82,9 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_peaks_supported, cbinfer_peaks_changed, cbinfer_cbpeaks_forward, cbinfer_peaks_list) and the grid sampling
  * (cbWarp, CB_WARP_*, cbinfer_warp_supported, cbinfer_cbwarp_forward) and the correlation layer (cbCorr,
  * cbinfer_correlation_supported, cbinfer_cbcorrelation_forward) and the per-pixel kernel application (cbAggr,
- * cbinfer_aggregate_supported, cbinfer_cbaggregate_forward). */
+ * cbinfer_aggregate_supported, cbinfer_cbaggregate_forward) and the deformable convolution (cbDeform, CB_DEFORM_*,
+ * cbinfer_deform_supported, cbinfer_deform_prepared_weights_bytes, cbinfer_deform_prep_weights,
+ * cbinfer_cbdeform_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1361,6 +1363,77 @@ int cbinfer_cbaggregate_forward(const void* w, const void* v, void* outputState,
                                 const int32_t* listV, int capV, const int32_t* countV, uint64_t* vBits, uint64_t* bits,
                                 uint64_t* maskCopy, int C, int H, int W, const cbAggr* aggr, int dtype,
                                 cbStream_t stream);
+
+/* ---- change-based deformable convolution (cb_deform.hip) --------------------------------------------------
+ * No counterpart in the reference.  DCNv1 / DCNv2 (torchvision.ops.deform_conv2d, mmcv's ModulatedDeformConv2d): the
+ * alignment modules of deformable video-restoration networks, DCN backbones, CenterNet-type heads.  x is [C, Hi, Wi], the
+ * weight [K, C, kH, kW] (one weight group), the state `out` [K, Ho, Wo] with Ho, Wo by cbinfer_geom_out_size; T = kH kW
+ * filter taps t = ky kW + kx, Go = offsetGroups dividing C, g(c) = c / (C / Go).  The field is [F, Ho, Wo]: first the
+ * 2 Go T offset planes -- plane 2 (g T + t) is dy, the next one dx, torchvision's and mmcv's layout -- and then, by
+ * `modulation`,
+ *   CB_DEFORM_NONE     nothing, F = 2 Go T, m = 1 and no multiply;
+ *   CB_DEFORM_PLANES   Go T multiplier planes, F = 3 Go T, m = plane 2 Go T + g T + t (torchvision's mask);
+ *   CB_DEFORM_SIGMOID  the same planes, m = sigmoid of them (mmcv's DCNv2 block on the 3 T planes of conv_offset).
+ *   out[k, oy, ox] = bias[k] + sum over c, t of W[k, c, t] * m[g(c), t, oy, ox]
+ *                                              * S(x[c], oy sH - pH + ky dH + dy, ox sW - pW + kx dW + dx),
+ * S the bilinear sample in which a tap outside the map contributes nothing.  x, the prepared weights, bias and `out` have
+ * one dtype (CB_F32 or CB_F16); the field has its own (fieldDtype), loaded exactly to f32, as cbWarp's coordDtype.
+ *
+ * THIS SECTION IS THE SPECIFICATION; it cites the grid-sampling section above instead of restating it.
+ *   coordinates: per axis base = o s - p + k d, an int that is exact in f32; s = (float)base + d, ONE f32 addition, then
+ *     the clamp of the grid sampling (L = 2^20, a NaN goes to -L and samples nothing).
+ *   sample: taps, the "counts" rule and weights are CB_WARP_BILINEAR with CB_WARP_ZEROS, in the written order: the four
+ *     weight products, acc = acc + w * p from +0 over the taps that count in the order nw, ne, sw, se, never an FMA.  A
+ *     tap that does not count is not read.
+ *   modulation: ONE more f32 multiply, sample * m (none with CB_DEFORM_NONE).  CB_DEFORM_SIGMOID evaluates
+ *     m = 1 / (1 + expf(-v)) in f32 as cb_binary.hip's sigmoid gate does, not rounded further, once per (pixel, group,
+ *     tap and 8-channel run).
+ *   contraction: the modulated sample is the pixel operand of the general-geometry layer's arithmetic.
+ *     CB_F32: the f32 sample as a bf16 triple, six products, f32 accumulation (CB_F32S's); CB_F16: the sample rounded
+ *     to f16 ONCE, then the f16 MFMA.  k is tap-major, (t, c) with C padded to 32 per tap by +0 weights; a padded k-slot
+ *     reads nothing.  Then bias, ReLU (relu != 0) and one rounding.  A short list is split along k over idle workgroups
+ *     exactly as cbinfer_conv_changed_geom splits it, summed in slice order: the number of slices is a function of the
+ *     NUMBER of listed pixels, K and C T alone.
+ *   listed pixels -- the exact footprint: (oy, ox) is listed iff the field is listed there, or any tap of it that counts
+ *     -- over all groups, filter taps and the four corners -- is listed in x's changes; a zero weight or a zero
+ *     multiplier does not matter.  The three operand forms (mask -- x's on the Hi x Wi map, the field's on Ho x Wo --,
+ *     list, none: EVERY pixel is listed) mean what they mean for the grid sampling.  A pixel's bits depend on its own
+ *     operand values and on the number of k-slices at most, never on WHICH other pixels are listed, on its place in a
+ *     tile or on the operands' forms.
+ *   launches: one launch in front per list (cbinfer_pool_footprint, 1x1 window: x's into `inBits`, the field's into
+ *     `bits`); TWO launches for the frame -- the footprint, which leaves the frame's mask in maskCopy, and the sampled
+ *     contraction, which reads it there --; one launch behind for a list of x, which clears `inBits`.  No host sync,
+ *     memset or allocation.
+ *   hand-on: maskCopy (cbinfer_mask_words(Ho, Wo) words) receives the frame's mask every frame; `inBits`
+ *     (cbinfer_mask_words(Hi, Wi) words) and `bits` (cbinfer_mask_words(Ho, Wo) words), zero on first use, are zero again
+ *     when the frame ends.  Unlisted pixels keep their bits; bits of the row padding are never set.
+ *   prepared weights: cbinfer_deform_prep_weights writes cbinfer_deform_prepared_weights_bytes bytes, W[Kpad64][T][Cpad32]
+ *     in the tensors' element type.  workspace: cbinfer_geom_workspace_bytes() bytes under that function's contract (the
+ *     arrival counters zero on first use and left zero).
+ * Limits (cbinfer_deform_supported): cbGeom's per axis (k <= 7, s <= 4, d <= 8, p <= 64); offsetGroups in 1 .. 16 dividing
+ * C; modulation one of the enumerators; fieldDtype CB_F32 or CB_F16; relu 0 or 1; Hi, Wi, Ho, Wo in 1 .. 2^15 - 1;
+ * 4 C Hi Wi < 2^30, K Ho Wo < 2^31, T Cpad32 < 2^24, K < 2^20.
+ * Bad arguments (the grid sampling's list -- a null tensor or mask buffer, outputState == x or field, an unknown dtype, a
+ * cbDeform beyond the limits, a capacity < 0, both a mask and a list for one operand, a count without a list, two of
+ * inBits / bits / maskCopy equal, an operand's mask equal to one of them --, null prepared weights, a null workspace)
+ * return CB_ERR_BADARG and launch nothing.  bias may be NULL. */
+enum { CB_DEFORM_NONE, CB_DEFORM_PLANES, CB_DEFORM_SIGMOID };
+typedef struct cbDeform {
+    cbGeom geom;
+    int offsetGroups, modulation, fieldDtype, relu;
+} cbDeform;
+/* host, pure: 1 if the deformable convolution of a [C, Hi, Wi] map to K channels is within the limits above, else 0 */
+int cbinfer_deform_supported(const cbDeform* deform, int C, int Hi, int Wi, int K);
+/* host, pure: 0 for a rejected geometry or dtype */
+long cbinfer_deform_prepared_weights_bytes(int K, int C, const cbDeform* deform, int dtype);
+int cbinfer_deform_prep_weights(const void* weight, void* prepared, int K, int C, const cbDeform* deform, int dtype,
+                                cbStream_t stream);
+/* The whole frame of a change-based deformable convolution enqueued without a host sync. */
+int cbinfer_cbdeform_forward(const void* x, const void* field, const void* preparedW, const void* bias, void* outputState,
+                             const uint64_t* maskX, const int32_t* listX, int capX, const int32_t* countX,
+                             const uint64_t* maskF, const int32_t* listF, int capF, const int32_t* countF,
+                             uint64_t* inBits, uint64_t* bits, uint64_t* maskCopy, void* workspace, int C, int Hi, int Wi,
+                             int K, const cbDeform* deform, int dtype, cbStream_t stream);
 
 /* ---- change-based pixel shuffle, pixel unshuffle and channel shuffle (cb_rearrange.hip) -----------------
  * No counterpart in the reference.  The three operators compute nothing: values are copied bit for bit, never converted,
