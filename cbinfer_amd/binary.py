@@ -2,7 +2,8 @@
 CBBinary2d('correlate'), the correlation layer / cost volume of flow and stereo networks (cb_corr.hip), and
 CBBinary2d('aggregate'), the per-pixel kernel application that takes such a volume back to a feature map (cb_aggr.hip,
 DESIGN 5.34), and CBBinary2d('deform'), the deformable convolution of a feature map and an offset field (cb_deform.hip,
-DESIGN 5.35).
+DESIGN 5.35), and CBBinary2d('attend'), local attention -- scores, softmax and weighted sum -- in one kernel
+(cb_attend.hip).
 
 The reference has no element-wise operator of two maps, and CBAdd2d is the sum alone: a gate `feat * sigmoid(gate)`, a
 layer scale `gamma[c] * x`, a residual by difference `x - net(x)`, an element-wise maximum or an nn.GLU over the
@@ -26,9 +27,11 @@ from .residual import _sequential
 _OPS = {'add': _lib.BIN_ADD, 'sub': _lib.BIN_SUB, 'mul': _lib.BIN_MUL, 'maximum': _lib.BIN_MAXIMUM,
         'minimum': _lib.BIN_MINIMUM}
 _GATES = {None: _lib.BIN_GATE_NONE, 'sigmoid': _lib.BIN_GATE_SIGMOID, 'hardsigmoid': _lib.BIN_GATE_HARDSIGMOID}
-# the correlation layer, the per-pixel kernel application and the deformable convolution have entry points of their own
-# and no CB_BIN_* code (cb_corr.hip, cb_aggr.hip, cb_deform.hip)
-CORRELATE, AGGREGATE, DEFORM = 'correlate', 'aggregate', 'deform'
+# the correlation layer, the per-pixel kernel application, the deformable convolution and the fused local attention have
+# entry points of their own and no CB_BIN_* code (cb_corr.hip, cb_aggr.hip, cb_deform.hip, cb_attend.hip)
+CORRELATE, AGGREGATE, DEFORM, ATTEND = 'correlate', 'aggregate', 'deform', 'attend'
+_BORDERS = {'mask': _lib.ATTEND_MASK, 'zero': _lib.ATTEND_ZERO}
+MAX_ATTEND_SPAN, MAX_HEAD_CHANNELS, MAX_HEADS = 48, 128, 64
 _MODULATIONS = {None: _lib.DEFORM_NONE, 'planes': _lib.DEFORM_PLANES, 'sigmoid': _lib.DEFORM_SIGMOID}
 _DEFORM_KEYS = ('weight', 'bias', 'stride', 'padding', 'dilation', 'offsetGroups', 'modulation', 'relu')
 MAX_DISPLACEMENT, MAX_STEP, MAX_CORR_CHANNELS, MAX_WEIGHT_PLANES = 64, 8, 512, 4096
@@ -80,7 +83,7 @@ class _CBBinaryBase(CBStateModule):
     def _set_function(self, name, op, gate, reverse):
         if op not in _OPS:
             raise CBinferError("%s: op=%r is not supported, only one of %s"
-                               % (name, op, ", ".join(repr(k) for k in list(_OPS) + [CORRELATE, AGGREGATE, DEFORM])))
+                               % (name, op, ", ".join(repr(k) for k in list(_OPS) + [CORRELATE, AGGREGATE, DEFORM, ATTEND])))
         if gate not in _GATES:
             raise CBinferError("%s: gate=%r is not supported, only None, 'sigmoid' or 'hardsigmoid'" % (name, gate))
         self.op, self.gate, self.reverse = op, gate, bool(reverse)
@@ -167,12 +170,36 @@ class CBBinary2d(_CBBinaryBase):
     S the bilinear sample in which a tap outside the map contributes nothing.  A pixel is recomputed iff the field changed
     there or x changed at one of its taps that count; the handed-on mask is that footprint on the OUTPUT map.  One weight
     group only; the keywords of the other ops do not go with it and its own go with no other op; it has no conversion
-    pass either."""
+    pass either.
+
+    op='attend' -- CBBinary2d('attend', displacement=4, step=1, heads=1, scale=None, border='mask', positionBias=None),
+    forward(q, kv) -- is local / neighbourhood attention (SASA, NAT-type blocks, HaloNet-style heads, local cross-frame
+    attention) as ONE kernel on the matrix cores (cb_attend.hip): what correlate -> softmax -> aggregate
+    compute, without the volume of heads x T score planes, which stays in a wave's registers.  q is [1, C, H, W]; kv is
+    [1, C + Cv, H, W] of the same H, W, dtype and device, its first C channels k and the remaining Cv channels v -- the kv
+    projection as ONE convolution and one change list (separately produced k and v go through CBConcat2d); the state is
+    [1, Cv, H, W].  heads divides C and Cv, d = C / heads, dv = Cv / heads, head h owns channels h d .. of q and k and
+    h dv .. of v and out:
+        s[h, t] = scale sum_c q[h d + c, y, x] k[h d + c, y + dy_t, x + dx_t] (+ positionBias[h, t]),
+        out[h dv + c, y, x] = sum_t softmax_t(s[h, .]) v[h dv + c, y + dy_t, x + dx_t],
+    t = i Dx + j in correlate's tap order.  scale: a float, default d ** -0.5.  positionBias: None or a constant
+    [heads, Dy Dx] / [heads, Dy, Dx] tensor (the relative position bias of NAT / Swin-type blocks), COPIED into a float32
+    buffer that follows .to() and stays float32 under .half().  border='mask': a tap outside the map takes no part in the
+    softmax (a pixel without any tap is +0); border='zero': such a tap has score 0 (plus its bias) and value 0, which is
+    what the hand-wired correlate -> softmax -> aggregate chain computes.  displacement / step as for 'correlate' with
+    x1 - x0 <= 48; d, dv <= 128; heads <= 64.  A pixel is recomputed iff q changed there or kv changed at one of its
+    window's in-map taps.  Both operands must hold FINITE values, as for 'aggregate'.  `other`, `gate`, `reverse`,
+    `normalize`, `groups` and the keywords of 'deform' do not go with it, its own go with no other op; it has no
+    conversion pass either."""
 
     def __init__(self, op, other=None, gate=None, reverse=False, displacement=None, step=None, normalize=None,
                  groups=None, weight=None, bias=None, stride=None, padding=None, dilation=None, offsetGroups=None,
-                 modulation=None, relu=False):
+                 modulation=None, relu=False, heads=None, scale=None, border=None, positionBias=None):
         super(CBBinary2d, self).__init__()
+        if op != ATTEND:
+            for key, value in dict(heads=heads, scale=scale, border=border, positionBias=positionBias).items():
+                if value is not None:
+                    raise CBinferError("CBBinary2d: %s= is a setting of op='attend', op=%r does not take it" % (key, op))
         window = dict(displacement=displacement, step=step, normalize=normalize)
         own = dict(zip(_DEFORM_KEYS, (weight, bias, stride, padding, dilation, offsetGroups, modulation, relu or None)))
         if op == DEFORM:
@@ -191,6 +218,16 @@ class CBBinary2d(_CBBinaryBase):
         for key, value in own.items():
             if value is not None:
                 raise CBinferError("CBBinary2d: %s= goes with op='deform' only, not with op=%r" % (key, op))
+        if op == ATTEND:
+            refused = dict(other=other, gate=gate, reverse=reverse or None, normalize=normalize, groups=groups)
+            for key, value in refused.items():
+                if value is not None:
+                    raise CBinferError("CBBinary2d: %s= does not go with op=%r" % (key, op))
+            self.op, self.gate, self.reverse = op, None, False
+            self._set_attend(displacement, step, heads, scale, border, positionBias)
+            self._buffers['outputState'] = self._buffers.pop('outputState')
+            self.otherNumber, self.hasOther = None, False
+            return
         if op in (CORRELATE, AGGREGATE):
             refused = (('other', other is not None), ('gate', gate is not None), ('reverse', bool(reverse)),
                        ('groups', groups is not None) if op == CORRELATE else ('normalize', normalize is not None))
@@ -365,6 +402,91 @@ class CBBinary2d(_CBBinaryBase):
                                          work['deform'], _lib.dtype_code(x), stream_ptr(x)))
         return self._result(work, Ho, Wo)
 
+    def _set_attend(self, displacement, step, heads, scale, border, positionBias):
+        self.displacement = 4 if displacement is None else displacement
+        self.step = 1 if step is None else step
+        self.window = correlation_window(self.displacement, self.step, "taps")
+        y0, y1, x0, x1, Dy, Dx = self.window
+        if x1 - x0 > MAX_ATTEND_SPAN:
+            raise CBinferError("CBBinary2d: displacement=%r: op='attend' takes a column range x1 - x0 of %d at most, "
+                               "got %d" % (self.displacement, MAX_ATTEND_SPAN, x1 - x0))
+        self.heads = 1 if heads is None else heads
+        if (not isinstance(self.heads, numbers.Integral) or isinstance(self.heads, bool) or
+                not 1 <= self.heads <= MAX_HEADS):
+            raise CBinferError("CBBinary2d: heads=%r must be an int in 1 .. %d" % (heads, MAX_HEADS))
+        if scale is not None and (not isinstance(scale, numbers.Real) or isinstance(scale, bool) or
+                                  not abs(float(scale)) < float('inf')):
+            raise CBinferError("CBBinary2d: scale=%r must be a finite number or None (d ** -0.5)" % (scale,))
+        self.scale = None if scale is None else float(scale)
+        self.border = 'mask' if border is None else border
+        if self.border not in _BORDERS:
+            raise CBinferError("CBBinary2d: border=%r is not supported, only 'mask' or 'zero'" % (border,))
+        buf = None
+        if positionBias is not None:
+            shapes = ((self.heads, Dy * Dx), (self.heads, Dy, Dx))
+            if (not torch.is_tensor(positionBias) or tuple(positionBias.shape) not in shapes or
+                    not positionBias.is_floating_point()):
+                raise CBinferError("CBBinary2d: positionBias must be a floating-point tensor of shape %s or %s, got %s"
+                                   % (shapes + (tuple(positionBias.shape) if torch.is_tensor(positionBias)
+                                                else type(positionBias).__name__,)))
+            buf = positionBias.detach().float().reshape(self.heads, Dy * Dx).clone().contiguous()
+        self.register_buffer('positionBias', buf)
+
+    def _apply(self, fn, *args, **kwargs):
+        # (the position bias follows the module's device and stays float32, the kernel's: .half() does not convert it)
+        held = self._buffers.get('positionBias')
+        super(CBBinary2d, self)._apply(fn, *args, **kwargs)
+        if held is not None and self._buffers['positionBias'].dtype != torch.float32:
+            self._buffers['positionBias'] = held.to(self._buffers['positionBias'].device)
+        return self
+
+    def _attend(self, q, kv):
+        name = 'CBBinary2d'
+        if kv is None:
+            raise CBinferError("CBBinary2d: forward(q, kv) takes two operands")
+        q, iq = split_operand(name, q, 'operand q')
+        check_map(name, q, 'operand q')
+        kv, ikv = split_operand(name, kv, 'operand kv')
+        check_map(name, kv, 'operand kv')
+        if tuple(kv.shape[2:]) != tuple(q.shape[2:]) or kv.dtype != q.dtype or kv.device != q.device:
+            raise CBinferError("CBBinary2d: the operands differ: q is %s %s on %s, kv is %s %s on %s"
+                               % (tuple(q.shape), q.dtype, q.device, tuple(kv.shape), kv.dtype, kv.device))
+        y0, y1, x0, x1, Dy, Dx = self.window
+        nc, H, W = q.size(1), q.size(2), q.size(3)
+        ncv = kv.size(1) - nc
+        if ncv < 1:
+            raise CBinferError("CBBinary2d: operand kv has %d channels: behind the %d channels of k (operand q's count) "
+                               "it holds no channel of v" % (kv.size(1), nc))
+        if nc % self.heads or ncv % self.heads:
+            raise CBinferError("CBBinary2d: heads=%d does not divide the %d channels of q and k and the %d channels of v"
+                               % (self.heads, nc, ncv))
+        if max(nc, ncv) // self.heads > MAX_HEAD_CHANNELS:
+            raise CBinferError("CBBinary2d: %d channels of q and %d of v over heads=%d: a head takes %d channels at most"
+                               % (nc, ncv, self.heads, MAX_HEAD_CHANNELS))
+        bias = self.positionBias
+        if bias is not None and bias.device != q.device:
+            raise CBinferError("CBBinary2d: operand q is on %s, positionBias on %s (move the module with .to())"
+                               % (q.device, bias.device))
+        require_device(q, kv)
+
+        def make():
+            scale = (nc // self.heads) ** -0.5 if self.scale is None else self.scale
+            att = _lib.Attend(y0, y1, x0, x1, self.step, self.heads, _BORDERS[self.border], int(bias is not None), scale)
+            if not C.cbinfer_attend_supported(ctypes.byref(att), nc, ncv, H, W):
+                raise CBinferError("CBBinary2d: attending %s to %s is beyond the library's limits"
+                                   % (tuple(q.shape), tuple(kv.shape)))
+            work = mask_workspace(H, W, q.device, nbits=2)      # (the output's working mask, then kv's)
+            return dict(work, attend=ctypes.pointer(att), kvBits=work['bits'][work['copy'].numel():])
+        work = self._cached_work((ATTEND, nc, ncv, H, W, q.device), make)
+        fq = operand_changes(name, 'operand q', iq, H, W, q.device, work['idx'], words=_WORDS, maskWhenMade=False)
+        fkv = operand_changes(name, 'operand kv', ikv, H, W, q.device, work['idx'], words=_WORDS, maskWhenMade=False)
+        if self._fresh_state((1, ncv, H, W), q):      # (written completely: no change information is used)
+            fq = fkv = EVERY_PIXEL
+        check(C.cbinfer_cbattend_forward(ptr(q), ptr(kv), ptr(bias), ptr(self.outputState), *form_args(fq),
+                                         *form_args(fkv), ptr(work['kvBits']), ptr(work['bits']), ptr(work['copy']), nc,
+                                         ncv, H, W, work['attend'], _lib.dtype_code(q), stream_ptr(q)))
+        return self._result(work, H, W)
+
     def _correlate(self, a, b):
         name = 'CBBinary2d'
         if b is None:
@@ -438,6 +560,8 @@ class CBBinary2d(_CBBinaryBase):
             return self._aggregate(a, b)
         if self.op == DEFORM:
             return self._deform_forward(a, b)
+        if self.op == ATTEND:
+            return self._attend(a, b)
         if self.hasOther and b is not None:
             raise CBinferError("CBBinary2d: the module has a constant operand `other`: forward(a) takes one argument")
         if not self.hasOther and b is None:
@@ -476,6 +600,10 @@ class CBBinary2d(_CBBinaryBase):
         if self.op == AGGREGATE:
             return 'CBBinary2d (op=aggregate, displacement=%r, step=%d, groups=%d, propChgIdxs=%s)' % (
                 self.displacement, self.step, self.groups, self.propChangeIndexes)
+        if self.op == ATTEND:
+            return ('CBBinary2d (op=attend, displacement=%r, step=%d, heads=%d, scale=%r, border=%s, positionBias=%s, '
+                    'propChgIdxs=%s)' % (self.displacement, self.step, self.heads, self.scale, self.border,
+                                         self.positionBias is not None, self.propChangeIndexes))
         if self.op == DEFORM:
             K, Cin, kH, kW = self.weight.shape
             return ('CBBinary2d (op=deform, %d -> %d, kernel=%dx%d, stride=%s, padding=%s, dilation=%s, offsetGroups=%d, '

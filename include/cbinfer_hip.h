@@ -84,7 +84,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_correlation_supported, cbinfer_cbcorrelation_forward) and the per-pixel kernel application (cbAggr,
  * cbinfer_aggregate_supported, cbinfer_cbaggregate_forward) and the deformable convolution (cbDeform, CB_DEFORM_*,
  * cbinfer_deform_supported, cbinfer_deform_prepared_weights_bytes, cbinfer_deform_prep_weights,
- * cbinfer_cbdeform_forward). */
+ * cbinfer_cbdeform_forward) and the fused local attention (cbAttend, CB_ATTEND_*, cbinfer_attend_supported,
+ * cbinfer_cbattend_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1363,6 +1364,69 @@ int cbinfer_cbaggregate_forward(const void* w, const void* v, void* outputState,
                                 const int32_t* listV, int capV, const int32_t* countV, uint64_t* vBits, uint64_t* bits,
                                 uint64_t* maskCopy, int C, int H, int W, const cbAggr* aggr, int dtype,
                                 cbStream_t stream);
+
+/* ---- change-based fused local attention (cb_attend.hip) ----------------------------------------------------
+ * No counterpart in the reference.  Local / neighbourhood attention (SASA, NAT-type blocks, HaloNet-style heads, the local
+ * cross-frame attention of video networks) in ONE launch: what correlate -> softmax -> aggregate compute, without the
+ * volume of heads x T score planes ever being written.  A window of displacements as the correlation layer's, T = Dy Dx
+ * taps t = i Dx + j at (dy_i, dx_j) = (y0 + i step, x0 + j step); q is [C, H, W]; kv is [C + Cv, H, W], its first C
+ * channels k and its remaining Cv channels v (the kv projection of an attention block as one convolution, and one change
+ * list); the state `out` is [Cv, H, W].  heads divides C and Cv, d = C / heads, dv = Cv / heads; head h owns channels
+ * h d .. of q and k and h dv .. of v and out:
+ *   s[h, t]             = scale * sum over c < d of q[h d + c, y, x] * k[h d + c, y + dy_i, x + dx_j]  (+ bias[h, t]),
+ *   p[h, .]             = softmax of s[h, .] over the taps that take part,
+ *   out[h dv + c, y, x] = sum over t of p[h, t] * v[h dv + c, y + dy_i, x + dx_j].
+ * border: CB_ATTEND_MASK -- a tap whose row or column lies outside the map takes no part: nothing to the softmax sum,
+ *   nothing to the output; a pixel with no in-map tap at all is +0.  CB_ATTEND_ZERO -- such a tap has score 0 (plus its
+ *   bias) and value 0: what cbinfer_cbcorrelation_forward (scale outside) -> softmax over the planes ->
+ *   cbinfer_cbaggregate_forward compute.
+ * positionBias: NULL (hasBias 0) or [heads, T] float32 whatever the dtype (hasBias 1): the relative position bias of NAT /
+ *   Swin-type blocks.  q, kv and `out` are contiguous, one dtype (CB_F32 or CB_F16), three different tensors.
+ *
+ * THIS SECTION IS THE SPECIFICATION.
+ *   FINITE OPERANDS: as for the kernel application, a 16-pixel group multiplies every column of the strips of k and v that
+ *     its windows span, the columns of v outside a pixel's own window by +0: q and kv must hold finite values.
+ *   listed pixels -- the exact footprint of the correlation layer with a := q, b := kv: pixel p is listed iff q changed at
+ *     p, or kv changed at a pixel p + (dy_i, dx_j) that lies in the map (under either border).  The three operand forms
+ *     -- mask, list with or without a device count, none: EVERY pixel is listed -- mean what they mean there.
+ *   arithmetic, per pixel and head, displacement rows i ASCENDING (rows outside the map: skipped under CB_ATTEND_MASK,
+ *     scores +0 and values 0 under CB_ATTEND_ZERO):
+ *     scores: the operands go to the matrix unit as they are (f32: v_mfma_f32_16x16x4_f32; f16: v_mfma_f32_16x16x32_f16),
+ *       products and sums in f32, c ascending in k-steps of 4 (32) channels, the channel tail and columns outside the map
+ *       filled with +0; then ONE f32 multiply by scale; then, with a bias, ONE f32 addition.  A tap that takes no part is
+ *       -inf by a select.
+ *     online softmax: rowmax over the row's taps; m' = max(m, rowmax); f = expf(m - m'); p_t = expf(s_t - m');
+ *       l = l * f + sum of the row's p_t; acc = acc * f; from m = -inf, l = 0, acc = 0 (a row with no tap of a pixel that
+ *       has had none leaves all three as they are).  The row's p_t are summed per lane over its columns ascending, then
+ *       over the four lanes of a pixel pairwise.
+ *     values: acc = acc + sum over the row's columns of p * v on the matrix unit, f32 accumulation; CB_F16 rounds p to f16
+ *       (p <= 1) first.
+ *     end: out = acc / l, ONE f32 division, ONE rounding to the dtype; l == 0 gives +0.  DESIGN 5.36 has the error bound.
+ *   unit of work: as the kernel application's -- a group with a listed pixel is computed whole and only its listed pixels
+ *     are stored; a pixel's bits depend on its own operand values and on x mod 16 alone.
+ *   launches and hand-on: as the correlation layer's, with q's list into `bits` and kv's into `kvBits`: one launch in
+ *     front per list, ONE launch for the frame, one launch behind it for a list of kv; maskCopy receives the frame's mask
+ *     every frame, `bits` and `kvBits` (cbinfer_mask_words(H, W) words each, zero on first use) are zero again when the
+ *     frame ends.  No host sync, memset, allocation or data atomics beyond the footprint launch's.
+ * Limits (cbinfer_attend_supported): the window's -- -64 <= y0 <= y1 <= 64, -64 <= x0 <= x1 <= 64, 1 <= step <= 8 dividing
+ * y1 - y0 and x1 - x0, T <= 512 -- and x1 - x0 <= 48 (a 16-pixel group spans at most 4 column tiles); 1 <= heads <= 64
+ * dividing C and Cv; d <= 128, dv <= 128; border one of the enumerators; hasBias 0 or 1; scale finite; H, W >= 1, H W
+ * within an int32.
+ * Bad arguments -- the correlation layer's list, with q == kv, outputState == q or kv, a cbAttend beyond the limits and a
+ * positionBias that is NULL with hasBias 1 or given with hasBias 0 -- return CB_ERR_BADARG and launch nothing. */
+enum { CB_ATTEND_MASK, CB_ATTEND_ZERO };
+typedef struct cbAttend {
+    int y0, y1, x0, x1, step, heads, border, hasBias;
+    float scale;
+} cbAttend;
+/* host, pure: 1 if the attention of a [C, H, W] map q on a [C + Cv, H, W] map kv is within the limits above, else 0 */
+int cbinfer_attend_supported(const cbAttend* attend, int C, int Cv, int H, int W);
+/* The whole frame of a change-based fused local attention enqueued without a host sync. */
+int cbinfer_cbattend_forward(const void* q, const void* kv, const float* positionBias, void* outputState,
+                             const uint64_t* maskQ, const int32_t* listQ, int capQ, const int32_t* countQ,
+                             const uint64_t* maskKV, const int32_t* listKV, int capKV, const int32_t* countKV,
+                             uint64_t* kvBits, uint64_t* bits, uint64_t* maskCopy, int C, int Cv, int H, int W,
+                             const cbAttend* attend, int dtype, cbStream_t stream);
 
 /* ---- change-based deformable convolution (cb_deform.hip) --------------------------------------------------
  * No counterpart in the reference.  DCNv1 / DCNv2 (torchvision.ops.deform_conv2d, mmcv's ModulatedDeformConv2d): the
