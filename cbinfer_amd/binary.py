@@ -3,7 +3,8 @@ CBBinary2d('correlate'), the correlation layer / cost volume of flow and stereo 
 CBBinary2d('aggregate'), the per-pixel kernel application that takes such a volume back to a feature map (cb_aggr.hip,
 DESIGN 5.34), and CBBinary2d('deform'), the deformable convolution of a feature map and an offset field (cb_deform.hip,
 DESIGN 5.35), and CBBinary2d('attend'), local attention -- scores, softmax and weighted sum -- in one kernel
-(cb_attend.hip).
+(cb_attend.hip), with partition= the partitioned window attention of Swin-type blocks (cb_winattend.hip,
+DESIGN 5.37).
 
 The reference has no element-wise operator of two maps, and CBAdd2d is the sum alone: a gate `feat * sigmoid(gate)`, a
 layer scale `gamma[c] * x`, a residual by difference `x - net(x)`, an element-wise maximum or an nn.GLU over the
@@ -32,6 +33,7 @@ _GATES = {None: _lib.BIN_GATE_NONE, 'sigmoid': _lib.BIN_GATE_SIGMOID, 'hardsigmo
 CORRELATE, AGGREGATE, DEFORM, ATTEND = 'correlate', 'aggregate', 'deform', 'attend'
 _BORDERS = {'mask': _lib.ATTEND_MASK, 'zero': _lib.ATTEND_ZERO}
 MAX_ATTEND_SPAN, MAX_HEAD_CHANNELS, MAX_HEADS = 48, 128, 64
+MAX_PARTITION, MAX_PARTITION_TOKENS, MAX_PARTITION_HEAD_CHANNELS = 16, 144, 64
 _MODULATIONS = {None: _lib.DEFORM_NONE, 'planes': _lib.DEFORM_PLANES, 'sigmoid': _lib.DEFORM_SIGMOID}
 _DEFORM_KEYS = ('weight', 'bias', 'stride', 'padding', 'dilation', 'offsetGroups', 'modulation', 'relu')
 MAX_DISPLACEMENT, MAX_STEP, MAX_CORR_CHANNELS, MAX_WEIGHT_PLANES = 64, 8, 512, 4096
@@ -190,14 +192,35 @@ class CBBinary2d(_CBBinaryBase):
     x1 - x0 <= 48; d, dv <= 128; heads <= 64.  A pixel is recomputed iff q changed there or kv changed at one of its
     window's in-map taps.  Both operands must hold FINITE values, as for 'aggregate'.  `other`, `gate`, `reverse`,
     `normalize`, `groups` and the keywords of 'deform' do not go with it, its own go with no other op; it has no
-    conversion pass either."""
+    conversion pass either.
+
+    op='attend' with partition= -- CBBinary2d('attend', partition=(Wy, Wx), shift=(sy, sx), heads=1, scale=None,
+    positionBias=None), forward(q, kv) -- is PARTITIONED window attention (Swin, Video-Swin frames, SwinIR-type
+    restoration networks, Twins' locally-grouped attention) as one kernel of its own (cb_winattend.hip).
+    The operands, heads and scale are those above.  The map is cut into non-overlapping Wy x Wx cells: pixel (y, x) lies
+    in cell (floor((y - sy) / Wy), floor((x - sx) / Wx)), so rows y < sy are cell row -1; cells are clipped at the map's
+    edge and the tokens of a cell are its in-map pixels.  Every token attends to every token of its own cell:
+        s[i, j] = scale sum_c q[h d + c, i] k[h d + c, j] (+ positionBias[h, yi - yj + Wy - 1, xi - xj + Wx - 1]),
+        out[h dv + c, i] = sum_j softmax_j(s[i, .]) v[h dv + c, j].
+    partition and shift: an int or a pair, 1 <= Wy, Wx <= 16, Wy Wx <= 144, 0 <= sy < Wy, 0 <= sx < Wx (shift defaults
+    to 0); d, dv <= 64; heads <= 64.  positionBias: a constant [heads, 2 Wy - 1, 2 Wx - 1] tensor or the same flattened
+    -- Swin's relative_position_bias_table.t() as it stands --, kept in float32.  On a map whose sides are multiples of
+    Wy and Wx this is exactly Swin's cyclic shift by (-sy, -sx) with its region mask: the three bands per axis of the
+    rolled map are the clipped cells.  Two differences: on other map sizes Swin zero-pads and the padding takes part in
+    its softmax, here the cells are clipped; and Swin's mask adds -100 where this rule excludes the key exactly.  A pixel
+    is recomputed iff q changed there or kv changed at ANY pixel of its cell; a cell without a change costs nothing.
+    displacement=, step= and border= do not go with partition=, shift= goes with nothing else.  Out of scope: Swin-V2's
+    cosine attention and per-head logit scale, global attention, a conversion pass (INTEGRATION.md has the wiring of a
+    Swin block pair)."""
 
     def __init__(self, op, other=None, gate=None, reverse=False, displacement=None, step=None, normalize=None,
                  groups=None, weight=None, bias=None, stride=None, padding=None, dilation=None, offsetGroups=None,
-                 modulation=None, relu=False, heads=None, scale=None, border=None, positionBias=None):
+                 modulation=None, relu=False, heads=None, scale=None, border=None, positionBias=None, partition=None,
+                 shift=None):
         super(CBBinary2d, self).__init__()
         if op != ATTEND:
-            for key, value in dict(heads=heads, scale=scale, border=border, positionBias=positionBias).items():
+            for key, value in dict(heads=heads, scale=scale, border=border, positionBias=positionBias,
+                                   partition=partition, shift=shift).items():
                 if value is not None:
                     raise CBinferError("CBBinary2d: %s= is a setting of op='attend', op=%r does not take it" % (key, op))
         window = dict(displacement=displacement, step=step, normalize=normalize)
@@ -224,7 +247,15 @@ class CBBinary2d(_CBBinaryBase):
                 if value is not None:
                     raise CBinferError("CBBinary2d: %s= does not go with op=%r" % (key, op))
             self.op, self.gate, self.reverse = op, None, False
-            self._set_attend(displacement, step, heads, scale, border, positionBias)
+            if partition is not None:
+                for key, value in dict(displacement=displacement, step=step, border=border).items():
+                    if value is not None:
+                        raise CBinferError("CBBinary2d: %s= does not go with partition= (the cells are the window)" % key)
+                self._set_partition(partition, shift, heads, scale, positionBias)
+            elif shift is not None:
+                raise CBinferError("CBBinary2d: shift= goes with partition= only")
+            else:
+                self._set_attend(displacement, step, heads, scale, border, positionBias)
             self._buffers['outputState'] = self._buffers.pop('outputState')
             self.otherNumber, self.hasOther = None, False
             return
@@ -402,14 +433,7 @@ class CBBinary2d(_CBBinaryBase):
                                          work['deform'], _lib.dtype_code(x), stream_ptr(x)))
         return self._result(work, Ho, Wo)
 
-    def _set_attend(self, displacement, step, heads, scale, border, positionBias):
-        self.displacement = 4 if displacement is None else displacement
-        self.step = 1 if step is None else step
-        self.window = correlation_window(self.displacement, self.step, "taps")
-        y0, y1, x0, x1, Dy, Dx = self.window
-        if x1 - x0 > MAX_ATTEND_SPAN:
-            raise CBinferError("CBBinary2d: displacement=%r: op='attend' takes a column range x1 - x0 of %d at most, "
-                               "got %d" % (self.displacement, MAX_ATTEND_SPAN, x1 - x0))
+    def _set_heads(self, heads, scale):
         self.heads = 1 if heads is None else heads
         if (not isinstance(self.heads, numbers.Integral) or isinstance(self.heads, bool) or
                 not 1 <= self.heads <= MAX_HEADS):
@@ -418,6 +442,43 @@ class CBBinary2d(_CBBinaryBase):
                                   not abs(float(scale)) < float('inf')):
             raise CBinferError("CBBinary2d: scale=%r must be a finite number or None (d ** -0.5)" % (scale,))
         self.scale = None if scale is None else float(scale)
+
+    def _set_partition(self, partition, shift, heads, scale, positionBias):
+        def pair(key, v):
+            v = (v, v) if isinstance(v, numbers.Integral) and not isinstance(v, bool) else v
+            if not (isinstance(v, (tuple, list)) and len(v) == 2 and
+                    all(isinstance(n, numbers.Integral) and not isinstance(n, bool) for n in v)):
+                raise CBinferError("CBBinary2d: %s=%r must be an int or a pair of ints" % (key, v))
+            return int(v[0]), int(v[1])
+        Wy, Wx = self.partition = pair('partition', partition)
+        if not (1 <= Wy <= MAX_PARTITION and 1 <= Wx <= MAX_PARTITION and Wy * Wx <= MAX_PARTITION_TOKENS):
+            raise CBinferError("CBBinary2d: partition=%r: a cell is 1 .. %d pixels a side and %d tokens at most"
+                               % (partition, MAX_PARTITION, MAX_PARTITION_TOKENS))
+        sy, sx = self.shift = pair('shift', 0 if shift is None else shift)
+        if not (0 <= sy < Wy and 0 <= sx < Wx):
+            raise CBinferError("CBBinary2d: shift=%r must be within 0 .. partition - 1 = (%d, %d)"
+                               % (shift, Wy - 1, Wx - 1))
+        self._set_heads(heads, scale)
+        buf = None
+        if positionBias is not None:
+            shapes = ((self.heads, (2 * Wy - 1) * (2 * Wx - 1)), (self.heads, 2 * Wy - 1, 2 * Wx - 1))
+            if (not torch.is_tensor(positionBias) or tuple(positionBias.shape) not in shapes or
+                    not positionBias.is_floating_point()):
+                raise CBinferError("CBBinary2d: positionBias must be a floating-point tensor of shape %s or %s, got %s"
+                                   % (shapes + (tuple(positionBias.shape) if torch.is_tensor(positionBias)
+                                                else type(positionBias).__name__,)))
+            buf = positionBias.detach().float().reshape(shapes[0]).clone().contiguous()
+        self.register_buffer('positionBias', buf)
+
+    def _set_attend(self, displacement, step, heads, scale, border, positionBias):
+        self.displacement = 4 if displacement is None else displacement
+        self.step = 1 if step is None else step
+        self.window = correlation_window(self.displacement, self.step, "taps")
+        y0, y1, x0, x1, Dy, Dx = self.window
+        if x1 - x0 > MAX_ATTEND_SPAN:
+            raise CBinferError("CBBinary2d: displacement=%r: op='attend' takes a column range x1 - x0 of %d at most, "
+                               "got %d" % (self.displacement, MAX_ATTEND_SPAN, x1 - x0))
+        self._set_heads(heads, scale)
         self.border = 'mask' if border is None else border
         if self.border not in _BORDERS:
             raise CBinferError("CBBinary2d: border=%r is not supported, only 'mask' or 'zero'" % (border,))
@@ -451,7 +512,7 @@ class CBBinary2d(_CBBinaryBase):
         if tuple(kv.shape[2:]) != tuple(q.shape[2:]) or kv.dtype != q.dtype or kv.device != q.device:
             raise CBinferError("CBBinary2d: the operands differ: q is %s %s on %s, kv is %s %s on %s"
                                % (tuple(q.shape), q.dtype, q.device, tuple(kv.shape), kv.dtype, kv.device))
-        y0, y1, x0, x1, Dy, Dx = self.window
+        part = getattr(self, 'partition', None)
         nc, H, W = q.size(1), q.size(2), q.size(3)
         ncv = kv.size(1) - nc
         if ncv < 1:
@@ -460,9 +521,10 @@ class CBBinary2d(_CBBinaryBase):
         if nc % self.heads or ncv % self.heads:
             raise CBinferError("CBBinary2d: heads=%d does not divide the %d channels of q and k and the %d channels of v"
                                % (self.heads, nc, ncv))
-        if max(nc, ncv) // self.heads > MAX_HEAD_CHANNELS:
+        most = MAX_HEAD_CHANNELS if part is None else MAX_PARTITION_HEAD_CHANNELS
+        if max(nc, ncv) // self.heads > most:
             raise CBinferError("CBBinary2d: %d channels of q and %d of v over heads=%d: a head takes %d channels at most"
-                               % (nc, ncv, self.heads, MAX_HEAD_CHANNELS))
+                               % (nc, ncv, self.heads, most))
         bias = self.positionBias
         if bias is not None and bias.device != q.device:
             raise CBinferError("CBBinary2d: operand q is on %s, positionBias on %s (move the module with .to())"
@@ -471,8 +533,15 @@ class CBBinary2d(_CBBinaryBase):
 
         def make():
             scale = (nc // self.heads) ** -0.5 if self.scale is None else self.scale
-            att = _lib.Attend(y0, y1, x0, x1, self.step, self.heads, _BORDERS[self.border], int(bias is not None), scale)
-            if not C.cbinfer_attend_supported(ctypes.byref(att), nc, ncv, H, W):
+            if part is None:
+                y0, y1, x0, x1, Dy, Dx = self.window
+                att = _lib.Attend(y0, y1, x0, x1, self.step, self.heads, _BORDERS[self.border], int(bias is not None),
+                                  scale)
+                supported = C.cbinfer_attend_supported
+            else:
+                att = _lib.WinAttend(*(part + self.shift), self.heads, int(bias is not None), scale)
+                supported = C.cbinfer_winattend_supported
+            if not supported(ctypes.byref(att), nc, ncv, H, W):
                 raise CBinferError("CBBinary2d: attending %s to %s is beyond the library's limits"
                                    % (tuple(q.shape), tuple(kv.shape)))
             work = mask_workspace(H, W, q.device, nbits=2)      # (the output's working mask, then kv's)
@@ -482,9 +551,10 @@ class CBBinary2d(_CBBinaryBase):
         fkv = operand_changes(name, 'operand kv', ikv, H, W, q.device, work['idx'], words=_WORDS, maskWhenMade=False)
         if self._fresh_state((1, ncv, H, W), q):      # (written completely: no change information is used)
             fq = fkv = EVERY_PIXEL
-        check(C.cbinfer_cbattend_forward(ptr(q), ptr(kv), ptr(bias), ptr(self.outputState), *form_args(fq),
-                                         *form_args(fkv), ptr(work['kvBits']), ptr(work['bits']), ptr(work['copy']), nc,
-                                         ncv, H, W, work['attend'], _lib.dtype_code(q), stream_ptr(q)))
+        forward = C.cbinfer_cbattend_forward if part is None else C.cbinfer_cbwinattend_forward
+        check(forward(ptr(q), ptr(kv), ptr(bias), ptr(self.outputState), *form_args(fq), *form_args(fkv),
+                      ptr(work['kvBits']), ptr(work['bits']), ptr(work['copy']), nc, ncv, H, W, work['attend'],
+                      _lib.dtype_code(q), stream_ptr(q)))
         return self._result(work, H, W)
 
     def _correlate(self, a, b):
@@ -600,6 +670,10 @@ class CBBinary2d(_CBBinaryBase):
         if self.op == AGGREGATE:
             return 'CBBinary2d (op=aggregate, displacement=%r, step=%d, groups=%d, propChgIdxs=%s)' % (
                 self.displacement, self.step, self.groups, self.propChangeIndexes)
+        if self.op == ATTEND and getattr(self, 'partition', None) is not None:
+            return ('CBBinary2d (op=attend, partition=%r, shift=%r, heads=%d, scale=%r, positionBias=%s, propChgIdxs=%s)'
+                    % (self.partition, self.shift, self.heads, self.scale, self.positionBias is not None,
+                       self.propChangeIndexes))
         if self.op == ATTEND:
             return ('CBBinary2d (op=attend, displacement=%r, step=%d, heads=%d, scale=%r, border=%s, positionBias=%s, '
                     'propChgIdxs=%s)' % (self.displacement, self.step, self.heads, self.scale, self.border,

@@ -85,7 +85,8 @@ typedef void* cbStream_t; /* hipStream_t */
  * cbinfer_aggregate_supported, cbinfer_cbaggregate_forward) and the deformable convolution (cbDeform, CB_DEFORM_*,
  * cbinfer_deform_supported, cbinfer_deform_prepared_weights_bytes, cbinfer_deform_prep_weights,
  * cbinfer_cbdeform_forward) and the fused local attention (cbAttend, CB_ATTEND_*, cbinfer_attend_supported,
- * cbinfer_cbattend_forward). */
+ * cbinfer_cbattend_forward) and the partitioned window attention (cbWinAttend, cbinfer_winattend_supported,
+ * cbinfer_cbwinattend_forward). */
 #define CBINFER_ABI_VERSION 11
 
 int cbinfer_abi_version(void);
@@ -1427,6 +1428,61 @@ int cbinfer_cbattend_forward(const void* q, const void* kv, const float* positio
                              const uint64_t* maskKV, const int32_t* listKV, int capKV, const int32_t* countKV,
                              uint64_t* kvBits, uint64_t* bits, uint64_t* maskCopy, int C, int Cv, int H, int W,
                              const cbAttend* attend, int dtype, cbStream_t stream);
+
+/* ---- change-based partitioned window attention (cb_winattend.hip) -----------------------------------------
+ * No counterpart in the reference.  The window attention of Swin-type blocks (Swin, Video-Swin frames, SwinIR-type
+ * restoration networks, Twins' locally-grouped attention): the map is cut into non-overlapping Wy x Wx CELLS and every
+ * token of a cell attends to every token of the same cell.  Pixel (y, x) lies in cell (floor((y - sy) / Wy),
+ * floor((x - sx) / Wx)) -- rows y < sy are cell row -1 --; cells are CLIPPED at the map's edge; the tokens of a cell are
+ * its in-map pixels, row-major, N <= Wy Wx of them.  q, kv, `out`, heads, d and dv as for the fused local attention; per
+ * head h and for query i and key j of one cell, at (yi, xi) and (yj, xj),
+ *   s[i, j]          = scale * sum over c < d of q[h d + c, i] * k[h d + c, j]  (+ bias[h, yi - yj + Wy - 1, xi - xj + Wx - 1]),
+ *   p[i, .]          = softmax of s[i, .] over the cell's tokens,
+ *   out[h dv + c, i] = sum over j of p[i, j] * v[h dv + c, j].
+ * positionBias: NULL (hasBias 0) or [heads, 2 Wy - 1, 2 Wx - 1] float32 whatever the dtype (hasBias 1): Swin's
+ * relative_position_bias_table, transposed.  q, kv and `out` are contiguous, one dtype, three different tensors.
+ *
+ * THIS SECTION IS THE SPECIFICATION.
+ *   FINITE OPERANDS: a cell is padded to 16-token tiles whose tail is multiplied as +0: q and kv must hold finite values.
+ *   listed pixels -- the exact footprint: pixel p is listed iff q changed at p, or kv changed at ANY pixel of p's cell.
+ *     The three operand forms -- mask, list with or without a device count, none: EVERY pixel is listed -- mean what they
+ *     mean for the correlation layer.
+ *   arithmetic, per cell, head and query:
+ *     scores: the operands go to the matrix unit as they are (f32: v_mfma_f32_16x16x4_f32; f16: v_mfma_f32_16x16x32_f16),
+ *       products and sums in f32, c ascending in k-steps of 4 (32) channels, the channel tail filled with +0; then ONE f32
+ *       multiply by scale; then, with a bias, ONE f32 addition.  A padding key is -inf by a select.
+ *     softmax, two passes: m = the maximum of the query's N scores; p_j = expf(s_j - m); l = sum of the p_j -- per lane
+ *       over its keys j = 16 t + 4 g + r, (t, r) ascending, then over the four lanes g of a query pairwise (g ^ 1 first).
+ *       A cell holds the query itself, so l >= 1.
+ *     values: acc = sum over j of p_j * v_j on the matrix unit, f32 accumulation, key tiles ascending; CB_F16 rounds p to
+ *       f16 (p <= 1) first.
+ *     end: out = acc / l, ONE f32 division, ONE rounding to the dtype.  DESIGN 5.37 has the error bound.
+ *   unit of work: a (cell, head).  A cell with a listed pixel is computed WHOLE and only its listed pixels are stored: a
+ *     pixel's bits depend on its cell's operand values alone, never on the other listed pixels or on the operands' forms.
+ *     A cell without a listed pixel ends after reading its segments of the frame's mask.
+ *   launches: one launch in front per operand in list form (q's list into `bits`, kv's into `kvBits`); ONE footprint
+ *     launch, which writes the frame's mask to maskCopy and zeroes `bits`; ONE frame launch, which also zeroes the words of
+ *     `kvBits` under the listed cells -- there is no launch behind the frame.  That is 2 launches for mask or bare
+ *     operands and one more per list (the fused local attention: 1, one more per list, one behind a list of kv).  No host
+ *     sync, memset, allocation or data atomics beyond the list launches'.
+ *   hand-on: maskCopy receives the frame's mask every frame; `bits` and `kvBits` (cbinfer_mask_words(H, W) words each, zero
+ *     on first use) are zero again when the frame ends.  Unlisted pixels keep their bits.
+ * Limits (cbinfer_winattend_supported): 1 <= Wy, Wx <= 16, Wy Wx <= 144, 0 <= sy < Wy, 0 <= sx < Wx; 1 <= heads <= 64
+ * dividing C and Cv; d <= 64, dv <= 64; hasBias 0 or 1; scale finite; H, W >= 1, H W within an int32.
+ * Bad arguments -- the fused local attention's list, with a cbWinAttend beyond the limits -- return CB_ERR_BADARG and launch
+ * nothing. */
+typedef struct cbWinAttend {
+    int Wy, Wx, sy, sx, heads, hasBias;
+    float scale;
+} cbWinAttend;
+/* host, pure: 1 if the window attention of a [C, H, W] map q on a [C + Cv, H, W] map kv is within the limits above, else 0 */
+int cbinfer_winattend_supported(const cbWinAttend* attend, int C, int Cv, int H, int W);
+/* The whole frame of a change-based partitioned window attention enqueued without a host sync. */
+int cbinfer_cbwinattend_forward(const void* q, const void* kv, const float* positionBias, void* outputState,
+                                const uint64_t* maskQ, const int32_t* listQ, int capQ, const int32_t* countQ,
+                                const uint64_t* maskKV, const int32_t* listKV, int capKV, const int32_t* countKV,
+                                uint64_t* kvBits, uint64_t* bits, uint64_t* maskCopy, int C, int Cv, int H, int W,
+                                const cbWinAttend* attend, int dtype, cbStream_t stream);
 
 /* ---- change-based deformable convolution (cb_deform.hip) --------------------------------------------------
  * No counterpart in the reference.  DCNv1 / DCNv2 (torchvision.ops.deform_conv2d, mmcv's ModulatedDeformConv2d): the
