@@ -3,10 +3,13 @@ float64 reference by shifted slices with the weight of its error bound, and the 
 and frames are the correlation layer's (tests/correlation_cases.py)."""
 import numpy as np
 
-from correlation_cases import MAPS, WINDOW_IDS, WINDOWS, footprint, frames, shifted, taps  # noqa: F401
+from correlation_cases import (LIMIT_MAP, LIMIT_WINDOW_IDS, LIMIT_WINDOWS, MAPS, STRIDE_WINDOW, WINDOW_IDS,  # noqa: F401
+                               WINDOWS, column_tiles, footprint, frames, shifted, strided_changes, taps)
 
 # (C, G): below one channel tile, a tile tail, groups narrower than a tile, one channel per group
 CHANNELS_GROUPS = [(5, 1), (67, 1), (40, 5), (5, 5)]
+# ... under correlation_cases.LIMIT_WINDOWS (float16: the zero tile that pads the K axis at NT = 1, 3, 5 and 9)
+LIMIT_CHANNELS_GROUPS = [(5, 1), (67, 1), (40, 5)]
 
 
 def operands(rng, Cn, G, window, size, npdt):

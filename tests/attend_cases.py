@@ -8,14 +8,32 @@ from correlation_cases import MAPS, WINDOW_IDS, WINDOWS, footprint, frames, shif
 SHAPES = [(5, 5, 1), (67, 40, 1), (32, 48, 2), (6, 6, 6)]
 BORDERS = ['mask', 'zero']
 U = 2.0 ** -24
+# dv = 80: the second block of v with one channel tile; d = 65, dv = 100: both second blocks with tails, over two heads;
+# d = dv = 128: the limit, every register of the Q fragment and two full chunks of k
+LIMIT_SHAPES = [(8, 80, 1), (130, 200, 2), (128, 128, 1)]
+# r4 (NT = 2) and a window of three column tiles, which float16 pads to four
+LIMIT_WINDOWS = [(4, 1, (-4, 4, -4, 4, 9, 9)), (((-1, 1), (-12, 12)), 1, (-1, 1, -12, 12, 3, 25))]
+# (C, Cv, heads), scale of the peaked softmax: scores of a standard deviation of 8 sqrt 8, so that some weights are zero in
+# float32 and the running maximum moves by tens between displacement rows (R >= 100 somewhere on the map)
+PEAKED = ((8, 16, 1), 8.0)
 
 
-def operands(rng, Cn, Cv, heads, window, size, npdt):
-    """(q, kv, bias [heads, T] or None): q, k standard normal, v standard normal x 2, a bias on the multi-head shapes."""
+def operands(rng, Cn, Cv, heads, window, size, npdt, bias=None):
+    """(q, kv, bias [heads, T] or None): q, k standard normal, v standard normal x 2, a bias on the multi-head shapes
+    (bias=True: on any shape; bias='planes': handed over as [heads, Dy, Dx])."""
     q = rng.standard_normal((Cn,) + tuple(size)).astype(npdt)
     kv = (rng.standard_normal((Cn + Cv,) + tuple(size)) * np.r_[np.ones(Cn), 2 * np.ones(Cv)][:, None, None]).astype(npdt)
-    bias = rng.standard_normal((heads, window[4] * window[5])).astype(np.float32) if heads > 1 else None
-    return q, kv, bias
+    table = rng.standard_normal((heads, window[4] * window[5])).astype(np.float32) if heads > 1 or bias else None
+    return q, kv, table.reshape(heads, window[4], window[5]) if bias == 'planes' else table
+
+
+def uniform_mean(kv, Cn, window, step, border):
+    """What scale = 0 without a bias computes, in float64: the mean of the values at the taps that take part -- under
+    'mask' the divisor is the count of in-map taps, under 'zero' all T."""
+    v, tp = kv[Cn:].astype(np.float64), taps(window, step)
+    total = sum(shifted(v, dy, dx) for dy, dx in tp)
+    count = sum(shifted(np.ones(v.shape[1:]), dy, dx) for dy, dx in tp) if border == 'mask' else len(tp)
+    return total / np.maximum(count, 1)
 
 
 def default_scale(Cn, heads):
@@ -28,6 +46,7 @@ def reference(q, kv, bias, window, step, heads, border, scale):
     value per head, repeated over its channels): out; A = sum_t p_t |v_t|; V1 = sum_t |v_t| over the taps that take
     part; and of [heads, H, W] maps: Q = max_t scale sum_c |q_c k_c|, R = max_t (max s - s_t), B = max |bias|."""
     q, kv = q.astype(np.float64), kv.astype(np.float64)
+    bias = None if bias is None else bias.reshape(heads, -1)      # ([heads, Dy, Dx] is the same table)
     Cn, (H, W) = q.shape[0], q.shape[1:]
     Cv = kv.shape[0] - Cn
     d, dv, tp = Cn // heads, Cv // heads, taps(window, step)
@@ -41,7 +60,7 @@ def reference(q, kv, bias, window, step, heads, border, scale):
         for t, (dy, dx) in enumerate(tp):
             p = qh * shifted(kh, dy, dx)
             s[t] = p.sum(0) * scale
-            Q[h] = np.maximum(Q[h], np.abs(p).sum(0) * scale)
+            Q[h] = np.maximum(Q[h], np.abs(p).sum(0) * abs(scale))      # (a magnitude: a negative scale has the same)
         if bias is not None:
             s = s + bias[h].astype(np.float64)[:, None, None]
         s = np.where(part, s, -np.inf)

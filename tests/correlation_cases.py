@@ -10,6 +10,21 @@ WINDOW_IDS = ["r4", "r2x6s2", "r20s2", "stereo10"]
 # group
 MAPS = [(7, 70), (3, 16)]
 CHANNELS = [5, 67]      # below one k-step, and a chunk tail
+# The column tile counts the four above never reach (they span 8, 12, 40 and 10 columns: NT = 2, 2, 4, 2): NT = 1, 3, 5, 9,
+# every odd one and both ends of the NTMAX = 9 kernels; stereo64 and r8x64s8 put taps at +-64, a whole-word shift of the
+# footprint.  LIMIT_MAP has three mask words per row (the word before and behind a tap's), a 16-group cut by the row end
+# (150 = 2 x 64 + 16 + 6) and taps at +-64 inside the map.
+LIMIT_WINDOWS = [(((-2, 2), (0, 0)), 1, (-2, 2, 0, 0, 5, 1)), ((1, 12), 1, (-1, 1, -12, 12, 3, 25)),
+                 (((0, 0), (-64, 0)), 1, (0, 0, -64, 0, 1, 65)), (((-8, 8), (-64, 64)), 8, (-8, 8, -64, 64, 3, 17))]
+LIMIT_WINDOW_IDS = ["column5", "r1x12", "stereo64", "r8x64s8"]
+LIMIT_MAP = (5, 150)
+# the window of the grid-stride tests (tests/test_gpu_window_limits.py)
+STRIDE_WINDOW = ((1, 2), 1, (-1, 1, -2, 2, 3, 5))
+
+
+def column_tiles(window):
+    """NT of the kernels: the 16-column tiles of b's row that a group of 16 pixels meets."""
+    return (16 + window[3] - window[2] + 15) // 16
 
 
 def taps(window, step):
@@ -66,8 +81,16 @@ def frames(window, step, H=7, W=70):
            ("both, list form", "list", False, pixels(H, W, (H - 1, W - 1)), pixels(H, W, (H - 1, W - 1))),
            ("both, list form with device count", "list", True, pixels(H, W, (1, 5)), pixels(H, W, (0, W - 4))),
            ("a only", "mask", False, pixels(H, W, (2, slice(10, 41))), none),
-           ("b only", "list", True, none, pixels(H, W, (5, 33))),
+           ("b only", "list", True, none, pixels(H, W, (H - 2, 33))),
            ("nothing", "list", False, none, none)]
     for label, _, _, SA, SB in out:
         assert footprint(SA, SB, window, step).mean() < 0.5, (label, window)
     return out
+
+
+def strided_changes(H, W, cap):
+    """(changed pixels of a, of b) of the change-based frame on a map of more than `cap` rows of one mask word each, walked
+    by `cap` workgroups: both operands change in rows of the first lap and in rows of the second (>= cap), idle words lie
+    between them."""
+    assert H >= cap + 5 and W >= 13
+    return pixels(H, W, (3, 5), (cap + 2, 9)), pixels(H, W, (cap // 2, 2), (cap + 4, 12))

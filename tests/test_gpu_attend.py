@@ -13,8 +13,8 @@ from optest import dev, gpu_lib as lib, gpu_pkg as pkg, host_words, npdtype, ope
 pytestmark = pytest.mark.gpu
 
 
-def module(pkg, displacement, step, heads, border, bias):
-    m = pkg.CBBinary2d('attend', displacement=displacement, step=step, heads=heads, border=border,
+def module(pkg, displacement, step, heads, border, bias, scale=None):
+    m = pkg.CBBinary2d('attend', displacement=displacement, step=step, heads=heads, border=border, scale=scale,
                        positionBias=None if bias is None else torch.from_numpy(bias)).cuda()
     m.propChangeIndexes = True
     return m
@@ -24,20 +24,23 @@ def handed_on(m):
     return host_words(m._binWork['copy']), not bool(m._binWork['bits'].any())
 
 
-def judged(pkg, shape, displacement, step, size, arith, border):
-    """One every-pixel frame against float64 within the bound, which in float32 stays below 2^-10 A: (output, reference)."""
-    (Cn, Cv, heads), case = shape, (displacement, step, size, shape, border, arith)
+def judged(pkg, shape, displacement, step, size, arith, border, scale=None, bias=None):
+    """One every-pixel frame against float64 within the bound, which in float32 stays below 2^-10 A: (output, reference).
+    scale: the module's scale= (the reference takes it as the float32 the library is handed), default d ** -0.5; bias: as
+    attend_cases.operands takes it."""
+    (Cn, Cv, heads), case = shape, (displacement, step, size, shape, border, arith, scale, bias)
     m = module(pkg, displacement, step, heads, border, None)
-    q, kv, bias = ac.operands(np.random.default_rng(17), Cn, Cv, heads, m.window, size, npdtype(arith))
-    m = module(pkg, displacement, step, heads, border, bias)
+    q, kv, bias = ac.operands(np.random.default_rng(17), Cn, Cv, heads, m.window, size, npdtype(arith), bias=bias)
+    m = module(pkg, displacement, step, heads, border, bias, scale)
     out = m(dev(q)[None], dev(kv)[None])[1][0]
     assert np.array_equal(handed_on(m)[0], pack(np.ones(size, dtype=bool))) and handed_on(m)[1], case
-    ref = ac.reference(q, kv, bias, m.window, step, heads, border, ac.default_scale(Cn, heads))
+    ref = ac.reference(q, kv, bias, m.window, step, heads, border,
+                       ac.default_scale(Cn, heads) if scale is None else float(np.float32(scale)))
     assert ((ac.bound(ref, m.window, False) < 2.0 ** -10 * ref['A']) | (ref['A'] == 0)).all(), case
     err, bar = np.abs(out.double().cpu().numpy() - ref['out']), ac.bound(ref, m.window, arith == "f16")
     assert not err[bar == 0].any(), case
     share = float((err / np.where(bar == 0, 1.0, bar)).max())
-    print("share of the bound", displacement, step, size, shape, border, arith, "%.4f" % share)
+    print("share of the bound", *case, "%.4f" % share)
     assert share <= 1.0, case
     return out, ref
 

@@ -15,10 +15,11 @@ pytestmark = pytest.mark.gpu
 
 
 class Layer(object):      # one state of cbinfer_cbdeform_forward with its prepared weights, masks and workspace
-    def __init__(self, lib, case, rng):
+    def __init__(self, lib, case, rng, inSize=(dc.HI, dc.WI)):
         gname, (Cn, Go, K), mod, bias, relu, arith, farith, _ = case
         self.lib, self.geom, self.dims, self.mod, self.relu = lib, dc.GEOMS[gname], (Cn, Go, K), mod, relu
-        self.npdt, self.fdt, self.size, self.f16 = npdtype(arith), npdtype(farith), dc.out_size(self.geom), arith == "f16"
+        self.npdt, self.fdt, self.inSize, self.f16 = npdtype(arith), npdtype(farith), inSize, arith == "f16"
+        self.size = dc.out_size(self.geom, *inSize)
         self.W = rng.standard_normal((K, Cn) + self.geom[:2]).astype(self.npdt)
         self.bias = rng.standard_normal(K).astype(self.npdt) if bias else None
         self.dtype, fcode = (lib.CB_F16 if a == "f16" else lib.CB_F32 for a in (arith, farith))
@@ -27,7 +28,7 @@ class Layer(object):      # one state of cbinfer_cbdeform_forward with its prepa
         self.wp, self.dW, self.dB = torch.zeros(nbytes, dtype=torch.uint8, device="cuda"), dev(self.W), dev(self.bias)
         assert lib.C.cbinfer_deform_prep_weights(lib.ptr(self.dW), lib.ptr(self.wp), K, Cn, self.d, self.dtype, stream()) == 0
         self.out = torch.full((K,) + self.size, 77.0, dtype=self.dW.dtype, device="cuda")
-        words = [lib.C.cbinfer_mask_words(dc.HI, dc.WI), lib.C.cbinfer_mask_words(*self.size)]
+        words = [lib.C.cbinfer_mask_words(*inSize), lib.C.cbinfer_mask_words(*self.size)]
         self.inBits, self.bits = (torch.zeros(n, dtype=torch.int64, device="cuda") for n in words)
         self.mcopy = torch.full((words[1],), -1, dtype=torch.int64, device="cuda")
         self.ws = torch.zeros(lib.C.cbinfer_geom_workspace_bytes(), dtype=torch.uint8, device="cuda")
@@ -38,7 +39,7 @@ class Layer(object):      # one state of cbinfer_cbdeform_forward with its prepa
         return self.lib.C.cbinfer_cbdeform_forward(
             ptr(self.keep[0]), ptr(self.keep[1]), ptr(self.wp), ptr(self.dB), ptr(self.out), ptr(fx[0]), ptr(fx[1]), fx[2],
             ptr(fx[3]), ptr(ff[0]), ptr(ff[1]), ff[2], ptr(ff[3]), ptr(self.inBits), ptr(self.bits), ptr(self.mcopy),
-            ptr(self.ws), Cn, dc.HI, dc.WI, K, self.d, self.dtype, stream())
+            ptr(self.ws), Cn, *self.inSize, K, self.d, self.dtype, stream())
 
     def reference(self, x, fld, xChanged):
         ref, S, hit = dc.reference(x, fld, self.W, self.bias, self.geom, self.dims[1], self.mod, self.relu, xChanged)

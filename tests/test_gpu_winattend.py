@@ -8,14 +8,15 @@ import torch
 
 import winattend_cases as wc
 from test_gpu_attend import Wired as Sliding
-from optest import dev, gpu_lib as lib, gpu_pkg as pkg, host_words, npdtype, operand, pack, raw, share_of  # noqa: F401
+from optest import (bits_of, dev, gpu_lib as lib, gpu_pkg as pkg, host_words, npdtype, operand, pack, raw,  # noqa: F401
+                    share_of)
 
 pytestmark = pytest.mark.gpu
 DTYPES = ["f32", "f16"]
 
 
-def module(pkg, part, shift, heads, bias):
-    m = pkg.CBBinary2d('attend', partition=part, shift=shift, heads=heads,
+def module(pkg, part, shift, heads, bias, scale=None):
+    m = pkg.CBBinary2d('attend', partition=part, shift=shift, heads=heads, scale=scale,
                        positionBias=None if bias is None else torch.from_numpy(bias)).cuda()
     m.propChangeIndexes = True
     return m
@@ -25,21 +26,26 @@ def handed_on(m):
     return host_words(m._binWork['copy']), not bool(m._binWork['bits'].any())
 
 
-def judged(pkg, shape, part, shift, size, arith, other=None):
+def judged(pkg, shape, part, shift, size, arith, other=None, scale=None, bias=None):
     """One every-pixel frame against float64 (and `other`, a second float64 formulation) within the bound, which in
-    float32 stays below 2^-10 A on the reference alone."""
-    (Cn, Cv, heads), case = shape, (part, shift, size, shape, arith)
-    q, kv, bias = wc.operands(np.random.default_rng(17), Cn, Cv, heads, part, size, npdtype(arith))
-    m = module(pkg, part, shift, heads, bias)
-    out = m(dev(q)[None], dev(kv)[None])[1][0].double().cpu().numpy()
+    float32 stays below 2^-10 A on the reference alone: (the output's bits, operands, reference).  scale: the module's
+    scale= (the reference takes it as the float32 the library is handed), default d ** -0.5; bias: as
+    winattend_cases.operands takes it."""
+    (Cn, Cv, heads), case = shape, (part, shift, size, shape, arith, scale, bias)
+    q, kv, bias = wc.operands(np.random.default_rng(17), Cn, Cv, heads, part, size, npdtype(arith), bias=bias)
+    m = module(pkg, part, shift, heads, bias, scale)
+    got = m(dev(q)[None], dev(kv)[None])[1][0]
+    out = got.double().cpu().numpy()
     assert np.array_equal(handed_on(m)[0], pack(np.ones(size, dtype=bool))) and handed_on(m)[1], case
-    ref = wc.reference(q, kv, bias, part, shift, heads, wc.default_scale(Cn, heads))
+    scale = wc.default_scale(Cn, heads) if scale is None else float(np.float32(scale))
+    ref = wc.reference(q, kv, bias, part, shift, heads, scale)
     assert (wc.bound(ref, False) < 2.0 ** -10 * ref['A']).all(), case
     bar = wc.bound(ref, arith == "f16")
-    for want in (ref['out'],) + (() if other is None else (other(q, kv, bias, part, shift, heads, wc.default_scale(Cn, heads)),)):
+    for want in (ref['out'],) + (() if other is None else (other(q, kv, bias, part, shift, heads, scale),)):
         share = float((np.abs(out - want) / bar).max())
-        print("share of the bound", part, shift, size, shape, arith, "%.4f" % share)
+        print("share of the bound", *case, "%.4f" % share)
         assert share <= 1.0, case
+    return bits_of(got.cpu().numpy()), (q, kv), ref
 
 
 @pytest.mark.parametrize("arith", DTYPES)

@@ -94,3 +94,31 @@ def test_entry_point_checks_its_arguments(lib):
                 dict(at=att(lib, step=9)), dict(at=att(lib, 0, 0, -49, 0)), dict(at=att(lib, heads=3)),
                 dict(at=att(lib, border=2)), dict(at=att(lib, scale=float('nan')))):
         assert go(**bad) == -1, bad
+
+
+def test_limit_cases_are_what_they_claim(pkg):
+    """attend_cases.LIMIT_WINDOWS resolve to two and three column tiles; LIMIT_SHAPES reach the second block of v and the
+    second chunk of k; PEAKED has R >= 100 somewhere on the float64 reference while the float32 bound stays below 2^-10 A,
+    in both dtypes and under both borders; scale = 0 makes the reference the mean of the values that take part."""
+    import numpy as np
+
+    import attend_cases as ac
+    from correlation_cases import column_tiles
+    for (displacement, step, window), NT in zip(ac.LIMIT_WINDOWS, (2, 3)):
+        assert pkg.CBBinary2d('attend', displacement=displacement, step=step).window == window
+        assert column_tiles(window) == NT
+    assert [(Cn // h > 64, Cv // h > 64) for Cn, Cv, h in ac.LIMIT_SHAPES] == [(False, True), (True, True), (True, True)]
+    (Cn, Cv, heads), scale = ac.PEAKED
+    window = ac.WINDOWS[0][2]
+    for npdt in (np.float32, np.float16):
+        q, kv, bias = ac.operands(np.random.default_rng(17), Cn, Cv, heads, window, (7, 70), npdt)
+        for border in ac.BORDERS:
+            ref = ac.reference(q, kv, bias, window, 1, heads, border, scale)
+            assert bias is None and ref['R'].max() >= 100
+            assert np.array_equal(ac.reference(q, kv, bias, window, 1, heads, border, -scale)['Q'], ref['Q'])
+            assert ((ac.bound(ref, window, False) < 2.0 ** -10 * ref['A']) | (ref['A'] == 0)).all()
+            flat = ac.reference(q, kv, None, window, 1, heads, border, 0.0)['out']
+            mean = ac.uniform_mean(kv, Cn, window, 1, border)
+            assert np.abs(flat - mean).max() <= 1e-12 * np.abs(mean).max()
+    table = ac.operands(np.random.default_rng(17), 5, 5, 1, window, (3, 16), np.float32, bias='planes')[2]
+    assert table.shape == (1, 9, 9) and ac.operands(np.random.default_rng(17), 5, 5, 1, window, (3, 16), np.float32)[2] is None

@@ -87,3 +87,26 @@ def test_entry_point_checks_its_arguments(lib):
                 dict(an=N2), dict(bn=N2), dict(am=BB), dict(am=BITS), dict(am=COPY), dict(bm=BB), dict(bm=BITS),
                 dict(bm=COPY), dict(co=corr_struct(lib, step=9)), dict(co=corr_struct(lib, -20, 20, -20, 20))):
         assert go(**bad) == -1, bad
+
+
+@pytest.mark.parametrize("displacement,step,window", cc.LIMIT_WINDOWS, ids=cc.LIMIT_WINDOW_IDS)
+def test_limit_windows_resolve_to_their_tile_counts(pkg, lib, displacement, step, window):
+    """correlation_cases.LIMIT_WINDOWS: what correlation_window() makes of them, the column tile counts NT = 1, 3, 5, 9 --
+    the last two in the NTMAX = 9 kernels --, and frames that list under half of 5x150 and, for NT >= 5, of 7x70."""
+    assert pkg.CBBinary2d('correlate', displacement=displacement, step=step).window == window
+    assert pkg.CBBinary2d('aggregate', displacement=displacement, step=step).window == window
+    NT = cc.column_tiles(window)
+    assert NT == dict(zip(cc.LIMIT_WINDOW_IDS, (1, 3, 5, 9)))[cc.LIMIT_WINDOW_IDS[cc.LIMIT_WINDOWS.index((displacement, step,
+                                                                                                         window))]]
+    assert lib.C.cbinfer_correlation_supported(corr_struct(lib, *window[:4], step), 67, *cc.LIMIT_MAP) == 1
+    assert len(cc.frames(window, step, *cc.LIMIT_MAP)) == 6 and (NT < 5 or len(cc.frames(window, step, *cc.MAPS[0])) == 6)
+    assert [cc.column_tiles(w) for _, _, w in cc.WINDOWS] == [2, 2, 4, 2]
+
+
+def test_strided_changes_list_under_half_in_both_laps():
+    """The change-based frame of the grid-stride tests on a map of cap + 5 rows: rows of both laps, under half listed."""
+    cap, (_, step, window) = 2048, cc.STRIDE_WINDOW
+    SA, SB = cc.strided_changes(cap + 5, 16, cap)
+    listed = cc.footprint(SA, SB, window, step)
+    assert SA[:cap].any() and SA[cap:].any() and SB[:cap].any() and SB[cap:].any()
+    assert listed[:cap].any() and listed[cap:].any() and listed.mean() < 0.5 and cc.column_tiles(window) == 2

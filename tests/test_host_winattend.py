@@ -89,3 +89,27 @@ def test_entry_point_checks_its_arguments(lib):
                 dict(at=win(lib, 17, 1)), dict(at=win(lib, sy=7)), dict(at=win(lib, heads=3)),
                 dict(at=win(lib, scale=float('nan')))):
         assert go(**bad) == -1, bad
+
+
+def test_limit_cases_are_what_they_claim(pkg):
+    """winattend_cases.LIMIT_PARTITIONS have the token tile counts 1, 1, 2, 3, 5, 7, 8, 9, 9 and shifts the module takes;
+    PEAKED has R >= 100 on the float64 reference of every map while the float32 bound stays below 2^-10 A."""
+    import numpy as np
+
+    import winattend_cases as wc
+    assert [wc.tiles(p) for p in wc.LIMIT_PARTITIONS] == [1, 1, 2, 3, 5, 7, 8, 9, 9]
+    assert sorted({wc.tiles(p) for p in wc.PARTITIONS}) == [1, 4, 9]
+    for part in wc.LIMIT_PARTITIONS + wc.PARTITIONS:
+        for shift in wc.shifts_within(part):
+            assert pkg.CBBinary2d('attend', partition=part, shift=shift).shift == shift
+        assert part in ((1, 1), (1, 16)) or wc.shifts_within(part) == sorted(wc.shifts(part))
+    assert wc.shifts_within((1, 1)) == [(0, 0)] and wc.shifts_within((1, 16)) == [(0, 0), (0, 8), (0, 15)]
+    (Cn, Cv, heads), part, scale = wc.PEAKED
+    for npdt in (np.float32, np.float16):
+        for size in wc.MAPS:
+            q, kv, bias = wc.operands(np.random.default_rng(17), Cn, Cv, heads, part, size, npdt)
+            ref = wc.reference(q, kv, bias, part, (3, 3), heads, scale)
+            assert ref['R'].max() >= 100 and (wc.bound(ref, False) < 2.0 ** -10 * ref['A']).all()
+            assert np.array_equal(wc.reference(q, kv, bias, part, (3, 3), heads, -scale)['Q'], ref['Q'])
+    flat = wc.operands(np.random.default_rng(17), 5, 5, 1, (2, 3), (5, 70), np.float32, bias='flat')[2]
+    assert flat.shape == (1, 15)

@@ -10,8 +10,28 @@ MAPS = [(14, 21), (16, 24), (5, 70)]      # divisible by 7; by 8 but not by 7 or
 SHAPES = [(5, 5, 1), (60, 60, 2), (32, 48, 2), (64, 64, 1), (6, 6, 6)]
 
 
+# The cell shapes PARTITIONS leaves out (its token tile counts are NT = 1, 4, 4, 4, 9): one token; one row segment, which
+# a shift lays across the mask-word boundary of a 70-wide map; NT = 2 and 3 (float16 pads 3 to 4); NT = 5, 7 and 8 of the
+# large variant (float16 pads the odd ones); 144 tokens with a side of 16 -- the 31-wide and the 31-high bias table.
+LIMIT_PARTITIONS = [(1, 1), (1, 16), (4, 6), (6, 7), (8, 9), (10, 10), (8, 16), (9, 16), (16, 9)]
+LIMIT_MAPS = MAPS + [(33, 20)]      # ... and a map on which a 16-row cell is whole, with a clipped one beside it
+LIMIT_SHAPES = [(32, 48, 2), (64, 64, 1)]      # a bias on the first; the limit d = dv = 64
+# (C, Cv, heads), partition, scale of the peaked softmax (attend_cases.PEAKED has the reasoning)
+PEAKED = ((8, 16, 1), (7, 7), 8.0)
+
+
+def tiles(part):
+    """NT of a whole cell: its 16-token tiles."""
+    return (part[0] * part[1] + 15) // 16
+
+
 def shifts(part):
     return [(0, 0), (part[0] // 2, part[1] // 2), (1, part[1] - 1)]
+
+
+def shifts_within(part):
+    """shifts(part) where a side of one pixel takes no shift: (1, 1) is left with the zero shift only."""
+    return sorted({(min(sy, part[0] - 1), min(sx, part[1] - 1)) for sy, sx in shifts(part)})
 
 
 def spans(n, w, s):
@@ -32,13 +52,14 @@ def footprint(SQ, SKV, part, shift):
     return listed
 
 
-def operands(rng, Cn, Cv, heads, part, size, npdt):
+def operands(rng, Cn, Cv, heads, part, size, npdt, bias=None):
     """(q, kv, bias [heads, 2 Wy - 1, 2 Wx - 1] or None): q, k standard normal, v standard normal x 2, a bias on the
-    multi-head shapes."""
+    multi-head shapes (bias=True: on any shape; bias='flat': handed over as [heads, (2 Wy - 1) (2 Wx - 1)])."""
     q = rng.standard_normal((Cn,) + tuple(size)).astype(npdt)
     kv = (rng.standard_normal((Cn + Cv,) + tuple(size)) * np.r_[np.ones(Cn), 2 * np.ones(Cv)][:, None, None]).astype(npdt)
-    bias = rng.standard_normal((heads, 2 * part[0] - 1, 2 * part[1] - 1)).astype(np.float32) if heads > 1 else None
-    return q, kv, bias
+    table = (rng.standard_normal((heads, 2 * part[0] - 1, 2 * part[1] - 1)).astype(np.float32)
+             if heads > 1 or bias else None)
+    return q, kv, table.reshape(heads, -1) if bias == 'flat' else table
 
 
 def reference(q, kv, bias, part, shift, heads, scale):
@@ -47,6 +68,7 @@ def reference(q, kv, bias, part, shift, heads, scale):
     N = the tokens of the pixel's cell."""
     q, kv = q.astype(np.float64), kv.astype(np.float64)
     Cn, (H, W), (Wy, Wx) = q.shape[0], q.shape[1:], part
+    bias = None if bias is None else bias.reshape(heads, 2 * Wy - 1, 2 * Wx - 1)      # (flattened: the same table)
     Cv = kv.shape[0] - Cn
     d, dv = Cn // heads, Cv // heads
     out, A, V1 = (np.zeros((Cv, H, W)) for _ in range(3))
@@ -66,7 +88,8 @@ def reference(q, kv, bias, part, shift, heads, scale):
             put = (slice(h * dv, (h + 1) * dv),) + box
             out[put], A[put] = (vc @ w.T).reshape(dv, y1 - y0, -1), (np.abs(vc) @ w.T).reshape(dv, y1 - y0, -1)
             V1[put] = np.abs(vc).sum(1)[:, None, None]
-            Q[(h,) + box] = (np.abs(prod).sum(0).max(1) * scale).reshape(y1 - y0, -1)
+            # (a magnitude: under a negative scale the score's error is bounded by |scale| sum |q k| as well)
+            Q[(h,) + box] = (np.abs(prod).sum(0).max(1) * abs(scale)).reshape(y1 - y0, -1)
             R[(h,) + box] = (s.max(1, keepdims=True) - s).max(1).reshape(y1 - y0, -1)
             N[(h,) + box] = n
     B = np.zeros(heads) if bias is None else np.abs(bias.astype(np.float64)).reshape(heads, -1).max(1)
